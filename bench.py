@@ -9,9 +9,12 @@ The delta log (register events, tile index, pc/instruction columns) is resident 
 sequential host interpreter that produced it is timed separately (`host_interpret_rows_per_s`, `zkir_exec_ms`).
 `--stage trace_fill` times K1 alone.  The trace / LDE / Merkle stages after K1 have no counterpart in the reference (no prover there).
 
-The JSON line also carries `by_config`: the other single-GPU BASELINE configs measured in the same run, outside the timed region —
-configs[2] (2^24-cycle fib: commit step + full proof, per-stage rooflines) and configs[4] (2^22-cycle SHA-256 chain: the five
-witness kernels with algorithmic bytes, ms and fraction of the HBM peak).
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, the per-stage HIP-event
+times of the timed steps and the rooflines computed from them.  `--dump-outputs DIR` then writes what the last timed step computed (see dump_outputs).
+`--full` adds everything else, all outside the timed region: the steady-state host / H2D / HBM-copy figures, the end-to-end proofs (every mode), zkir_exec,
+the pipelined service, the N > 1 segment proofs and host-in-the-loop runs, the parity spot-check, the oracle golden root, the CPU baseline and `by_config`,
+the other single-GPU BASELINE configs — configs[2] (2^24-cycle fib: commit step + full proof, per-stage rooflines) and configs[4] (2^22-cycle SHA-256
+chain: the five witness kernels with algorithmic bytes, ms and fraction of the HBM peak).  --no-cpu-baseline / --no-prove / --no-by-config trim a --full run.
 
 N ranks = N row shards of one (N * 2^k)-cycle run (weak scaling): each rank fills and commits its own row range from its own
 register snapshot with no data-path collective; the per-rank Merkle roots are all-gathered over RCCL (16 B per rank) and every
@@ -522,6 +525,56 @@ def emit(full: dict):
     print(text, flush=True)
 
 
+DUMP_SEED = 20240601          # fixed: two builds run with the same arguments sample the same rows
+DUMP_TRACE_ROWS = 16384       # sampled trace rows and LDE rows (all columns of each)
+DUMP_MERKLE_NODES = 65536
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _u32(t):
+    """A device int32 tensor -> its words as float64 (exact: every u32 is a float64 integer)."""
+    import numpy as np
+    return t.contiguous().cpu().numpy().view(np.uint32).astype(np.float64)
+
+
+def _u64(t):
+    """A device int64 tensor -> float64 of shape (..., 2): [low 32 bits, high 32 bits] (a float64 cannot hold every u64)."""
+    import numpy as np
+    a = t.contiguous().cpu().numpy().view(np.uint64)
+    return np.stack([(a & 0xFFFFFFFF).astype(np.float64), (a >> np.uint64(32)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(out_dir, trace, n, L=None, W=None, tree=None, root=None):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float64.  u32 words are stored as they are, u64 words as
+    [low, high] 32-bit halves.  The step's outputs are larger than the 64 MB budget (372 B/row of trace, W x 2n LDE words, 4n - 1 Merkle nodes), so the
+    trace and LDE rows and the Merkle nodes are a sample drawn with DUMP_SEED (the same rows for the same arguments); the root is written whole.
+      trace_<column>   (R, ...)  the K1 execution-trace columns of R sampled rows (pc / instruction: the delivered columns of the same rows)
+      lde              (R, W)    the blow-up-2 LDE matrix, R sampled rows of the 2n, every column
+      merkle_nodes     (S, 4)    S sampled nodes of the 4n - 1 node Merkle tree (leaves first, root last)
+      merkle_root      (4,)      the commitment root (N > 1: the capped root over every rank's subtree)"""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = trace.cycle.device
+    rows = torch.from_numpy(np.sort(rng.choice(n, size=min(DUMP_TRACE_ROWS, n), replace=False))).to(dev)
+    arrays = {"trace_cycle": _u64(trace.cycle[rows]), "trace_pc": _u64(trace.pc[rows]), "trace_instruction": _u32(trace.instruction[rows]),
+              "trace_registers": _u64(trace.registers[:, rows].T), "trace_bound_bits": _u32(trace.bound_bits[:, rows].T),
+              "trace_bound_tag": trace.bound_tag[:, rows].T.contiguous().cpu().numpy().astype(np.float64),
+              "trace_bound_payload": _u64(trace.bound_payload[:, rows].T), "trace_reg_state": trace.reg_state[:, rows].T.contiguous().cpu().numpy().astype(np.float64)}
+    if L is not None:
+        lrows = torch.from_numpy(np.sort(rng.choice(2 * n, size=min(DUMP_TRACE_ROWS, 2 * n), replace=False))).to(dev)
+        arrays["lde"] = _u32(L[:, lrows, :].permute(1, 0, 2).reshape(len(lrows), W))              # B8 layout: column c at [c // 8, row, c % 8]
+        nodes = tree.view(-1, 4)
+        nidx = torch.from_numpy(np.sort(rng.choice(nodes.shape[0], size=min(DUMP_MERKLE_NODES, nodes.shape[0]), replace=False))).to(dev)
+        arrays["merkle_nodes"] = _u32(nodes[nidx])
+        arrays["merkle_root"] = np.asarray(root, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"bench: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -536,7 +589,12 @@ def main():
                     "(profiling runs: keeps the rocprofv3 per-kernel averages to the kernels of the timed steps)")
     ap.add_argument("--no-by-config", action="store_true", help="skip the configs[2] / configs[4] sections (profiling runs)")
     ap.add_argument("--only-config", choices=["2", "3", "4"], default=None, help="run only that by_config section and print it (profiling runs; 3 = 2^26 rows on one GPU)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every side measurement and check (proofs, by_config, CPU baseline, ...: "
+                    "see the module docstring); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64, seeded sample, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # Read by the HSA runtime when it initialises (the first HIP call of the process), so it has to be in the environment BEFORE torch
     # touches the device: the host driver only supports dmabuf IPC, and RCCL's intra-node transport needs it
@@ -597,11 +655,14 @@ def main():
         host_first_s = host_s = time.perf_counter() - t0
         assert log.n_rows == total_rows and log.halt_reason == rt.HaltReason.CycleLimit()
         # steady state: the log buffers of a finished run are recycled (host.h block pool), so later runs do not page-fault their way
-        # through ~50 B/row of fresh memory; time a second run and give its buffers back
-        for _ in range(2):
-            t0 = time.perf_counter()
-            rt.interpret(blob, [], rt.VMConfig(max_cycles=total_rows, enable_execution_trace=True), tile_rows=args.tile_rows).close()
-            host_s = min(host_s, time.perf_counter() - t0)
+        # through ~50 B/row of fresh memory; time a second run and give its buffers back (--full: a plain run reports no host figure)
+        if args.full:
+            for _ in range(2):
+                t0 = time.perf_counter()
+                rt.interpret(blob, [], rt.VMConfig(max_cycles=total_rows, enable_execution_trace=True), tile_rows=args.tile_rows).close()
+                host_s = min(host_s, time.perf_counter() - t0)
+        else:
+            host_first_s = host_s = None
         shard = log
     else:
         # Execution is sequential (vm.rs:208-358): the state at row g*n exists only once rows [0, g*n) have been executed.  Rank g
@@ -609,7 +670,7 @@ def main():
         # so GPU g has its shard after g*n*t_untraced + n*t_traced, sooner than a single traced interpreter on rank 0 would reach
         # those rows, and nothing travels between the processes (round 2 wrote every shard to /dev/shm as .npz and read it back).
         # The window also covers the segment-proof shard of the rank ([g(n-1), g(n-1)+n): overlaps the previous rank's by one row).
-        want_segments = args.stage == "commit" and not args.no_prove
+        want_segments = args.full and args.stage == "commit" and not args.no_prove
         vm_cfg = rt.VMConfig(max_cycles=total_rows, enable_execution_trace=True)
         lo = rank * (n - 1) if want_segments else rank * n
         dist.barrier()
@@ -634,16 +695,19 @@ def main():
     torch.zeros(1 << 20, device="cuda").sum().item()   # HIP context / allocator warm-up is not part of the H2D figure
     # The delta log sits in pinned pool blocks (host.h: Buf / block_acquire), so the copies are plain DMA.  The FIRST multi-megabyte host-to-device copy of a process costs
     # ~7 ms whatever the memory is (scripts/time_upload.py, profiles/r06_pinned_delta_log.txt: the runtime sets its copy path up), so the upload is timed twice and the
-    # second one is the figure; the first is reported beside it.
+    # second one is the figure; the first is reported beside it (--full; a plain run uploads once and reports neither).
+    h2d_first_s = h2d_s = None
+    if args.full:
+        t0 = time.perf_counter()
+        ddl = pl.upload(shard)
+        torch.cuda.synchronize()
+        h2d_first_s = time.perf_counter() - t0
+        del ddl
     t0 = time.perf_counter()
     ddl = pl.upload(shard)
     torch.cuda.synchronize()
-    h2d_first_s = time.perf_counter() - t0
-    del ddl
-    t0 = time.perf_counter()
-    ddl = pl.upload(shard)
-    torch.cuda.synchronize()
-    h2d_s = time.perf_counter() - t0
+    if args.full:
+        h2d_s = time.perf_counter() - t0
     trace = pl.DeviceTrace(ddl)
     fill_args = pl.trace_fill_args(ddl, trace)
     commit = args.stage == "commit"
@@ -716,16 +780,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
     stage_ms = {name: float(np.mean([marks[i][j].elapsed_time(marks[i][j + 1]) for i in range(args.steps)])) for j, (name, _) in enumerate(stages)}
+    if args.dump_outputs and rank == 0:
+        root_now = (cap_root[0] if dist_mode else tree[-4:]).cpu().numpy().view(np.uint32).tolist() if commit else None
+        dump_outputs(args.dump_outputs, trace, n, *((L, W, tree, root_now) if commit else ()))
 
     # ---- measured HBM copy bandwidth of this device (report the measured peak next to the nominal 8 TB/s): the library's 16-byte-per-lane grid-stride copy
     #      (zkir_amd_experimental.h; MI355X_MICROARCH.md quotes ~6.3 TB/s for it — torch's copy_ reached 4.76: VERDICT r4 weak #6)
-    lib.zkir_hbm_copy_peak_gbs.restype = C.c_double
-    lib.zkir_hbm_copy_peak_gbs.argtypes = [C.c_uint64, C.c_void_p]
-    hbm_copy_gbs = max(float(lib.zkir_hbm_copy_peak_gbs(1 << 30, sp())) for _ in range(3))
+    hbm_copy_gbs = None
+    if args.full:
+        lib.zkir_hbm_copy_peak_gbs.restype = C.c_double
+        lib.zkir_hbm_copy_peak_gbs.argtypes = [C.c_uint64, C.c_void_p]
+        hbm_copy_gbs = max(float(lib.zkir_hbm_copy_peak_gbs(1 << 30, sp())) for _ in range(3))
 
     # ---- end-to-end prove (BASELINE metric's "end-to-end prove ms"): AIR quotient + openings + DEEP + FRI on top of the commit ----
     prove_ms, prove_stage_ms, proof_bytes, verify_ms, prove_ms_100bit = None, None, None, None, None
-    if commit and not dist_mode and not args.no_prove:   # a proof is for the whole run (its AIR pins cycle[0] = 0): single-GPU only
+    if args.full and commit and not dist_mode and not args.no_prove:   # a proof is for the whole run (its AIR pins cycle[0] = 0): single-GPU only
         pub = rt.public_inputs(log, blob)
         for _ in range(3):                            # first call allocates the context's workspace
             t0 = time.perf_counter()
@@ -748,7 +817,7 @@ def main():
     # ---- the opt-in proof MODES of round 4 at the same size: the fib run in mode 2 (+ the I/O argument), and the array loop of spec.memory_loop_program
     #      (4 of 13 rows are loads / stores) in modes 0, 2 and 3 (+ the memory argument; the memory witness made on the device) — what saying more costs
     prove_by_mode = prove_ms_mode2 = None
-    if commit and not dist_mode and not args.no_prove and k <= 22:
+    if args.full and commit and not dist_mode and not args.no_prove and k <= 22:
         try:
             def timed_prove(tr_, pub_, reps=5):
                 best, pr_, st_ = None, None, None
@@ -806,7 +875,7 @@ def main():
     # ---- N > 1: the run PROVEN, one segment per GPU (no data-path collective: a segment needs its own rows only); the proofs are
     #      gathered on rank 0 and verified there as ONE run (zkir_verify_chain: first state initial, states link, same public inputs)
     segment_prove = None
-    if commit and dist_mode and not args.no_prove:
+    if args.full and commit and dist_mode and not args.no_prove:
         try:
             run_pub = rt.PublicInputsC.from_buffer_copy(run_pub_bytes[0]).with_program(blob)   # the borrowed program pointer of another process means nothing here
             seg_proofs, seg_ms = [], None
@@ -849,7 +918,7 @@ def main():
     #      with upload + K1 streamed underneath) -> main trace -> LDE -> Merkle -> all-gather + cap; (b) G INDEPENDENT runs, one per
     #      GPU, each interpreted by its own rank: the mode whose aggregate scales with G, since one run is bounded by one core
     multi_e2e = None
-    if commit and dist_mode:
+    if args.full and commit and dist_mode:
         try:
             def commit_from(cols, n_rows):
                 pl._check(lib.zkir_main_trace_launch(C.byref(cols), n_rows, 0, m.data_ptr(), sp()))
@@ -913,7 +982,7 @@ def main():
 
     # ---- the drop-in entry point itself: zkir_exec = host interpretation + H2D + K1 in one call (VM::new + VM::run, trace left in HBM)
     exec_s = None
-    if not dist_mode and k <= 24:
+    if args.full and not dist_mode and k <= 24:
         ts = []
         for _ in range(5):
             t0 = time.perf_counter()
@@ -925,7 +994,7 @@ def main():
 
     # ---- the same proof with the host in the loop: independent runs pipelined through interpret -> H2D -> K1 -> prove ----------
     pipelined = pipelined_commit = None
-    if commit and not dist_mode and k <= 22 and not args.no_prove:
+    if args.full and commit and not dist_mode and k <= 22 and not args.no_prove:
         from zkir_amd import service
         job = (blob, [], rt.VMConfig(max_cycles=n, enable_execution_trace=True))
         service.prove_many([job] * 2, k, producers=1, ctx=ctx, keep_proofs=False)
@@ -942,14 +1011,15 @@ def main():
                      "note": "host interpretation + H2D + trace fill + full proof of independent 2^k-row runs: three interpreting threads and two proving threads (own "
                              "context and stream each: one proof's host transcript round trips are covered by the other's kernels) (zkir_amd/service.py)"}
 
-    # ---- parity spot checks outside the timed region (full parity lives in tests/ -m gpu) ----------
-    n_chk = min(4096, n)
-    got = trace.registers[:, :n_chk].cpu().numpy().view(np.uint64)
-    ev_np = shard.reg_events
-    for r in (1, 2, 3, 4):
-        e = ev_np[ev_np["reg"] == r]
-        pos = np.searchsorted(e["vis"], np.arange(n_chk), side="right") - 1
-        assert np.array_equal(got[r], e["value"][pos]), "bench parity spot-check failed"
+    # ---- parity spot checks outside the timed region (--full; full parity lives in tests/ -m gpu) ----------
+    if args.full:
+        n_chk = min(4096, n)
+        got = trace.registers[:, :n_chk].cpu().numpy().view(np.uint64)
+        ev_np = shard.reg_events
+        for r in (1, 2, 3, 4):
+            e = ev_np[ev_np["reg"] == r]
+            pos = np.searchsorted(e["vis"], np.arange(n_chk), side="right") - 1
+            assert np.array_equal(got[r], e["value"][pos]), "bench parity spot-check failed"
     root = tree[-4:].cpu().numpy().view(np.uint32).tolist() if commit else None
     roots = None
     if commit and dist_mode:
@@ -961,7 +1031,7 @@ def main():
 
     # ---- the other single-GPU BASELINE configs, outside the timed region (free the configs[1] buffers first) ----
     by_config = None
-    if rank == 0 and not dist_mode and commit and not args.no_by_config and k == 20:
+    if args.full and rank == 0 and not dist_mode and commit and not args.no_by_config and k == 20:
         if commit:
             del m, L, tree
             ctx.close()
@@ -1042,9 +1112,9 @@ def main():
             "prove_by_mode": prove_by_mode,
             "pipelined_end_to_end": pipelined, "pipelined_commit_end_to_end": pipelined_commit, "segment_prove": segment_prove,
             "merkle_root": root, "merkle_roots_all_ranks": roots, "allgather_cap_ms": stage_ms.get("allgather_cap"),
-            "merkle_root_equals_oracle_golden": _root_vs_golden(k, root) if (commit and not dist_mode) else None,
-            "host_interpret_rows_per_s": total_rows / host_s, "host_interpret_first_run_rows_per_s": total_rows / host_first_s,
-            "host_interpret_ns_per_instruction": host_s / total_rows * 1e9, "host_interpret_s": host_s,
+            "merkle_root_equals_oracle_golden": _root_vs_golden(k, root) if (args.full and commit and not dist_mode) else None,
+            "host_interpret_rows_per_s": total_rows / host_s if host_s else None, "host_interpret_first_run_rows_per_s": total_rows / host_first_s if host_first_s else None,
+            "host_interpret_ns_per_instruction": host_s / total_rows * 1e9 if host_s else None, "host_interpret_s": host_s,
             # N = 1: the one interpretation of the run.  N > 1: EVERY rank executes its own prefix (rank g: g n rows untraced + n rows traced, on its own
             # core: zkir_interpret_window) — G interpreters per node, no shard transport; `host_interpret_s` is then the slowest rank's (the last one's)
             "host_interpretations_per_node": world, "shard_distribution_s": 0.0,
@@ -1057,7 +1127,7 @@ def main():
             "zkir_exec_rows_per_s": n / exec_s if exec_s else None,
             "host_cpu": _host_cpu(),
         }
-        if not args.no_cpu_baseline and not dist_mode:
+        if args.full and not args.no_cpu_baseline and not dist_mode:
             out["cpu_baseline"] = _cpu_baseline(blob, k, commit)
             side = out["cpu_baseline"].get("commit_stage_self_defined")
             if side and root is not None:

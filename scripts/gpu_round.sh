@@ -23,9 +23,9 @@ PY
 }
 for w in $WHAT; do case $w in
 tests) (cd $R && timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -15) > $OUT/pytest_gpu.log 2>&1; tail -5 $OUT/pytest_gpu.log;;
-bench) (cd $R && timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err); head -c 3000 $OUT/bench.json; echo; tail -3 $OUT/bench.err;;
+bench) (cd $R && timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err); head -c 3000 $OUT/bench.json; echo; tail -3 $OUT/bench.err;;
 prof)
-  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/kt_c1 -o b -- python $R/bench.py --no-cpu-baseline --no-prove --no-by-config > $OUT/kt_c1.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/kt_c1 -o b -- python $R/bench.py --full --no-cpu-baseline --no-prove --no-by-config > $OUT/kt_c1.log 2>&1
   summ $OUT/kt_c1 $OUT/${TAG}_config1_kernel_stats.txt
   timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/kt_c2 -o b -- python $R/bench.py --only-config 2 > $OUT/kt_c2.log 2>&1
   summ $OUT/kt_c2 $OUT/${TAG}_config2_kernel_stats.txt
@@ -35,8 +35,8 @@ prof)
 pmc)
   export ZKIR_EXEC_STREAM=0   # whole-run K1 launches only: the streaming zkir_exec adds partial-range launches to the per-kernel averages
   for c in FETCH_SIZE WRITE_SIZE; do d=$(echo $c | tr A-Z a-z | sed 's/_size//'); 
-    timeout 600 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$d -o b -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-prove --no-by-config > $OUT/pmc_$d.log 2>&1; done
-  timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $OUT/pmc_valu -o b -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-prove --no-by-config > $OUT/pmc_valu.log 2>&1
+    timeout 600 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$d -o b -- python $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-prove --no-by-config > $OUT/pmc_$d.log 2>&1; done
+  timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $OUT/pmc_valu -o b -- python $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-prove --no-by-config > $OUT/pmc_valu.log 2>&1
   python $R/scripts/extract_prof.py $OUT $OUT/${TAG}_bench_commit trace_fill main_trace lde_middle ntt_strided leaf_hash compress subtree | cut -c1-150
   python $R/scripts/extract_valu.py $OUT/pmc_valu $OUT/${TAG}_bench_commit_valu_busy.txt
   rm -rf $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_valu;;

@@ -8,6 +8,7 @@ import os
 import sys
 from contextlib import redirect_stderr, redirect_stdout
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -111,3 +112,75 @@ def test_shipped_code_object_registers_and_spills():
     assert h["quotient_kernel<0>"]["regs"]["vgpr_spill"] <= 8             # (three waves per SIMD with a handful of spilled registers beat two waves without: profiles/r05c_p2_variants.txt)
     committed = json.load(open(bench._newest_profile("r*_isa_hist.json")))
     assert committed["leaf_hash_kernel"]["classes"] == h["leaf_hash_kernel"]["classes"], "profiles/r*_isa_hist.json is not this build's: re-run scripts/isa_hist.py --json"
+
+
+def _sample(n, size, rng):
+    return np.sort(rng.choice(n, size=min(size, n), replace=False))
+
+
+def _join_u64(a):
+    return a[..., 0].astype(np.uint64) | (a[..., 1].astype(np.uint64) << np.uint64(32))
+
+
+def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
+    """--dump-outputs on host tensors of the 2^20-row shapes (zero-stride views stand in for the 1.3 GB LDE and the trace): float64 files within 64 MB,
+    the u32 / u64 words exact at the rows DUMP_SEED draws, the same files twice."""
+    import types
+    import torch
+    n, W = 1 << 20, 152
+    g = torch.Generator().manual_seed(7)
+    col = lambda dt: torch.randint(-2**31, 2**31 - 1, (n,), generator=g, dtype=torch.int64).to(dt)     # noqa: E731
+    tr = types.SimpleNamespace(cycle=torch.arange(n, dtype=torch.int64), pc=col(torch.int64) << 24, instruction=col(torch.int32),
+                               registers=col(torch.int64).mul(2**29).expand(16, n), bound_bits=col(torch.int32).expand(16, n),
+                               bound_tag=col(torch.uint8).expand(16, n), bound_payload=col(torch.int64).expand(16, n), reg_state=col(torch.uint8).expand(16, n))
+    L = torch.randint(-2**31, 2**31 - 1, (W // 8, 1, 8), generator=g, dtype=torch.int32).expand(W // 8, 2 * n, 8)
+    tree = torch.randint(-2**31, 2**31 - 1, (4 * (4 * n - 1),), generator=g, dtype=torch.int32)
+    root = tree[-4:].numpy().view(np.uint32).tolist()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), tr, n, L, W, tree, root)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "lde.npy" in files and "merkle_root.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        a = np.load(tmp_path / "a" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / f)), f
+    rng = np.random.default_rng(bench.DUMP_SEED)
+    rows, lrows = _sample(n, bench.DUMP_TRACE_ROWS, rng), _sample(2 * n, bench.DUMP_TRACE_ROWS, rng)
+    nodes = _sample(4 * n - 1, bench.DUMP_MERKLE_NODES, rng)
+    assert np.array_equal(_join_u64(np.load(tmp_path / "a" / "trace_registers.npy")), tr.registers[:, rows].T.numpy().view(np.uint64))
+    assert np.array_equal(_join_u64(np.load(tmp_path / "a" / "trace_pc.npy")), tr.pc[rows].numpy().view(np.uint64))
+    assert np.array_equal(np.load(tmp_path / "a" / "trace_instruction.npy").astype(np.uint32), tr.instruction[rows].numpy().view(np.uint32))
+    want_lde = L[:, lrows, :].permute(1, 0, 2).reshape(len(lrows), W).numpy().view(np.uint32)
+    assert np.array_equal(np.load(tmp_path / "a" / "lde.npy").astype(np.uint32), want_lde)
+    assert np.array_equal(np.load(tmp_path / "a" / "merkle_nodes.npy").astype(np.uint32), tree.view(-1, 4)[nodes].numpy().view(np.uint32))
+    assert np.load(tmp_path / "a" / "merkle_root.npy").astype(np.uint32).tolist() == root
+
+
+@pytest.mark.gpu
+def test_plain_run_and_its_dump_equal_the_oracle(tmp_path):
+    """A plain run times the steps and stops (no proof, no CPU baseline); what --dump-outputs wrote of its last step — trace rows, LDE rows, root — is
+    what the CPU oracle computes for the same run."""
+    import subprocess
+    from oracle import api as oracle, stark_api as so
+    from zkir_amd import spec
+    k = 14
+    n = 1 << k
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2-rows", str(k),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    line = _strict(lines[0])
+    for key in CONTRACT:
+        assert key in line, key
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["prove_ms"] is None and "cpu_baseline" not in line
+    rows = oracle.run(spec.fib_endless_program().to_bytes(), max_cycles=n, enable_execution_trace=True).rows
+    want_root, want_L = so.commit_trace(rows, 1, want_lde=True)
+    assert np.load(tmp_path / "merkle_root.npy").astype(np.uint32).tolist() == list(map(int, want_root)) == line["merkle_root"]
+    rng = np.random.default_rng(bench.DUMP_SEED)
+    idx, lidx = _sample(n, bench.DUMP_TRACE_ROWS, rng), _sample(2 * n, bench.DUMP_TRACE_ROWS, rng)
+    for name in ("cycle", "pc", "registers", "bound_payload"):
+        assert np.array_equal(_join_u64(np.load(tmp_path / f"trace_{name}.npy")), rows[name][idx]), name
+    for name in ("instruction", "bound_bits", "bound_tag", "reg_state"):
+        assert np.array_equal(np.load(tmp_path / f"trace_{name}.npy"), rows[name][idx].astype(np.float64)), name
+    assert np.array_equal(np.load(tmp_path / "lde.npy").astype(np.uint32), want_L[:, lidx].T)
