@@ -447,7 +447,7 @@ uint32_t zkir_proof_version_of_mode(uint32_t mode);   /* modes 2 / 3: 11 (round 
  * codeword degree, 12 grinding, 20-27 query / Merkle / FRI checks, 30 length; modes 2 / 3 also 50-53 = zkir_verify_io's checks on the tapes the proof carries, 51 the
  * counters' ends; mode 3 also 54 = the touched cells are not canonical 8-byte cell addresses in strictly increasing order; a mode-3 proof is never a segment: 2;
  * modes 3 / 4 also 55 = a touched cell / a hash call's output overlaps the code segment (mode 4 admits the boundary cell); mode 4 also 56 = a malformed hash-tape record
- * (ranges, order, cell count, a previous access that is not before the call), 57 = a malformed wide-tape record (a limb out of range, not an opcode 3..7, a zero divisor, cycles
+ * (ranges, order, cell count, a previous access that is not before the call, a SHA-256 output pointer that is not a multiple of 4), 57 = a malformed wide-tape record (a limb out of range, not an opcode 3..7, a zero divisor, cycles
  * not increasing); a tape whose records are well-formed but are not the run's fails the lookup argument (10)).
  * expect may be NULL: the header's own public inputs are then only checked for internal consistency.
  * The queries (independent, ~10,000 Poseidon2 permutations of Merkle paths at 2^20 rows) are checked on up to eight host threads (half the logical cores; ZKIR_VERIFY_THREADS=n

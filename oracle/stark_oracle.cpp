@@ -422,8 +422,9 @@ static uint64_t image_cell(const uint8_t* blob, size_t n, uint64_t addr) {
 // ---- (mode 4) hash calls: what the verifier recomputes.  The digests are the oracle's own (zkir_oracle.cpp: the functions behind syscalls 3 / 5 / 6, pinned by the reference's KATs).
 extern "C" { void zo_sha256(const uint8_t* d, size_t n, uint32_t out_words[8]); void zo_keccak256(const uint8_t* d, size_t n, uint8_t out[32]); void zo_blake3(const uint8_t* d, size_t n, uint8_t out[32]); }
 static const uint64_t HASH_MAX_LEN = 1u << 20;                  // a proof states hash calls of up to 1 MiB of input (the record's length word is one field element)
+// (a SHA-256 output pointer must be a multiple of 4: the reference writes the digest with write_u32, crypto.rs:251-254, which refuses a misaligned address)
 static inline bool hash_call_in_range(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint32_t kind) {
-  return (kind == 3 || kind == 5 || kind == 6) && len <= HASH_MAX_LEN && in_ptr < (1ull << 40) && in_ptr + len <= (1ull << 40) && out_ptr < (1ull << 40) && out_ptr + 32 <= (1ull << 40);
+  return (kind == 3 || kind == 5 || kind == 6) && (kind != 3 || (out_ptr & 3) == 0) && len <= HASH_MAX_LEN && in_ptr < (1ull << 40) && in_ptr + len <= (1ull << 40) && out_ptr < (1ull << 40) && out_ptr + 32 <= (1ull << 40);
 }
 // the aligned 8-byte cells under [in, in + len) and [out, out + 32), ascending, each once
 static void hash_call_cells(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, std::vector<uint64_t>& addrs) {

@@ -14,6 +14,11 @@ rows) — the large-size counterpart of tests/test_gpu_stark.py's small mode-3 p
 Also (`python tests/golden/make_config_proofs.py mode2 [log2_rows ...]`, default 12 16 20; round 5): the MODE-2 proof (the I/O argument) of a fib run that halts by itself and
 WRITES its result — the proof whose output tape says what the run computed.
 
+Also (`python tests/golden/make_config_proofs.py mode4 [name:log2_rows ...]`, default sha_chain:18 sha_chain:20 wide_loop:20 signed_division_loop:20; round 7): MODE-4 proofs
+(format v12: 288 + 128 columns) at sizes where the GPU prover runs many workgroups of quotient_kernel<4>, main_trace_kernel<4>, wide_tape_fix_kernel and the lookup-aux
+columns — configs[4]'s SHA-256 chain (one hash-tape record per 6 rows), the endless wide loop (MULH DIVU REMU DIV REM on 40-bit operands: the chunk relation) and the endless
+signed-division loop (the same opcodes on raw 64-bit registers: the wide tape), each encoded HERE; through so::prove_lean on ZKIR_ORACLE_THREADS threads.
+
 Does not import the product.  Run: python tests/golden/make_config_proofs.py [log2_rows ...]   (default 16 18 20; 22: 45 minutes, 23: 104 minutes and ~36 GB, one thread)
 2^24 rows (BASELINE configs[2]'s own size; round 6) goes through so::prove_lean — the memory-lean, threaded restatement of so::prove that tests/test_stark_oracle.py holds
 equal to it word for word in every mode (38 GB instead of ~70; ZKIR_ORACLE_THREADS std::threads, default all cores) — and so does any size when ZKIR_ORACLE_LEAN=1.
@@ -21,6 +26,7 @@ equal to it word for word in every mode (38 GB instead of ~70; ZKIR_ORACLE_THREA
 import hashlib
 import json
 import os
+import struct
 import sys
 import time
 
@@ -129,6 +135,67 @@ def main_params(ks, num_queries=84, pow_bits=16):
         json.dump(cur, open(path, "w"), indent=1)
 
 
+# ---- mode 4 (round 7) ---------------------------------------------------------------------------------------------------------------------------------------------
+MUL, MULH, DIVU, REMU, DIV, REM, ORI, SRLI, SB, SW, BNE = 0x02, 0x03, 0x04, 0x05, 0x06, 0x07, 0x14, 0x1C, 0x38, 0x3A, 0x41
+
+
+def blob_data(code, data):
+    """The v3.4 blob with a data section behind the code (program.rs:170-186, 300-315)."""
+    hdr = struct.pack("<IIBBBBIIIII", 0x52494B5A, 0x00030004, 20, 2, 2, 0, 0x1000, 4 * len(code), len(data), 0, 1 << 20)
+    return hdr + b"".join(struct.pack("<I", w & 0xFFFFFFFF) for w in code) + bytes(data)
+
+
+def sha_chain():
+    """configs[4]: the 32-byte seed 0..31 copied from the data section to 0x10000, then forever sha256(in, 32, out) and swap(in, out) (6 rows per call)."""
+    code = [i_(ADDI, 5, 0, 0x1000 + 4 * 19), i_(ADDI, 6, 0, 0x8000), sh_(SLLI, 6, 6, 1), i_(ADDI, 7, 5, 32),
+            i_(LW, 8, 5, 0), s_(SW, 6, 8, 0), i_(ADDI, 5, 5, 4), i_(ADDI, 6, 6, 4), b_(BNE, 5, 7, -16),
+            i_(ADDI, 11, 0, 0x8000), sh_(SLLI, 11, 11, 1), i_(ADDI, 13, 11, 32), i_(ADDI, 12, 0, 32),
+            i_(ADDI, 10, 0, 3), ECALL_, i_(ADDI, 9, 11, 0), i_(ADDI, 11, 13, 0), i_(ADDI, 13, 9, 0), j_(JAL, 0, -20)]
+    return blob_data(code, bytes(range(32)))
+
+
+def wide_loop():
+    """x <- x * 0x2545F + 0x4057 (mod 2^40), d = (x >> 17) | 1, MULH DIVU REMU DIV REM of x by d, XORed into a checksum stored and loaded back: 18 rows per iteration."""
+    return blob_data([i_(ADDI, 1, 0, 12345), i_(ADDI, 2, 0, 0x2545), sh_(SLLI, 2, 2, 4), i_(ADDI, 2, 2, 0xF), i_(ADDI, 12, 0, 0), i_(ADDI, 6, 0, 0x8000), sh_(SLLI, 6, 6, 1),
+                      r_(MUL, 1, 1, 2), i_(ADDI, 1, 1, 0x4057), sh_(SRLI, 3, 1, 17), i_(ORI, 3, 3, 1),
+                      r_(MULH, 4, 1, 1), r_(DIVU, 5, 1, 3), r_(REMU, 7, 1, 3), r_(DIV, 8, 4, 3), r_(REM, 9, 4, 3), r_(MULH, 10, 5, 3),
+                      r_(XOR, 12, 12, 4), r_(XOR, 12, 12, 5), r_(XOR, 12, 12, 7), r_(XOR, 12, 12, 8), r_(XOR, 12, 12, 9), r_(XOR, 12, 12, 10),
+                      s_(SD, 6, 12, 0), i_(LD, 13, 6, 0), j_(JAL, 0, -72)], b"")
+
+
+def signed_division_loop():
+    """An odd byte stored and loaded back with LB (sign-extended above 2^40 when its top bit is set), divided, reduced and multiplied on the raw 64-bit registers: 12 rows."""
+    return blob_data([i_(ADDI, 6, 0, 0x8000), sh_(SLLI, 6, 6, 1), i_(ADDI, 1, 0, 0x95),
+                      s_(SB, 6, 1, 0), i_(LB, 2, 6, 0), i_(ANDI, 3, 1, 0x3F), i_(ADDI, 3, 3, 7),
+                      r_(DIV, 4, 2, 3), r_(REM, 5, 2, 3), r_(DIVU, 7, 2, 3), r_(MULH, 8, 2, 2), r_(REMU, 9, 3, 2), r_(DIV, 10, 3, 2),
+                      i_(ADDI, 1, 1, 2), j_(JAL, 0, -44)], b"")
+
+
+MODE4_PROGRAMS = {"sha_chain": sha_chain, "wide_loop": wide_loop, "signed_division_loop": signed_division_loop}
+
+
+def main_mode4(specs):
+    path = os.path.join(HERE, "config_proofs.json")
+    threads = int(os.environ.get("ZKIR_ORACLE_THREADS", os.cpu_count() or 1))
+    for sp in specs:
+        name, k = sp.split(":")[0], int(sp.split(":")[1])
+        prog = MODE4_PROGRAMS[name]()
+        t0 = time.time()
+        res = oracle.run(prog, max_cycles=1 << k, enable_execution_trace=True)
+        assert res.halt_kind == 2 and len(res.rows) == 1 << k                 # CycleLimit
+        pub = so.public_inputs(len(res.rows), prog, [], list(res.outputs), (res.halt_kind, res.halt_code), wide_mode=True)
+        rows = res.rows
+        del res
+        proof = np.ascontiguousarray(so.prove_lean(rows, pub, threads=threads, cap_words=1 << 25), dtype="<u4")
+        assert int(proof[1]) == 12 and int(proof[9]) == 4 and so.verify(proof, pub) == 0
+        e = entry(proof, k, t0)
+        e.update({"threads": threads, "prover": "so::prove_lean", "program_blob_hex": prog.hex()})
+        print("mode4", name, k, e["words"], e["sha256"], e["oracle_seconds"], flush=True)
+        cur = json.load(open(path))
+        cur.setdefault("mode4_proofs", {}).setdefault(name, {})[str(k)] = e
+        json.dump(cur, open(path, "w"), indent=1)
+
+
 def sample_positions(n_words: int):
     return [int(i * (n_words - 1) // (N_SAMPLES - 1)) for i in range(N_SAMPLES)]
 
@@ -136,6 +203,8 @@ def sample_positions(n_words: int):
 def main():
     if sys.argv[1:2] == ["mode3"]:
         return main_mode3([int(a) for a in sys.argv[2:]] or [14, 16])
+    if sys.argv[1:2] == ["mode4"]:
+        return main_mode4(sys.argv[2:] or ["sha_chain:18", "sha_chain:20", "wide_loop:20", "signed_division_loop:20"])
     if sys.argv[1:2] == ["params"]:
         return main_params([int(a) for a in sys.argv[2:]] or [12, 16])
     if sys.argv[1:2] == ["mode2"]:

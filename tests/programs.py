@@ -362,3 +362,190 @@ def off_code(name):
     f = globals()[name]
     import inspect
     return f(base=OFF_CODE) if "base" in inspect.signature(f).parameters else f()
+
+
+# ---- memory edges of proof modes 3 / 4: addresses whose limbs carry, wrap or sit at the top of the 40-bit space (tests/test_memory_edges.py) --------------------
+P8 = 8 * 0x78000001                  # 8 p: two cells this far apart are the same Baby Bear element (0x3C0000008, ~15 GiB)
+TOP = (1 << 40) - 8                  # the last cell below 2^40
+_LOADS = {1: (O.LB, O.LBU), 2: (O.LH, O.LHU), 4: (O.LW,), 8: (O.LD,)}
+_STORES = {1: O.SB, 2: O.SH, 4: O.SW, 8: O.SD}
+
+
+def _widths_at(base_reg, imm):
+    """SD a pattern at base + imm, read it back at every width (signed and unsigned), overwrite a byte, a halfword and a word, read the doubleword again."""
+    code = [E(O.SD, rs1=base_reg, rs2=1, imm=imm), E(O.LD, 2, base_reg, imm=imm), E(O.LW, 3, base_reg, imm=imm + 4), E(O.LH, 4, base_reg, imm=imm + 6),
+            E(O.LHU, 4, base_reg, imm=imm + 6), E(O.LB, 7, base_reg, imm=imm + 7), E(O.LBU, 7, base_reg, imm=imm + 3)]
+    code += [E(O.SB, rs1=base_reg, rs2=2, imm=imm + 1), E(O.SH, rs1=base_reg, rs2=3, imm=imm + 2), E(O.SW, rs1=base_reg, rs2=4, imm=imm + 4), E(O.LD, 8, base_reg, imm=imm)]
+    return code
+
+
+def _pattern():
+    return li40(1, 0x80F1E2D3C4)          # every byte distinct, the top bit of bytes 4 (0x80) / 3 (0xF1) / 7 set once the stores have run
+
+
+def edge_limb_carries():
+    """base[0] + imm carries into limb 1 (and a negative imm17 borrows through it): bases whose limb 0 sits just below 2^20, immediates 8 .. 65528 and -8 .. -65536,
+    every width; a byte access at imm = +65535.  The cells stay far above the code and below 2^40."""
+    code = _pattern()
+    for base in (0x3_FFFF8, 0x5_FFFC0, 0x7_F8000, 0xABCDE_FFFF8):
+        code += li40(5, base)
+        for imm in (8, 0x40, 0x8000, 65528):
+            code += _widths_at(5, imm)
+        code += [E(O.SB, rs1=5, rs2=1, imm=65535), E(O.LB, 9, 5, imm=65535), E(O.LBU, 9, 5, imm=65535)]
+    for base in (0x3_00010, 0x6_10000, 0x8_00008, 0xFFFFF_00000):
+        code += li40(5, base)
+        for imm in (-8, -16, -0x8000, -65536):
+            code += _widths_at(5, imm)
+    return _p(code + [EB]), [], {}
+
+
+def edge_high_limbs():
+    """Cells whose limb 1 is 0xFFFFF, 0x80000, 0x55555 (every width), and the top cell 2^40 - 8: an SD / LD pair, a byte stored into each of its eight bytes, read back."""
+    code = _pattern()
+    for hi in (0xFFFFF, 0x80000, 0x55555):
+        code += li40(5, (hi << 20) | 0xABCD0) + _widths_at(5, 0) + _widths_at(5, -0x10)
+    code += li40(5, TOP) + [E(O.SD, rs1=5, rs2=1, imm=0), E(O.LD, 2, 5, imm=0)]
+    for k in range(8):
+        code += [A(9, 0, 0x81 + 0x11 * k), E(O.SB, rs1=5, rs2=9, imm=k), E(O.LB, 3, 5, imm=k), E(O.LBU, 4, 5, imm=k)]
+    code += [E(O.LD, 2, 5, imm=0), E(O.LW, 3, 5, imm=4), E(O.LH, 4, 5, imm=6)]
+    code += li40(5, TOP - 0x10000 + 8) + _widths_at(5, 65528 - 8)                  # the top cell again, reached through limb-0 carry
+    return _p(code + [EB]), [], {}
+
+
+def edge_wrap64():
+    """A raw 64-bit base plus imm wrapping past 2^64 or landing below 2^40 (column C_CM2): an LB sign-extended base 0xFFFF_FFFF_FFFF_FF80 + 0x2080 = 0x2000; bases that arrive by
+    READ (raw 64 bits) — 2^64 - 8 + 0x3008, 2^64 - 0x8000 + 0xA000, and 2^40 + 8 with negative immediates (2^40 - 8: the top cell, 2^40 - 65528)."""
+    code = _pattern() + [A(5, 0, 0x4000), A(9, 0, 0x80), E(O.SB, rs1=5, rs2=9, imm=0), E(O.LB, 6, 5, imm=0)]      # r6 = 0xFFFF_FFFF_FFFF_FF80 (Q1)
+    code += _widths_at(6, 0x2080)
+    for imm in (0x3008, 0xA000, -16, -65536):
+        code += [A(10, 0, 1), EC] + _widths_at(10, imm)                               # READ: r10 = the next input, raw
+    return _p(code + [EB]), [(1 << 64) - 8, (1 << 64) - 0x8000, (1 << 40) + 8, (1 << 40) + 8], {}
+
+
+def edge_aliases():
+    """Two (three) distinct cells whose addresses differ by a multiple of 8 p — the same value as ONE field element — written and read back alternately."""
+    code = _pattern() + li40(5, 0x20000) + li40(6, 0x20000 + P8) + li40(7, 0x20000 + 68 * P8)
+    for r in range(3):
+        code += [A(9, 0, 0x111 * (r + 1)), E(O.SD, rs1=5, rs2=9, imm=0), A(9, 0, 0x222 * (r + 1)), E(O.SD, rs1=6, rs2=9, imm=0),
+                 E(O.LD, 2, 5, imm=0), E(O.LD, 3, 6, imm=0), A(9, 0, 0x333 * (r + 1)), E(O.SW, rs1=7, rs2=9, imm=4), E(O.LD, 4, 7, imm=0), E(O.LD, 2, 5, imm=0),
+                 E(O.SB, rs1=6, rs2=1, imm=r), E(O.LD, 3, 6, imm=0), E(O.LD, 4, 5, imm=0)]
+    return _p(code + [EB]), [], {}
+
+
+_BC_WORDS = 41                       # an odd number of code words: the boundary cell B = 0x1000 + 4 * 41 - 4 holds the last code word and the first data word
+BC = 0x1000 + 4 * _BC_WORDS - 4
+
+
+def _bc_program(stores):
+    """Code of _BC_WORDS words (an EBREAK, then padding that is never executed) + 8 data bytes; `stores` = [(address, opcode)] with r1 the stored value."""
+    code = _pattern()
+    for addr, op in stores:
+        code += li40(5, addr) + [E(op, rs1=5, rs2=1, imm=0), E(O.LD, 2, 5, imm=-(addr & 7))]
+    code += [EB]
+    assert len(code) <= _BC_WORDS
+    code += [A(7, 0, 2)] * (_BC_WORDS - len(code))
+    return _p(code, data=bytes(range(0x41, 0x49)))
+
+
+def edge_bc_alias_ok():
+    """Next to the boundary cell's aliases, what proves: a store into the HIGH half of B + 8 p, into the low half of B + 8 p + 8, a byte into B's data half."""
+    return _bc_program([(BC + P8 + 4, O.SW), (BC + P8 + 8, O.SW), (BC + P8 + 8 + 3, O.SB), (BC + 5, O.SB)]), [], {}
+
+
+def edge_bc_alias_low_1():
+    """A store into the low half of B + 8 p: the boundary-cell constraint sees delta = cell - B = 0 — no proof in format v12 (the prover refuses)."""
+    return _bc_program([(BC + P8, O.SW)]), [], {}
+
+
+def edge_bc_alias_low_68():
+    """The same at B + 68 * 8 p, the last alias below 2^40 (a byte store)."""
+    assert BC + 68 * P8 < (1 << 40) <= BC + 69 * P8
+    return _bc_program([(BC + 68 * P8 + 2, O.SB)]), [], {}
+
+
+def edge_at_2p40():
+    """An access at exactly 2^40 (the top cell's register + 8: the address add is a wrapping u64 add, not a 40-bit one): the VM runs it, no proof exists."""
+    return _p(_pattern() + li40(5, TOP) + [E(O.SD, rs1=5, rs2=1, imm=0), E(O.LD, 2, 5, imm=8), EB]), [], {}
+
+
+def edge_above_2p40():
+    """A store above 2^40 (2^40 - 8 + 65528) after accesses that have a proof: the VM runs it, no proof exists."""
+    return _p(_pattern() + li40(5, TOP) + [E(O.SD, rs1=5, rs2=1, imm=0), E(O.SB, rs1=5, rs2=1, imm=65528), E(O.LD, 2, 5, imm=0), EB]), [], {}
+
+
+MEM_EDGES = {f.__name__: f for f in (edge_limb_carries, edge_high_limbs, edge_wrap64, edge_aliases, edge_bc_alias_ok)}      # these have a mode-3 / mode-4 proof
+MEM_EDGES_NO_PROOF = {f.__name__: f for f in (edge_bc_alias_low_1, edge_bc_alias_low_68, edge_at_2p40, edge_above_2p40)}     # the VM runs them; no proof exists
+ALL.update(MEM_EDGES)
+ALL.update(MEM_EDGES_NO_PROOF)
+
+
+# ---- hash-call edges of proof mode 4 (tests/test_memory_edges.py) -----------------------------------------------------------------------------------------------
+HASH_MAX_LEN = 1 << 20               # a mode-4 proof states hash calls of up to 1 MiB of input
+
+
+def _call(num, in_ptr, length, out_ptr):
+    """r11 = in, r12 = len, r13 = out (any 40-bit value), r10 = the syscall; ECALL."""
+    return li40(11, in_ptr) + li40(12, length) + li40(13, out_ptr) + [A(10, 0, num), EC]
+
+
+def hash_edge_calls():
+    """Keccak-256 and BLAKE3 digests written at out = 1, 3, 5 (mod 8) — 5 cells instead of 4, byte writes — SHA-256 at out = 4 (mod 8), zero-length inputs, inputs that overlap
+    their own output.  The hashed messages are the reference's KAT messages ("" and "hello" at 0x2000)."""
+    code = [A(5, 0, 0x2000)] + _store_bytes(5, b"hello")
+    for num, ln, out in ((5, 5, 0x3001), (5, 0, 0x3043), (5, 5, 0x3085), (6, 0, 0x3101), (6, 0, 0x3143), (6, 5, 0x3185), (3, 5, 0x3204), (3, 0, 0x324C)):
+        code += [A(11, 5, 0), A(12, 0, ln), A(13, 0, out), A(10, 0, num), EC]
+    code += [A(11, 0, 0x3300), A(12, 0, 40), A(13, 0, 0x3311), A(10, 0, 5), EC]     # the output inside the input: the message is read before the digest is written
+    code += [A(11, 0, 0x3404), A(12, 0, 64), A(13, 0, 0x3404), A(10, 0, 3), EC]     # the same first byte
+    code += [A(11, 0, 0x3001), A(12, 0, 75), A(13, 0, 0x3003), A(10, 0, 6), EC]     # re-hash the digests above, the output over them
+    return _p(code + [EB]), [], {}
+
+
+def hash_edge_top():
+    """An input that ends exactly at 2^40 and an output at 2^40 - 32 (the top cell holds its last 8 bytes)."""
+    code = li40(5, (1 << 40) - 40) + _store_bytes(5, bytes(range(0xC0, 0xC8)))
+    code += _call(5, (1 << 40) - 37, 37, (1 << 40) - 32) + _call(3, (1 << 40) - 32, 32, (1 << 40) - 64) + _call(6, (1 << 40) - 64, 64, (1 << 40) - 33)
+    return _p(code + [EB]), [], {}
+
+
+def hash_edge_boundary():
+    """A digest written over the boundary cell's data half (out = B + 4) and one that starts inside it (out = B + 6); the first message is read from B itself (the last code
+    word and the first data word) and the data word behind it."""
+    code = _call(6, BC, 12, BC + 4) + _call(5, BC + 4, 32, BC + 6) + [EB]
+    assert len(code) <= _BC_WORDS
+    code += [A(7, 0, 2)] * (_BC_WORDS - len(code))
+    return _p(code, data=bytes(range(0x41, 0x49))), [], {}
+
+
+def hash_edge_max_len():
+    """A SHA-256 call over exactly MAX_LEN = 1 MiB (memory that is zero but for one byte)."""
+    code = li40(5, 0x100000 + 12345) + [A(9, 0, 0xAB), E(O.SB, rs1=5, rs2=9, imm=0)] + _call(3, 0x100000, HASH_MAX_LEN, 0x300000)
+    return _p(code + [EB]), [], {}
+
+
+def hash_edge_len_over():
+    """MAX_LEN + 1 bytes of input: the VM hashes them, a mode-4 proof cannot state the call."""
+    return _p(_call(5, 0x100000, HASH_MAX_LEN + 1, 0x300000) + [EB]), [], {}
+
+
+def hash_edge_out_over_2p40():
+    """A digest whose last 16 bytes land above 2^40 (byte writes: the VM runs it)."""
+    return _p(_call(6, 0x2000, 8, (1 << 40) - 16) + [EB]), [], {}
+
+
+def hash_edge_in_over_code():
+    """A message read from the code segment (the VM reads it; the AIR states no code cell)."""
+    return _p(_call(5, 0x1000, 16, 0x3000) + [EB]), [], {}
+
+
+def hash_edge_out_over_code():
+    """A digest written over the first eight code words, already executed (strict protection is off, vm.rs:175)."""
+    return _p([A(0, 0, 0)] * 8 + _call(6, 0x2000, 8, 0x1000) + [EB]), [], {}
+
+
+def hash_misaligned_sha_shape():
+    """err_misaligned_sha_out with its SHA-256 output pointer moved to 0x3000: the run the VM completes, whose rows a forger starts from."""
+    return _p([A(11, 0, 0x2000), A(12, 0, 0), A(13, 0, 0x3000), A(10, 0, 3), EC, EB]), [], {}
+
+
+HASH_EDGES = {f.__name__: f for f in (hash_edge_calls, hash_edge_top, hash_edge_boundary, hash_edge_max_len)}                      # these have a mode-4 proof
+HASH_EDGES_NO_PROOF = {f.__name__: f for f in (hash_edge_len_over, hash_edge_out_over_2p40, hash_edge_in_over_code, hash_edge_out_over_code)}

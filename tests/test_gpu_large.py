@@ -547,3 +547,31 @@ def test_mode3_proof_equals_the_oracles_on_the_memory_ring(k):
     assert hashlib.sha256(proof.tobytes()).hexdigest() == g["sha256"]
     assert rt.verify(proof, pub) == 0
     ctx.close(); log.close()
+
+
+@pytest.mark.parametrize("name,k", [("sha_chain", 18), ("sha_chain", 20), ("wide_loop", 20), ("signed_division_loop", 20)])
+def test_mode4_proof_equals_the_oracles_at_size(name, k):
+    """MODE 4 (format v12) where the GPU prover runs many workgroups of main_trace_kernel<4>, quotient_kernel<4>, wide_tape_fix_kernel and the lookup-aux columns: the complete
+    proof of configs[4]'s SHA-256 chain (one hash-tape record per 6 rows; proven from the host witness, which carries the tape), of the endless wide loop (MULH DIVU REMU DIV REM
+    on 40-bit operands: the chunk relation) and of the endless signed-division loop (raw 64-bit operands: the wide tape) halted at 2^k cycles equals the proof the CPU oracle
+    computed for it (tests/golden/config_proofs.json: mode4_proofs, each program encoded by the generator's own encoder)."""
+    import hashlib
+    import json
+    import os
+    from zkir_amd import pipeline as pl, stark
+    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "config_proofs.json")))
+    g = gold["mode4_proofs"][name][str(k)]
+    blob = {"sha_chain": spec.sha256_chain_program, "wide_loop": spec.wide_loop_program, "signed_division_loop": spec.signed_division_loop_program}[name]().to_bytes()
+    assert blob.hex() == g["program_blob_hex"]
+    log = rt.interpret(blob, [], rt.VMConfig(max_cycles=1 << k, enable_execution_trace=True))
+    ddl = pl.upload(log); tr = pl.DeviceTrace(ddl); pl.trace_fill(pl.trace_fill_args(ddl, tr))
+    ctx = stark.StarkContext(k)
+    pub = rt.public_inputs(log, blob, [], wide_mode=True, mem_witness="device")
+    proof = np.ascontiguousarray(stark.prove(ctx, tr, pub), dtype="<u4")
+    assert proof[1] == 12 and proof[9] == 4 and len(proof) == g["words"]
+    pos = [int(i * (len(proof) - 1) // (len(g["samples"]) - 1)) for i in range(len(g["samples"]))]
+    bad = [p for p, w in zip(pos, g["samples"]) if int(proof[p]) != w]
+    assert not bad, f"mode-4 proof differs from the oracle's at sampled words {bad[:8]} (of {len(proof)})"
+    assert hashlib.sha256(proof.tobytes()).hexdigest() == g["sha256"]
+    assert rt.verify(proof, pub) == 0
+    ctx.close(); log.close()

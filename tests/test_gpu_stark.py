@@ -888,3 +888,141 @@ def test_mode3_wrong_execution_is_rejected_on_the_gpu_path():
         assert rt.verify(bad, pub2) != 0 and so.verify(bad) != 0, hex(op)
         tr2.registers[rd, k + 1:hi + 1] = saved
     ctx2.close(); log2.close()
+
+
+# ---- modes 3 / 4 at the address and hash-call edges (tests/test_memory_edges.py: the same programs against a Python model and the oracle on the CPU) -----------------------
+_EDGE_CASES = [(n, m) for n in sorted(programs.MEM_EDGES) for m in (3, 4) if not (n == "edge_bc_alias_ok" and m == 3)] + [(n, 4) for n in sorted(programs.HASH_EDGES)]
+
+
+def _edge_main_trace(which, mode):
+    """The device main trace of an edge run (main_trace_kernel<3> / <4> + wide_tape_fix_kernel, host witness) and the oracle's, both as committed columns."""
+    import ctypes as C
+    import torch
+    blob, ins, ores, log, tr, opub, pub = _mode3_case(which, "host", wide=mode == 4)
+    nr = len(ores.rows)
+    N = 1 << so.padded_log_n(nr); wm = so.committed_width(mode)
+    out = torch.zeros((wm // 8, N, 8), dtype=torch.int32, device="cuda")
+    scratch = torch.zeros(2 * N + 2 * (N // 1024 + 2) + 64, dtype=torch.int32, device="cuda")
+    tape = torch.tensor([int(x) - (1 << 64) if int(x) >> 63 else int(x) for x in ins] if len(ins) else [0], dtype=torch.int64, device="cuda")
+
+    class IoArgs(C.Structure):
+        _fields_ = [("inputs", C.c_void_p), ("n_inputs", C.c_uint64), ("writes_before", C.c_uint64), ("reads_before", C.c_uint64)]
+    io = IoArgs(tape.data_ptr(), len(ins), 0, 0)
+    mo = torch.from_numpy(np.ctypeslib.as_array(C.cast(pub.mem_old, C.POINTER(C.c_uint64)), (nr,)).astype(np.int64)).cuda()
+    mt = torch.from_numpy(np.ctypeslib.as_array(C.cast(pub.mem_told, C.POINTER(C.c_uint32)), (nr,)).astype(np.int32)).cuda()
+    L = rt.lib()
+    if mode == 4:
+        L.zkir_main_trace_wide_launch.restype = C.c_int
+        L.zkir_main_trace_wide_launch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = L.zkir_main_trace_wide_launch(C.byref(tr.c), nr, C.byref(io), mo.data_ptr(), mt.data_ptr(), int.from_bytes(blob[16:20], "little"), scratch.data_ptr(), out.data_ptr(), None)
+    else:
+        L.zkir_main_trace_mem_launch.restype = C.c_int
+        L.zkir_main_trace_mem_launch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = L.zkir_main_trace_mem_launch(C.byref(tr.c), nr, C.byref(io), mo.data_ptr(), mt.data_ptr(), scratch.data_ptr(), out.data_ptr(), None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().view(np.uint32).transpose(0, 2, 1).reshape(wm, N)
+    want = so.to_committed(so.main_trace(ores.rows, opub), mode)
+    log.close()
+    return got, want
+
+
+@pytest.mark.parametrize("which,mode", [c for c in _EDGE_CASES if c[0] != "hash_edge_max_len"])
+def test_edge_device_main_trace_equals_the_oracles(which, mode):
+    """Every committed column of every row at the address edges — limb-0 carries and borrows (c0, c1, C_CM2), limb 1 at 0xFFFFF / 0x80000 / 0x55555, the top cell, wrapped
+    64-bit bases, cells 8 p apart, the boundary cell's neighbours and odd hash-output pointers: the failure names the column and the first row."""
+    got, want = _edge_main_trace(which, mode)
+    for k in range(len(want)):
+        assert np.array_equal(got[k], want[k]), f"committed column {k}: first difference at row {int(np.nonzero(got[k] != want[k])[0][0])}"
+
+
+@pytest.mark.parametrize("which", sorted(programs.MEM_EDGES))
+def test_edge_memory_witness_device_equals_host_replay(which):
+    """memcheck.hip (its sort key packs (ea >> 3) << 26: the top cell 2^40 - 8 is its largest key; cells 8 p apart must stay apart) against the host's replay: old bytes and old
+    time of every row, the touched cells with their final bytes and times."""
+    import ctypes as C
+    import torch
+    from zkir_amd import pipeline as pl
+    blob, ins, cfg = programs.ALL[which]()
+    log = rt.interpret(blob, ins, rt.VMConfig(enable_execution_trace=True))
+    n = log.n_rows
+    ddl = pl.upload(log); tr = pl.DeviceTrace(ddl); pl.trace_fill(pl.trace_fill_args(ddl, tr)); torch.cuda.synchronize()
+    hw = rt.MemcheckWitness(log, blob)
+    pub = rt.PublicInputsC(); pub.with_memory(hw)
+    nc = hw.n_cells
+    host = [np.ctypeslib.as_array(C.cast(p, C.POINTER(t)), (m,)).copy() for p, t, m in
+            ((pub.mem_old, C.c_uint64, n), (pub.mem_told, C.c_uint32, n), (pub.cell_addr, C.c_uint64, nc), (pub.cell_bytes, C.c_uint64, nc), (pub.cell_time, C.c_uint32, nc))]
+    d_old, d_told = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    d_ca, d_cb, d_ct, dn = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint32), C.c_uint64(0)
+    L = rt.lib()
+    L.zkir_memcheck_witness_device.restype = C.c_int
+    L.zkir_memcheck_witness_device.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_void_p]
+    assert L.zkir_memcheck_witness_device(C.byref(tr.c), n, blob, len(blob), d_old.ctypes.data, d_told.ctypes.data, d_ca.ctypes.data, d_cb.ctypes.data, d_ct.ctypes.data, n, C.byref(dn), None) == 0
+    assert dn.value == nc and nc >= 3
+    for got, want, name in zip((d_old, d_told, d_ca[:nc], d_cb[:nc], d_ct[:nc]), host, ("old bytes", "old time", "cell address", "cell bytes", "cell time")):
+        assert np.array_equal(got, want), f"{name}: first difference at {int(np.nonzero(got != want)[0][0])}"
+    log.close()
+
+
+@pytest.mark.parametrize("witness", ["device", "host"])
+@pytest.mark.parametrize("which,mode", _EDGE_CASES)
+def test_edge_proof_bytes_match_oracle_and_verify(which, mode, witness):
+    """The whole proof at the edges, from either memory witness: equal to the oracle's word for word, accepted by both verifiers, tampered copies rejected alike."""
+    from zkir_amd import stark
+    blob, ins, ores, log, tr, opub, pub = _mode3_case(which, witness, wide=mode == 4)
+    ctx = stark.StarkContext(stark.padded_log_n(len(ores.rows)))
+    proof = stark.prove(ctx, tr, pub)
+    want = so.prove(ores.rows, opub)
+    assert proof[9] == mode and len(proof) == len(want)
+    if not np.array_equal(proof, want):
+        bad = np.nonzero(proof != want)[0]
+        raise AssertionError(f"mode-{mode} proof differs at word {bad[0]} of {len(want)} ({len(bad)} words differ)")
+    assert so.verify(proof, opub) == 0 and rt.verify(proof, pub) == 0 and rt.verify(proof) == 0
+    for pos in (8, 30, 160, len(proof) // 2, len(proof) - 1):
+        t = proof.copy()
+        t[pos] = (int(t[pos]) + 1) % P
+        assert so.verify(t) != 0 and rt.verify(t) == so.verify(t), pos
+    ctx.close(); log.close()
+
+
+def _refused(which, mode, witness):
+    from zkir_amd import pipeline as pl, stark
+    blob, ins, cfg = getattr(programs, which)()
+    log = rt.interpret(blob, ins, rt.VMConfig(enable_execution_trace=True))
+    ddl = pl.upload(log); tr = pl.DeviceTrace(ddl); pl.trace_fill(pl.trace_fill_args(ddl, tr))
+    ctx = stark.StarkContext(stark.padded_log_n(log.n_rows))
+    try:
+        with pytest.raises(rt.RuntimeError) as e:
+            pub = rt.public_inputs(log, blob, ins, mem_mode=mode == 3, wide_mode=mode == 4, mem_witness=witness)
+            stark.prove(ctx, tr, pub)
+    finally:
+        ctx.close(); log.close()
+    assert e.value.code == rt.ERR_ARGUMENT
+    return e.value.message
+
+
+@pytest.mark.parametrize("witness", ["device", "host"])
+@pytest.mark.parametrize("mode", [3, 4])
+@pytest.mark.parametrize("which", ["edge_at_2p40", "edge_above_2p40"])
+def test_accesses_at_or_above_2p40_are_refused(which, mode, witness):
+    """No proof states an address of 2^40 or more: the prover refuses — memcheck.hip on the device path, the host's replay on the other — naming why."""
+    msg = _refused(which, mode, witness)
+    assert ("accesses an address of 2^40 or more" in msg) if witness == "device" else ("is not below 2^40" in msg), msg
+
+
+@pytest.mark.parametrize("witness", ["device", "host"])
+@pytest.mark.parametrize("which", ["edge_bc_alias_low_1", "edge_bc_alias_low_68"])
+def test_a_boundary_cell_alias_store_is_refused(which, witness):
+    """a store into the low half of B + 8 p j has delta = 0 in I_BC, so its row violates I_BC + 1 — the oracle's proof of it is rejected (10,
+    tests/test_memory_edges.py).  The GPU prover refuses the run (lookup_index_kernel reports the row) instead of emitting a proof that does not verify."""
+    msg = _refused(which, 4, witness)
+    assert "has no proof in this AIR" in msg and "B + 8 p j" in msg, msg
+
+
+@pytest.mark.parametrize("which,needle", [("hash_edge_len_over", "is outside what a proof states"), ("hash_edge_out_over_2p40", "is outside what a proof states"),
+                                          ("hash_edge_in_over_code", "overlaps the code segment"), ("hash_edge_out_over_code", "overlaps the code segment")])
+def test_hash_calls_without_a_proof_are_refused(which, needle):
+    """Hash calls a mode-4 proof cannot state (more than 1 MiB of input, an output past 2^40, a buffer over the code): the prover refuses with a message; both verifiers reject
+    the oracle's proof of the run with the same code (tests/test_memory_edges.py)."""
+    msg = _refused(which, 4, "device")
+    assert needle in msg, msg

@@ -18,8 +18,9 @@ constexpr uint64_t MAX_LEN = 1u << 20;                           // a proof stat
 struct Cell { uint64_t addr, bytes; uint32_t t; };
 struct Call { uint64_t cycle, in_ptr, len, out_ptr; uint32_t kind; std::vector<Cell> cells; };
 
+// (SHA-256 writes its digest with write_u32, crypto.rs:251-254: an output pointer that is not a multiple of 4 stops the reference with MisalignedAccess — no run carries such a call)
 inline bool in_range(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint32_t kind) {
-  return (kind == 3 || kind == 5 || kind == 6) && len <= MAX_LEN && in_ptr < (1ull << 40) && in_ptr + len <= (1ull << 40) && out_ptr < (1ull << 40) && out_ptr + 32 <= (1ull << 40);
+  return (kind == 3 || kind == 5 || kind == 6) && (kind != 3 || (out_ptr & 3) == 0) && len <= MAX_LEN && in_ptr < (1ull << 40) && in_ptr + len <= (1ull << 40) && out_ptr < (1ull << 40) && out_ptr + 32 <= (1ull << 40);
 }
 inline void cells_of(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, std::vector<uint64_t>& addrs) {
   addrs.clear();

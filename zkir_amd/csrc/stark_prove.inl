@@ -221,6 +221,12 @@ __global__ __launch_bounds__(NT) void lookup_index_kernel(const uint32_t* __rest
       mem_row = (kld | kst) != 0;
       uint32_t win = 15;
       for (int v = 0; v < air::N_WIN; v++) if (M[b8(p_e + (uint32_t)v, i, N)]) win = (uint32_t)v;
+      if (deferred == 4 && kst && win < 15 && air::is_low_window((int)win)) {
+        // (mode 4) a store into the low half of a cell B + 8 p j, j != 0 (every ~15 GiB): delta = cell - B is ONE field element (I_BC), 0 there — nb = 0 and I_BC + 1 fails.
+        // Such a row has no proof in format v12: refused here rather than proven into a proof that does not verify.  (r[0..3]: the address's 10-bit chunks)
+        const uint64_t cell = ((uint64_t)r[0] | ((uint64_t)r[1] << 10) | ((uint64_t)r[2] << 20) | ((uint64_t)r[3] << 30)) & ~7ull, Bc = air::boundary_cell(4 * (uint64_t)n_code);
+        if (cell != Bc && (cell > Bc ? cell - Bc : Bc - cell) % bb::P == 0) ok = false;
+      }
       const uint32_t p_klg = (uint32_t)air::phys_col(air::C_KLG, 3), p_lb = (uint32_t)air::phys_col(air::C_LB, 3), p_lr = (uint32_t)air::phys_col(air::C_LR, 3);
       const uint32_t klg = M[b8(p_klg, i, N)];
       lg_which = klg ? (M[b8(p_klg + 1, i, N)] ? 0 : M[b8(p_klg + 2, i, N)] ? 1 : 2) : -1;
@@ -1274,9 +1280,10 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   HIP_OK(sync_d2h());
   n_io = io_counts[0];
   if (bad_row != ~0ull) {
-    char m[448];
+    char m[640];
     snprintf(m, sizeof m, "zkir_prove: row %llu of the trace has no proof in this AIR: its (pc, instruction word) is not in the program's code table (self-modified code, "
-                          "a pc outside the code segment), a written limb is out of range, (mode 3) its memory witness is not the row's, or (mode 4) a wide-arithmetic chunk is out of range", bad_row);
+                          "a pc outside the code segment), a written limb is out of range, (mode 3) its memory witness is not the row's, or (mode 4) a wide-arithmetic chunk is out of range, or it stores into the low half "
+                          "of a cell B + 8 p j (j != 0; B the boundary cell, p the field's modulus), which the boundary-cell constraint cannot tell from B", bad_row);
     zkir::set_last_error({ZKIR_ERR_ARGUMENT, m});
     return ZKIR_ERR_ARGUMENT;
   }

@@ -273,7 +273,7 @@ int zkir_memcheck_witness_of_mode(const zkir_delta_log* log, const uint8_t* blob
       if (mode != 4) { delete w; return refuse("the run executes a hash syscall (row " + std::to_string(i) + "): its memory effect is not stated by the AIR"); }
       // (mode 4) a hash call: its record for the tape, its effect on the replayed memory (the message is read out of the OLD bytes; every touched cell gets the call's time)
       hashcall::Call hc{i, reg[11], reg[12], reg[13], (uint32_t)reg[10], {}};
-      if (!hashcall::in_range(hc.in_ptr, hc.len, hc.out_ptr, hc.kind)) { delete w; return refuse("the hash syscall at row " + std::to_string(i) + " is outside what a proof states (kind 3 / 5 / 6, at most 1 MiB of input, buffers below 2^40)"); }
+      if (!hashcall::in_range(hc.in_ptr, hc.len, hc.out_ptr, hc.kind)) { delete w; return refuse("the hash syscall at row " + std::to_string(i) + " is outside what a proof states (kind 3 / 5 / 6, at most 1 MiB of input, buffers below 2^40, a SHA-256 output at a multiple of 4)"); }
       std::vector<uint64_t> addrs, nbv;
       hashcall::cells_of(hc.in_ptr, hc.len, hc.out_ptr, addrs);
       for (const uint64_t a : addrs) { const Slot& c = find(a); hc.cells.push_back(hashcall::Cell{a, c.bytes, c.t}); }
