@@ -64,6 +64,24 @@ def build_variant(tag: str, defines, csrc: str = CSRC) -> str:
     return out
 
 
+# Test probe (tests/hip/arith_probe.hip): the bb:: primitives and Poseidon2 formulations of babybear.h / poseidon2.h exported elementwise, host and
+# device, for the arithmetic edge tests.  Built with stark.hip's flags so that its device code is what the hash kernels inline; not part of the library
+# (and not of sources_sha16()).
+PROBE_SRC = os.path.join(HERE, "..", "tests", "hip", "arith_probe.hip")
+PROBE_OUT = os.path.join(HERE, "..", "tests", "hip", "libzkir_arith_probe.so")
+
+
+def build_probe(force: bool = False, verbose: bool = False) -> str:
+    src, out = os.path.normpath(PROBE_SRC), os.path.normpath(PROBE_OUT)
+    deps = [os.path.join(CSRC, "babybear.h"), os.path.join(CSRC, "poseidon2.h")]
+    if force or _newer(src, out, deps):
+        cmd = [HIPCC, f"--offload-arch={ARCH}", *COMMON, *EXTRA["stark.hip"], "-shared", src, "-o", out]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return out
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     deps = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
@@ -90,6 +108,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
+    build_probe(force, verbose)
     return OUT
 
 
