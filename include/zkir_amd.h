@@ -116,6 +116,15 @@ typedef struct zkir_sha_block {
   uint64_t timestamp;
 } zkir_sha_block;     /* 72 bytes */
 
+/* What an executed SHA-256 / Keccak-256 / BLAKE3 syscall WROTE (only with enable_execution_trace): the row (relative to the log, like zkir_mem_event.row) and the 32 bytes as
+ * they lie in memory at out .. out + 32 after the call (SHA-256: the eight big-endian-parsed words stored little-endian, crypto.rs:251-254; the other two: the digest bytes in
+ * order).  The device memory witness of mode 4 (memcheck.hip) takes the written bytes from here: a digest depends on what earlier calls wrote, and no trace column holds it. */
+typedef struct zkir_hash_out {
+  uint32_t row;
+  uint32_t reserved;
+  uint8_t bytes[32];
+} zkir_hash_out;      /* 40 bytes */
+
 typedef struct zkir_delta_log zkir_delta_log;   /* opaque, host memory */
 
 /* Run the program on the host interpreter (bit-exact to VM::run, vm.rs:208-358) and record the delta
@@ -177,6 +186,8 @@ size_t zkir_delta_log_n_norm_events(const zkir_delta_log*);
 const zkir_norm_event* zkir_delta_log_norm_events(const zkir_delta_log*);
 size_t zkir_delta_log_n_sha_blocks(const zkir_delta_log*);
 const zkir_sha_block* zkir_delta_log_sha_blocks(const zkir_delta_log*);
+size_t zkir_delta_log_n_hash_outs(const zkir_delta_log*);     /* one per executed hash syscall of the log's rows, in row order */
+const zkir_hash_out* zkir_delta_log_hash_outs(const zkir_delta_log*);
 
 /* ---- device stage: kernels on caller-owned device memory ------------------------------------- */
 
@@ -378,11 +389,18 @@ typedef struct zkir_public_inputs {
    * 128-bit products — through the WIDE TAPE: one record (cycle, rs1, rs2, opcode) per such row, gathered by zkir_prove itself, the verifier computes the result), the code segment's boundary cell, and
    * HASH SYSCALLS as a tape: the proof carries one record per SHA-256 / Keccak-256 / BLAKE3 call (cycle, pointers, length, kind, and per touched 8-byte cell its bytes before
    * the call and the time of its previous access) and the verifier computes every digest itself.  PROVER side: hash_section = those records in the proof's own word layout
-   * (csrc/hashcall.h), BORROWED from a zkir_memcheck_witness made with zkir_memcheck_witness_of_mode(.., 4, ..) (zkir_public_inputs_set_memory sets it).  A run that makes
-   * hash calls is proven from that host witness: the device witness (mem_old == NULL) covers loads and stores only, and zkir_prove refuses such a run without the section. */
+   * (csrc/hashcall.h), BORROWED from a zkir_memcheck_witness made with zkir_memcheck_witness_of_mode(.., 4, ..) (zkir_public_inputs_set_memory sets it).  With mem_old == NULL (what
+   * zkir_public_inputs_of leaves) zkir_prove builds the memory witness AND this tape on the device (memcheck.hip): every old byte comes from the program image and earlier
+   * writes; what a hash call WROTE comes from hash_outs below (the interpreter's record, one per executed call). */
   const uint32_t* hash_section;
   uint64_t hash_section_words;
+  /* (ABI 7) PROVER side, BORROWED from the run's delta log (zkir_public_inputs_of sets them; ignored in a verifier's `expect`): the written digests of the run's hash
+   * syscalls in row order.  Needed only by the device witness of a mode-4 run that makes hash calls; their count must be the trace's number of hash rows. */
+  const zkir_hash_out* hash_outs;
+  uint64_t n_hash_outs;
 } zkir_public_inputs;
+/* sizeof(zkir_public_inputs) of the library (a binding checks its own struct against it) */
+uint64_t zkir_public_inputs_size(void);
 /* (mode 3) The memory witness of a WHOLE run (host, sequential like the interpreter: memory is a chain — what a load returns depends on every earlier store): the
  * log's rows are replayed with their register state (rebuilt from the register events), every load / store looks up its aligned 8-byte cell — the program image at first
  * (code at 0x1000, data behind it: vm.rs:153-170), zero elsewhere — and records the cell's bytes and the time of its previous access.  Refused (ZKIR_ERR_ARGUMENT): a shard /
@@ -400,6 +418,16 @@ uint64_t zkir_memcheck_witness_n_accesses(const zkir_memcheck_witness* w);
  * a whole run, the outputs are HOST arrays (mem_old / mem_told: n_real entries, zero where the row is no load / store; the cell arrays: capacity `cap`, *n_cells = the count). */
 int zkir_memcheck_witness_device(const zkir_trace_columns* trace, uint64_t n_real, const uint8_t* program_blob, size_t blob_len, uint64_t* mem_old, uint32_t* mem_told,
                                  uint64_t* cell_addr, uint64_t* cell_bytes, uint32_t* cell_time, uint64_t cap, uint64_t* n_cells, void* hip_stream);
+/* (mode 4) The device witness of a run WITH hash syscalls, as a call of its own (what zkir_prove runs in mode 4 when the public inputs bring no witness and hash_outs is not
+ * empty): mode must be 4 (3 = zkir_memcheck_witness_device, which refuses hash calls: ZKIR_ERR_ARGUMENT here).  hash_outs: the log's records (host).  The outputs of
+ * zkir_memcheck_witness_device (hash rows' own mem_old / mem_told are 0; the cells include those only hash calls touched) + the proof's hash section (csrc/hashcall.h) in
+ * hash_words (host, capacity hash_cap_words; *n_hash_words = its length, ZKIR_ERR_ARGUMENT if it exceeds the capacity). */
+int zkir_memcheck_witness_device_mode(const zkir_trace_columns* trace, uint64_t n_real, const uint8_t* program_blob, size_t blob_len, uint32_t mode, const zkir_hash_out* hash_outs,
+                                      uint64_t n_hash_outs, uint64_t* mem_old, uint32_t* mem_told, uint64_t* cell_addr, uint64_t* cell_bytes, uint32_t* cell_time, uint64_t cap,
+                                      uint64_t* n_cells, uint32_t* hash_words, uint64_t hash_cap_words, uint64_t* n_hash_words, void* hip_stream);
+/* Host test entry of the closed forms the device witness uses (csrc/hashcall.h): the number of distinct 8-byte cells a hash call (in, len, out) touches, and in *rank the
+ * position of `cell` among them in ascending order (~0 if the call does not touch it; rank may be NULL).  Returns ~0 when hashcall::in_range(in, len, out, kind) is false. */
+uint64_t zkir_hash_call_cells_host(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint32_t kind, uint64_t cell, uint64_t* rank);
 /* points pub's mode-3 fields at the witness (which must outlive the proving call) and sets pub->deferred = 3 */
 void zkir_public_inputs_set_memory(zkir_public_inputs* pub, const zkir_memcheck_witness* w);
 /* Poseidon2 sponge digest of a byte string (host): [len as four 16-bit pieces] ++ [LE 16-bit halfwords] */
@@ -558,7 +586,7 @@ const char* zkir_last_error(void);
  *   4: zkir_prove's stage_ms is NINE floats (round 4 added the lookup stage: a caller built against eight overflows by 4 bytes)
  *   5: zkir_public_inputs.reserved became fri_params (same offset; zero = the old behaviour); zkir_verify* compare the proof's FRI parameters with `expect`'s
  * A binding checks zkir_abi_version() == ZKIR_AMD_ABI_VERSION when it loads the library. */
-#define ZKIR_AMD_ABI_VERSION 6u   /* 6 (round 6): zkir_public_inputs grew (hash_section), mode 4 entry points, pinned log blocks */
+#define ZKIR_AMD_ABI_VERSION 7u   /* 6 (round 6): zkir_public_inputs grew (hash_section), mode 4 entry points, pinned log blocks; 7: zkir_public_inputs grew at its end (hash_outs, n_hash_outs) */
 uint32_t zkir_abi_version(void);
 const char* zkir_version(void);
 

@@ -65,6 +65,10 @@ pub struct ZkirPublicInputs {
     // mode 4 (round 6): the hash calls of the run as the proof's hash section — borrowed from a zkir_memcheck_witness made with zkir_memcheck_witness_of_mode(.., 4, ..)
     pub hash_section: *const u32,
     pub hash_section_words: u64,
+    // (ABI 7) what the run's hash syscalls wrote: 40-byte records (row u32, reserved u32, 32 bytes) borrowed from the run's delta log — zkir_public_inputs_of sets them;
+    // with no witness set, zkir_prove builds the mode-4 memory witness and the hash tape on the device from them
+    pub hash_outs: *const u8,
+    pub n_hash_outs: u64,
 }
 pub enum ZkirMemcheckWitness {}
 
@@ -107,7 +111,7 @@ extern "C" {
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct ZkirProverParams { pub mode: u32, pub num_queries: u32, pub pow_bits: u32 }
-pub const ZKIR_AMD_ABI_VERSION: u32 = 6;
+pub const ZKIR_AMD_ABI_VERSION: u32 = 7;
 
 /// include/zkir_amd.h return codes <-> RuntimeError (error.rs:7-37); the message text is the reference's own.
 fn map_error(code: c_int) -> RuntimeError {

@@ -119,6 +119,10 @@ int zkir_delta_log_shard(const zkir_delta_log* src, uint64_t row_begin, uint64_t
     }
     for (size_t m = 0; m < src->norm_events.size(); m++) if (src->norm_events[m].cycle >= row_begin && src->norm_events[m].cycle < row_end) d->norm_events.push(src->norm_events[m]);
     for (size_t m = 0; m < src->sha_blocks.size(); m++) if (src->sha_blocks[m].timestamp >= row_begin && src->sha_blocks[m].timestamp < row_end) d->sha_blocks.push(src->sha_blocks[m]);
+    for (size_t m = 0; m < src->hash_outs.size(); m++) {
+      zkir_hash_out ho = src->hash_outs[m];
+      if (ho.row >= rb && ho.row < re) { ho.row -= (uint32_t)rb; d->hash_outs.push(ho); }
+    }
   };
   d->pc.append(src->pc.data() + rb, d->n_rows);
   d->inst.append(src->inst.data() + rb, d->n_rows);
@@ -216,6 +220,8 @@ size_t zkir_delta_log_n_norm_events(const zkir_delta_log* l) { return l->norm_ev
 const zkir_norm_event* zkir_delta_log_norm_events(const zkir_delta_log* l) { return l->norm_events.data(); }
 size_t zkir_delta_log_n_sha_blocks(const zkir_delta_log* l) { return l->sha_blocks.size(); }
 const zkir_sha_block* zkir_delta_log_sha_blocks(const zkir_delta_log* l) { return l->sha_blocks.data(); }
+size_t zkir_delta_log_n_hash_outs(const zkir_delta_log* l) { return l->hash_outs.size(); }
+const zkir_hash_out* zkir_delta_log_hash_outs(const zkir_delta_log* l) { return l->hash_outs.data(); }
 
 // ---- drop-in layer ------------------------------------------------------------------------------
 static inline uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }

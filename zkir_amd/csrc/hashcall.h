@@ -1,5 +1,5 @@
 // hashcall.h — (AIR mode 4) the hash syscalls of a run as a TAPE: what the prover's host side (stark_prove.inl), the host witness (zkir_memcheck_witness_of_mode) and the
-// verifier (verify.cpp) share.  Host only.  Spec: oracle/stark_oracle.cpp "MODE 4 (b)"; reference semantics: zkir-runtime/src/syscall.rs:121-171, crypto.rs:223-395.
+// verifier (verify.cpp) share.  Host only, but for the closed forms below marked HC_HD, which the device witness (memcheck.hip) runs in its kernels.  Spec: oracle/stark_oracle.cpp "MODE 4 (b)"; reference semantics: zkir-runtime/src/syscall.rs:121-171, crypto.rs:223-395.
 //
 // A record = (cycle, input pointer, input length, output pointer, kind 3 / 5 / 6) + per aligned 8-byte cell the call touches — the cells under [in, in + len) and
 // [out, out + 32), ascending, each once — the cell's bytes BEFORE the call and the time of its previous access.  In a proof: [n] then per call [cycle] [in: two 20-bit limbs]
@@ -12,6 +12,12 @@
 
 #include "host.h"
 
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define HC_HD __host__ __device__
+#else
+#define HC_HD
+#endif
+
 namespace hashcall {
 
 constexpr uint64_t MAX_LEN = 1u << 20;                           // a proof states hash calls of up to 1 MiB of input
@@ -19,7 +25,7 @@ struct Cell { uint64_t addr, bytes; uint32_t t; };
 struct Call { uint64_t cycle, in_ptr, len, out_ptr; uint32_t kind; std::vector<Cell> cells; };
 
 // (SHA-256 writes its digest with write_u32, crypto.rs:251-254: an output pointer that is not a multiple of 4 stops the reference with MisalignedAccess — no run carries such a call)
-inline bool in_range(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint32_t kind) {
+HC_HD inline bool in_range(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint32_t kind) {
   return (kind == 3 || kind == 5 || kind == 6) && (kind != 3 || (out_ptr & 3) == 0) && len <= MAX_LEN && in_ptr < (1ull << 40) && in_ptr + len <= (1ull << 40) && out_ptr < (1ull << 40) && out_ptr + 32 <= (1ull << 40);
 }
 inline void cells_of(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, std::vector<uint64_t>& addrs) {
@@ -28,6 +34,27 @@ inline void cells_of(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, std::vecto
   for (uint64_t a = out_ptr & ~7ull; a < out_ptr + 32; a += 8) addrs.push_back(a);
   std::sort(addrs.begin(), addrs.end());
   addrs.erase(std::unique(addrs.begin(), addrs.end()), addrs.end());
+}
+// cells_of in closed form (for a call that is in_range): the cells are the integers of [in >> 3, (in + len - 1) >> 3] (none when len == 0) and of [out >> 3, (out + 31) >> 3] —
+// two intervals, ONE when they share a cell.  n_cells_of = how many; cell_at(r) = the r-th in ascending order (an address); rank_of(cell address) = its position, ~0 when the
+// call does not touch it.  The device witness gives every touched cell of a call a thread of its own with these (tests/test_hash_outs.py holds them against cells_of).
+struct Spans { uint64_t lo1, n1, lo2, n2; };                      // cell INDICES: [lo1, lo1 + n1) then [lo2, lo2 + n2), lo1 + n1 < lo2 or n2 == 0
+HC_HD inline Spans spans_of(uint64_t in_ptr, uint64_t len, uint64_t out_ptr) {
+  const uint64_t oa = out_ptr >> 3, ob = (out_ptr + 31) >> 3;
+  if (len == 0) return Spans{oa, ob - oa + 1, 0, 0};
+  const uint64_t ia = in_ptr >> 3, ib = (in_ptr + len - 1) >> 3;
+  if (ia <= ob && oa <= ib) { const uint64_t lo = ia < oa ? ia : oa, hi = ib > ob ? ib : ob; return Spans{lo, hi - lo + 1, 0, 0}; }
+  if (ia < oa) return Spans{ia, ib - ia + 1, oa, ob - oa + 1};
+  return Spans{oa, ob - oa + 1, ia, ib - ia + 1};
+}
+HC_HD inline uint64_t n_cells_of(uint64_t in_ptr, uint64_t len, uint64_t out_ptr) { const Spans s = spans_of(in_ptr, len, out_ptr); return s.n1 + s.n2; }
+HC_HD inline uint64_t cell_at(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint64_t r) { const Spans s = spans_of(in_ptr, len, out_ptr); return (r < s.n1 ? s.lo1 + r : s.lo2 + (r - s.n1)) << 3; }
+HC_HD inline uint64_t rank_of(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint64_t cell) {
+  const Spans s = spans_of(in_ptr, len, out_ptr);
+  const uint64_t c = cell >> 3;
+  if ((cell & 7) == 0 && c >= s.lo1 && c - s.lo1 < s.n1) return c - s.lo1;
+  if ((cell & 7) == 0 && c >= s.lo2 && c - s.lo2 < s.n2) return s.n1 + (c - s.lo2);
+  return ~0ull;
 }
 // the 32 bytes the syscall leaves at out .. out + 32: SHA-256 writes its eight big-endian-parsed words with write_u32 (little-endian), crypto.rs:251-254; the other two the digest's bytes in order
 inline void output_bytes(uint32_t kind, const uint8_t* msg, size_t len, uint8_t out[32]) {

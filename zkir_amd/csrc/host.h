@@ -145,6 +145,7 @@ struct zkir_delta_log {
   std::vector<uint64_t> rc_cycles;   // cycle of the checkpoint that flushed witness k (vm.rs:316-344); row sharding cuts by it
   zkir::Buf<zkir_norm_event> norm_events;
   zkir::Buf<zkir_sha_block> sha_blocks;
+  zkir::Buf<zkir_hash_out> hash_outs;    // what every executed hash syscall wrote (row relative to this log): the device witness of mode 4 reads the digests from here
 };
 
 namespace zkir {
@@ -175,6 +176,21 @@ void set_last_error(const Status& st);
 size_t memcheck_scratch_bytes(uint64_t n_real, uint64_t image_len);
 int memcheck_device(const zkir_trace_columns* trace, uint64_t n_real, const uint8_t* blob, size_t blob_len, void* scratch, size_t scratch_bytes, uint64_t* mem_old, uint32_t* mem_told,
                     std::vector<uint64_t>& cell_addr, std::vector<uint64_t>& cell_bytes, std::vector<uint32_t>& cell_time, HostPin& pin, void* hip_stream);
+// (mode 4) the same for a run WITH hash syscalls (outs: the log's zkir_hash_out records, host): also builds the proof's hash section and, in the section's cell order, every
+// touched cell's bytes AFTER its call.  The counts are known only after a first pass over the rows, so the call makes its own device allocations: the scratch (freed before
+// it returns) and HashWitness's block (the tape stays on the device for the section's chunk digests).  h_tape / h_side: pinned host copies (from `pin`).
+struct HashWitness {
+  void* d_block = nullptr;               // device: [side: n_hcells u64][tape: n_words u32]
+  const uint32_t* d_tape = nullptr; const uint32_t* h_tape = nullptr; const uint64_t* h_side = nullptr;
+  uint64_t n_words = 0, n_hcells = 0, n_calls = 0;
+  HashWitness() = default;
+  HashWitness(const HashWitness&) = delete;
+  HashWitness& operator=(const HashWitness&) = delete;
+  ~HashWitness();
+};
+int memcheck_device_hash(const zkir_trace_columns* trace, uint64_t n_real, const uint8_t* blob, size_t blob_len, const zkir_hash_out* outs, uint64_t n_outs, uint64_t* mem_old,
+                         uint32_t* mem_told, std::vector<uint64_t>& cell_addr, std::vector<uint64_t>& cell_bytes, std::vector<uint32_t>& cell_time, HashWitness& hw, HostPin& pin,
+                         void* hip_stream);
 
 // ntt.hip — coset LDE of `width` columns (device pointers; tables owned by zkir_stark_ctx, all in Montgomery form)
 struct LdeTables {

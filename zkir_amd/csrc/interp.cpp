@@ -270,7 +270,7 @@ class Machine {
       tracing_ = true; skipping_ = false;
       if (!st.ok()) return st;
       // side logs of the skipped rows do not belong to the window
-      log_.rc_events.clear(); log_.rc_offsets.clear(); log_.rc_cycles.clear(); log_.norm_events.clear(); log_.sha_blocks.clear();
+      log_.rc_events.clear(); log_.rc_offsets.clear(); log_.rc_cycles.clear(); log_.norm_events.clear(); log_.sha_blocks.clear(); log_.hash_outs.clear();
       base_ = cycle_;                                                  // = win_begin_, or the halting cycle if the run ended before the window
       log_.cycle_base = base_;                                         // known to a streaming consumer before the first tile is published
       if (halted_) { finish_log(true); log_.rc_offsets.push_back(0); return {}; }
@@ -577,10 +577,12 @@ bool Machine::hash_syscall(int which) {
   if (il > (1ull << 32)) return fail({ZKIR_ERR_OTHER, "hash input length too large"});   // the reference would abort in Vec::with_capacity
   std::vector<uint8_t> in((size_t)il);
   for (uint64_t i = 0; i < il; i++) { uint8_t b; load<uint8_t>(ip + i, b); in[i] = b; }           // one width-1 Read per byte (crypto.rs:232-235)
+  zkir_hash_out rec{(uint32_t)(cycle_ - base_), 0, {0}};                                          // the 32 bytes as they lie at out .. out + 32 after the call
   if (which == 0) {
     uint32_t h[8];
     sha256(in.data(), in.size(), h);
     for (int i = 0; i < 8; i++) if (!store<uint32_t>(op + 4 * (uint64_t)i, h[i])) return false;  // crypto.rs:252-255
+    for (int i = 0; i < 8; i++) for (int k = 0; k < 4; k++) rec.bytes[4 * i + k] = (uint8_t)(h[i] >> (8 * k));
     wr_value(10, 0);
     wr_bound(14, BoundT{32, ZKIR_BOUND_CRYPTO_OUTPUT, 0});                                        // syscall.rs:135
     if (tracing_ && il < 56) {                                                                    // single-block message -> SHA chip input (crypto.rs:108-139)
@@ -597,7 +599,9 @@ bool Machine::hash_syscall(int which) {
     if (which == 1) keccak256(in.data(), in.size(), dgst); else blake3(in.data(), in.size(), dgst);
     for (int i = 0; i < 32; i++) store<uint8_t>(op + (uint64_t)i, dgst[i]);                       // crypto.rs:351-353, :390-392
     wr_value(10, 0);
+    memcpy(rec.bytes, dgst, 32);
   }
+  if (tracing_) log_.hash_outs.push(rec);
   return true;
 }
 

@@ -1156,10 +1156,27 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   const std::vector<int> ks = fri_schedule((int)log_n);
   const int n_layers = (int)ks.size();
 
+  zkir::HostPin& pin = c->pin;                                 // every host block of unbounded size crosses through pinned staging (host.h)
+  pin.reset();
+  // (mode 4) a run with hash syscalls and no witness from the caller: the memory witness AND the hash tape are built on the device (memcheck.hip), the written digests coming
+  // from the interpreter's records (pub->hash_outs).  It runs HERE, before the workspace is sized: how many cells the run touches and how long its tape is are known only
+  // after its count pass (a call may touch 131 078 cells), so it makes its own device allocations; mem_old / mem_told are copied into the workspace below.
+  const bool HASH_DEV = WIDE && !MEM_HOST && pub->hash_outs != nullptr && pub->n_hash_outs != 0;
+  std::vector<uint64_t> cell_addr_v, cell_bytes_v; std::vector<uint32_t> cell_time_v;     // (mode 3) the touched cells: the device witness's, or the caller's
+  zkir::HashWitness hw;
+  struct DevMem { void* p = nullptr; ~DevMem() { if (p) (void)hipFree(p); } } hw_rows;     // mem_old [n_real] | mem_told [n_real] of that witness
+  if (HASH_DEV) {
+    if (pub->writes_before || pub->reads_before) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: mode 3 proves a WHOLE run; a memory witness passed in the public inputs must be complete (zkir_memcheck_witness_of + zkir_public_inputs_set_memory)"}); return ZKIR_ERR_ARGUMENT; }
+    HIP_OK(hipMalloc(&hw_rows.p, (size_t)pub->n_real * 12 + 256));
+    const int wrc = zkir::memcheck_device_hash(trace, pub->n_real, blob, blob_len, pub->hash_outs, pub->n_hash_outs, (uint64_t*)hw_rows.p, (uint32_t*)((uint64_t*)hw_rows.p + pub->n_real),
+                                               cell_addr_v, cell_bytes_v, cell_time_v, hw, pin, s);
+    if (wrc) return wrc;
+    if (dbg_t) fprintf(stderr, "zkir_prove mode 4: device witness with %llu hash calls (%llu cells, %llu tape words) at %.2f ms\n", (unsigned long long)hw.n_calls, (unsigned long long)hw.n_hcells, (unsigned long long)hw.n_words, since(t_entry));
+  }
   // (mode 4) a run with hash calls can touch more cells than it has rows (a 5000-byte BLAKE3 input is 626 cells): the cell arrays and the section buffer are sized by the
-  // caller's witness when it brings one (the device witness sees loads and stores only: at most one cell per row)
-  const uint64_t CELL_CAP = std::max<uint64_t>(N, MEM_HOST ? pub->n_cells + 1 : 0);
-  const size_t SEC_WORDS = std::max<size_t>(8 * (size_t)CELL_CAP, WIDE ? (size_t)pub->hash_section_words + (size_t)pub->hash_section_words / 100 : 0) + 4096;   // (the memory section, then the hash section, each with its chunk digests behind it)
+  // witness — the caller's when it brings one, the device's of a run with hash calls (a device witness of loads and stores only touches at most one cell per row)
+  const uint64_t CELL_CAP = std::max<uint64_t>(N, MEM_HOST ? pub->n_cells + 1 : HASH_DEV ? cell_addr_v.size() + 1 : 0);
+  const size_t SEC_WORDS = std::max<size_t>(8 * (size_t)CELL_CAP, !WIDE ? 0 : HASH_DEV ? (size_t)hw.n_words / 64 + 128 : (size_t)pub->hash_section_words + (size_t)pub->hash_section_words / 100) + 4096;   // (the memory section, then the hash section, each with its chunk digests behind it; the device-built tape stays in its own block: only its digests come here)
   {                                               // workspace: 12 W (M + L) + 440 (trees, quotient, weights, FRI) bytes per row, allocated once per context
     static_assert(WMX % 8 == 0 && air::W_COMMITTED_DEFAULT % 8 == 0, "the main trace fills whole B8 blocks");
     const size_t want = (size_t)(12 * WM + 12 * WA + 16 + 544 + (IO ? 48 : 0) + (MEM ? 48 : 0) + (WIDE ? 8 : 0)) * N + (size_t)air::MAX_NUM_QUERIES * 64 * 1024 + (8u << 20) + (size_t)n_code * 24 + (1u << 16) +
@@ -1173,8 +1190,6 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     c->arena_off = 0;
   }
   Arena ar{c};
-  zkir::HostPin& pin = c->pin;                                 // every host block of unbounded size crosses through pinned staging (host.h)
-  pin.reset();
   auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
     void* p = pin.take(bytes);
     if (!p) return hipErrorOutOfMemory;
@@ -1234,7 +1249,6 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   const double t_pre = since(t_entry);
   mark(0);
   int rc;
-  std::vector<uint64_t> cell_addr_v, cell_bytes_v; std::vector<uint32_t> cell_time_v;     // (mode 3) the touched cells: the device witness's, or the caller's
   if (IO) {
     if (pub->n_inputs) HIP_OK(h2d(dInputs, pub->inputs, (size_t)pub->n_inputs * 8));
     const zkir_io_args io{dInputs, pub->n_inputs, pub->writes_before, pub->reads_before};
@@ -1243,6 +1257,9 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
         HIP_OK(h2d(dMemOld, pub->mem_old, (size_t)pub->n_real * 8));
         HIP_OK(h2d(dMemTold, pub->mem_told, (size_t)pub->n_real * 4));
         cell_addr_v.assign(pub->cell_addr, pub->cell_addr + pub->n_cells); cell_bytes_v.assign(pub->cell_bytes, pub->cell_bytes + pub->n_cells); cell_time_v.assign(pub->cell_time, pub->cell_time + pub->n_cells);
+      } else if (HASH_DEV) {
+        HIP_OK(hipMemcpyAsync(dMemOld, hw_rows.p, (size_t)pub->n_real * 8, hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(dMemTold, (uint64_t*)hw_rows.p + pub->n_real, (size_t)pub->n_real * 4, hipMemcpyDeviceToDevice, s));
       } else {
         // scratch = the LDE output buffer, which nothing has written yet (WM * 2N words: 1600 B per row against the ~70 B per row the witness needs)
         const size_t need = zkir::memcheck_scratch_bytes(pub->n_real, blob_len);
@@ -1352,7 +1369,16 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   struct { const uint32_t* p; size_t n; const uint32_t* data() const { return p; } size_t size() const { return n; } } hash_sec{no_calls, 1};   // a VIEW of the caller's tape (a 2^22-cycle chain: 134 MB — not copied)
   const double t_hash0 = since(t_entry);
   if (WIDE) {
-    if (pub->hash_section && pub->hash_section_words) {
+    if (HASH_DEV) {                                             // the tape built on the device: its host copy is checked as the verifier will check it (a trace that is not a run of the VM gets no proof)
+      size_t used = 0;
+      const int hrc = hashcall::parse_section(hw.h_tape, (size_t)hw.n_words, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, hcalls, &used);
+      if (hrc == 55) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: a hash syscall of the run writes its output where it overlaps the code segment: such a run has no mode-4 proof"}); return ZKIR_ERR_ARGUMENT; }
+      if (hrc || used != hw.n_words) {
+        char m[200]; snprintf(m, sizeof m, "zkir_prove: the hash tape built from the trace is malformed (check %d): the trace is not a run of the VM", hrc ? hrc : 4);
+        zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
+      }
+      hash_sec.p = hw.h_tape; hash_sec.n = used;
+    } else if (pub->hash_section && pub->hash_section_words) {
       size_t used = 0;
       const int hrc = hashcall::parse_section(pub->hash_section, (size_t)pub->hash_section_words, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, hcalls, &used);
       if (hrc || used != pub->hash_section_words) {
@@ -1368,7 +1394,13 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
     }
     const size_t n_chunks_sec = (hash_sec.size() + SECTION_CHUNK - 1) / SECTION_CHUNK;
-    if (hash_sec.size() + 4 * n_chunks_sec + 64 <= SEC_WORDS) {           // chunk digests on the device (the buffer of the memory section, free again)
+    if (HASH_DEV && 4 * n_chunks_sec + 64 <= SEC_WORDS) {                 // the tape is read where it was built: only the chunk digests come back
+      hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks_sec + 63) / 64)), dim3(64), 0, s, c->d_p2, hw.d_tape, (uint64_t)hash_sec.size(), dSec);
+      std::vector<uint32_t> sec_dg(4 * n_chunks_sec);
+      HIP_OK(hipMemcpyAsync(sec_dg.data(), dSec, sec_dg.size() * 4, hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
+      ch.observe_n(sec_dg.data(), sec_dg.size());
+    } else if (hash_sec.size() + 4 * n_chunks_sec + 64 <= SEC_WORDS) {           // chunk digests on the device (the buffer of the memory section, free again)
       uint32_t* dSecDg = dSec + ((hash_sec.size() + 63) & ~(size_t)63);
       HIP_OK(h2d(dSec, hash_sec.data(), hash_sec.size() * 4));
       hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks_sec + 63) / 64)), dim3(64), 0, s, c->d_p2, dSec, (uint64_t)hash_sec.size(), dSecDg);
@@ -1489,6 +1521,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
         return bb::e_sub(alpha_lm, fp);
       };
       hash_aux.resize(hcalls.size());
+      std::vector<uint64_t> side_off;                            // (device witness) where a call's cells start in the side array of new bytes: no message gather, no digest here
+      if (HASH_DEV) { side_off.resize(hcalls.size()); uint64_t o = 0; for (size_t ci = 0; ci < hcalls.size(); ci++) { side_off[ci] = o; o += hcalls[ci].cells.size(); } }
       const unsigned parts = hashcall::parts_for(hcalls.size());
       std::vector<E4> Tpart(parts, bb::e_zero());
       hashcall::for_calls(hcalls.size(), parts, [&](unsigned part, size_t lo, size_t hi) {        // (host threads: 175 k calls at 2^20 rows of the SHA chain are ~1 s on one core)
@@ -1500,10 +1534,11 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
           E4 fp = bb::e_mul_fm(lamv[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_HASH));
           for (int j = 0; j < 11; j++) fp = bb::e_add(fp, bb::e_mul_fm(lamv[j], bb::to_mont(e[j])));
           d.push_back(bb::e_sub(alpha_lm, fp)); sign.push_back(2);                                // (2: a call's own entry — its inverse is also the row's HH)
-          hashcall::new_bytes(hc, nb);
+          const uint64_t* nbp;
+          if (HASH_DEV) nbp = hw.h_side + side_off[ci]; else { hashcall::new_bytes(hc, nb); nbp = nb.data(); }
           for (size_t k = 0; k < hc.cells.size(); k++) {
             d.push_back(mem_d(hc.cells[k].addr, hc.cells[k].t, hc.cells[k].bytes)); sign.push_back(-1);
-            d.push_back(mem_d(hc.cells[k].addr, (uint32_t)((hc.cycle + 1) % bb::P), nb[k])); sign.push_back(1);
+            d.push_back(mem_d(hc.cells[k].addr, (uint32_t)((hc.cycle + 1) % bb::P), nbp[k])); sign.push_back(1);
           }
         }
         std::vector<E4> pre(d.size());

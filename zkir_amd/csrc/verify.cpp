@@ -216,12 +216,21 @@ int zkir_public_inputs_of(const zkir_delta_log* log, const uint8_t* blob, size_t
   out->entry_point = entry;
   zkir_digest_bytes(blob, blob_len, out->program_digest);
   out->program_blob = blob; out->program_blob_len = blob_len;              // borrowed: the prover reads the instruction ROM from it
+  if (log->cycle_base == 0 && log->n_rows == log->cycles) { out->hash_outs = log->hash_outs.size() ? log->hash_outs.data() : nullptr; out->n_hash_outs = log->hash_outs.size(); }   // (a whole traced run: the device witness of mode 4 reads what its hash calls wrote)
   std::vector<uint64_t> io;
   io.push_back(n_inputs); io.insert(io.end(), inputs, inputs + n_inputs);
   io.push_back(log->outputs.size()); io.insert(io.end(), log->outputs.begin(), log->outputs.end());
   io.push_back((uint64_t)log->halt_kind); io.push_back(log->halt_kind == ZKIR_HALT_EXIT ? log->halt_code : 0); io.push_back(log->cycles);
   zkir_digest_bytes((const uint8_t*)io.data(), io.size() * 8, out->io_digest);
   return ZKIR_OK;
+}
+
+uint64_t zkir_public_inputs_size(void) { return sizeof(zkir_public_inputs); }
+uint64_t zkir_hash_call_cells_host(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint32_t kind, uint64_t cell, uint64_t* rank) {
+  if (rank) *rank = ~0ull;
+  if (!hashcall::in_range(in_ptr, len, out_ptr, kind)) return ~0ull;
+  if (rank) *rank = hashcall::rank_of(in_ptr, len, out_ptr, cell);
+  return hashcall::n_cells_of(in_ptr, len, out_ptr);
 }
 
 int zkir_verify(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect) { return verify_impl(w, len, expect, true, nullptr); }

@@ -42,7 +42,8 @@ RC_EVENT_DTYPE = np.dtype([("value", "<u8"), ("pc", "<u8")])
 NORM_EVENT_DTYPE = np.dtype([("cycle", "<u8"), ("pc", "<u8"), ("raw_value", "<u8"), ("reg", "u1"), ("state", "u1"), ("opcode", "u1"),
                              ("pad", "u1", (5,))])
 SHA_BLOCK_DTYPE = np.dtype([("message_block", "<u4", (16,)), ("timestamp", "<u8")])
-assert REG_EVENT_DTYPE.itemsize == 32 and MEM_EVENT_DTYPE.itemsize == 24 and NORM_EVENT_DTYPE.itemsize == 32 and SHA_BLOCK_DTYPE.itemsize == 72
+HASH_OUT_DTYPE = np.dtype([("row", "<u4"), ("reserved", "<u4"), ("bytes", "u1", (32,))])      # zkir_hash_out
+assert REG_EVENT_DTYPE.itemsize == 32 and MEM_EVENT_DTYPE.itemsize == 24 and NORM_EVENT_DTYPE.itemsize == 32 and SHA_BLOCK_DTYPE.itemsize == 72 and HASH_OUT_DTYPE.itemsize == 40
 
 _MEMOP_DTYPE = np.dtype([("address", "<u8"), ("value", "<u8"), ("timestamp", "<u8"), ("is_write", "u1"), ("width", "u1"),
                          ("bound_bits", "<u4"), ("bound_tag", "u1"), ("bound_payload", "<u8")])
@@ -99,7 +100,9 @@ class PublicInputsC(C.Structure):             # zkir_public_inputs
                 # mode 3 (`deferred` == 3: mode 2 + the memory argument): the memory witness of the run (borrowed pointers into a MemcheckWitness: with_memory())
                 ("mem_old", C.c_void_p), ("mem_told", C.c_void_p), ("cell_addr", C.c_void_p), ("cell_bytes", C.c_void_p), ("cell_time", C.c_void_p), ("n_cells", C.c_uint64),
                 # mode 4 (`deferred` == 4: mode 3 + the wide-arithmetic class + hash syscalls as a tape): the hash calls as the proof's hash section (borrowed from a MemcheckWitness)
-                ("hash_section", C.c_void_p), ("hash_section_words", C.c_uint64)]
+                ("hash_section", C.c_void_p), ("hash_section_words", C.c_uint64),
+                # (ABI 7) what the run's hash syscalls wrote, borrowed from the run's delta log (zkir_public_inputs_of): the device witness of mode 4 reads the digests from here
+                ("hash_outs", C.c_void_p), ("n_hash_outs", C.c_uint64)]
 
     def with_params(self, num_queries: int = 0, pow_bits: int = 0) -> "PublicInputsC":
         """zkir_public_inputs_set_params: the prover's FRI parameters (0 = the defaults: 50 queries, 12 grinding bits; accepted 50..128 / 12..24).  A verifier given this
@@ -145,6 +148,7 @@ class PublicInputsC(C.Structure):             # zkir_public_inputs
 
     def copy(self) -> "PublicInputsC":
         q = PublicInputsC.from_buffer_copy(bytes(self))
+        q._log_ref = getattr(self, "_log_ref", None)          # (hash_outs points into the log's buffer)
         q.with_io(getattr(self, "_in_ref", []), getattr(self, "_out_ref", []))
         if hasattr(self, "_mem_ref"):
             q.with_memory(self._mem_ref)
@@ -182,6 +186,32 @@ class MemcheckWitness:
                 self._h = None
         except Exception:
             pass
+
+
+def memcheck_witness_device(trace, log: "DeltaLog", program, mode: int = 4, hash_outs: Optional[np.ndarray] = None, stream=None) -> dict:
+    """zkir_memcheck_witness_device_mode: the memory witness made ON THE DEVICE (memcheck.hip), as numpy arrays — mem_old / mem_told per row, the touched cells (cell_addr,
+    cell_bytes, cell_time) and, in mode 4, the proof's hash section (hash_section; [0] for mode 3).  trace: the device columns of the whole run (a TraceColumnsC or an object
+    with one as `.c` / `.columns`); hash_outs: the records to use instead of the log's."""
+    blob = bytes(program) if isinstance(program, (bytes, bytearray)) else program.to_bytes()
+    cols = trace if isinstance(trace, TraceColumnsC) else getattr(trace, "c", None) or trace.columns
+    n = int(log.n_rows)
+    outs = np.ascontiguousarray(log.hash_outs if hash_outs is None else hash_outs, dtype=HASH_OUT_DTYPE)
+    cap, wcap = n + 4096, 1 + 48 * len(outs) + 4096           # a first guess; the call reports the counts when they exceed it, and is repeated with them
+    while True:
+        old, told = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+        ca, cb, ct = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+        hs = np.zeros(wcap, np.uint32)
+        nc, nw = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().zkir_memcheck_witness_device_mode(C.byref(cols), n, blob, len(blob), int(mode), outs.ctypes.data if len(outs) else None, len(outs), old.ctypes.data, told.ctypes.data,
+                                                     ca.ctypes.data, cb.ctypes.data, ct.ctypes.data, cap, C.byref(nc), hs.ctypes.data, wcap, C.byref(nw), stream)
+        if rc == ERR_ARGUMENT and (nc.value > cap or nw.value > wcap):
+            cap, wcap = max(cap, int(nc.value)), max(wcap, int(nw.value))
+            continue
+        if rc != ZKIR_OK:
+            _raise(rc)
+        break
+    k = int(nc.value)
+    return {"mem_old": old, "mem_told": told, "cell_addr": ca[:k], "cell_bytes": cb[:k], "cell_time": ct[:k], "hash_section": hs[:max(1, int(nw.value))]}
 
 
 class MemoryWitnessC(C.Structure):            # zkir_memory_witness
@@ -235,7 +265,7 @@ def lib() -> C.CDLL:
                       ("mem_events", C.c_void_p), ("n_rc_events", C.c_size_t), ("rc_events", C.c_void_p),
                       ("n_rc_witnesses", C.c_size_t), ("rc_offsets", C.c_void_p), ("rc_cycles", C.c_void_p), ("rc_chunk_bits", C.c_uint32),
                       ("n_norm_events", C.c_size_t), ("norm_events", C.c_void_p), ("n_sha_blocks", C.c_size_t),
-                      ("sha_blocks", C.c_void_p)]:
+                      ("sha_blocks", C.c_void_p), ("n_hash_outs", C.c_size_t), ("hash_outs", C.c_void_p)]:
         f = getattr(L, "zkir_delta_log_" + name)
         f.restype = res
         f.argtypes = [C.c_void_p]
@@ -299,6 +329,16 @@ def lib() -> C.CDLL:
     L.zkir_public_inputs_of.restype = C.c_int
     L.zkir_public_inputs_of.argtypes = [V, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, U32, C.POINTER(PublicInputsC)]
     L.zkir_proof_version.restype = U32
+    L.zkir_abi_version.restype = U32
+    L.zkir_public_inputs_size.restype = U64
+    L.zkir_hash_call_cells_host.restype = U64
+    L.zkir_hash_call_cells_host.argtypes = [U64, U64, U64, U32, U64, C.POINTER(U64)]
+    L.zkir_memcheck_witness_device_mode.restype = C.c_int
+    L.zkir_memcheck_witness_device_mode.argtypes = [C.POINTER(TraceColumnsC), U64, C.c_char_p, C.c_size_t, U32, V, U64, V, V, V, V, V, U64, C.POINTER(U64), V, U64, C.POINTER(U64), V]
+    L.zkir_prove_result.restype = C.c_int
+    L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+    L.zkir_proof_bytes_free.restype = None
+    L.zkir_proof_bytes_free.argtypes = [C.POINTER(C.c_uint8)]
     L.zkir_proof_free.restype = None
     L.zkir_proof_free.argtypes = [C.POINTER(C.c_uint32)]
     L.zkir_proof_num_queries.restype = U32
@@ -397,6 +437,7 @@ class DeltaLog:
         self.rc_chunk_bits = L.zkir_delta_log_rc_chunk_bits(h)
         self.norm_events = _view(L.zkir_delta_log_norm_events(h), L.zkir_delta_log_n_norm_events(h), NORM_EVENT_DTYPE)
         self.sha_blocks = _view(L.zkir_delta_log_sha_blocks(h), L.zkir_delta_log_n_sha_blocks(h), SHA_BLOCK_DTYPE)
+        self.hash_outs = _view(L.zkir_delta_log_hash_outs(h), L.zkir_delta_log_n_hash_outs(h), HASH_OUT_DTYPE)     # what every executed hash syscall wrote (row, 32 bytes)
 
     def shard(self, row_begin: int, row_end: int) -> "DeltaLog":
         """zkir_delta_log_shard: self-contained delta log of rows [row_begin, row_end) (multi-GPU row sharding)."""
@@ -422,7 +463,7 @@ class DeltaLog:
 
 
 def public_inputs(log: DeltaLog, program: Program | bytes, inputs: Sequence[int] = (), deferred: bool = False, io_mode: bool = False, mem_mode: bool = False,
-                  mem_witness: str = "device", num_queries: int = 0, pow_bits: int = 0, wide_mode: bool = False) -> PublicInputsC:
+                  mem_witness: str = "device", num_queries: int = 0, pow_bits: int = 0, wide_mode: bool = False, hash_witness: str = "host") -> PublicInputsC:
     """zkir_public_inputs_of: what a proof of this run is bound to (row count, mode, entry pc, program digest, io digest).  io_mode = mode 2: the default VM mode
     with the I/O argument (WRITE / READ ecalls tied to the tapes, which the proof then carries).  mem_mode = mode 3: mode 2 with the memory argument (loads and stores
     constrained, every access tied to a consistent memory; the proof carries the touched cells).  mem_witness = "device": zkir_prove computes the run's memory witness on the
@@ -430,7 +471,10 @@ def public_inputs(log: DeltaLog, program: Program | bytes, inputs: Sequence[int]
     implementation; needs no device) and handed to zkir_prove.  num_queries / pow_bits: the prover's FRI parameters (zkir_prover_params; 0 = the defaults, 50 + 12).
     wide_mode = mode 4 (round 6): mode 3 with MULH / DIVU / REMU / DIV / REM constrained — by a chunk relation on operands below 2^40, through the wide tape (a record per row, the verifier
     recomputes the result on the raw 64-bit registers) above — hash syscalls as a tape, the code segment's boundary cell: every run of the VM that stays below 2^40 in its addresses and off
-    its own code has a mode-4 proof."""
+    its own code has a mode-4 proof.  hash_witness (mode 4, a run that makes hash syscalls): "host" = such a run is proven from the host replay, whatever mem_witness says (the
+    hash tape comes with it); "device" = the struct is left without a witness and zkir_prove builds the memory witness and the tape on the GPU (memcheck.hip), taking what
+    each call wrote from the log's hash_outs records."""
+    assert hash_witness in ("host", "device")
     blob = bytes(program) if isinstance(program, (bytes, bytearray)) else program.to_bytes()
     arr = (C.c_uint64 * max(1, len(inputs)))(*[int(x) & (2**64 - 1) for x in inputs])
     out = PublicInputsC()
@@ -439,7 +483,8 @@ def public_inputs(log: DeltaLog, program: Program | bytes, inputs: Sequence[int]
     if rc != ZKIR_OK:
         _raise(rc)
     out.with_io(list(inputs), list(log.outputs))      # the C call borrowed temporaries: re-point at arrays / bytes this struct owns
-    if wide_mode and mem_witness == "device" and log.n_rows and int(np.count_nonzero((log.inst & 0x7F) == 0x50)) > (1 if log.halt_reason.kind == HALT_EXIT else 0):
+    out._log_ref = log                                # (hash_outs is borrowed from the log)
+    if wide_mode and mem_witness == "device" and hash_witness != "device" and log.n_rows and int(np.count_nonzero((log.inst & 0x7F) == 0x50)) > (1 if log.halt_reason.kind == HALT_EXIT else 0):
         mem_witness = "host"                          # a run that may make hash syscalls (an ECALL beside the exit) is proven from the host witness: the hash tape comes with it
     if (mem_mode or wide_mode) and mem_witness == "host":
         out.with_memory(MemcheckWitness(log, blob, 4 if wide_mode else 3))
@@ -702,6 +747,22 @@ class ExecutionResult:
         if self._r:
             lib().zkir_result_stage_ms(self._r, ms)
         return dict(zip(("interpret", "device_alloc", "h2d", "k1_and_sync"), [float(x) for x in ms]))
+
+    def prove(self, mode: int = 0, num_queries: int = 0, pow_bits: int = 0) -> np.ndarray:
+        """zkir_prove_result: the proof of this whole traced run (VM.run with enable_execution_trace) as u32 words — the context, the public inputs and, in modes 3 / 4, the
+        memory witness (mode 4: the hash tape too) are made inside the call, on the device."""
+        if not self._r:
+            raise ValueError("prove() needs the device handle of a traced run (VMConfig.enable_execution_trace)")
+        pr = ProverParamsC(int(mode), int(num_queries), int(pow_bits))
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+        L = lib()
+        rc = L.zkir_prove_result(self._r, C.byref(pr), C.byref(p), C.byref(n))
+        if rc != ZKIR_OK:
+            _raise(rc)
+        try:
+            return np.frombuffer(C.string_at(p, n.value), dtype="<u4").copy()
+        finally:
+            L.zkir_proof_bytes_free(p)
 
     def public_inputs(self) -> PublicInputsC:
         """Public inputs of a proof of this run (zkir_public_inputs_of)."""
