@@ -167,6 +167,154 @@ BB_HD int64_t sacc_add(int64_t acc, int32_t x) {
   return acc + x;
 #endif
 }
+// ---- WIDE signed butterflies (the forward DIT passes of the LDE, ntt.hip) ------------------------------------------------------
+// A DIT butterfly multiplies BEFORE it adds, so its sums can be formed in 64 bits by the multiply-add itself and reduced afterwards:
+//     a + b w / R  =  (a ONE + b w) / R,   ONE = R mod p,
+// one v_mad_i64_i32 per term and a 2-instruction signed Montgomery reduction per result, with no conditional subtraction anywhere.
+// State words are int32 residues of ANY magnitude below 2^31 (canonical words included); twiddles are Montgomery-form and CENTRED,
+// |w| <= (p - 1) / 2.  The products are spelled as instructions on the device: written as (int64_t)a * b + c, clang proves signs where it
+// can and emits unsigned products plus corrections.
+constexpr int32_t W_ONE = (int32_t)R1;              // 2^28 - 2
+constexpr int32_t W_HALF = (int32_t)((P - 1) / 2);  // largest centred twiddle
+BB_HD int64_t wmul(int32_t a, int32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int64_t r;
+  asm("v_mad_i64_i32 %0, vcc, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b) : "vcc");
+  return r;
+#else
+  return (int64_t)a * b;
+#endif
+}
+BB_HD int64_t wmad(int64_t acc, int32_t a, int32_t b) {       // acc + a b
+#if defined(__HIP_DEVICE_COMPILE__)
+  int64_t r;
+  asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc) : "vcc");
+  return r;
+#else
+  return (int64_t)((uint64_t)acc + (uint64_t)((int64_t)a * b));
+#endif
+}
+// the same with a compile-time multiplier held in a scalar register (ONE, P)
+template <int32_t K>
+BB_HD int64_t wmulk(int32_t a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int64_t r;
+  asm("v_mad_i64_i32 %0, vcc, %1, %2, 0" : "=v"(r) : "v"(a), "s"(K) : "vcc");
+  return r;
+#else
+  return (int64_t)a * K;
+#endif
+}
+template <int32_t K>
+BB_HD int64_t wmadk(int64_t acc, int32_t a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int64_t r;
+  asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(r) : "v"(a), "s"(K), "v"(acc) : "vcc");
+  return r;
+#else
+  return (int64_t)((uint64_t)acc + (uint64_t)((int64_t)a * K));
+#endif
+}
+// acc / R: smont_reduce_wide with its multiply-add spelled out.  Needs |acc| < 2^63 - 2^31 p; |result| < |acc| / 2^32 + p / 2 + 1.
+BB_HD int32_t wredc(int64_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int32_t m = (int32_t)((uint32_t)acc * NEG_PINV);
+  return (int32_t)((uint64_t)wmadk<(int32_t)P>(acc, m) >> 32);
+#else
+  return smont_reduce_wide(acc);
+#endif
+}
+// canonical [0, p) -> centred [-(p-1)/2, (p-1)/2], and (-p, p) -> canonical: add / min only, nothing a compiler turns into a select
+BB_HD int32_t centre(uint32_t w) { const uint32_t u = w + (uint32_t)W_HALF, d = u - P; return (int32_t)((d < u ? d : u) - (uint32_t)W_HALF); }
+BB_HD uint32_t wcanon(int32_t x) { const uint32_t u = (uint32_t)x, s = u + P; return s < u ? s : u; }
+// mont_mul(a, b) centred, for canonical a, b: the bias (p-1)/2 rides in as the 64-bit addend of the product, so the one conditional subtraction a canonical
+// product needs anyway lands in [0, p) around the bias.  a b + 2^32 (p-1)/2 + 2^32 p < 2^64, and the high word is in [(p-1)/2, 1.97 p).
+// (The device products are spelled as instructions taking the 32-bit operands as they are: from (uint64_t)a * b the compiler hoists the zero-extended PAIR of a
+// loop-invariant operand out of the loop and holds two registers for it.)
+BB_HD int32_t mont_mul_centred(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint64_t t, u;
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(t) : "v"(a), "v"(b), "s"((uint64_t)(uint32_t)W_HALF << 32) : "vcc");
+  const uint32_t m = (uint32_t)t * NEG_PINV;
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(u) : "v"(m), "s"(P), "v"(t) : "vcc");
+  return (int32_t)(reduce_2p((uint32_t)(u >> 32)) - (uint32_t)W_HALF);
+#else
+  return (int32_t)(reduce_2p(mont_mul_add_lazy(a, b, (uint64_t)(uint32_t)W_HALF << 32)) - (uint32_t)W_HALF);
+#endif
+}
+// one radix-2 DIT butterfly: (a, b) -> (a + b w / R, a - b w / R), nw = -w.  3 multiply-adds + 2 reductions = 7 instructions
+BB_HD void dit2w(int32_t& a, int32_t& b, int32_t w, int32_t nw) {
+  const int64_t A = wmulk<W_ONE>(a);
+  const int32_t b0 = b;
+  a = wredc(wmad(A, b0, w)); b = wredc(wmad(A, b0, nw));
+}
+// the radix-4 DIT quad (two stages; twiddles w1 = w2^2 of the first, w2 and w2i = w2 j of the second, n* their negations; outputs placed as dit4 in ntt.hip
+// places them).  The first stage's sums of the EVEN pair stay 64-bit and are the addends of the second stage's products; those of the odd pair are reduced, because
+// they are multiplied.  (All four first-stage terms in one sum would not close: the outputs would grow to 8 p.)  10 multiply-adds + 6 reductions = 22 instructions.
+BB_HD void dit4w(int32_t& x0, int32_t& x1, int32_t& x2, int32_t& x3, int32_t w1, int32_t n1, int32_t w2, int32_t n2, int32_t w2i, int32_t n2i) {
+  const int64_t X0 = wmulk<W_ONE>(x0), X2 = wmulk<W_ONE>(x2);
+  const int64_t y0 = wmad(X0, x1, w1), y1 = wmad(X0, x1, n1);
+  const int32_t y2 = wredc(wmad(X2, x3, w1)), y3 = wredc(wmad(X2, x3, n1));
+  x0 = wredc(wmad(y0, y2, w2)); x2 = wredc(wmad(y0, y2, n2));
+  x1 = wredc(wmad(y1, y3, w2i)); x3 = wredc(wmad(y1, y3, n2i));
+}
+// The same quad on TWO columns sharing their twiddles, as the kernels run it.  On the device the multiply-adds of a step are ONE asm statement for both columns (the
+// compiler pads every asm statement with a hazard nop of its own: ten statements per column would cost ten), the columns alternating so that no instruction waits for
+// the one before it; the low-word products of the reductions stay in C++, where the low half of a 64-bit sum is a sub-register.
+// (The asm path exists on the device only: tests/test_gpu_lde_wide.py exercises it through stark.lde against the oracle; tests/cpp/wide_quad_test.cpp covers the C++ path.)
+BB_HD void dit4w2(int32_t* a, int32_t* b, int32_t w1, int32_t n1, int32_t w2, int32_t n2, int32_t w2i, int32_t n2i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int64_t ay0, ay1, at2, at3, by0, by1, bt2, bt3;
+  asm("v_mad_i64_i32 %1, vcc, %8, %18, 0\n\tv_mad_i64_i32 %5, vcc, %12, %18, 0\n\t"              // X0 (in y1's registers)
+      "v_mad_i64_i32 %3, vcc, %10, %18, 0\n\tv_mad_i64_i32 %7, vcc, %14, %18, 0\n\t"             // X2 (in t3's)
+      "v_mad_i64_i32 %0, vcc, %9, %16, %1\n\tv_mad_i64_i32 %4, vcc, %13, %16, %5\n\t"            // y0 = X0 + x1 w1
+      "v_mad_i64_i32 %2, vcc, %11, %16, %3\n\tv_mad_i64_i32 %6, vcc, %15, %16, %7\n\t"           // t2 = X2 + x3 w1
+      "v_mad_i64_i32 %1, vcc, %9, %17, %1\n\tv_mad_i64_i32 %5, vcc, %13, %17, %5\n\t"            // y1 = X0 - x1 w1
+      "v_mad_i64_i32 %3, vcc, %11, %17, %3\n\tv_mad_i64_i32 %7, vcc, %15, %17, %7"                 // t3 = X2 - x3 w1
+      : "=&v"(ay0), "=&v"(ay1), "=&v"(at2), "=&v"(at3), "=&v"(by0), "=&v"(by1), "=&v"(bt2), "=&v"(bt3)
+      : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(w1), "v"(n1), "s"(W_ONE) : "vcc");
+  {
+    const int32_t m0 = (int32_t)((uint32_t)at2 * NEG_PINV), m1 = (int32_t)((uint32_t)bt2 * NEG_PINV), m2 = (int32_t)((uint32_t)at3 * NEG_PINV), m3 = (int32_t)((uint32_t)bt3 * NEG_PINV);
+    asm("v_mad_i64_i32 %0, vcc, %4, %8, %0\n\tv_mad_i64_i32 %1, vcc, %5, %8, %1\n\tv_mad_i64_i32 %2, vcc, %6, %8, %2\n\tv_mad_i64_i32 %3, vcc, %7, %8, %3"
+        : "+v"(at2), "+v"(bt2), "+v"(at3), "+v"(bt3) : "v"(m0), "v"(m1), "v"(m2), "v"(m3), "s"((int32_t)P) : "vcc");
+  }
+  const int32_t ay2 = (int32_t)((uint64_t)at2 >> 32), ay3 = (int32_t)((uint64_t)at3 >> 32), by2 = (int32_t)((uint64_t)bt2 >> 32), by3 = (int32_t)((uint64_t)bt3 >> 32);
+  int64_t au0, au1, bu0, bu1;                                  // the sums of outputs 0 and 1; those of 2 and 3 replace y0 and y1
+  asm("v_mad_i64_i32 %0, vcc, %8, %12, %4\n\tv_mad_i64_i32 %2, vcc, %10, %12, %6\n\t"
+      "v_mad_i64_i32 %1, vcc, %9, %14, %5\n\tv_mad_i64_i32 %3, vcc, %11, %14, %7\n\t"
+      "v_mad_i64_i32 %4, vcc, %8, %13, %4\n\tv_mad_i64_i32 %6, vcc, %10, %13, %6\n\t"
+      "v_mad_i64_i32 %5, vcc, %9, %15, %5\n\tv_mad_i64_i32 %7, vcc, %11, %15, %7"
+      : "=&v"(au0), "=&v"(au1), "=&v"(bu0), "=&v"(bu1), "+v"(ay0), "+v"(ay1), "+v"(by0), "+v"(by1)
+      : "v"(ay2), "v"(ay3), "v"(by2), "v"(by3), "v"(w2), "v"(n2), "v"(w2i), "v"(n2i) : "vcc");
+  {
+    const int32_t m0 = (int32_t)((uint32_t)au0 * NEG_PINV), m1 = (int32_t)((uint32_t)bu0 * NEG_PINV), m2 = (int32_t)((uint32_t)au1 * NEG_PINV), m3 = (int32_t)((uint32_t)bu1 * NEG_PINV);
+    const int32_t m4 = (int32_t)((uint32_t)ay0 * NEG_PINV), m5 = (int32_t)((uint32_t)by0 * NEG_PINV), m6 = (int32_t)((uint32_t)ay1 * NEG_PINV), m7 = (int32_t)((uint32_t)by1 * NEG_PINV);
+    asm("v_mad_i64_i32 %0, vcc, %8, %16, %0\n\tv_mad_i64_i32 %1, vcc, %9, %16, %1\n\tv_mad_i64_i32 %2, vcc, %10, %16, %2\n\tv_mad_i64_i32 %3, vcc, %11, %16, %3\n\t"
+        "v_mad_i64_i32 %4, vcc, %12, %16, %4\n\tv_mad_i64_i32 %5, vcc, %13, %16, %5\n\tv_mad_i64_i32 %6, vcc, %14, %16, %6\n\tv_mad_i64_i32 %7, vcc, %15, %16, %7"
+        : "+v"(au0), "+v"(bu0), "+v"(au1), "+v"(bu1), "+v"(ay0), "+v"(by0), "+v"(ay1), "+v"(by1)
+        : "v"(m0), "v"(m1), "v"(m2), "v"(m3), "v"(m4), "v"(m5), "v"(m6), "v"(m7), "s"((int32_t)P) : "vcc");
+  }
+  a[0] = (int32_t)((uint64_t)au0 >> 32); a[1] = (int32_t)((uint64_t)au1 >> 32); a[2] = (int32_t)((uint64_t)ay0 >> 32); a[3] = (int32_t)((uint64_t)ay1 >> 32);
+  b[0] = (int32_t)((uint64_t)bu0 >> 32); b[1] = (int32_t)((uint64_t)bu1 >> 32); b[2] = (int32_t)((uint64_t)by0 >> 32); b[3] = (int32_t)((uint64_t)by1 >> 32);
+#else
+  dit4w(a[0], a[1], a[2], a[3], w1, n1, w2, n2, w2i, n2i);
+  dit4w(b[0], b[1], b[2], b[3], w1, n1, w2, n2, w2i, n2i);
+#endif
+}
+// The bounds, computed: magnitudes through one butterfly / quad from words of at most `x`.
+constexpr uint64_t WREDC_IN_MAX = (1ull << 63) - ((uint64_t)P << 31);                    // what a reduction takes: |acc| + 2^31 p < 2^63
+constexpr uint64_t wredc_out_bound(uint64_t acc) { return (acc >> 32) + 1 + P / 2 + 1; }  // |acc| / 2^32 rounded up, + p / 2 + 1
+struct WBound { uint64_t acc, out; };                                                     // largest reduction input, largest output word
+constexpr WBound dit2w_bound(uint64_t x) { const uint64_t a = x * (uint64_t)W_ONE + x * (uint64_t)W_HALF; return WBound{a, wredc_out_bound(a)}; }
+constexpr WBound dit4w_bound(uint64_t x) {
+  const uint64_t s1 = x * (uint64_t)W_ONE + x * (uint64_t)W_HALF;                         // y0, y1 (kept wide) and the sums reduced to y2, y3
+  const uint64_t s2 = s1 + wredc_out_bound(s1) * (uint64_t)W_HALF;                        // second-stage sums
+  return WBound{s2, wredc_out_bound(s2)};
+}
+static_assert(dit4w_bound(1ull << 31).acc < WREDC_IN_MAX && dit2w_bound(1ull << 31).acc < WREDC_IN_MAX, "every sum of a quad on int32 words is a legal reduction input");
+static_assert(dit4w_bound(1ull << 31).out < (1ull << 31) && dit2w_bound(1ull << 31).out < (1ull << 31), "any quad output (and any canonical word) is a legal quad input");
+static_assert(dit4w_bound(P).out < P && dit2w_bound(P).out < P, "closure: words in (-p, p) -- canonical ones included -- stay in (-p, p), which is what wcanon() takes");
+
 BB_HD uint32_t to_mont(uint32_t a) { return mont_mul(a, R2); }
 BB_HD uint32_t from_mont(uint32_t a) { return mont_mul(a, 1u); }
 // canonical * canonical -> canonical (two reductions; for cold paths)

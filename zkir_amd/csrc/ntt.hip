@@ -47,8 +47,6 @@ __device__ __forceinline__ void wave_sync_lds() { asm volatile("s_waitcnt lgkmcn
 
 // ---- four columns at a time --------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint4 add4(uint4 a, uint4 b) { return make_uint4(bb::add(a.x, b.x), bb::add(a.y, b.y), bb::add(a.z, b.z), bb::add(a.w, b.w)); }
-__device__ __forceinline__ uint4 sub4(uint4 a, uint4 b) { return make_uint4(bb::sub(a.x, b.x), bb::sub(a.y, b.y), bb::sub(a.z, b.z), bb::sub(a.w, b.w)); }
-__device__ __forceinline__ uint4 addl4(uint4 a, uint4 b) { return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }                   // < 2p: only ever the lazy operand of a product
 __device__ __forceinline__ uint4 subl4(uint4 a, uint4 b) { return make_uint4(a.x - b.x + bb::P, a.y - b.y + bb::P, a.z - b.z + bb::P, a.w - b.w + bb::P); }
 __device__ __forceinline__ uint4 mul4(uint4 a, uint32_t w) { return make_uint4(bb::mont_mul(a.x, w), bb::mont_mul(a.y, w), bb::mont_mul(a.z, w), bb::mont_mul(a.w, w)); }
 
@@ -60,18 +58,33 @@ __device__ __forceinline__ void dif4(uint4& x0, uint4& x1, uint4& x2, uint4& x3,
   x0 = add4(y0, y1); x1 = mul4(subl4(y0, y1), w2);
   x2 = add4(y2, y3); x3 = mul4(subl4(y2, y3), w2);
 }
+
+// ---- the forward side in WIDE SIGNED arithmetic (babybear.h: dit4w / dit2w) ------------------------------------------------------
+// Representation contract, private to lde_run: from the first forward round to the last, words are int32 residues in (-p, p) — a
+// canonical word is one, so the inverse side and the coset scale hand over as they are — and twiddles are centred.  The LAST forward
+// kernel of a chain (`canon` != 0) brings its results back to [0, p) on the way out.
+struct WTw { int32_t w, n; };                                                  // a centred twiddle and its negation
+__device__ __forceinline__ WTw wtw(int32_t w) { return WTw{w, -w}; }
 // forward (DIT) radix-4 quad: stages with twiddles w1 = w2^2 (first stage), w2 / w2i = w2 * j (second stage); outputs in positions
 // (0, 2, 1, 3) order of the classic DIT flow: o0 -> i0, o1 -> i0 + d, o2 -> i0 + 2d, o3 -> i0 + 3d
-__device__ __forceinline__ void dit4(uint4& x0, uint4& x1, uint4& x2, uint4& x3, uint32_t w1, uint32_t w2, uint32_t w2i) {
-  const uint4 t1 = mul4(x1, w1), t3 = mul4(x3, w1);
-  const uint4 y0 = add4(x0, t1), y1 = sub4(x0, t1), y2 = addl4(x2, t3), y3 = subl4(x2, t3);
-  const uint4 u2 = mul4(y2, w2), u3 = mul4(y3, w2i);
-  x0 = add4(y0, u2); x2 = sub4(y0, u2); x1 = add4(y1, u3); x3 = sub4(y1, u3);
+__device__ __forceinline__ void dit4w4(uint4& x0, uint4& x1, uint4& x2, uint4& x3, WTw w1, WTw w2, WTw w2i) {
+#define ZKIR_Q(c, e) { int32_t a[4] = {(int32_t)x0.c, (int32_t)x1.c, (int32_t)x2.c, (int32_t)x3.c}, b[4] = {(int32_t)x0.e, (int32_t)x1.e, (int32_t)x2.e, (int32_t)x3.e}; \
+                       bb::dit4w2(a, b, w1.w, w1.n, w2.w, w2.n, w2i.w, w2i.n); \
+                       x0.c = (uint32_t)a[0]; x1.c = (uint32_t)a[1]; x2.c = (uint32_t)a[2]; x3.c = (uint32_t)a[3]; x0.e = (uint32_t)b[0]; x1.e = (uint32_t)b[1]; x2.e = (uint32_t)b[2]; x3.e = (uint32_t)b[3]; }
+  // two columns at a time: the scheduler would otherwise interleave all four chains and hold their 64-bit sums at once
+  ZKIR_Q(x, y) __builtin_amdgcn_sched_barrier(0); ZKIR_Q(z, w)
+#undef ZKIR_Q
 }
+__device__ __forceinline__ void dit2w4(uint4& a, uint4& b, WTw w) {
+#define ZKIR_Q(c) { int32_t p = (int32_t)a.c, q = (int32_t)b.c; bb::dit2w(p, q, w.w, w.n); a.c = (uint32_t)p; b.c = (uint32_t)q; }
+  ZKIR_Q(x) ZKIR_Q(y) ZKIR_Q(z) ZKIR_Q(w)
+#undef ZKIR_Q
+}
+__device__ __forceinline__ uint4 canon4(uint4 v) { return make_uint4(bb::wcanon((int32_t)v.x), bb::wcanon((int32_t)v.y), bb::wcanon((int32_t)v.z), bb::wcanon((int32_t)v.w)); }
 
 // ---- one radix-2 stage straight through global memory (odd stage counts only; one lane = one butterfly of four columns) -----
 template <bool DIT>
-__global__ __launch_bounds__(NT) void ntt_stage_kernel(uint4* __restrict__ data, uint64_t blk_u4, int L, int s0, const uint32_t* __restrict__ tw) {
+__global__ __launch_bounds__(NT) void ntt_stage_kernel(uint4* __restrict__ data, uint64_t blk_u4, int L, int s0, const uint32_t* __restrict__ tw, int canon) {
   uint4* x = data + (uint64_t)blockIdx.y * blk_u4;
   const uint64_t item = (uint64_t)blockIdx.x * NT + threadIdx.x;              // (pair t, half h)
   const uint32_t n = 1u << L;
@@ -81,7 +94,12 @@ __global__ __launch_bounds__(NT) void ntt_stage_kernel(uint4* __restrict__ data,
   if (DIT) { stride = 1u << s0; const uint32_t hi = t >> s0, lo = t & (stride - 1); p = (hi << (s0 + 1)) + lo; w = tw[lo << (L - s0 - 1)]; }
   else { stride = n >> (s0 + 1); const uint32_t hi = t / stride, lo = t % stride; p = hi * (n >> s0) + lo; w = tw[lo << s0]; }
   const uint4 a = x[(uint64_t)p * 2 + h], b = x[(uint64_t)(p + stride) * 2 + h];
-  if (DIT) { const uint4 tt = mul4(b, w); x[(uint64_t)p * 2 + h] = add4(a, tt); x[(uint64_t)(p + stride) * 2 + h] = sub4(a, tt); }
+  if (DIT) {
+    uint4 a2 = a, b2 = b;
+    dit2w4(a2, b2, wtw(bb::centre(w)));
+    if (canon) { a2 = canon4(a2); b2 = canon4(b2); }
+    x[(uint64_t)p * 2 + h] = a2; x[(uint64_t)(p + stride) * 2 + h] = b2;
+  }
   else { x[(uint64_t)p * 2 + h] = add4(a, b); x[(uint64_t)(p + stride) * 2 + h] = mul4(subl4(a, b), w); }
 }
 
@@ -122,7 +140,7 @@ __device__ __forceinline__ u32x4 trace_quad01(const TraceSrc01& q, uint32_t blk,
 // LDS holds the two halves as separate planes so that consecutive lanes touch consecutive 16-byte words.
 template <bool DIT, int R, int C, int NTH, bool FUSED = false>
 __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__ data, uint64_t blk_u4, uint32_t tiles_per_block, uint32_t total, int L, int s0,
-                                                              const uint32_t* __restrict__ tw, const uint32_t* __restrict__ small, int log_small, uint32_t j4_m, TraceSrc01 fsrc = TraceSrc01{}) {
+                                                              const uint32_t* __restrict__ tw, const uint32_t* __restrict__ small, int log_small, uint32_t j4_m, int canon, TraceSrc01 fsrc = TraceSrc01{}) {
   constexpr int B = 2 * R;
   constexpr uint32_t POS = 1u << (B + C), QUADS = POS / 4, CMASK = (1u << C) - 1, PLANE = POS + 4;       // +4: the two planes start in different banks
   constexpr uint32_t MOVES = 2 * POS / NTH;
@@ -200,29 +218,41 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
       const int b = 2 * r;
 #pragma unroll
       for (uint32_t k = 0; k < QUADS / NTH; k++) {
-        const uint32_t q = threadIdx.x + k * NTH;
+        uint32_t q = threadIdx.x + k * NTH;
+        // (forward: the LDS addresses are recomputed each round — a handful of full-rate instructions; hoisted out of the tile loop, as the compiler would have
+        //  them, the ten of them push the 1024-lane instance past its 128 registers.  The empty asm only hides q's origin from the optimiser; what it buys depends
+        //  on the compiler, so the register counts of profiles/*_isa_hist.txt are to be re-read after a toolchain change)
+        if constexpr (DIT) asm volatile("" : "+v"(q));
         const uint32_t lo_l = q & CMASK, qq = q >> C;
-        uint32_t i0, d, wa, wb, wc;
-        if (!DIT) {
+        uint4* pl0 = lds4; uint4* pl1 = lds4 + PLANE;
+        if constexpr (!DIT) {
           const int lg = B - 2 - b;                            // log2(h2) in row units
           const uint32_t h2 = 1u << lg, mid_lo = qq & (h2 - 1), mid_hi = qq >> lg;
-          i0 = ((((mid_hi << (lg + 2)) | mid_lo)) << C) | lo_l; d = h2 << C;
-          wa = bb::mont_mul(tp[r], sm[r]);
-          wb = bb::mont_mul(wa, j4_m); wc = bb::mont_mul(wa, wa);
+          const uint32_t i0 = ((((mid_hi << (lg + 2)) | mid_lo)) << C) | lo_l, d = h2 << C;
+          const uint32_t wa = bb::mont_mul(tp[r], sm[r]);
+          const uint32_t wb = bb::mont_mul(wa, j4_m), wc = bb::mont_mul(wa, wa);
+          // both halves' eight words are read before either quad is computed: one LDS latency per round instead of two
+          uint4 x0 = pl0[i0], x1 = pl0[i0 + d], x2 = pl0[i0 + 2 * d], x3 = pl0[i0 + 3 * d];
+          uint4 y0 = pl1[i0], y1 = pl1[i0 + d], y2 = pl1[i0 + 2 * d], y3 = pl1[i0 + 3 * d];
+          dif4(x0, x1, x2, x3, wa, wb, wc);
+          pl0[i0] = x0; pl0[i0 + d] = x1; pl0[i0 + 2 * d] = x2; pl0[i0 + 3 * d] = x3;
+          dif4(y0, y1, y2, y3, wa, wb, wc);
+          pl1[i0] = y0; pl1[i0 + d] = y1; pl1[i0 + 2 * d] = y2; pl1[i0 + 3 * d] = y3;
         } else {
           const uint32_t dm = 1u << b, mid_lo = qq & (dm - 1), mid_hi = qq >> b;
-          i0 = ((((mid_hi << (b + 2)) | mid_lo)) << C) | lo_l; d = dm << C;
-          wb = bb::mont_mul(tp[r], sm[r]);                                      // w2
-          wa = bb::mont_mul(wb, wb); wc = bb::mont_mul(wb, j4_m);               // w1, w2i
+          const uint32_t i0 = ((((mid_hi << (b + 2)) | mid_lo)) << C) | lo_l, d = dm << C;
+          const WTw w2 = wtw(bb::mont_mul_centred(tp[r], sm[r]));               // centred; its canonical form derives the other two
+          const uint32_t w2u = bb::wcanon(w2.w);
+          const WTw w1 = wtw(bb::mont_mul_centred(w2u, w2u)), w2i = wtw(bb::mont_mul_centred(w2u, j4_m));
+          // the wide quad holds 64-bit sums: one half at a time keeps the kernel inside 128 registers
+          uint4 x0 = pl0[i0], x1 = pl0[i0 + d], x2 = pl0[i0 + 2 * d], x3 = pl0[i0 + 3 * d];
+          dit4w4(x0, x1, x2, x3, w1, w2, w2i);
+          pl0[i0] = x0; pl0[i0 + d] = x1; pl0[i0 + 2 * d] = x2; pl0[i0 + 3 * d] = x3;
+          __builtin_amdgcn_sched_barrier(0);
+          uint4 y0 = pl1[i0], y1 = pl1[i0 + d], y2 = pl1[i0 + 2 * d], y3 = pl1[i0 + 3 * d];
+          dit4w4(y0, y1, y2, y3, w1, w2, w2i);
+          pl1[i0] = y0; pl1[i0 + d] = y1; pl1[i0 + 2 * d] = y2; pl1[i0 + 3 * d] = y3;
         }
-        // both halves' eight words are read before either quad is computed: one LDS latency per round instead of two
-        uint4* pl0 = lds4; uint4* pl1 = lds4 + PLANE;
-        uint4 x0 = pl0[i0], x1 = pl0[i0 + d], x2 = pl0[i0 + 2 * d], x3 = pl0[i0 + 3 * d];
-        uint4 y0 = pl1[i0], y1 = pl1[i0 + d], y2 = pl1[i0 + 2 * d], y3 = pl1[i0 + 3 * d];
-        if (!DIT) dif4(x0, x1, x2, x3, wa, wb, wc); else dit4(x0, x1, x2, x3, wa, wb, wc);
-        pl0[i0] = x0; pl0[i0 + d] = x1; pl0[i0 + 2 * d] = x2; pl0[i0 + 3 * d] = x3;
-        if (!DIT) dif4(y0, y1, y2, y3, wa, wb, wc); else dit4(y0, y1, y2, y3, wa, wb, wc);
-        pl1[i0] = y0; pl1[i0 + d] = y1; pl1[i0 + 2 * d] = y2; pl1[i0 + 3 * d] = y3;
       }
       // A wave's 64 quads (2^(6-C) values of qq) cover one contiguous "home block" of 4 * 2^(6-C) rows in every round whose quad span
       // fits it: DIF rounds with log2(h2) <= 6 - C, DIT rounds with b <= 6 - C.  Between two such rounds the data never leaves the wave.
@@ -232,7 +262,9 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
 #pragma unroll
     for (uint32_t k = 0; k < MOVES; k++) {
       const uint32_t e = threadIdx.x + k * NTH, row = e >> (C + 1), wv = e & ((2u << C) - 1);
-      x[((uint64_t)base + (uint64_t)row * stride_mid) * 2 + wv] = lds4[(wv & 1) * PLANE + ((row << C) | (wv >> 1))];
+      uint4 v = lds4[(wv & 1) * PLANE + ((row << C) | (wv >> 1))];
+      if (DIT && canon) v = canon4(v);                       // the chain's last forward pass: (-p, p) -> [0, p)
+      x[((uint64_t)base + (uint64_t)row * stride_mid) * 2 + wv] = v;
     }
     if (wn >= total) break;
     w = wn; x = xn; base = base_n; lo0 = lo0_n;
@@ -248,7 +280,7 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
 // Twiddles: one table read (the finest stage's) and its squares, times the constant 4th / 8th roots.
 template <bool DIT, int S>
 __global__ __launch_bounds__(NT) void ntt_reg_kernel(uint4* __restrict__ data, uint64_t blk_u4, int L, int s0, const uint32_t* __restrict__ tw, uint32_t r4_m, uint32_t r8_m,
-                                                       uint32_t r8_3_m) {
+                                                       uint32_t r8_3_m, int canon) {
   constexpr int E = 1 << S;
   const uint32_t n = 1u << L;
   uint4* x = data + (uint64_t)blockIdx.y * blk_u4;
@@ -289,25 +321,19 @@ __global__ __launch_bounds__(NT) void ntt_reg_kernel(uint4* __restrict__ data, u
     // DIT: stage j pairs (k, k + 2^j); twiddle of the pair with low index kl = U_j * rho_{2^(j+1)}^kl, U_(S-1) = w^(lo << (L - s0 - S)), U_(j-1) = U_j^2
     const uint32_t Uf = tw[lo << (L - s0 - S)];
     const uint32_t Um = bb::mont_mul(Uf, Uf);
-    if (S == 3) {
-      const uint32_t U0 = bb::mont_mul(Um, Um);
-      const uint32_t m1 = bb::mont_mul(Um, r4_m), f1 = bb::mont_mul(Uf, r8_m), f2 = bb::mont_mul(Uf, r4_m), f3 = bb::mont_mul(Uf, r8_3_m);
+    if (S == 3) {                                              // stages 0 and 1 as wide quads, stage 2 as wide radix-2 butterflies
+      const WTw u0 = wtw(bb::mont_mul_centred(Um, Um)), um = wtw(bb::centre(Um)), m1 = wtw(bb::mont_mul_centred(Um, r4_m));
 #pragma unroll
-      for (int g = 0; g < 8; g += 2) { const uint4 tt = mul4(v[g + 1], U0); const uint4 a = v[g]; v[g] = add4(a, tt); v[g + 1] = sub4(a, tt); }
+      for (int g = 0; g < 8; g += 4) dit4w4(v[g], v[g + 1], v[g + 2], v[g + 3], u0, um, m1);
+      const WTw wf[4] = {wtw(bb::centre(Uf)), wtw(bb::mont_mul_centred(Uf, r8_m)), wtw(bb::mont_mul_centred(Uf, r4_m)), wtw(bb::mont_mul_centred(Uf, r8_3_m))};
 #pragma unroll
-      for (int g = 0; g < 8; g += 4) {
-        { const uint4 tt = mul4(v[g + 2], Um); const uint4 a = v[g]; v[g] = add4(a, tt); v[g + 2] = sub4(a, tt); }
-        { const uint4 tt = mul4(v[g + 3], m1); const uint4 a = v[g + 1]; v[g + 1] = add4(a, tt); v[g + 3] = sub4(a, tt); }
-      }
-      const uint32_t wf[4] = {Uf, f1, f2, f3};
-#pragma unroll
-      for (int k = 0; k < 4; k++) { const uint4 tt = mul4(v[k + 4], wf[k]); const uint4 a = v[k]; v[k] = add4(a, tt); v[k + 4] = sub4(a, tt); }
+      for (int k = 0; k < 4; k++) dit2w4(v[k], v[k + 4], wf[k]);
     } else {
-      const uint32_t f1 = bb::mont_mul(Uf, r4_m);
+      dit4w4(v[0], v[1], v[2], v[3], wtw(bb::centre(Um)), wtw(bb::centre(Uf)), wtw(bb::mont_mul_centred(Uf, r4_m)));
+    }
+    if (canon) {
 #pragma unroll
-      for (int g = 0; g < 4; g += 2) { const uint4 tt = mul4(v[g + 1], Um); const uint4 a = v[g]; v[g] = add4(a, tt); v[g + 1] = sub4(a, tt); }
-      { const uint4 tt = mul4(v[2], Uf); const uint4 a = v[0]; v[0] = add4(a, tt); v[2] = sub4(a, tt); }
-      { const uint4 tt = mul4(v[3], f1); const uint4 a = v[1]; v[1] = add4(a, tt); v[3] = sub4(a, tt); }
+      for (int k = 0; k < E; k++) v[k] = canon4(v[k]);
     }
   }
 #pragma unroll
@@ -328,7 +354,7 @@ inline int persist() { static const int v = getenv("ZKIR_NTT_PERSIST") ? atoi(ge
 
 template <bool DIT, int R, int C, int NTH, bool FUSED = false>
 void launch_strided_r4(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, int s0, const uint32_t* tw, const uint32_t* small, int log_small, uint32_t j4_m, hipStream_t s,
-                       const TraceSrc01* fsrc = nullptr) {
+                       const TraceSrc01* fsrc = nullptr, int canon = 0) {
   constexpr size_t lds = 16u * 2 * ((1u << (2 * R + C)) + 4);
   auto k = ntt_strided_r4_kernel<DIT, R, C, NTH, FUSED>;
   static std::atomic<uint64_t> attr_done{0};                                   // one bit per device id: the attribute is per (function, device)
@@ -339,7 +365,7 @@ void launch_strided_r4(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, int
   const unsigned per_cu = (unsigned)((160u << 10) / lds) > 0 ? (unsigned)((160u << 10) / lds) : 1u;       // workgroups resident per CU (LDS-limited)
   unsigned grid = persist() ? cu_count() * (per_cu > 8 ? 8 : per_cu) : total;
   if (grid > total) grid = total;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NTH), lds, s, (uint4*)data, 2 * n, tiles, total, L, s0, tw, small, log_small, j4_m, fsrc ? *fsrc : TraceSrc01{});
+  hipLaunchKernelGGL(k, dim3(grid), dim3(NTH), lds, s, (uint4*)data, 2 * n, tiles, total, L, s0, tw, small, log_small, j4_m, canon, fsrc ? *fsrc : TraceSrc01{});
 }
 
 inline int strided_c() { static const int c = getenv("ZKIR_NTT_C") ? atoi(getenv("ZKIR_NTT_C")) : 2; return c; }
@@ -357,24 +383,25 @@ void run_strided_stages(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, in
     else if (stages == 7) take = 4;
     else if (stages == 5) take = 3;
     else take = stages;                                          // 8, 6, 4, 3, 2, 1
+    const int canon = DIT && take == stages;                     // the chain's last forward kernel hands out canonical words
     switch (take) {
       case 10:
         // tile rows of 4 positions = 128 contiguous bytes (a full cache line; 128 KiB of LDS, one workgroup of 16 waves per CU) or of
         // 2 positions = 64 bytes (64 KiB, two workgroups of 8 waves): ZKIR_NTT_C picks (benchmarking), default from the measurements
-        if (strided_c() == 2) launch_strided_r4<DIT, 5, 2, 1024>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s);
-        else launch_strided_r4<DIT, 5, 1, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s);
+        if (strided_c() == 2) launch_strided_r4<DIT, 5, 2, 1024>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon);
+        else launch_strided_r4<DIT, 5, 1, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon);
         break;
-      case 8: launch_strided_r4<DIT, 4, 3, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s); break;
-      case 6: launch_strided_r4<DIT, 3, 4, 256>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s); break;
-      case 4: launch_strided_r4<DIT, 2, 5, 128>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s); break;
+      case 8: launch_strided_r4<DIT, 4, 3, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon); break;
+      case 6: launch_strided_r4<DIT, 3, 4, 256>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon); break;
+      case 4: launch_strided_r4<DIT, 2, 5, 128>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon); break;
       case 3:
-        hipLaunchKernelGGL((ntt_reg_kernel<DIT, 3>), dim3((unsigned)(((n >> 3) * 2 + NT - 1) / NT), n_blocks), dim3(NT), 0, s, (uint4*)data, 2 * n, L, s0, tw, j4_m, r8_m, r8_3_m);
+        hipLaunchKernelGGL((ntt_reg_kernel<DIT, 3>), dim3((unsigned)(((n >> 3) * 2 + NT - 1) / NT), n_blocks), dim3(NT), 0, s, (uint4*)data, 2 * n, L, s0, tw, j4_m, r8_m, r8_3_m, canon);
         break;
       case 2:
-        hipLaunchKernelGGL((ntt_reg_kernel<DIT, 2>), dim3((unsigned)(((n >> 2) * 2 + NT - 1) / NT), n_blocks), dim3(NT), 0, s, (uint4*)data, 2 * n, L, s0, tw, j4_m, r8_m, r8_3_m);
+        hipLaunchKernelGGL((ntt_reg_kernel<DIT, 2>), dim3((unsigned)(((n >> 2) * 2 + NT - 1) / NT), n_blocks), dim3(NT), 0, s, (uint4*)data, 2 * n, L, s0, tw, j4_m, r8_m, r8_3_m, canon);
         break;
       default:
-        hipLaunchKernelGGL(ntt_stage_kernel<DIT>, dim3((unsigned)((n + NT - 1) / NT), n_blocks), dim3(NT), 0, s, (uint4*)data, 2 * n, L, s0, tw);
+        hipLaunchKernelGGL(ntt_stage_kernel<DIT>, dim3((unsigned)((n + NT - 1) / NT), n_blocks), dim3(NT), 0, s, (uint4*)data, 2 * n, L, s0, tw, canon);
         break;
     }
     s0 += take; stages -= take;
@@ -433,9 +460,9 @@ __global__ __launch_bounds__(NT) void lde_small_kernel(const uint32_t* __restric
 // carries.  LDS: A = both halves of the chunk (32 KiB; later the forward buffer of half 1), Bf = the forward buffer of half 0 (32 KiB):
 // 64 KiB per workgroup, two workgroups per CU.
 constexpr int MID_NT = 512;
-__global__ __launch_bounds__(MID_NT) void lde_middle_r4_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, uint32_t chunks_per_block, uint32_t total, int L,
+__global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void lde_middle_r4_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, uint32_t chunks_per_block, uint32_t total, int L,
                                                                 const uint32_t* __restrict__ small_inv, const uint32_t* __restrict__ small_fwd,
-                                                                const uint32_t* __restrict__ g_lo, const uint32_t* __restrict__ g_hi, uint32_t j4_inv_m, uint32_t j4_fwd_m) {
+                                                                const uint32_t* __restrict__ g_lo, const uint32_t* __restrict__ g_hi, uint32_t j4_inv_m, uint32_t j4_fwd_m, int canon) {
   constexpr int Bm = 10;
   constexpr uint32_t APL = 1024;
   __shared__ uint4 A[2 * APL];
@@ -514,20 +541,25 @@ __global__ __launch_bounds__(MID_NT) void lde_middle_r4_kernel(const uint4* __re
         const uint32_t lo = t & ((1u << s) - 1), hi = t >> s;
         const uint32_t i0 = (hi << (s + 2)) | lo, d = 1u << s;
         const uint32_t w2 = tw_f[r];                            // w_2048^(lo << (9-s)): twiddle of stage s+1
-        const uint32_t w1 = bb::mont_mul(w2, w2), w2i = bb::mont_mul(w2, j4_fwd_m);
+        const WTw c2 = wtw(bb::centre(w2)), c1 = wtw(bb::mont_mul_centred(w2, w2)), c2i = wtw(bb::mont_mul_centred(w2, j4_fwd_m));
         uint4 x0, x1, x2, x3;
         if (r == 0) {                                          // after stage 0: F[j] = A[j >> 1]
           x0 = a[i0 >> 1]; x1 = a[(i0 + d) >> 1]; x2 = a[(i0 + 2 * d) >> 1]; x3 = a[(i0 + 3 * d) >> 1];
           __syncthreads();                                     // half 1 overwrites what it has just read
         } else { x0 = F[i0]; x1 = F[i0 + d]; x2 = F[i0 + 2 * d]; x3 = F[i0 + 3 * d]; }
-        dit4(x0, x1, x2, x3, w1, w2, w2i);
+        dit4w4(x0, x1, x2, x3, c1, c2, c2i);
         F[i0] = x0; F[i0 + d] = x1; F[i0 + 2 * d] = x2; F[i0 + 3 * d] = x3;
         // rounds 0..2 (spans up to 128) stay inside the wave's own 256 positions [256 v, 256 v + 256) of F; rounds 3 and 4 cross waves
         if (r < 2) wave_sync_lds(); else __syncthreads();
       }
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++) { const uint32_t e = t + k * MID_NT; y[((uint64_t)2 * base + e) * 2] = Bf[e]; y[((uint64_t)2 * base + e) * 2 + 1] = A[e]; }
+    for (int k = 0; k < 4; k++) {
+      const uint32_t e = t + k * MID_NT;
+      uint4 v0 = Bf[e], v1 = A[e];
+      if (canon) { v0 = canon4(v0); v1 = canon4(v1); }        // log_n = 10: no strided forward pass follows
+      y[((uint64_t)2 * base + e) * 2] = v0; y[((uint64_t)2 * base + e) * 2 + 1] = v1;
+    }
     __syncthreads();
     if (wn >= total) break;
     w = wn;
@@ -558,7 +590,7 @@ void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out,
     unsigned grid = persist() ? cu_count() * 2 : total;                     // 64 KiB of LDS: two workgroups per CU
     if (grid > total) grid = total;
     hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
-                       j4_inv_m, j4_fwd_m);
+                       j4_inv_m, j4_fwd_m, L == 10);
   }
   // forward DIT strided stages 11 .. L of the size-2N transform
   run_strided_stages<true>(out, (uint64_t)2 * N, n_blocks, L + 1, 11, L - 10, t.tw_fwd, t.small_fwd, 11, j4_fwd_m, r8_fwd_m, r8_fwd3_m, s);
@@ -566,7 +598,8 @@ void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out,
 
 
 // EXPERIMENT (profiles/r04*_lde_tile_variants.txt): ONE strided pass at stage 0 over n_blocks blocks of 2^log_n rows with a chosen tile geometry — the timing of the
-// tilings side by side on the same data (the values are a partial transform: only the time means anything).
+// tilings side by side on the same data (the values are a partial transform: only the time means anything);
+// a forward pass is launched without `canon`, so it leaves signed words in (-p, p), not field elements).
 //   0: 10 stages, 1024 rows x 4 positions (128-byte rows), 128 KiB, 1024 lanes: one workgroup per CU   (what lde_run uses)
 //   1: 10 stages, 1024 rows x 2 positions (64-byte rows),   64 KiB,  512 lanes: two per CU
 //   2:  8 stages,  256 rows x 8 positions (256-byte rows),  64 KiB,  512 lanes: two per CU
@@ -613,7 +646,7 @@ bool lde_run_fused01(const LdeTables& t, const zkir_trace_columns* trace, uint64
     unsigned grid = persist() ? cu_count() * 2 : total;
     if (grid > total) grid = total;
     hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
-                       j4_inv_m, j4_fwd_m);
+                       j4_inv_m, j4_fwd_m, L == 10);
   }
   run_strided_stages<true>(out, (uint64_t)2 * N, n_blocks, L + 1, 11, L - 10, t.tw_fwd, t.small_fwd, 11, j4_fwd_m, r8_fwd_m, r8_fwd3_m, s);
   return true;
