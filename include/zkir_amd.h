@@ -428,6 +428,26 @@ int zkir_memcheck_witness_device_mode(const zkir_trace_columns* trace, uint64_t 
 /* Host test entry of the closed forms the device witness uses (csrc/hashcall.h): the number of distinct 8-byte cells a hash call (in, len, out) touches, and in *rank the
  * position of `cell` among them in ascending order (~0 if the call does not touch it; rank may be NULL).  Returns ~0 when hashcall::in_range(in, len, out, kind) is false. */
 uint64_t zkir_hash_call_cells_host(uint64_t in_ptr, uint64_t len, uint64_t out_ptr, uint32_t kind, uint64_t cell, uint64_t* rank);
+/* (mode 4) The hash tape's and the wide tape's share of the lookup table side, as calls of their own.
+ * hash_words: a hash section in the proof's layout (host); new_bytes: per touched cell, in the section's order, the
+ * cell's bytes after its call (host, n = the section's total cell count); wide_words: a wide section [n] + 8 words
+ * per record, any record order (host); alpha, lambda: canonical E4.  Out (host, canonical): sum[4]; hh[4 * n_calls];
+ * ww[4 * n_records] in the given record order.  _launch: what zkir_prove runs on the tape its device witness built
+ * (csrc/tape_table.inl); _host: the host form (what zkir_prove runs for the hash calls of a caller's host witness).
+ * A section hashcall::parse_section rejects (with no row bound and no code segment) is ZKIR_ERR_ARGUMENT in both. */
+int zkir_tape_table_side_launch(const uint32_t* hash_words, uint64_t n_hash_words, const uint64_t* new_bytes,
+                                const uint32_t* wide_words, uint64_t n_wide_words, const uint32_t alpha[4],
+                                const uint32_t lambda[4], uint32_t sum[4], uint32_t* hh, uint32_t* ww, void* hip_stream);
+int zkir_tape_table_side_host(const uint32_t* hash_words, uint64_t n_hash_words, const uint64_t* new_bytes,
+                              const uint32_t* wide_words, uint64_t n_wide_words, const uint32_t alpha[4],
+                              const uint32_t lambda[4], uint32_t sum[4], uint32_t* hh, uint32_t* ww);
+/* the device's form of hashcall::parse_section's checks on a hash section (host words, n_real rows, the code segment
+ * [0x1000, code_end)): *code = 0 well-formed / 4 truncated / 55 an output on code bytes / 56 a malformed record — of
+ * the LOWEST failing record.  _host: parse_section itself. */
+int zkir_hash_tape_check_launch(const uint32_t* hash_words, uint64_t n_hash_words, uint64_t n_real, uint64_t code_end,
+                                int* code, void* hip_stream);
+int zkir_hash_tape_check_host(const uint32_t* hash_words, uint64_t n_hash_words, uint64_t n_real, uint64_t code_end,
+                              int* code);
 /* points pub's mode-3 fields at the witness (which must outlive the proving call) and sets pub->deferred = 3 */
 void zkir_public_inputs_set_memory(zkir_public_inputs* pub, const zkir_memcheck_witness* w);
 /* Poseidon2 sponge digest of a byte string (host): [len as four 16-bit pieces] ++ [LE 16-bit halfwords] */

@@ -104,6 +104,13 @@ extern "C" {
     fn zkir_prove_result(result: *const ZkirResult, params: *const ZkirProverParams, proof: *mut *mut u8, len: *mut usize) -> c_int;
     fn zkir_proof_bytes_free(proof: *mut u8);
     fn zkir_abi_version() -> u32;
+    // (mode 4) the tapes' share of the lookup table side and the hash tape's record checks as calls of their own (host arrays in, host arrays out)
+    pub fn zkir_tape_table_side_launch(hash_words: *const u32, n_hash_words: u64, new_bytes: *const u64, wide_words: *const u32, n_wide_words: u64, alpha: *const u32, lambda: *const u32,
+                                       sum: *mut u32, hh: *mut u32, ww: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn zkir_tape_table_side_host(hash_words: *const u32, n_hash_words: u64, new_bytes: *const u64, wide_words: *const u32, n_wide_words: u64, alpha: *const u32, lambda: *const u32,
+                                     sum: *mut u32, hh: *mut u32, ww: *mut u32) -> c_int;
+    pub fn zkir_hash_tape_check_launch(hash_words: *const u32, n_hash_words: u64, n_real: u64, code_end: u64, code: *mut c_int, stream: *mut c_void) -> c_int;
+    pub fn zkir_hash_tape_check_host(hash_words: *const u32, n_hash_words: u64, n_real: u64, code_end: u64, code: *mut c_int) -> c_int;
 }
 
 /// zkir_prover_params: the proof's mode (0 default VM mode, 1 deferred model, 2 + the I/O argument, 3 + the memory argument) and its FRI parameters

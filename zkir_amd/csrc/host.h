@@ -178,10 +178,13 @@ int memcheck_device(const zkir_trace_columns* trace, uint64_t n_real, const uint
                     std::vector<uint64_t>& cell_addr, std::vector<uint64_t>& cell_bytes, std::vector<uint32_t>& cell_time, HostPin& pin, void* hip_stream);
 // (mode 4) the same for a run WITH hash syscalls (outs: the log's zkir_hash_out records, host): also builds the proof's hash section and, in the section's cell order, every
 // touched cell's bytes AFTER its call.  The counts are known only after a first pass over the rows, so the call makes its own device allocations: the scratch (freed before
-// it returns) and HashWitness's block (the tape stays on the device for the section's chunk digests).  h_tape / h_side: pinned host copies (from `pin`).
+// it returns) and HashWitness's block (the tape, the cells' new bytes and the calls' cell-offset prefix stay on the device: the section's chunk digests, the record checks
+// and the lookup table side read them there).  h_tape: the tape's pinned host copy (from `pin`): the proof carries it.
 struct HashWitness {
-  void* d_block = nullptr;               // device: [side: n_hcells u64][tape: n_words u32]
-  const uint32_t* d_tape = nullptr; const uint32_t* h_tape = nullptr; const uint64_t* h_side = nullptr;
+  void* d_block = nullptr;               // device: [side: n_hcells u64][prefix: n_calls + 1 u64][tape: n_words u32]
+  const uint32_t* d_tape = nullptr; const uint32_t* h_tape = nullptr;
+  const uint64_t* d_side = nullptr;      // per touched cell, in the tape's order, the cell's bytes after its call
+  const uint64_t* d_prefix = nullptr;    // [k]: how many cells the calls before call k touch; [n_calls] = n_hcells
   uint64_t n_words = 0, n_hcells = 0, n_calls = 0;
   HashWitness() = default;
   HashWitness(const HashWitness&) = delete;

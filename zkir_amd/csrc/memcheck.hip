@@ -275,6 +275,11 @@ __global__ __launch_bounds__(NT) void hcells_kernel(const HashCallD* __restrict_
   const uint64_t r = h - d.hoff;                                // < d.n_cells: the next call's hoff is d.hoff + d.n_cells
   keys[d.acc_off + r] = ((hashcall::cell_at(d.in_ptr, d.len, d.out_ptr, r) >> 3) << ROW_BITS) | d.row;
 }
+// the calls' cell-offset prefix, kept for the readers of the tape behind the witness (the record checks, the lookup table side): prefix[n_calls] = the total
+__global__ __launch_bounds__(NT) void hprefix_kernel(const HashCallD* __restrict__ calls, uint32_t n_calls, uint64_t n_hcells, uint64_t* __restrict__ prefix) {
+  const uint32_t k = blockIdx.x * NT + threadIdx.x;
+  if (k <= n_calls) prefix[k] = k < n_calls ? calls[k].hoff : n_hcells;
+}
 __global__ __launch_bounds__(NT) void helem_kernel(zkir_trace_columns t, uint64_t n, const uint64_t* __restrict__ keys, const HashCallD* __restrict__ calls, const uint32_t* __restrict__ rowcall,
                                                     const zkir_hash_out* __restrict__ outs, MemElem* __restrict__ el) {
   const uint64_t j = (uint64_t)blockIdx.x * NT + threadIdx.x;
@@ -476,10 +481,11 @@ int memcheck_device_hash(const zkir_trace_columns* trace, uint64_t n_real, const
   hw.n_words = n_words; hw.n_hcells = H; hw.n_calls = n_calls;
   const char* oom = "zkir_prove (mode 4): out of device memory for the memory witness of a run with hash syscalls (its size follows the cells the calls touch)";
   if (A >> 32) { set_last_error({ZKIR_ERR_DEVICE, oom}); return ZKIR_ERR_DEVICE; }
-  if (hipMalloc(&hw.d_block, H * 8 + n_words * 4 + 256) != hipSuccess) { (void)hipGetLastError(); hw.d_block = nullptr; set_last_error({ZKIR_ERR_DEVICE, oom}); return ZKIR_ERR_DEVICE; }
-  uint64_t* d_side = (uint64_t*)hw.d_block; uint32_t* d_tape = (uint32_t*)(d_side + H);
-  hw.d_tape = d_tape;
+  if (hipMalloc(&hw.d_block, H * 8 + (n_calls + 1) * 8 + n_words * 4 + 256) != hipSuccess) { (void)hipGetLastError(); hw.d_block = nullptr; set_last_error({ZKIR_ERR_DEVICE, oom}); return ZKIR_ERR_DEVICE; }
+  uint64_t* d_side = (uint64_t*)hw.d_block; uint64_t* d_prefix = d_side + H; uint32_t* d_tape = (uint32_t*)(d_prefix + n_calls + 1);
+  hw.d_tape = d_tape; hw.d_side = d_side; hw.d_prefix = d_prefix;
   MC_OK(hipMemsetAsync(d_tape, 0, 4, s));                      // (a run whose only hash call sits on the halt row: an empty tape)
+  MC_OK(hipMemsetAsync(d_prefix, 0, 8, s));
   cell_addr.clear(); cell_bytes.clear(); cell_time.clear();
   if (A) {
     const size_t tmp_bytes = (sort_tmp_bytes(A) + 255) & ~(size_t)255;
@@ -511,6 +517,7 @@ int memcheck_device_hash(const zkir_trace_columns* trace, uint64_t n_real, const
     }
     hipLaunchKernelGGL(hrows_kernel, dim3(n_rt), dim3(NT), 0, s, *trace, n_real, d_part, d_outs, keys, d_calls, d_rowcall, mem_old, mem_told, d_flags);
     if (H) hipLaunchKernelGGL(hcells_kernel, dim3(grid_for(H)), dim3(NT), 0, s, d_calls, (uint32_t)n_calls, H, keys);
+    if (n_calls) hipLaunchKernelGGL(hprefix_kernel, dim3(grid_for(n_calls + 1)), dim3(NT), 0, s, d_calls, (uint32_t)n_calls, H, d_prefix);
     lap("keys");
     size_t tb = tmp_bytes;
     MC_OK(rocprim::radix_sort_keys(tmp, tb, keys, skeys, (size_t)A, 0, 63, s));
@@ -539,14 +546,13 @@ int memcheck_device_hash(const zkir_trace_columns* trace, uint64_t n_real, const
       memcpy(cell_addr.data(), ha, nc * 8); memcpy(cell_bytes.data(), hbv, nc * 8); memcpy(cell_time.data(), ht, nc * 4);
     }
   }
-  // the tape and the cells' new bytes: copied to the host ONCE (the proof body, the record checks and the table side read them there)
-  uint32_t* ht_ = pin.take_n<uint32_t>(n_words); uint64_t* hs_ = pin.take_n<uint64_t>(H + 1);
-  if (!ht_ || !hs_) return dev_fail("pinned staging", hipErrorOutOfMemory);
+  // the tape: copied to the host ONCE (the proof carries it); the cells' new bytes stay on the device, where the table side reads them
+  uint32_t* ht_ = pin.take_n<uint32_t>(n_words);
+  if (!ht_) return dev_fail("pinned staging", hipErrorOutOfMemory);
   MC_OK(hipMemcpyAsync(ht_, d_tape, n_words * 4, hipMemcpyDeviceToHost, s));
-  if (H) MC_OK(hipMemcpyAsync(hs_, d_side, H * 8, hipMemcpyDeviceToHost, s));
   MC_OK(hipStreamSynchronize(s));
-  hw.h_tape = ht_; hw.h_side = hs_;
-  lap("tape and cells copied");
+  hw.h_tape = ht_;
+  lap("tape copied");
   return ZKIR_OK;
 }
 

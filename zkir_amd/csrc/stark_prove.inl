@@ -1025,6 +1025,8 @@ struct StageEvents {             // RAII: released on every return path
   ~StageEvents() { if (on) for (auto& e : ev) (void)hipEventDestroy(e); }
 };
 
+#include "tape_table.inl"
+
 // the header words of a v4 proof (so::header_words): parameters, public inputs, the two boundary states read off the main trace
 void header_words(uint32_t log_n, const zkir_public_inputs& pub, const uint32_t* states, std::vector<uint32_t>& w) {      // states: 2 NS words (+ 4 counters in mode 2)
   w.clear();
@@ -1095,6 +1097,148 @@ uint32_t zkir_proof_version(void) { return air::proof_version(0); }
 uint32_t zkir_proof_version_of_mode(uint32_t mode) { return air::proof_version((int)mode); }
 
 void zkir_proof_free(uint32_t* proof) { free(proof); }
+
+// ---- (mode 4) the tapes' share of the lookup table side and the hash tape's record checks as calls of their own (include/zkir_amd.h) -----------------------------------
+}  // extern "C"
+namespace {
+struct TapeDevMem { void* p = nullptr; ~TapeDevMem() { if (p) (void)hipFree(p); } };
+int tape_refuse(const std::string& m) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT; }
+// the lookup parameters the table side reads (alpha, lambda^0 .. lambda^11), Montgomery, from canonical challenges
+bool tape_lk_of(const uint32_t alpha[4], const uint32_t lambda[4], uint32_t* lk /* air::N_LK */) {
+  if (!alpha || !lambda) return false;
+  for (int k = 0; k < 4; k++) if (alpha[k] >= bb::P || lambda[k] >= bb::P) return false;
+  for (int k = 0; k < air::N_LK; k++) lk[k] = 0;
+  E4 lam{{1, 0, 0, 0}}, l1{{lambda[0], lambda[1], lambda[2], lambda[3]}};
+  for (int k = 0; k < 4; k++) lk[air::LK_ALPHA + k] = bb::to_mont(alpha[k]);
+  for (int j = 0; j <= air::N_TUPLE; j++) { for (int k = 0; k < 4; k++) lk[air::LK_LAM + 4 * j + k] = bb::to_mont(lam.c[k]); lam = h_e_mul(lam, l1); }
+  return true;
+}
+// a wide section [n] + 8 n words (nullptr / no words: empty): its record count, or -1
+int64_t wide_section_records(const uint32_t* w, uint64_t n_words) {
+  if (!w || !n_words) return 0;
+  return n_words == 1 + 8 * (uint64_t)w[0] ? (int64_t)w[0] : -1;
+}
+void tape_outputs(const E4& T, const HashAux* hh_list, uint64_t n_hh, const HashAux* ww_list, uint64_t n_ww, uint32_t sum[4], uint32_t* hh, uint32_t* ww) {
+  const E4 t = bb::e_from_mont(T);
+  for (int k = 0; k < 4; k++) sum[k] = t.c[k];
+  for (uint64_t i = 0; i < n_hh; i++) { const E4 h = bb::e_from_mont(hh_list[i].h); for (int k = 0; k < 4; k++) hh[4 * i + k] = h.c[k]; }
+  for (uint64_t i = 0; i < n_ww; i++) { const E4 h = bb::e_from_mont(ww_list[i].h); for (int k = 0; k < 4; k++) ww[4 * i + k] = h.c[k]; }
+}
+static const uint32_t tape_no_calls[1] = {0u};
+}  // namespace
+extern "C" {
+
+int zkir_tape_table_side_host(const uint32_t* hash_words, uint64_t n_hash_words, const uint64_t* new_bytes, const uint32_t* wide_words, uint64_t n_wide_words, const uint32_t alpha[4],
+                              const uint32_t lambda[4], uint32_t sum[4], uint32_t* hh, uint32_t* ww) {
+  uint32_t lk[air::N_LK];
+  if (!hash_words || !n_hash_words) { hash_words = tape_no_calls; n_hash_words = 1; }
+  const int64_t n_wide = wide_section_records(wide_words, n_wide_words);
+  if (!sum || n_wide < 0 || !tape_lk_of(alpha, lambda, lk)) return tape_refuse("zkir_tape_table_side_host: alpha and lambda must be canonical, the wide section [n] + 8 n words, and sum not null");
+  std::vector<hashcall::Call> calls;
+  size_t used = 0;
+  const int hrc = hashcall::parse_section(hash_words, (size_t)n_hash_words, ~0ull, 0, calls, &used);
+  if (hrc || used != n_hash_words) { char m[160]; snprintf(m, sizeof m, "zkir_tape_table_side_host: the hash section is malformed (check %d)", hrc ? hrc : 4); return tape_refuse(m); }
+  uint64_t cells = 0;
+  for (const auto& c : calls) cells += c.cells.size();
+  if ((cells && !new_bytes) || (!calls.empty() && !hh) || (n_wide && !ww)) return tape_refuse("zkir_tape_table_side_host: new_bytes / hh / ww must not be null where the sections have entries");
+  std::vector<HashAux> ha, wa;
+  E4 T = bb::e_zero();
+  if (!calls.empty()) T = bb::e_add(T, hash_table_side_host(calls, new_bytes, lk, ha));
+  if (n_wide) T = bb::e_add(T, wide_table_side_host(wide_words + 1, (size_t)n_wide, lk, wa));
+  tape_outputs(T, ha.data(), ha.size(), wa.data(), wa.size(), sum, hh, ww);
+  return ZKIR_OK;
+}
+
+int zkir_tape_table_side_launch(const uint32_t* hash_words, uint64_t n_hash_words, const uint64_t* new_bytes, const uint32_t* wide_words, uint64_t n_wide_words, const uint32_t alpha[4],
+                                const uint32_t lambda[4], uint32_t sum[4], uint32_t* hh, uint32_t* ww, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t lk[air::N_LK];
+  if (!hash_words || !n_hash_words) { hash_words = tape_no_calls; n_hash_words = 1; }
+  const int64_t n_wide = wide_section_records(wide_words, n_wide_words);
+  if (!sum || n_wide < 0 || !tape_lk_of(alpha, lambda, lk)) return tape_refuse("zkir_tape_table_side_launch: alpha and lambda must be canonical, the wide section [n] + 8 n words, and sum not null");
+  std::vector<uint64_t> prefix((size_t)std::min<uint64_t>(hash_words[0], n_hash_words / 8) + 2);
+  const TapeWalk wk = hash_tape_walk(hash_words, n_hash_words, prefix.data());
+  if (wk.cut || wk.used != n_hash_words) return tape_refuse("zkir_tape_table_side_launch: the hash section is malformed (check 4)");
+  const uint64_t n_calls = wk.n_calls, H = wk.cells;
+  if ((H && !new_bytes) || (n_calls && !hh) || (n_wide && !ww)) return tape_refuse("zkir_tape_table_side_launch: new_bytes / hh / ww must not be null where the sections have entries");
+  E4 T = bb::e_zero();
+  if (!n_calls && !n_wide) { tape_outputs(T, nullptr, 0, nullptr, 0, sum, hh, ww); return ZKIR_OK; }      // (nothing to launch)
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_tape = 0, o_prefix = o_tape + al(n_hash_words * 4), o_side = o_prefix + al((n_calls + 1) * 8), o_wide = o_side + al(H * 8 + 8), o_lk = o_wide + al((size_t)n_wide * 32 + 32),
+               o_hlist = o_lk + al(sizeof lk), o_wlist = o_hlist + al(n_calls * sizeof(HashAux) + 32), o_part = o_wlist + al((size_t)n_wide * sizeof(HashAux) + 32),
+               o_check = o_part + al(2 * (size_t)TAPE_MAX_BLOCKS * sizeof(E4)), total = o_check + 256;
+  TapeDevMem dm;
+  HIP_OK(hipMalloc(&dm.p, total));
+  unsigned char* d = (unsigned char*)dm.p;
+  zkir::HostPin pin;
+  auto up = [&](size_t off, const void* src, size_t bytes) -> hipError_t {
+    if (!bytes) return hipSuccess;
+    void* h = pin.take(bytes);
+    if (!h) return hipErrorOutOfMemory;
+    memcpy(h, src, bytes);
+    return hipMemcpyAsync(d + off, h, bytes, hipMemcpyHostToDevice, s);
+  };
+  HIP_OK(up(o_tape, hash_words, n_hash_words * 4)); HIP_OK(up(o_prefix, prefix.data(), (n_calls + 1) * 8)); HIP_OK(up(o_side, new_bytes, H * 8));
+  HIP_OK(up(o_wide, wide_words + (n_wide ? 1 : 0), (size_t)n_wide * 32)); HIP_OK(up(o_lk, lk, sizeof lk));
+  // the records must be what the kernels take them for (every count word the walk's, every field in range): the checks of hashcall::parse_section, with no row bound and no code segment
+  int code = 0;
+  int rc = hash_tape_check_run((const uint32_t*)(d + o_tape), (const uint64_t*)(d + o_prefix), n_calls, n_calls, ~0ull, 0, (unsigned long long*)(d + o_check), pin, s, &code);
+  if (rc) return rc;
+  if (code) { char m[160]; snprintf(m, sizeof m, "zkir_tape_table_side_launch: the hash section is malformed (check %d)", code); return tape_refuse(m); }
+  TapePartials hp, wp;
+  rc = hash_table_side_enqueue((const uint32_t*)(d + o_tape), (const uint64_t*)(d + o_prefix), (const uint64_t*)(d + o_side), n_calls, H, (const uint32_t*)(d + o_lk), (HashAux*)(d + o_hlist),
+                               (E4*)(d + o_part), pin, s, &hp);
+  if (rc) return rc;
+  rc = wide_table_side_enqueue((const uint32_t*)(d + o_wide), (uint32_t)n_wide, (const uint32_t*)(d + o_lk), (HashAux*)(d + o_wlist), (E4*)(d + o_part) + TAPE_MAX_BLOCKS, pin, s, &wp);
+  if (rc) return rc;
+  HashAux* hl = pin.take_n<HashAux>((size_t)n_calls + 1); HashAux* wl = pin.take_n<HashAux>((size_t)n_wide + 1);
+  if (!hl || !wl) HIP_OK(hipErrorOutOfMemory);
+  if (n_calls) HIP_OK(hipMemcpyAsync(hl, d + o_hlist, n_calls * sizeof(HashAux), hipMemcpyDeviceToHost, s));
+  if (n_wide) HIP_OK(hipMemcpyAsync(wl, d + o_wlist, (size_t)n_wide * sizeof(HashAux), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (check_launch("zkir_tape_table_side_launch") != ZKIR_OK) return ZKIR_ERR_DEVICE;
+  hp.add_to(T); wp.add_to(T);
+  tape_outputs(T, hl, n_calls, wl, (uint64_t)n_wide, sum, hh, ww);
+  return ZKIR_OK;
+}
+
+int zkir_hash_tape_check_host(const uint32_t* hash_words, uint64_t n_hash_words, uint64_t n_real, uint64_t code_end, int* code) {
+  if (!code || (!hash_words && n_hash_words)) return tape_refuse("zkir_hash_tape_check_host: null argument");
+  std::vector<hashcall::Call> calls;
+  size_t used = 0;
+  *code = hashcall::parse_section(hash_words, (size_t)n_hash_words, n_real, code_end, calls, &used);
+  return ZKIR_OK;
+}
+
+int zkir_hash_tape_check_launch(const uint32_t* hash_words, uint64_t n_hash_words, uint64_t n_real, uint64_t code_end, int* code, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!code || (!hash_words && n_hash_words)) return tape_refuse("zkir_hash_tape_check_launch: null argument");
+  if (n_hash_words < 1) { *code = 4; return ZKIR_OK; }
+  if (hash_words[0] > n_real) { *code = 56; return ZKIR_OK; }
+  std::vector<uint64_t> prefix((size_t)std::min<uint64_t>(hash_words[0], n_hash_words / 8) + 2);
+  const TapeWalk wk = hash_tape_walk(hash_words, n_hash_words, prefix.data());
+  const uint64_t n_check = wk.n_full + (wk.header_only ? 1 : 0), words = wk.used + (wk.header_only ? 8 : 0);
+  unsigned long long best = wk.cut && !wk.header_only ? ((unsigned long long)wk.n_full << 8) | 4u : ~0ull;      // (the walk left the buffer before record n_full's header)
+  if (n_check) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_prefix = al(words * 4), o_check = o_prefix + al((n_check + 1) * 8);
+    TapeDevMem dm;
+    HIP_OK(hipMalloc(&dm.p, o_check + 256));
+    unsigned char* d = (unsigned char*)dm.p;
+    zkir::HostPin pin;
+    void* ht = pin.take(words * 4); void* hp = pin.take(n_check * 8);
+    if (!ht || !hp) HIP_OK(hipErrorOutOfMemory);
+    memcpy(ht, hash_words, words * 4); memcpy(hp, prefix.data(), n_check * 8);
+    HIP_OK(hipMemcpyAsync(d, ht, words * 4, hipMemcpyHostToDevice, s)); HIP_OK(hipMemcpyAsync(d + o_prefix, hp, n_check * 8, hipMemcpyHostToDevice, s));
+    int dcode = 0; uint64_t dcall = ~0ull;
+    const int rc = hash_tape_check_run((const uint32_t*)d, (const uint64_t*)(d + o_prefix), n_check, wk.n_full, n_real, code_end, (unsigned long long*)(d + o_check), pin, s, &dcode, &dcall);
+    if (rc) return rc;
+    if (check_launch("zkir_hash_tape_check_launch") != ZKIR_OK) return ZKIR_ERR_DEVICE;
+    if (dcode) best = std::min(best, ((unsigned long long)dcall << 8) | (unsigned)dcode);
+  }
+  *code = best == ~0ull ? 0 : (int)(best & 0xFF);
+  return ZKIR_OK;
+}
 
 // Full proof of the run whose K1 output is `trace` (pub->n_real executed rows, padded to 2^ctx.log_n).  Phases are timed with HIP events
 // when stage_ms != NULL (NINE floats): [0] main trace (+ lookup indices), [1] LDE, [2] trace Merkle, [3] lookup argument (inverse tables, aux trace, its LDE and
@@ -1179,7 +1323,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   const size_t SEC_WORDS = std::max<size_t>(8 * (size_t)CELL_CAP, !WIDE ? 0 : HASH_DEV ? (size_t)hw.n_words / 64 + 128 : (size_t)pub->hash_section_words + (size_t)pub->hash_section_words / 100) + 4096;   // (the memory section, then the hash section, each with its chunk digests behind it; the device-built tape stays in its own block: only its digests come here)
   {                                               // workspace: 12 W (M + L) + 440 (trees, quotient, weights, FRI) bytes per row, allocated once per context
     static_assert(WMX % 8 == 0 && air::W_COMMITTED_DEFAULT % 8 == 0, "the main trace fills whole B8 blocks");
-    const size_t want = (size_t)(12 * WM + 12 * WA + 16 + 544 + (IO ? 48 : 0) + (MEM ? 48 : 0) + (WIDE ? 8 : 0)) * N + (size_t)air::MAX_NUM_QUERIES * 64 * 1024 + (8u << 20) + (size_t)n_code * 24 + (1u << 16) +
+    const size_t want = (size_t)(12 * WM + 12 * WA + 16 + 544 + (IO ? 48 : 0) + (MEM ? 48 : 0) + (WIDE ? 8 : 0)) * N + (size_t)air::MAX_NUM_QUERIES * 64 * 1024 + (8u << 20) + (size_t)n_code * 24 + (1u << 16) + (WIDE ? (1u << 17) : 0) +
                         (IO ? (size_t)pub->n_inputs * 8 : 0) + (MEM ? (size_t)air::MEM_MULT * 24 + (size_t)CELL_CAP * 28 + SEC_WORDS * 4 + blob_len + (1u << 16) : 0);
     if (c->arena_size < want) {
       if (c->arena) (void)hipFree(c->arena);
@@ -1220,13 +1364,14 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   IoEntry* dIo = nullptr; uint32_t* dIoCount = nullptr; uint64_t* dInputs = nullptr; uint32_t* dIoScratch = nullptr;
   uint64_t* dMemOld = nullptr; uint32_t* dMemTold = nullptr; uint4* dMemSide = nullptr; E4* dInvMem = nullptr; uint2* dWideSide = nullptr;
   uint64_t *dCellAddr = nullptr, *dCellBytes = nullptr; uint32_t* dCellTime = nullptr; uint8_t* dImage = nullptr; E4* dCellPart = nullptr; uint32_t* dSec = nullptr;
+  E4* dTapePart = nullptr; unsigned long long* dTapeCheck = nullptr;
   HIP_OK(ar.take(&dPP, 1)); HIP_OK(ar.take(&dState, 16)); HIP_OK(ar.take(&dBest, 4)); HIP_OK(ar.take(&dBound, 2 * NS + 4)); HIP_OK(ar.take(&dBad, 1));
   if (IO) { HIP_OK(ar.take(&dIo, N)); HIP_OK(ar.take(&dIoCount, 4)); HIP_OK(ar.take(&dInputs, (size_t)pub->n_inputs + 1)); HIP_OK(ar.take(&dIoScratch, 2 * N + 2 * (N / 1024 + 2))); }
   if (MEM) {
     HIP_OK(ar.take(&dMemOld, N)); HIP_OK(ar.take(&dMemTold, N)); HIP_OK(ar.take(&dMemSide, 2 * N)); HIP_OK(ar.take(&dInvMem, air::MEM_MULT));
     HIP_OK(ar.take(&dCellAddr, CELL_CAP)); HIP_OK(ar.take(&dCellBytes, CELL_CAP)); HIP_OK(ar.take(&dCellTime, CELL_CAP)); HIP_OK(ar.take(&dImage, (size_t)blob_len + 1)); HIP_OK(ar.take(&dCellPart, CELL_CAP / NT + 1));
     HIP_OK(ar.take(&dSec, SEC_WORDS));                      // the memory section (seven words per touched cell) and its chunk digests
-    if (WIDE) HIP_OK(ar.take(&dWideSide, N));
+    if (WIDE) { HIP_OK(ar.take(&dWideSide, N)); HIP_OK(ar.take(&dTapePart, 2 * (size_t)TAPE_MAX_BLOCKS)); HIP_OK(ar.take(&dTapeCheck, 1)); }   // (the tapes' table side: two kernels' partial sums; the record checks' result)
   }
   HIP_OK(ar.take(&dM, WM * N)); HIP_OK(ar.take(&dL, WM * N2)); HIP_OK(ar.take(&dTree, 4 * (2 * N2 - 1)));
   HIP_OK(ar.take(&dA, WA * N)); HIP_OK(ar.take(&dAL, WA * N2)); HIP_OK(ar.take(&dATree, 4 * (2 * N2 - 1)));
@@ -1312,6 +1457,9 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     if ((size_t)nw * 8 > SEC_WORDS) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more wide-tape rows than the workspace holds"}); return ZKIR_ERR_OTHER; }
     wrecs.resize(nw);
     HIP_OK(hipMemcpyAsync(wrecs.data(), dSec, (size_t)nw * 32, hipMemcpyDeviceToHost, s));
+    // the records stay on the device for the table side (wide_table_side_kernel), in the order they were appended: moved into the quotient's buffer, which nothing
+    // writes before the aux trace is committed (nw <= N records of 32 bytes in 64 N bytes) — the section buffer is about to hold the proof's sections
+    HIP_OK(hipMemcpyAsync(dQ, dSec, (size_t)nw * 32, hipMemcpyDeviceToDevice, s));
     HIP_OK(hipStreamSynchronize(s));
     std::sort(wrecs.begin(), wrecs.end(), [](const WideRec& x, const WideRec& y) { return x.w[0] < y.w[0]; });
   }
@@ -1364,20 +1512,22 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     ch.observe_n(sec_dg.data(), sec_dg.size());
   }
   // (mode 4) the hash calls: the tape the proof carries (from the caller's host witness), checked as the verifier will check it, observed like the memory section
-  std::vector<hashcall::Call> hcalls;
+  std::vector<hashcall::Call> hcalls;                          // (the caller's host witness only: the device-built tape is never parsed into calls)
+  uint64_t n_hash_calls = 0;
   static const uint32_t no_calls[1] = {0u};
   struct { const uint32_t* p; size_t n; const uint32_t* data() const { return p; } size_t size() const { return n; } } hash_sec{no_calls, 1};   // a VIEW of the caller's tape (a 2^22-cycle chain: 134 MB — not copied)
   const double t_hash0 = since(t_entry);
   if (WIDE) {
     if (HASH_DEV) {                                             // the tape built on the device: its host copy is checked as the verifier will check it (a trace that is not a run of the VM gets no proof)
-      size_t used = 0;
-      const int hrc = hashcall::parse_section(hw.h_tape, (size_t)hw.n_words, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, hcalls, &used);
+      // hashcall::parse_section's checks, where the tape lies (hash_tape_check_kernel); its length is 1 + 8 calls + 5 cells by construction
+      int hrc = 0;
+      rc = hash_tape_check_run(hw.d_tape, hw.d_prefix, hw.n_calls, hw.n_calls, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, dTapeCheck, pin, s, &hrc); if (rc) return rc;
       if (hrc == 55) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: a hash syscall of the run writes its output where it overlaps the code segment: such a run has no mode-4 proof"}); return ZKIR_ERR_ARGUMENT; }
-      if (hrc || used != hw.n_words) {
-        char m[200]; snprintf(m, sizeof m, "zkir_prove: the hash tape built from the trace is malformed (check %d): the trace is not a run of the VM", hrc ? hrc : 4);
+      if (hrc) {
+        char m[200]; snprintf(m, sizeof m, "zkir_prove: the hash tape built from the trace is malformed (check %d): the trace is not a run of the VM", hrc);
         zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
       }
-      hash_sec.p = hw.h_tape; hash_sec.n = used;
+      hash_sec.p = hw.h_tape; hash_sec.n = (size_t)hw.n_words; n_hash_calls = hw.n_calls;
     } else if (pub->hash_section && pub->hash_section_words) {
       size_t used = 0;
       const int hrc = hashcall::parse_section(pub->hash_section, (size_t)pub->hash_section_words, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, hcalls, &used);
@@ -1385,12 +1535,12 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
         char m[160]; snprintf(m, sizeof m, "zkir_prove: the hash section of the public inputs is malformed (check %d): build it with zkir_memcheck_witness_of_mode(.., 4, ..)", hrc ? hrc : 4);
         zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
       }
-      hash_sec.p = pub->hash_section; hash_sec.n = used;
+      hash_sec.p = pub->hash_section; hash_sec.n = used; n_hash_calls = hcalls.size();
     }
-    if (hcalls.size() != io_counts[1]) {
+    if (n_hash_calls != io_counts[1]) {
       char m[256];
       snprintf(m, sizeof m, "zkir_prove: the run makes %u hash syscalls and the public inputs' hash section records %llu: a run with hash syscalls is proven (mode 4) from the host "
-                            "witness (zkir_memcheck_witness_of_mode(.., 4, ..) + zkir_public_inputs_set_memory)", io_counts[1], (unsigned long long)hcalls.size());
+                            "witness (zkir_memcheck_witness_of_mode(.., 4, ..) + zkir_public_inputs_set_memory)", io_counts[1], (unsigned long long)n_hash_calls);
       zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
     }
     const size_t n_chunks_sec = (hash_sec.size() + SECTION_CHUNK - 1) / SECTION_CHUNK;
@@ -1411,7 +1561,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     } else {                                                                         // (more records than the workspace holds: the digests on the host)
       for (size_t at = 0; at < hash_sec.size(); at += SECTION_CHUNK) { uint32_t dg[4]; hash_elems_host(c->consts, hash_sec.data() + at, std::min((size_t)SECTION_CHUNK, hash_sec.size() - at), dg); ch.observe_n(dg, 4); }
     }
-    if (dbg_t) fprintf(stderr, "zkir_prove mode 4: hash section (%zu calls, %zu words) parsed, hashed and observed in %.2f ms\n", hcalls.size(), hash_sec.size(), since(t_entry) - t_hash0);
+    if (dbg_t) fprintf(stderr, "zkir_prove mode 4: hash section (%llu calls, %zu words) %s, hashed and observed in %.2f ms\n", (unsigned long long)n_hash_calls, hash_sec.size(),
+                       HASH_DEV ? "checked on the device" : "parsed", since(t_entry) - t_hash0);
   }
   // (mode 4 d) the wide tape as a proof section: [n] then the records, eight words each; checked as the verifier will check it, observed like the hash section
   std::vector<uint32_t> wide_sec;
@@ -1505,92 +1656,35 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       for (uint64_t k = cn[0]; k < cn[2]; k++) term(k, pub->outputs[k], 2);
       for (uint64_t k = cn[1]; k < cn[3]; k++) term(k, pub->inputs[k], 3);
     }
-    std::vector<HashAux> hash_aux;                             // (mode 4) the hash rows' helper values HH, to be scattered into the aux trace below
-    if (WIDE && !hcalls.empty()) {
-      // the hash calls' share of the table side, formed like the verifier will form it (verify.cpp; oracle: so::hash_table_sum): + 1 / (alpha - fp(call)) per call, and the call's
-      // memory accesses, which no row states: per touched cell - 1 / (alpha - fp(cell, told, old bytes)) + 1 / (alpha - fp(cell, cycle + 1, new bytes)).  One batch inversion.
-      E4 lamv[air::N_TUPLE + 1];
-      for (int j = 0; j <= air::N_TUPLE; j++) for (int c4 = 0; c4 < 4; c4++) lamv[j].c[c4] = pp->lk[air::LK_LAM + 4 * j + c4];
-      E4 alpha_lm; for (int c4 = 0; c4 < 4; c4++) alpha_lm.c[c4] = pp->lk[air::LK_ALPHA + c4];
-      auto mem_d = [&](uint64_t addr, uint32_t t, uint64_t bytes) {
-        E4 fp = bb::e_mul_fm(lamv[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_MEM));
-        fp.c[0] = bb::add(fp.c[0], bb::to_mont((uint32_t)(addr & 0xFFFFF)));
-        fp = bb::e_add(fp, bb::e_mul_fm(lamv[1], bb::to_mont((uint32_t)((addr >> 20) & 0xFFFFF))));
-        fp = bb::e_add(fp, bb::e_mul_fm(lamv[2], bb::to_mont(t)));
-        for (int k = 0; k < 8; k++) fp = bb::e_add(fp, bb::e_mul_fm(lamv[3 + k], bb::to_mont((uint32_t)((bytes >> (8 * k)) & 0xFF))));
-        return bb::e_sub(alpha_lm, fp);
-      };
-      hash_aux.resize(hcalls.size());
-      std::vector<uint64_t> side_off;                            // (device witness) where a call's cells start in the side array of new bytes: no message gather, no digest here
-      if (HASH_DEV) { side_off.resize(hcalls.size()); uint64_t o = 0; for (size_t ci = 0; ci < hcalls.size(); ci++) { side_off[ci] = o; o += hcalls[ci].cells.size(); } }
-      const unsigned parts = hashcall::parts_for(hcalls.size());
-      std::vector<E4> Tpart(parts, bb::e_zero());
-      hashcall::for_calls(hcalls.size(), parts, [&](unsigned part, size_t lo, size_t hi) {        // (host threads: 175 k calls at 2^20 rows of the SHA chain are ~1 s on one core)
-        std::vector<E4> d; std::vector<int8_t> sign; std::vector<uint64_t> nb;
-        for (size_t ci = lo; ci < hi; ci++) {
-          const hashcall::Call& hc = hcalls[ci];
-          const uint32_t e[11] = {(uint32_t)(hc.cycle % bb::P), (uint32_t)(hc.in_ptr & 0xFFFFF), (uint32_t)((hc.in_ptr >> 20) & 0xFFFFF), (uint32_t)(hc.in_ptr >> 40), (uint32_t)(hc.len & 0xFFFFF),
-                                  (uint32_t)((hc.len >> 20) & 0xFFFFF), (uint32_t)(hc.len >> 40), (uint32_t)(hc.out_ptr & 0xFFFFF), (uint32_t)((hc.out_ptr >> 20) & 0xFFFFF), (uint32_t)(hc.out_ptr >> 40), hc.kind};
-          E4 fp = bb::e_mul_fm(lamv[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_HASH));
-          for (int j = 0; j < 11; j++) fp = bb::e_add(fp, bb::e_mul_fm(lamv[j], bb::to_mont(e[j])));
-          d.push_back(bb::e_sub(alpha_lm, fp)); sign.push_back(2);                                // (2: a call's own entry — its inverse is also the row's HH)
-          const uint64_t* nbp;
-          if (HASH_DEV) nbp = hw.h_side + side_off[ci]; else { hashcall::new_bytes(hc, nb); nbp = nb.data(); }
-          for (size_t k = 0; k < hc.cells.size(); k++) {
-            d.push_back(mem_d(hc.cells[k].addr, hc.cells[k].t, hc.cells[k].bytes)); sign.push_back(-1);
-            d.push_back(mem_d(hc.cells[k].addr, (uint32_t)((hc.cycle + 1) % bb::P), nbp[k])); sign.push_back(1);
-          }
-        }
-        std::vector<E4> pre(d.size());
-        E4 acc = bb::e_one_m();
-        for (size_t i = 0; i < d.size(); i++) { pre[i] = acc; acc = bb::e_mul_m(acc, d[i]); }
-        E4 inv = bb::e_inv_m(acc), Tp = bb::e_zero();
-        size_t call = hi;
-        for (size_t i = d.size(); i-- > 0;) {
-          const E4 di = bb::e_mul_m(inv, pre[i]);
-          inv = bb::e_mul_m(inv, d[i]);
-          if (sign[i] < 0) Tp = bb::e_sub(Tp, di); else Tp = bb::e_add(Tp, di);
-          if (sign[i] == 2) { call--; hash_aux[call].row = (uint32_t)hcalls[call].cycle; hash_aux[call].pad[0] = hash_aux[call].pad[1] = hash_aux[call].pad[2] = 0; hash_aux[call].h = di; }
-        }
-        Tpart[part] = Tp;
-      });
-      for (const E4& tp : Tpart) T = bb::e_add(T, tp);
-      if (dbg_t) fprintf(stderr, "zkir_prove mode 4: the hash calls' table side (%u host threads) at %.2f ms\n", parts, since(t_entry));
-    }
-    std::vector<HashAux> wide_aux;                             // (mode 4 d) the wide-tape rows' helper values WW
-    if (WIDE && !wrecs.empty()) {
-      // the wide tape's share of the table side, formed like the verifier will form it (verify.cpp; oracle: so::wide_table_sum): + 1 / (alpha - fp(cycle, rs1, rs2, the
-      // reference's result, opcode)) per record — the result is computed HERE (air::wide_result); the inverse is also the row's WW.  One batch inversion.
-      E4 lamv[air::N_TUPLE + 1];
-      for (int j = 0; j <= air::N_TUPLE; j++) for (int c4 = 0; c4 < 4; c4++) lamv[j].c[c4] = pp->lk[air::LK_LAM + 4 * j + c4];
-      E4 alpha_lm; for (int c4 = 0; c4 < 4; c4++) alpha_lm.c[c4] = pp->lk[air::LK_ALPHA + c4];
-      wide_aux.resize(wrecs.size());
-      const unsigned parts = hashcall::parts_for(wrecs.size() / 4);
-      std::vector<E4> Tpart(parts, bb::e_zero());
-      hashcall::for_calls(wrecs.size(), parts, [&](unsigned part, size_t lo, size_t hi) {        // (host threads: a run with 2^18 tape rows is ~50 ms on one core)
-        std::vector<E4> d(hi - lo), pre(hi - lo);
-        for (size_t k = lo; k < hi; k++) {
-          const uint32_t* r = wrecs[k].w;
-          const uint64_t a = (uint64_t)r[1] | ((uint64_t)r[2] << 20) | ((uint64_t)r[3] << 40), b = (uint64_t)r[4] | ((uint64_t)r[5] << 20) | ((uint64_t)r[6] << 40);
-          const uint64_t y = air::wide_result(r[7], a, b);
-          const uint32_t e[11] = {r[0] % bb::P, r[1], r[2], r[3], r[4], r[5], r[6], (uint32_t)(y & 0xFFFFF), (uint32_t)((y >> 20) & 0xFFFFF), (uint32_t)(y >> 40), r[7]};
-          E4 fp = bb::e_mul_fm(lamv[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_WIDE));
-          for (int j = 0; j < 11; j++) fp = bb::e_add(fp, bb::e_mul_fm(lamv[j], bb::to_mont(e[j])));
-          d[k - lo] = bb::e_sub(alpha_lm, fp);
-        }
-        E4 acc = bb::e_one_m(), Tp = bb::e_zero();
-        for (size_t k = 0; k < d.size(); k++) { pre[k] = acc; acc = bb::e_mul_m(acc, d[k]); }
-        E4 inv = bb::e_inv_m(acc);
-        for (size_t k = d.size(); k-- > 0;) {
-          const E4 dk = bb::e_mul_m(inv, pre[k]);
-          inv = bb::e_mul_m(inv, d[k]);
-          Tp = bb::e_add(Tp, dk);
-          HashAux& x = wide_aux[lo + k];
-          x.row = wrecs[lo + k].w[0]; x.pad[0] = x.pad[1] = x.pad[2] = 0; x.h = dk;
-        }
-        Tpart[part] = Tp;
-      });
-      for (const E4& tp : Tpart) T = bb::e_add(T, tp);
+    // (mode 4) the tapes' share of the table side, formed like the verifier will form it (verify.cpp; oracle: so::hash_table_sum, so::wide_table_sum), and the rows' helper
+    // values HH / WW as lists of (row, value), scattered into the aux trace below once T is known.  The lists lie in the section buffer (free again: 32 N bytes), the hash
+    // rows' first, the wide-tape rows' behind it: a row is never both.  From the device witness everything is formed where the tape lies (tape_table.inl); a caller's host
+    // witness brings no new bytes, so its hash calls go through the host function (a digest per call) — its wide tape through the kernel all the same.
+    std::vector<HashAux> hash_aux;                             // (the host witness's hash rows only)
+    const uint32_t n_wide = (uint32_t)wrecs.size();
+    const size_t wide_aux_off = ((size_t)n_hash_calls * sizeof(HashAux) + 255) & ~(size_t)255;
+    HashAux* dHashAux = reinterpret_cast<HashAux*>(dSec);
+    HashAux* dWideAux = reinterpret_cast<HashAux*>(reinterpret_cast<char*>(dSec) + wide_aux_off);
+    if (WIDE && (n_hash_calls || n_wide)) {
+      if (n_hash_calls * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more hash calls than the workspace holds"}); return ZKIR_ERR_OTHER; }
+      if (n_wide && wide_aux_off + (size_t)n_wide * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more wide-tape rows than the workspace holds"}); return ZKIR_ERR_OTHER; }
+      const double t_side0 = since(t_entry);
+      TapePartials hash_part, wide_part;
+      if (HASH_DEV) { rc = hash_table_side_enqueue(hw.d_tape, hw.d_prefix, hw.d_side, hw.n_calls, hw.n_hcells, dPP->lk, dHashAux, dTapePart, pin, s, &hash_part); if (rc) return rc; }
+      rc = wide_table_side_enqueue(dQ, n_wide, dPP->lk, dWideAux, dTapePart + TAPE_MAX_BLOCKS, pin, s, &wide_part); if (rc) return rc;
+      unsigned host_parts = 0;
+      if (!HASH_DEV && !hcalls.empty()) {                      // (beside the wide tape's kernel)
+        T = bb::e_add(T, hash_table_side_host(hcalls, nullptr, pp->lk, hash_aux, &host_parts));
+        HIP_OK(h2d(dHashAux, hash_aux.data(), hash_aux.size() * sizeof(HashAux)));
+      }
+      HIP_OK(hipStreamSynchronize(s));
+      hash_part.add_to(T); wide_part.add_to(T);
+      if (dbg_t) {
+        if (HASH_DEV) fprintf(stderr, "zkir_prove mode 4: table side of %llu hash calls (%llu cells) and %u wide-tape records on the device (%u + %u workgroups) in %.2f ms, at %.2f ms\n",
+                              (unsigned long long)n_hash_calls, (unsigned long long)hw.n_hcells, n_wide, hash_part.n, wide_part.n, since(t_entry) - t_side0, since(t_entry));
+        else fprintf(stderr, "zkir_prove mode 4: table side of %llu hash calls on the host (%u threads) and %u wide-tape records on the device (%u workgroups) in %.2f ms, at %.2f ms\n",
+                     (unsigned long long)n_hash_calls, host_parts, n_wide, wide_part.n, since(t_entry) - t_side0, since(t_entry));
+      }
     }
     const E4 tn = bb::e_mul_fm(T, bb::to_mont(bb::inv((uint32_t)(N % bb::P))));
     for (int k = 0; k < 4; k++) pp->lk[air::LK_TN + k] = tn.c[k];
@@ -1603,19 +1697,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     if (MEM) hipLaunchKernelGGL(mem_aux_kernel, dim3(grid_for(N)), dim3(NT), 0, s, dSide, dMemSide, N, dInvRc, dInvMem, dPP, dA, dWideSide);   // P0..P8, HMR, HMW, FPN of every row
     if (WIDE) {                                               // the hash-call helpers HH (and the block's four padding columns): zero but on the hash-syscall rows
       HIP_OK(hipMemsetAsync(dA + (size_t)(air::A_HH / 8) * N * 8, 0, (size_t)N * 32, s));
-      if (!hash_aux.empty()) {
-        if (hash_aux.size() * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more hash calls than the workspace holds"}); return ZKIR_ERR_OTHER; }
-        HashAux* dHashAux = reinterpret_cast<HashAux*>(dSec);   // (the section buffer is free again: 32 N bytes)
-        HIP_OK(h2d(dHashAux, hash_aux.data(), hash_aux.size() * sizeof(HashAux)));
-        hipLaunchKernelGGL(hash_aux_kernel, dim3(grid_for(hash_aux.size())), dim3(NT), 0, s, dHashAux, (uint32_t)hash_aux.size(), N, dA, 0u);
-      }
-      if (!wide_aux.empty()) {                                  // WW of the wide-tape rows (behind the hash rows' list in the same buffer: a row is never both)
-        const size_t off = (hash_aux.size() * sizeof(HashAux) + 255) & ~(size_t)255;
-        if (off + wide_aux.size() * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more wide-tape rows than the workspace holds"}); return ZKIR_ERR_OTHER; }
-        HashAux* dWideAux = reinterpret_cast<HashAux*>(reinterpret_cast<char*>(dSec) + off);
-        HIP_OK(h2d(dWideAux, wide_aux.data(), wide_aux.size() * sizeof(HashAux)));
-        hipLaunchKernelGGL(hash_aux_kernel, dim3(grid_for(wide_aux.size())), dim3(NT), 0, s, dWideAux, (uint32_t)wide_aux.size(), N, dA, 1u);
-      }
+      if (n_hash_calls) hipLaunchKernelGGL(hash_aux_kernel, dim3(grid_for(n_hash_calls)), dim3(NT), 0, s, dHashAux, (uint32_t)n_hash_calls, N, dA, 0u);
+      if (n_wide) hipLaunchKernelGGL(hash_aux_kernel, dim3(grid_for(n_wide)), dim3(NT), 0, s, dWideAux, n_wide, N, dA, 1u);     // WW of the wide-tape rows
     }
     const uint32_t n_scan = (uint32_t)((N + SCAN_ROWS - 1) / SCAN_ROWS);
     hipLaunchKernelGGL(scan_local_kernel, dim3(n_scan), dim3(NT), 0, s, dA, N, dSums);

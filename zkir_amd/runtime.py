@@ -214,6 +214,48 @@ def memcheck_witness_device(trace, log: "DeltaLog", program, mode: int = 4, hash
     return {"mem_old": old, "mem_told": told, "cell_addr": ca[:k], "cell_bytes": cb[:k], "cell_time": ct[:k], "hash_section": hs[:max(1, int(nw.value))]}
 
 
+def tape_table_side(hash_section, new_bytes, wide_section, alpha, lam, device: bool = True, stream=None) -> dict:
+    """zkir_tape_table_side_launch / _host: (mode 4) the hash tape's and the wide tape's share of the lookup table side.  hash_section: a hash section in the proof's layout;
+    new_bytes: per touched cell, in the section's order, the cell's bytes after its call; wide_section: [n] + 8 words per record, any record order; alpha, lam: canonical E4
+    (four words each).  Returns {"sum": [4], "hh": [n_calls, 4], "ww": [n_records, 4]}, canonical words.  device=False: the host form."""
+    hs = np.ascontiguousarray(hash_section if hash_section is not None and len(hash_section) else [0], dtype=np.uint32)
+    ws = np.ascontiguousarray(wide_section if wide_section is not None and len(wide_section) else [0], dtype=np.uint32)
+    nb = np.ascontiguousarray(new_bytes if new_bytes is not None else [], dtype=np.uint64)
+    a, l = np.ascontiguousarray(alpha, dtype=np.uint32), np.ascontiguousarray(lam, dtype=np.uint32)
+    if a.shape != (4,) or l.shape != (4,):
+        raise ValueError("alpha and lam are four words each")
+    n_calls, q, cells = int(hs[0]), 1, 0                          # the arrays the call writes are sized by the sections' own counts: walked here, checked by the call
+    for _ in range(n_calls):
+        if q + 8 > len(hs):
+            raise ValueError("the hash section is truncated")
+        k = int(hs[q + 7]); cells += k; q += 8 + 5 * k
+    if q != len(hs) or cells != len(nb):
+        raise ValueError(f"the hash section has {len(hs)} words and states {cells} touched cells in {q} words; new_bytes has {len(nb)} entries")
+    if len(ws) != 1 + 8 * int(ws[0]):
+        raise ValueError("the wide section is [n] + 8 words per record")
+    out = {"sum": np.zeros(4, np.uint32), "hh": np.zeros((n_calls, 4), np.uint32), "ww": np.zeros((int(ws[0]), 4), np.uint32)}
+    args = [hs.ctypes.data, len(hs), nb.ctypes.data if len(nb) else None, ws.ctypes.data, len(ws), a.ctypes.data, l.ctypes.data, out["sum"].ctypes.data,
+            out["hh"].ctypes.data if n_calls else None, out["ww"].ctypes.data if int(ws[0]) else None]
+    rc = lib().zkir_tape_table_side_launch(*args, stream) if device else lib().zkir_tape_table_side_host(*args)
+    if rc != ZKIR_OK:
+        _raise(rc)
+    return out
+
+
+def hash_tape_check(hash_section, n_real: int, code_end: int, device: bool = True, stream=None) -> int:
+    """zkir_hash_tape_check_launch / _host: hashcall::parse_section's checks of a hash section — 0 well-formed, 4 truncated, 55 a call's output on code bytes, 56 a malformed
+    record; of the lowest failing record.  device=False: parse_section itself."""
+    hs = np.ascontiguousarray(hash_section, dtype=np.uint32)
+    code = C.c_int(-1)
+    if device:
+        rc = lib().zkir_hash_tape_check_launch(hs.ctypes.data if len(hs) else None, len(hs), int(n_real), int(code_end), C.byref(code), stream)
+    else:
+        rc = lib().zkir_hash_tape_check_host(hs.ctypes.data if len(hs) else None, len(hs), int(n_real), int(code_end), C.byref(code))
+    if rc != ZKIR_OK:
+        _raise(rc)
+    return int(code.value)
+
+
 class MemoryWitnessC(C.Structure):            # zkir_memory_witness
     _fields_ = [("n_ops", C.c_uint64), ("n_rows", C.c_uint64), ("row_order", MemopColumnsC), ("row_offsets", C.c_void_p), ("sorted", MemopColumnsC)]
 
@@ -335,6 +377,11 @@ def lib() -> C.CDLL:
     L.zkir_hash_call_cells_host.argtypes = [U64, U64, U64, U32, U64, C.POINTER(U64)]
     L.zkir_memcheck_witness_device_mode.restype = C.c_int
     L.zkir_memcheck_witness_device_mode.argtypes = [C.POINTER(TraceColumnsC), U64, C.c_char_p, C.c_size_t, U32, V, U64, V, V, V, V, V, U64, C.POINTER(U64), V, U64, C.POINTER(U64), V]
+    if hasattr(L, "zkir_tape_table_side_launch"):             # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_tape_table_side_launch.restype = C.c_int; L.zkir_tape_table_side_launch.argtypes = [V, U64, V, V, U64, V, V, V, V, V, V]
+        L.zkir_tape_table_side_host.restype = C.c_int; L.zkir_tape_table_side_host.argtypes = [V, U64, V, V, U64, V, V, V, V, V]
+        L.zkir_hash_tape_check_launch.restype = C.c_int; L.zkir_hash_tape_check_launch.argtypes = [V, U64, U64, U64, C.POINTER(C.c_int), V]
+        L.zkir_hash_tape_check_host.restype = C.c_int; L.zkir_hash_tape_check_host.argtypes = [V, U64, U64, U64, C.POINTER(C.c_int)]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
