@@ -301,6 +301,36 @@ BB_HD void dit4w2(int32_t* a, int32_t* b, int32_t w1, int32_t n1, int32_t w2, in
   dit4w(b[0], b[1], b[2], b[3], w1, n1, w2, n2, w2i, n2i);
 #endif
 }
+// ---- the same quad for a MULTIPLY-FIRST natural -> bit-reversed (Cooley-Tukey) transform: the inverse side of the LDE ---------------------
+// Two stages on x0..x3 at distances 0, d, 2d, 3d: the first pairs (x0, x2) and (x1, x3) with w1, the second (x0, x1) with w2 and (x2, x3) with w2i = w2 j, w1 = w2^2
+// (the twiddle belongs to the BLOCK, not to the position inside it).  That is dit4w's arithmetic with x1 and x2 exchanged on the way in and on the way out: the
+// pair that is only added (x0, x2 here) keeps its first-stage sums 64-bit, the pair that is multiplied (x1, x3) has them reduced — the same sums as in dit4w, so its
+// bounds hold as they are (restated below).
+BB_HD void ct4w(int32_t& x0, int32_t& x1, int32_t& x2, int32_t& x3, int32_t w1, int32_t n1, int32_t w2, int32_t n2, int32_t w2i, int32_t n2i) {
+  dit4w(x0, x2, x1, x3, w1, n1, w2, n2, w2i, n2i);
+}
+BB_HD void ct4w2(int32_t* a, int32_t* b, int32_t w1, int32_t n1, int32_t w2, int32_t n2, int32_t w2i, int32_t n2i) {
+  int32_t p[4] = {a[0], a[2], a[1], a[3]}, q[4] = {b[0], b[2], b[1], b[3]};
+  dit4w2(p, q, w1, n1, w2, n2, w2i, n2i);
+  a[0] = p[0]; a[1] = p[2]; a[2] = p[1]; a[3] = p[3]; b[0] = q[0]; b[1] = q[2]; b[2] = q[1]; b[3] = q[3];
+}
+// x g / R for a word in (-p, p) and a CANONICAL Montgomery-form factor g (the coset scale g^k / N between the two sides): one signed product and one reduction,
+// the result again in (-p, p) — no conditional subtraction, no canonicalisation before the forward rounds.
+BB_HD int32_t wscale(int32_t x, uint32_t g) { return wredc(wmul(x, (int32_t)g)); }
+// four words (a lane's four columns of one position) times one factor: on the device the products are one asm statement and the reductions' multiply-adds another
+BB_HD void wscale4(int32_t* x, uint32_t g) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int64_t t0, t1, t2, t3;
+  asm("v_mad_i64_i32 %0, vcc, %4, %8, 0\n\tv_mad_i64_i32 %1, vcc, %5, %8, 0\n\tv_mad_i64_i32 %2, vcc, %6, %8, 0\n\tv_mad_i64_i32 %3, vcc, %7, %8, 0"
+      : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3) : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(g) : "vcc");
+  const int32_t m0 = (int32_t)((uint32_t)t0 * NEG_PINV), m1 = (int32_t)((uint32_t)t1 * NEG_PINV), m2 = (int32_t)((uint32_t)t2 * NEG_PINV), m3 = (int32_t)((uint32_t)t3 * NEG_PINV);
+  asm("v_mad_i64_i32 %0, vcc, %4, %8, %0\n\tv_mad_i64_i32 %1, vcc, %5, %8, %1\n\tv_mad_i64_i32 %2, vcc, %6, %8, %2\n\tv_mad_i64_i32 %3, vcc, %7, %8, %3"
+      : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3) : "v"(m0), "v"(m1), "v"(m2), "v"(m3), "s"((int32_t)P) : "vcc");
+  x[0] = (int32_t)((uint64_t)t0 >> 32); x[1] = (int32_t)((uint64_t)t1 >> 32); x[2] = (int32_t)((uint64_t)t2 >> 32); x[3] = (int32_t)((uint64_t)t3 >> 32);
+#else
+  for (int i = 0; i < 4; i++) x[i] = wscale(x[i], g);
+#endif
+}
 // The bounds, computed: magnitudes through one butterfly / quad from words of at most `x`.
 constexpr uint64_t WREDC_IN_MAX = (1ull << 63) - ((uint64_t)P << 31);                    // what a reduction takes: |acc| + 2^31 p < 2^63
 constexpr uint64_t wredc_out_bound(uint64_t acc) { return (acc >> 32) + 1 + P / 2 + 1; }  // |acc| / 2^32 rounded up, + p / 2 + 1
@@ -314,6 +344,12 @@ constexpr WBound dit4w_bound(uint64_t x) {
 static_assert(dit4w_bound(1ull << 31).acc < WREDC_IN_MAX && dit2w_bound(1ull << 31).acc < WREDC_IN_MAX, "every sum of a quad on int32 words is a legal reduction input");
 static_assert(dit4w_bound(1ull << 31).out < (1ull << 31) && dit2w_bound(1ull << 31).out < (1ull << 31), "any quad output (and any canonical word) is a legal quad input");
 static_assert(dit4w_bound(P).out < P && dit2w_bound(P).out < P, "closure: words in (-p, p) -- canonical ones included -- stay in (-p, p), which is what wcanon() takes");
+// ct4w is dit4w on permuted arguments: the sums kept 64-bit are the first-stage sums of the pair that is only added, the sums reduced are those that are multiplied
+constexpr WBound ct4w_bound(uint64_t x) { return dit4w_bound(x); }
+constexpr WBound wscale_bound(uint64_t x) { const uint64_t a = x * (uint64_t)(P - 1); return WBound{a, wredc_out_bound(a)}; }      // canonical factor: at most p - 1
+static_assert(ct4w_bound(1ull << 31).acc < WREDC_IN_MAX && ct4w_bound(1ull << 31).out < (1ull << 31), "every sum of an inverse quad on int32 words is a legal reduction input, every output a legal input");
+static_assert(ct4w_bound(P).out < P, "closure of the inverse rounds: canonical words and words in (-p, p) stay in (-p, p)");
+static_assert(wscale_bound(P).acc < WREDC_IN_MAX && wscale_bound(P).out < P, "the coset scale of a word in (-p, p) is a word in (-p, p): the forward rounds take it as it is");
 
 BB_HD uint32_t to_mont(uint32_t a) { return mont_mul(a, R2); }
 BB_HD uint32_t from_mont(uint32_t a) { return mont_mul(a, 1u); }

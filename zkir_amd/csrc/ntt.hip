@@ -8,8 +8,9 @@
 // kernels being VALU-bound — the twiddle bookkeeping (3 of the 7 Montgomery products per radix-4 quad were twiddle derivations
 // when a lane carried one column) are shared by four (strided passes: eight) columns.
 //
-// Per block: inverse DIF NTT over H (natural -> bit-reversed), coset scale g^k / N, zero-interleave, forward DIT NTT over the
-// 2N coset (bit-reversed -> natural).  LDS-staged passes: strided passes move tiles of 2^B rows x 2^C positions (2^C * 32 bytes
+// Per block: inverse NTT over H as a MULTIPLY-FIRST Cooley-Tukey transform (natural -> bit-reversed: the twiddle of a butterfly belongs to
+// its block, see "the inverse side" below), coset scale g^k / N, zero-interleave, forward DIT NTT over the 2N coset (bit-reversed -> natural);
+// both sides run the wide signed radix-4 quad of babybear.h on int32 residues in (-p, p).  LDS-staged passes: strided passes move tiles of 2^B rows x 2^C positions (2^C * 32 bytes
 // consecutive per tile row keep loads coalesced); the last 10 inverse stages, the scaling and the first 11 forward stages are
 // fused in one contiguous-chunk kernel.  HBM traffic per element and column: 8 B per strided pass, 12 B for the fused middle.
 #include <hip/hip_runtime.h>
@@ -45,24 +46,10 @@ __device__ __forceinline__ void st4(uint4* p, u32x4 v) { *reinterpret_cast<u32x4
 // instead of all of them waiting at the same instruction.
 __device__ __forceinline__ void wave_sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// ---- four columns at a time --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 add4(uint4 a, uint4 b) { return make_uint4(bb::add(a.x, b.x), bb::add(a.y, b.y), bb::add(a.z, b.z), bb::add(a.w, b.w)); }
-__device__ __forceinline__ uint4 subl4(uint4 a, uint4 b) { return make_uint4(a.x - b.x + bb::P, a.y - b.y + bb::P, a.z - b.z + bb::P, a.w - b.w + bb::P); }
-__device__ __forceinline__ uint4 mul4(uint4 a, uint32_t w) { return make_uint4(bb::mont_mul(a.x, w), bb::mont_mul(a.y, w), bb::mont_mul(a.z, w), bb::mont_mul(a.w, w)); }
-
-// inverse (DIF) radix-4 quad: two stages on x0..x3 (spans 2d, d) with twiddles wA (first stage, even pair), wB = wA * j (odd pair),
-// w2 = wA^2 (second stage); differences only feed a product: no reduction
-__device__ __forceinline__ void dif4(uint4& x0, uint4& x1, uint4& x2, uint4& x3, uint32_t wA, uint32_t wB, uint32_t w2) {
-  const uint4 y0 = add4(x0, x2), y2 = mul4(subl4(x0, x2), wA);
-  const uint4 y1 = add4(x1, x3), y3 = mul4(subl4(x1, x3), wB);
-  x0 = add4(y0, y1); x1 = mul4(subl4(y0, y1), w2);
-  x2 = add4(y2, y3); x3 = mul4(subl4(y2, y3), w2);
-}
-
-// ---- the forward side in WIDE SIGNED arithmetic (babybear.h: dit4w / dit2w) ------------------------------------------------------
-// Representation contract, private to lde_run: from the first forward round to the last, words are int32 residues in (-p, p) — a
-// canonical word is one, so the inverse side and the coset scale hand over as they are — and twiddles are centred.  The LAST forward
-// kernel of a chain (`canon` != 0) brings its results back to [0, p) on the way out.
+// ---- both sides in WIDE SIGNED arithmetic, four columns at a time (babybear.h: dit4w / ct4w / dit2w / wscale) ----------------------
+// Representation contract, private to lde_run: words enter canonical — a legal word of (-p, p) — and stay int32 residues in (-p, p) from the
+// first inverse round through the coset scale to the last forward round; twiddles are centred.  The LAST forward kernel of a chain
+// (`canon` != 0) brings its results back to [0, p) on the way out; nothing is canonicalised in between (`in` is scratch and holds signed words).
 struct WTw { int32_t w, n; };                                                  // a centred twiddle and its negation
 __device__ __forceinline__ WTw wtw(int32_t w) { return WTw{w, -w}; }
 // forward (DIT) radix-4 quad: stages with twiddles w1 = w2^2 (first stage), w2 / w2i = w2 * j (second stage); outputs in positions
@@ -74,6 +61,27 @@ __device__ __forceinline__ void dit4w4(uint4& x0, uint4& x1, uint4& x2, uint4& x
   // two columns at a time: the scheduler would otherwise interleave all four chains and hold their 64-bit sums at once
   ZKIR_Q(x, y) __builtin_amdgcn_sched_barrier(0); ZKIR_Q(z, w)
 #undef ZKIR_Q
+}
+// ---- the inverse side: stage s = 0 .. L-1 has span h = N / 2^(s+1); block j < 2^s holds the pairs (a, b) = (x[2hj + i], x[2hj + i + h]) -> (a + w b, a - w b) with
+// w = w_N^-(brv_s(j) N / 2^(s+1)): multiply first, so the sums ride in the multiply-adds exactly as on the forward side.  A radix-4 round (stages s, s+1 on x0..x3 at
+// distances 0, d, 2d, 3d, d = h / 2) needs w2 = the twiddle of stage s+1's block 2j, w1 = w2^2 and w2i = w2 j (j the inverse 4th root).  For a pass that starts at
+// stage s0, a block index at local stage b is hi 2^b + j (hi: the s0 high bits a tile / chunk / lane group fixes), brv(hi 2^b + j) = brv_b(j) 2^s0 + brv_s0(hi), and
+//     w2 = small_inv[brv_b(j) << (8 - b)]  *  tw_inv[brv_s0(hi) << (L - s0 - b - 2)]
+// — a root of order 2^(b+2) <= 1024 that depends on (lane, round) only, times a factor that is UNIFORM over the tile or chunk (1 for s0 = 0).  The data movement
+// (natural -> bit-reversed, shrinking spans) is that of the add-first transform this replaces, so tiles, LDS indices and the wave-local rounds are unchanged.
+// Every inverse kernel lde_run can pick for log_n >= 10 is of this one factorisation: the arrays between stages differ from the add-first ones by twiddle factors.
+__device__ __forceinline__ void ct4w4(uint4& x0, uint4& x1, uint4& x2, uint4& x3, WTw w1, WTw w2, WTw w2i) { dit4w4(x0, x2, x1, x3, w1, w2, w2i); }
+// the three twiddles of an inverse round from the (lane, round) root `sm` and the uniform factor `f` (both canonical Montgomery form); `unit`: f = 1
+__device__ __forceinline__ void ct_twiddles(uint32_t sm, uint32_t f, bool unit, uint32_t j4_m, WTw& w1, WTw& w2, WTw& w2i) {
+  uint32_t w2u;
+  if (unit) { w2u = sm; w2 = wtw(bb::centre(sm)); }
+  else { w2 = wtw(bb::mont_mul_centred(sm, f)); w2u = bb::wcanon(w2.w); }
+  w1 = wtw(bb::mont_mul_centred(w2u, w2u)); w2i = wtw(bb::mont_mul_centred(w2u, j4_m));
+}
+__device__ __forceinline__ uint4 scale4(uint4 v, uint32_t g) {
+  int32_t x[4] = {(int32_t)v.x, (int32_t)v.y, (int32_t)v.z, (int32_t)v.w};
+  bb::wscale4(x, g);
+  return make_uint4((uint32_t)x[0], (uint32_t)x[1], (uint32_t)x[2], (uint32_t)x[3]);
 }
 __device__ __forceinline__ void dit2w4(uint4& a, uint4& b, WTw w) {
 #define ZKIR_Q(c) { int32_t p = (int32_t)a.c, q = (int32_t)b.c; bb::dit2w(p, q, w.w, w.n); a.c = (uint32_t)p; b.c = (uint32_t)q; }
@@ -92,15 +100,11 @@ __global__ __launch_bounds__(NT) void ntt_stage_kernel(uint4* __restrict__ data,
   const uint32_t t = (uint32_t)(item >> 1), h = (uint32_t)(item & 1);
   uint32_t p, stride, w;
   if (DIT) { stride = 1u << s0; const uint32_t hi = t >> s0, lo = t & (stride - 1); p = (hi << (s0 + 1)) + lo; w = tw[lo << (L - s0 - 1)]; }
-  else { stride = n >> (s0 + 1); const uint32_t hi = t / stride, lo = t % stride; p = hi * (n >> s0) + lo; w = tw[lo << s0]; }
-  const uint4 a = x[(uint64_t)p * 2 + h], b = x[(uint64_t)(p + stride) * 2 + h];
-  if (DIT) {
-    uint4 a2 = a, b2 = b;
-    dit2w4(a2, b2, wtw(bb::centre(w)));
-    if (canon) { a2 = canon4(a2); b2 = canon4(b2); }
-    x[(uint64_t)p * 2 + h] = a2; x[(uint64_t)(p + stride) * 2 + h] = b2;
-  }
-  else { x[(uint64_t)p * 2 + h] = add4(a, b); x[(uint64_t)(p + stride) * 2 + h] = mul4(subl4(a, b), w); }
+  else { stride = n >> (s0 + 1); const uint32_t hi = t / stride, lo = t % stride; p = hi * (n >> s0) + lo; w = tw[bitrev(hi, s0) << (L - s0 - 1)]; }   // the block's twiddle
+  uint4 a = x[(uint64_t)p * 2 + h], b = x[(uint64_t)(p + stride) * 2 + h];
+  dit2w4(a, b, wtw(bb::centre(w)));                                            // both directions multiply first: (a + w b, a - w b)
+  if (DIT && canon) { a = canon4(a); b = canon4(b); }
+  x[(uint64_t)p * 2 + h] = a; x[(uint64_t)(p + stride) * 2 + h] = b;
 }
 
 // ---- EXPERIMENT (round 4, profiles/HISTORY.md): the first inverse pass GENERATING its input instead of reading it — blocks 0 and 1 of the main trace (cycle, pc limbs,
@@ -136,7 +140,8 @@ __device__ __forceinline__ u32x4 trace_quad01(const TraceSrc01& q, uint32_t blk,
 // place, one column block per blockIdx.y.  With R = 5 a single pass covers ten stages (tile 1024 x 2 positions x 32 B = 64 KiB of
 // LDS), so a 2^20-row matrix needs ONE strided pass on each side of the fused middle kernel.  A lane owns one quad of positions and
 // runs it for both halves of the block (eight columns) with one set of twiddles: a read of a compact table (root of order <= 1024 /
-// 2048) times a per-lane running power; the other stage's twiddle is its square and the odd pair's is its product with a 4th root.
+// 2048) times a per-lane running power (forward) or a per-tile uniform factor (inverse; 1 in a pass that starts at stage 0, which then
+// reads nothing but the tile); the other stage's twiddle is its square and the odd pair's is its product with a 4th root.
 // LDS holds the two halves as separate planes so that consecutive lanes touch consecutive 16-byte words.
 template <bool DIT, int R, int C, int NTH, bool FUSED = false>
 __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__ data, uint64_t blk_u4, uint32_t tiles_per_block, uint32_t total, int L, int s0,
@@ -152,66 +157,77 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
   // Persistent workgroups: each walks the (block, tile) work list with a stride of the grid and keeps the NEXT tile's 16-byte loads
   // in flight (registers) while it runs the radix-4 rounds of the current one — with one or two workgroups per CU (64-128 KiB of LDS
   // each) nothing else would hide the global-memory latency of a tile load behind arithmetic.
-  auto geometry = [&](uint32_t w, uint4*& x, uint32_t& base, uint32_t& lo0) {
+  auto geometry = [&](uint32_t w, uint4*& x, uint32_t& base, uint32_t& lo0, uint32_t& hi) {
     const uint32_t tile = w % tiles_per_block;
     x = data + (uint64_t)(w / tiles_per_block) * blk_u4;
-    const uint32_t hi = tile / lo_tiles;
+    hi = tile / lo_tiles;
     lo0 = (tile % lo_tiles) << C;
     base = (DIT ? (hi << (s0 + B)) : hi * (n >> s0)) + lo0;
   };
   static_assert(QUADS == NTH, "one quad per lane and round");
   u32x4 pre[MOVES];
-  uint4* x; uint32_t base, lo0;
+  uint4* x; uint32_t base, lo0, hi;
   uint32_t w = blockIdx.x;
   if (w >= total) return;
   // vmcnt retires IN ORDER: a table read issued after the next tile's prefetch would make its s_waitcnt drain the whole prefetch
   // before the first round starts (rocm 7.2 emitted s_waitcnt vmcnt(0) in round 0 for exactly that) — so nothing is read from global
   // memory between the issue of a prefetch and its use.  The compact-table factors depend on (lane, round) only: read ONCE per
-  // workgroup; the tile-dependent power tw[lo << ..] of the NEXT tile is fetched as the last load of that tile's prefetch.
+  // workgroup; the tile-dependent factors of the NEXT tile (forward: the power tw[lo << ..]; inverse, s0 > 0: one uniform factor per round) are
+  // fetched as the last loads of that tile's prefetch.
   uint32_t sm[R];
 #pragma unroll
   for (int r = 0; r < R; r++) {
     const int b = 2 * r;
     const uint32_t qq = threadIdx.x >> C;
-    if (!DIT) { const int lg = B - 2 - b; sm[r] = small[(qq & ((1u << lg) - 1)) << (log_small - (B - b))]; }
+    if (!DIT) sm[r] = small[bitrev(qq >> (B - 2 - b), b) << (log_small - (b + 2))];          // root of order 2^(b+2), exponent brv_b(block inside the tile)
     else sm[r] = small[(qq & ((1u << b) - 1)) << (log_small - (b + 2))];
   }
-  geometry(w, x, base, lo0);
+  const bool unit = s0 == 0;                                                   // inverse: the tile factor is 1
+  uint32_t tf_next[R] = {};                                                    // inverse, s0 > 0: tw[brv_s0(hi) << (L - s0 - 2r - 2)]
+  auto tile_factors = [&](uint32_t hi_t) {
+    if (DIT || unit) return;
+    const uint32_t e = bitrev(hi_t, s0);
+#pragma unroll
+    for (int r = 0; r < R; r++) tf_next[r] = tw[e << (L - s0 - 2 * r - 2)];
+  };
+  geometry(w, x, base, lo0, hi);
   static_for<0, (int)MOVES>([&](auto kc) {                                     // tile rows are 2^C consecutive positions = 2^(C+1) uint4
     constexpr uint32_t k = decltype(kc)::value;
     const uint32_t e = threadIdx.x + k * NTH, row = e >> (C + 1), wv = e & ((2u << C) - 1);
     if constexpr (FUSED) pre[k] = trace_quad01(fsrc, w / tiles_per_block, wv & 1, (uint64_t)base + (uint64_t)row * stride_mid + (wv >> 1));
     else pre[k] = ld4(&x[((uint64_t)base + (uint64_t)row * stride_mid) * 2 + wv]);
   });
-  uint32_t tw_cur = DIT ? tw[(lo0 + (threadIdx.x & CMASK)) << (L - s0 - B)] : tw[(lo0 + (threadIdx.x & CMASK)) << s0];
+  uint32_t tw_cur = 0;
+  if (DIT) tw_cur = tw[(lo0 + (threadIdx.x & CMASK)) << (L - s0 - B)];
+  tile_factors(hi);
   for (;;) {
     static_for<0, (int)MOVES>([&](auto kc) {
       constexpr uint32_t k = decltype(kc)::value;
       const uint32_t e = threadIdx.x + k * NTH, row = e >> (C + 1), wv = e & ((2u << C) - 1);
       st4(&lds4[(wv & 1) * PLANE + ((row << C) | (wv >> 1))], pre[k]);
     });
-    uint32_t tp[R];                                            // per-lane power used by round r
+    uint32_t tp[R];                                            // forward: per-lane power used by round r; inverse: this tile's uniform factor of round r
     if (DIT) {                                                 // round r needs w^(lo << (L-1-s0-(2r+1))): finest at r = R-1, each earlier round is its 4th power
       uint32_t u = tw_cur;
 #pragma unroll
       for (int r = R - 1; r >= 0; r--) { tp[r] = u; u = bb::mont_mul(u, u); u = bb::mont_mul(u, u); }
-    } else {                                                   // round r needs w^-(lo << (s0+2r))
-      uint32_t u = tw_cur;
+    } else {
 #pragma unroll
-      for (int r = 0; r < R; r++) { tp[r] = u; u = bb::mont_mul(u, u); u = bb::mont_mul(u, u); }
+      for (int r = 0; r < R; r++) tp[r] = tf_next[r];
     }
     __syncthreads();
     const uint32_t wn = w + gridDim.x;
-    uint4* xn = x; uint32_t base_n = base, lo0_n = lo0;
+    uint4* xn = x; uint32_t base_n = base, lo0_n = lo0, hi_n = hi;
     if (wn < total) {                                          // next tile: loads issued now, consumed after this tile's rounds
-      geometry(wn, xn, base_n, lo0_n);
+      geometry(wn, xn, base_n, lo0_n, hi_n);
       static_for<0, (int)MOVES>([&](auto kc) {
         constexpr uint32_t k = decltype(kc)::value;
         const uint32_t e = threadIdx.x + k * NTH, row = e >> (C + 1), wv = e & ((2u << C) - 1);
         if constexpr (FUSED) pre[k] = trace_quad01(fsrc, wn / tiles_per_block, wv & 1, (uint64_t)base_n + (uint64_t)row * stride_mid + (wv >> 1));
         else pre[k] = ld4(&xn[((uint64_t)base_n + (uint64_t)row * stride_mid) * 2 + wv]);
       });
-      tw_cur = DIT ? tw[(lo0_n + (threadIdx.x & CMASK)) << (L - s0 - B)] : tw[(lo0_n + (threadIdx.x & CMASK)) << s0];
+      if (DIT) tw_cur = tw[(lo0_n + (threadIdx.x & CMASK)) << (L - s0 - B)];
+      tile_factors(hi_n);
     }
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -219,24 +235,25 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
 #pragma unroll
       for (uint32_t k = 0; k < QUADS / NTH; k++) {
         uint32_t q = threadIdx.x + k * NTH;
-        // (forward: the LDS addresses are recomputed each round — a handful of full-rate instructions; hoisted out of the tile loop, as the compiler would have
+        // (the LDS addresses are recomputed each round — a handful of full-rate instructions; hoisted out of the tile loop, as the compiler would have
         //  them, the ten of them push the 1024-lane instance past its 128 registers.  The empty asm only hides q's origin from the optimiser; what it buys depends
         //  on the compiler, so the register counts of profiles/*_isa_hist.txt are to be re-read after a toolchain change)
-        if constexpr (DIT) asm volatile("" : "+v"(q));
+        asm volatile("" : "+v"(q));
         const uint32_t lo_l = q & CMASK, qq = q >> C;
         uint4* pl0 = lds4; uint4* pl1 = lds4 + PLANE;
         if constexpr (!DIT) {
           const int lg = B - 2 - b;                            // log2(h2) in row units
           const uint32_t h2 = 1u << lg, mid_lo = qq & (h2 - 1), mid_hi = qq >> lg;
           const uint32_t i0 = ((((mid_hi << (lg + 2)) | mid_lo)) << C) | lo_l, d = h2 << C;
-          const uint32_t wa = bb::mont_mul(tp[r], sm[r]);
-          const uint32_t wb = bb::mont_mul(wa, j4_m), wc = bb::mont_mul(wa, wa);
-          // both halves' eight words are read before either quad is computed: one LDS latency per round instead of two
+          WTw w1, w2, w2i;                                     // the BLOCK's twiddles: (lane, round) root x the tile's uniform factor
+          ct_twiddles(sm[r], tp[r], unit, j4_m, w1, w2, w2i);
+          // the wide quad holds 64-bit sums: one half at a time keeps the kernel inside 128 registers
           uint4 x0 = pl0[i0], x1 = pl0[i0 + d], x2 = pl0[i0 + 2 * d], x3 = pl0[i0 + 3 * d];
-          uint4 y0 = pl1[i0], y1 = pl1[i0 + d], y2 = pl1[i0 + 2 * d], y3 = pl1[i0 + 3 * d];
-          dif4(x0, x1, x2, x3, wa, wb, wc);
+          ct4w4(x0, x1, x2, x3, w1, w2, w2i);
           pl0[i0] = x0; pl0[i0 + d] = x1; pl0[i0 + 2 * d] = x2; pl0[i0 + 3 * d] = x3;
-          dif4(y0, y1, y2, y3, wa, wb, wc);
+          __builtin_amdgcn_sched_barrier(0);
+          uint4 y0 = pl1[i0], y1 = pl1[i0 + d], y2 = pl1[i0 + 2 * d], y3 = pl1[i0 + 3 * d];
+          ct4w4(y0, y1, y2, y3, w1, w2, w2i);
           pl1[i0] = y0; pl1[i0 + d] = y1; pl1[i0 + 2 * d] = y2; pl1[i0 + 3 * d] = y3;
         } else {
           const uint32_t dm = 1u << b, mid_lo = qq & (dm - 1), mid_hi = qq >> b;
@@ -255,7 +272,8 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
         }
       }
       // A wave's 64 quads (2^(6-C) values of qq) cover one contiguous "home block" of 4 * 2^(6-C) rows in every round whose quad span
-      // fits it: DIF rounds with log2(h2) <= 6 - C, DIT rounds with b <= 6 - C.  Between two such rounds the data never leaves the wave.
+      // fits it: inverse rounds with log2(h2) <= 6 - C (the spans shrink: every later round fits too), DIT rounds with b <= 6 - C.  Between two such
+      // rounds the data never leaves the wave.
       const bool wave_local = !DIT ? (r + 1 < R && B - 2 - b <= 6 - C) : (r + 1 < R && b + 2 <= 6 - C);
       if (wave_local) wave_sync_lds(); else __syncthreads();
     }
@@ -267,7 +285,7 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
       x[((uint64_t)base + (uint64_t)row * stride_mid) * 2 + wv] = v;
     }
     if (wn >= total) break;
-    w = wn; x = xn; base = base_n; lo0 = lo0_n;
+    w = wn; x = xn; base = base_n; lo0 = lo0_n; hi = hi_n;
     // (no barrier here: a lane refills exactly the LDS words it has just copied out — the copy-in and copy-out loops share one slot map —
     //  and the barrier after the refill orders everything before the first round)
   }
@@ -277,7 +295,7 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
 // (stage counts of 12 = 10 + 2, 13 = 10 + 3, 11 = 8 + 3 ...).  One lane = one (position, half-block) = four columns; it loads its 2^S
 // rows (16 bytes each, consecutive lanes on consecutive 16-byte words), runs the S stages in registers and stores them back: 8 B per
 // element of HBM traffic for S stages, where the tiny-tile LDS pass (2 stages) followed by the single-stage pass moved 16 B for 3.
-// Twiddles: one table read (the finest stage's) and its squares, times the constant 4th / 8th roots.
+// Twiddles: one table read (the finest stage's; inverse: the factor of the lane's block hi) and its squares, times the constant 4th / 8th roots.
 template <bool DIT, int S>
 __global__ __launch_bounds__(NT) void ntt_reg_kernel(uint4* __restrict__ data, uint64_t blk_u4, int L, int s0, const uint32_t* __restrict__ tw, uint32_t r4_m, uint32_t r8_m,
                                                        uint32_t r8_3_m, int canon) {
@@ -294,28 +312,20 @@ __global__ __launch_bounds__(NT) void ntt_reg_kernel(uint4* __restrict__ data, u
 #pragma unroll
   for (int k = 0; k < E; k++) v[k] = x[base + (uint64_t)k * d * 2];
   if (!DIT) {
-    // DIF: stage j pairs (k, k + E/2^(j+1)); twiddle of the pair with low index kl = T_j * rho_{2^(S-j)}^kl, T_j = T0^(2^j), T0 = w^-(lo << s0)
-    const uint32_t T0 = tw[lo << s0];
-    const uint32_t T1 = bb::mont_mul(T0, T0);
-    if (S == 3) {
-      const uint32_t T2 = bb::mont_mul(T1, T1);
-      const uint32_t a1 = bb::mont_mul(T0, r8_m), a2 = bb::mont_mul(T0, r4_m), a3 = bb::mont_mul(T0, r8_3_m), b1 = bb::mont_mul(T1, r4_m);
-      const uint32_t w0[4] = {T0, a1, a2, a3};
+    // inverse (multiply first, natural -> bit-reversed): stage j pairs (k, k + E/2^(j+1)) inside blocks of E/2^j; the block m of local stage j has the twiddle
+    // T_j * rho_{2^(j+1)}^-brv_j(m), T_j = w^-(brv_s0(hi) << (L - s0 - j - 1)) — one read for the last stage's T, the earlier ones are its squares
+    const uint32_t Tf = tw[bitrev(hi, s0) << (L - s0 - S)];
+    const uint32_t Tm = bb::mont_mul(Tf, Tf);
+    if (S == 3) {                                              // stages 0 and 1 as wide quads on (0, 2, 4, 6) and (1, 3, 5, 7), stage 2 as wide radix-2 butterflies
+      const WTw t0 = wtw(bb::mont_mul_centred(Tm, Tm)), tm = wtw(bb::centre(Tm)), m1 = wtw(bb::mont_mul_centred(Tm, r4_m));
 #pragma unroll
-      for (int k = 0; k < 4; k++) { const uint4 a = v[k], b = v[k + 4]; v[k] = add4(a, b); v[k + 4] = mul4(subl4(a, b), w0[k]); }
+      for (int g = 0; g < 2; g++) ct4w4(v[g], v[g + 2], v[g + 4], v[g + 6], t0, tm, m1);
+      // blocks m = 0..3 of the last stage: rho_8^-brv_2(m) = 1, j, rho_8, rho_8^3
+      const WTw wf[4] = {wtw(bb::centre(Tf)), wtw(bb::mont_mul_centred(Tf, r4_m)), wtw(bb::mont_mul_centred(Tf, r8_m)), wtw(bb::mont_mul_centred(Tf, r8_3_m))};
 #pragma unroll
-      for (int g = 0; g < 8; g += 4) {
-        { const uint4 a = v[g], b = v[g + 2]; v[g] = add4(a, b); v[g + 2] = mul4(subl4(a, b), T1); }
-        { const uint4 a = v[g + 1], b = v[g + 3]; v[g + 1] = add4(a, b); v[g + 3] = mul4(subl4(a, b), b1); }
-      }
-#pragma unroll
-      for (int g = 0; g < 8; g += 2) { const uint4 a = v[g], b = v[g + 1]; v[g] = add4(a, b); v[g + 1] = mul4(subl4(a, b), T2); }
+      for (int m = 0; m < 4; m++) dit2w4(v[2 * m], v[2 * m + 1], wf[m]);
     } else {
-      const uint32_t a1 = bb::mont_mul(T0, r4_m);
-      { const uint4 a = v[0], b = v[2]; v[0] = add4(a, b); v[2] = mul4(subl4(a, b), T0); }
-      { const uint4 a = v[1], b = v[3]; v[1] = add4(a, b); v[3] = mul4(subl4(a, b), a1); }
-#pragma unroll
-      for (int g = 0; g < 4; g += 2) { const uint4 a = v[g], b = v[g + 1]; v[g] = add4(a, b); v[g + 1] = mul4(subl4(a, b), T1); }
+      ct4w4(v[0], v[1], v[2], v[3], wtw(bb::centre(Tm)), wtw(bb::centre(Tf)), wtw(bb::mont_mul_centred(Tf, r4_m)));
     }
   } else {
     // DIT: stage j pairs (k, k + 2^j); twiddle of the pair with low index kl = U_j * rho_{2^(j+1)}^kl, U_(S-1) = w^(lo << (L - s0 - S)), U_(j-1) = U_j^2
@@ -453,15 +463,15 @@ __global__ __launch_bounds__(NT) void lde_small_kernel(const uint32_t* __restric
   }
 }
 
-// ---- fused middle, N >= 1024: the last 10 inverse-DIF stages on a contiguous chunk of 1024 positions of the size-N block, the coset
+// ---- fused middle, N >= 1024: the last 10 inverse stages (multiply-first, s0 = L - 10: hi = the chunk) on a contiguous chunk of 1024 positions of the size-N block, the coset
 // scale g^k / N (k = bit-reversal of the position), zero-interleave, and the first 11 forward-DIT stages of the size-2N transform,
 // written as the 2048-position chunk of `out`.  Register-resident radix-4 rounds: 5 + 5 LDS round trips for the 21 stages, one
-// twiddle read per quad (the others are its square and its product with a 4th root of unity), shared by the four columns a lane
-// carries.  LDS: A = both halves of the chunk (32 KiB; later the forward buffer of half 1), Bf = the forward buffer of half 0 (32 KiB):
+// twiddle read per quad (inverse: times the chunk's uniform factor of the round; the others are its square and its product with a 4th root of
+// unity), shared by the four columns a lane carries.  LDS: A = both halves of the chunk (32 KiB; later the forward buffer of half 1), Bf = the forward buffer of half 0 (32 KiB):
 // 64 KiB per workgroup, two workgroups per CU.
 constexpr int MID_NT = 512;
 __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void lde_middle_r4_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, uint32_t chunks_per_block, uint32_t total, int L,
-                                                                const uint32_t* __restrict__ small_inv, const uint32_t* __restrict__ small_fwd,
+                                                                const uint32_t* __restrict__ tw_inv, const uint32_t* __restrict__ small_inv, const uint32_t* __restrict__ small_fwd,
                                                                 const uint32_t* __restrict__ g_lo, const uint32_t* __restrict__ g_hi, uint32_t j4_inv_m, uint32_t j4_fwd_m, int canon) {
   constexpr int Bm = 10;
   constexpr uint32_t APL = 1024;
@@ -472,17 +482,19 @@ __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   uint32_t w = blockIdx.x;
   if (w >= total) return;
   // vmcnt retires in order (see the strided kernel): no global read between the issue of the next chunk's prefetch and its use.
-  // The twiddles of the ten rounds depend on (lane, round) only: read once per workgroup.  The coset scale of the lane's four
-  // positions depends on the chunk: read at the top of the chunk, BEFORE the next prefetch is issued.
+  // The compact-table twiddles of the ten rounds depend on (lane, round) only: read once per workgroup.  The coset scale of the lane's four
+  // positions and the five uniform factors of the inverse rounds depend on the chunk: they come with the chunk's prefetch, as its last loads, and are
+  // consumed (gs, cf) at the top of the chunk, BEFORE the next prefetch is issued.
   uint32_t tw_i[5], tw_f[5];
 #pragma unroll
   for (int r = 0; r < 5; r++) {
     const int lg = 8 - 2 * r;
-    tw_i[r] = small_inv[((t & 255) & ((1u << lg) - 1)) << (2 * r)];           // w_1024^-(lo << 2r)
+    tw_i[r] = small_inv[bitrev((t & 255) >> lg, 2 * r) << lg];                 // w_(2^(2r+2))^-brv_2r(block inside the chunk)
     const int sft = 2 * r + 1;
     tw_f[r] = small_fwd[(t & ((1u << sft) - 1)) << (Bm - sft - 1)];            // w_2048^(lo << (9-s)): twiddle of stage s+1
   }
   u32x4 pre[4];
+  uint32_t cf_next[5];                                         // tw_inv[brv_(L-10)(chunk) << (8 - 2r)]: the chunk's factor of inverse round r
   uint32_t glo[4], ghi[4];                                     // factors of g^k / N for the lane's four positions 4q .. 4q + 3 of the last inverse round, k = bitrev_L(position)
   auto fetch = [&](uint32_t ww) {                              // one chunk's loads, in the order they are consumed: the 1024 positions, then the scale factors
     const uint4* x = in + ((uint64_t)(ww / chunks_per_block) * n + ((uint64_t)(ww % chunks_per_block) << Bm)) * 2;
@@ -491,6 +503,9 @@ __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const uint32_t p0 = ((ww % chunks_per_block) << Bm) + 4 * (t & 255);
 #pragma unroll
     for (int i = 0; i < 4; i++) { const uint32_t k = bitrev(p0 + i, L); glo[i] = g_lo[k & 1023]; ghi[i] = g_hi[k >> 10]; }
+    const uint32_t ce = bitrev(ww % chunks_per_block, L - Bm);
+#pragma unroll
+    for (int r = 0; r < 5; r++) cf_next[r] = tw_inv[ce << (8 - 2 * r)];
   };
   fetch(w);
   for (;;) {
@@ -501,10 +516,13 @@ __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     uint32_t gs[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) gs[i] = bb::mont_mul(glo[i], ghi[i]);
+    uint32_t cf[5];
+#pragma unroll
+    for (int r = 0; r < 5; r++) cf[r] = cf_next[r];
     __syncthreads();
     const uint32_t wn = w + gridDim.x;
     if (wn < total) fetch(wn);
-    // ---- inverse DIF, rounds r = 0..4: stages (2r, 2r+1), spans h1 = 2^(9-2r), h2 = h1/2; lane = (quad q, half h) ----
+    // ---- inverse, rounds r = 0..4: stages (2r, 2r+1) of the chunk, spans h1 = 2^(9-2r), h2 = h1/2; lane = (quad q, half h); block = hi ----
     {
       const uint32_t q = t & 255;
       uint4* a = A + (t >> 8) * APL;
@@ -513,12 +531,12 @@ __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         const int lg = 8 - 2 * r;                              // log2(h2)
         const uint32_t h2 = 1u << lg, lo = q & (h2 - 1), hi = q >> lg;
         const uint32_t i0 = (hi << (lg + 2)) | lo;
-        const uint32_t wA = tw_i[r];                            // w_1024^-(lo << 2r)
-        const uint32_t wB = bb::mont_mul(wA, j4_inv_m), w2 = bb::mont_mul(wA, wA);
+        WTw c1, c2, c2i;
+        ct_twiddles(tw_i[r], cf[r], false, j4_inv_m, c1, c2, c2i);
         uint4 x0 = a[i0], x1 = a[i0 + h2], x2 = a[i0 + 2 * h2], x3 = a[i0 + 3 * h2];
-        dif4(x0, x1, x2, x3, wA, wB, w2);
-        if (r == 4) {                                          // last round (positions 4q..4q+3, i0 = 4q): the coset scale g^k / N
-          x0 = mul4(x0, gs[0]); x1 = mul4(x1, gs[1]); x2 = mul4(x2, gs[2]); x3 = mul4(x3, gs[3]);
+        ct4w4(x0, x1, x2, x3, c1, c2, c2i);
+        if (r == 4) {                                          // last round (positions 4q..4q+3, i0 = 4q): the coset scale g^k / N, one signed product per word
+          x0 = scale4(x0, gs[0]); x1 = scale4(x1, gs[1]); x2 = scale4(x2, gs[2]); x3 = scale4(x3, gs[3]);
         }
         a[i0] = x0; a[i0 + h2] = x1; a[i0 + 2 * h2] = x2; a[i0 + 3 * h2] = x3;
         // rounds 1..4 stay inside the wave's own 256 positions of its plane (q = 64 v .. 64 v + 63): only round 0 hands data to other waves
@@ -583,13 +601,13 @@ void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out,
     hipLaunchKernelGGL(lde_small_kernel, dim3(n_blocks), dim3(NT), (8u << L), s, in, out, L, t.small_inv, t.small_fwd, t.g_lo, t.g_hi);
     return;
   }
-  // inverse DIF strided stages 0 .. L-11 (the compact table then has order 1024)
+  // inverse strided stages 0 .. L-11 (multiply-first; the compact table then has order 1024)
   run_strided_stages<false>(in, N, n_blocks, L, 0, L - 10, t.tw_inv, t.small_inv, 10, j4_inv_m, r8_inv_m, r8_inv3_m, s);
   {
     const uint32_t chunks = N >> 10, total = chunks * n_blocks;
     unsigned grid = persist() ? cu_count() * 2 : total;                     // 64 KiB of LDS: two workgroups per CU
     if (grid > total) grid = total;
-    hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
+    hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.tw_inv, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
                        j4_inv_m, j4_fwd_m, L == 10);
   }
   // forward DIT strided stages 11 .. L of the size-2N transform
@@ -645,7 +663,7 @@ bool lde_run_fused01(const LdeTables& t, const zkir_trace_columns* trace, uint64
     const uint32_t chunks = N >> 10, total = chunks * n_blocks;
     unsigned grid = persist() ? cu_count() * 2 : total;
     if (grid > total) grid = total;
-    hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
+    hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.tw_inv, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
                        j4_inv_m, j4_fwd_m, L == 10);
   }
   run_strided_stages<true>(out, (uint64_t)2 * N, n_blocks, L + 1, 11, L - 10, t.tw_fwd, t.small_fwd, 11, j4_fwd_m, r8_fwd_m, r8_fwd3_m, s);
