@@ -448,6 +448,23 @@ int zkir_hash_tape_check_launch(const uint32_t* hash_words, uint64_t n_hash_word
                                 int* code, void* hip_stream);
 int zkir_hash_tape_check_host(const uint32_t* hash_words, uint64_t n_hash_words, uint64_t n_real, uint64_t code_end,
                               int* code);
+/* (mode 4) What every hash call of a section wrote, recomputed from the tape alone (a verifier has no record of the run): new_bytes[h] = touched cell h's bytes after its
+ * call, in the section's cell order — the cell's old bytes with the call's 32 output bytes laid over them, the message read out of the OLD bytes (hashcall::new_bytes).
+ * hash_words, new_bytes: host; new_bytes has one entry per touched cell.  _launch: hash_tape_new_bytes_kernel (csrc/tape_digest.inl), a lane per call of at most 1024
+ * bytes, longer calls hashed on host threads; _host: hashcall::new_bytes over the parsed calls.  A section hashcall::parse_section rejects (with no row bound and no
+ * code segment) is ZKIR_ERR_ARGUMENT in both, the check's number in the message. */
+int zkir_hash_tape_new_bytes_launch(const uint32_t* hash_words, uint64_t n_hash_words, uint64_t* new_bytes, void* hip_stream);
+int zkir_hash_tape_new_bytes_host(const uint32_t* hash_words, uint64_t n_hash_words, uint64_t* new_bytes);
+/* zkir_verify with the three stages that are linear in a mode-4 proof's tapes — the record checks, the sections' chunk digests, the tapes' share of the lookup table side
+ * (the digest of every hash call among it) — run on the current HIP device.  The verdict is zkir_verify's for every input: 0, or the same check's number.  Modes 0-3 and a
+ * mode-4 proof with both tapes empty ARE zkir_verify: nothing is uploaded, nothing is launched.  A NEGATIVE result is no verdict: -ZKIR_ERR_DEVICE (no usable device, a
+ * failed HIP call) or -ZKIR_ERR_OTHER (no host memory); zkir_last_error says which.  Calls on one device are serialised inside; the device block and the pinned staging of the
+ * largest tape seen stay with the process, one set per HIP device the entry was called on. */
+int zkir_verify_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, void* hip_stream);
+/* diagnostics of the calling thread's last zkir_verify* call: host wall time in ms of [0] parsing (the tapes' record checks among it), [1] the sections' chunk digests,
+ * [2] the hash tape's share of the table side, [3] the wide tape's, [4] the rest; *device_stages = how many of these stages ran on the device (0 for every host entry).
+ * Either pointer may be NULL.  ZKIR_ERR_ARGUMENT before the thread's first verification.  ZKIR_VERIFY_TIMES in the environment prints the clocks on stderr. */
+int zkir_verify_last_stages(double ms[5], uint32_t* device_stages);
 /* points pub's mode-3 fields at the witness (which must outlive the proving call) and sets pub->deferred = 3 */
 void zkir_public_inputs_set_memory(zkir_public_inputs* pub, const zkir_memcheck_witness* w);
 /* Poseidon2 sponge digest of a byte string (host): [len as four 16-bit pieces] ++ [LE 16-bit halfwords] */

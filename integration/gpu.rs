@@ -111,6 +111,13 @@ extern "C" {
                                      sum: *mut u32, hh: *mut u32, ww: *mut u32) -> c_int;
     pub fn zkir_hash_tape_check_launch(hash_words: *const u32, n_hash_words: u64, n_real: u64, code_end: u64, code: *mut c_int, stream: *mut c_void) -> c_int;
     pub fn zkir_hash_tape_check_host(hash_words: *const u32, n_hash_words: u64, n_real: u64, code_end: u64, code: *mut c_int) -> c_int;
+    // (mode 4) what every hash call of a section wrote, recomputed from the tape alone (new_bytes: one entry per touched cell), and the verifier that runs its tape stages on the GPU:
+    // the same verdict as zkir_verify; a negative result is a device failure, not a verdict
+    pub fn zkir_hash_tape_new_bytes_launch(hash_words: *const u32, n_hash_words: u64, new_bytes: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn zkir_hash_tape_new_bytes_host(hash_words: *const u32, n_hash_words: u64, new_bytes: *mut u64) -> c_int;
+    pub fn zkir_verify_device(proof: *const u32, words: u64, expect: *const ZkirPublicInputs, stream: *mut c_void) -> c_int;
+    // diagnostics: the host clocks (ms: parsing, section digests, hash table side, wide table side, rest) of this thread's last zkir_verify* call and how many stages ran on the GPU
+    pub fn zkir_verify_last_stages(ms: *mut f64, device_stages: *mut u32) -> c_int;
 }
 
 /// zkir_prover_params: the proof's mode (0 default VM mode, 1 deferred model, 2 + the I/O argument, 3 + the memory argument) and its FRI parameters

@@ -31,6 +31,7 @@
 #include "host.h"
 #include "hashcall.h"
 #include "poseidon2.h"
+#include "verify_stages.h"
 
 namespace {
 

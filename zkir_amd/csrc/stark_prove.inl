@@ -1026,6 +1026,7 @@ struct StageEvents {             // RAII: released on every return path
 };
 
 #include "tape_table.inl"
+#include "tape_digest.inl"
 
 // the header words of a v4 proof (so::header_words): parameters, public inputs, the two boundary states read off the main trace
 void header_words(uint32_t log_n, const zkir_public_inputs& pub, const uint32_t* states, std::vector<uint32_t>& w) {      // states: 2 NS words (+ 4 counters in mode 2)
@@ -1239,6 +1240,10 @@ int zkir_hash_tape_check_launch(const uint32_t* hash_words, uint64_t n_hash_word
   *code = best == ~0ull ? 0 : (int)(best & 0xFF);
   return ZKIR_OK;
 }
+
+}  // extern "C"
+#include "verify_device.inl"
+extern "C" {
 
 // Full proof of the run whose K1 output is `trace` (pub->n_real executed rows, padded to 2^ctx.log_n).  Phases are timed with HIP events
 // when stage_ms != NULL (NINE floats): [0] main trace (+ lookup indices), [1] LDE, [2] trace Merkle, [3] lookup argument (inverse tables, aux trace, its LDE and

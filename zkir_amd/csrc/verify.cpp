@@ -6,6 +6,8 @@
 // quotient kernel instantiates); tests/ compare its verdicts with the oracle's so::verify on valid, tampered and cheating proofs.
 // Transcript and proof layout: see zkir_prove (stark_prove.inl) and DESIGN.md §8.8.
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <atomic>
@@ -18,6 +20,7 @@
 #include "host.h"
 #include "hashcall.h"
 #include "poseidon2.h"
+#include "verify_stages.h"
 
 namespace {
 
@@ -136,7 +139,8 @@ void initial_state(uint64_t entry, uint32_t st[NS]) {
   st[1] = (uint32_t)(entry & 0xFFFFF); st[2] = (uint32_t)((entry >> 20) & 0xFFFFF); st[3] = (uint32_t)(entry >> 40);
 }
 
-int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out = nullptr);
+int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out = nullptr,
+                const zkir::TapeStages* stages = nullptr);
 inline int header_words_of(int mode) { return HEADER_WORDS + (mode >= 2 ? 4 : 0); }     // modes 2 / 3: + (oc, ic) of the first row, of the last row
 // (mode 3) the bytes of cell `addr` (a multiple of 8) in the VM's INITIAL memory: the code words at 0x1000, the data section right behind them (vm.rs:153-170), zero elsewhere
 uint64_t image_cell(const uint8_t* blob, size_t n, uint64_t addr) {
@@ -178,7 +182,138 @@ bool io_digest_matches(const uint32_t* digest4, const IoSection& io, uint64_t cy
 int halt_binding(const uint32_t* w, const uint32_t* last_state, int halt_kind, uint64_t halt_code);
 bool last_row_writes(const uint32_t* w, const uint32_t* last_state, int halt_kind, uint64_t* value);
 
+// Host wall time of a verification's phases: [0] parsing (the record checks of the tapes among it), [1] the sections' chunk digests, [2] the hash tape's share of the table
+// side, [3] the wide tape's, [4] the rest.  Kept per thread for zkir_verify_last_stages; printed on stderr when ZKIR_VERIFY_TIMES is set (nothing by default).
+struct LastStages { double ms[5] = {0, 0, 0, 0, 0}; uint32_t device_stages = 0; bool valid = false; };
+thread_local LastStages last_stages;
+struct StageClock {
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  double ms[5] = {0, 0, 0, 0, 0};
+  void lap(int k) { const auto now = std::chrono::steady_clock::now(); ms[k] += std::chrono::duration<double, std::milli>(now - t).count(); t = now; }
+  ~StageClock() {
+    lap(4);
+    for (int k = 0; k < 5; k++) last_stages.ms[k] = ms[k];
+    last_stages.device_stages = 0; last_stages.valid = true;
+    if (getenv("ZKIR_VERIFY_TIMES"))
+      fprintf(stderr, "zkir_verify: parse %.3f ms | section digests %.3f | hash table side %.3f | wide table side %.3f | rest %.3f\n", ms[0], ms[1], ms[2], ms[3], ms[4]);
+  }
+};
+
+// ---- the host forms of the tape stages (verify_stages.h) ----------------------------------------------------------------------------------------------------------------
+E4 lk_e4(const uint32_t* lk_m, int at) { E4 e; memcpy(e.c, lk_m + at, 16); return e; }
+int host_hash_check(void* self, const uint32_t* w, size_t avail, uint64_t n_real, uint64_t code_end, size_t* used) {
+  return hashcall::parse_section(w, avail, n_real, code_end, static_cast<zkir::HostTapes*>(self)->hcalls, used);
+}
+int host_wide_check(void* self, const uint32_t* sec, size_t n_wide, uint64_t n_real) {
+  zkir::HostTapes& h = *static_cast<zkir::HostTapes*>(self);
+  h.wide = sec; h.n_wide = n_wide;
+  for (size_t k = 0; k < n_wide; k++) {
+    const uint32_t* c = sec + 1 + 8 * k;
+    if (c[1] >= (1u << 20) || c[2] >= (1u << 20) || c[3] >= (1u << 24) || c[4] >= (1u << 20) || c[5] >= (1u << 20) || c[6] >= (1u << 24) || c[7] < 3 || c[7] > 7) return 57;
+    if (c[0] >= n_real || (k && c[0] <= c[-8]) || (c[7] >= 4 && !(c[4] | c[5] | c[6]))) return 57;
+  }
+  return 0;
+}
+// The chunks are independent: long sections (a 2^22-cycle hash chain's tape is 34 M words = 4 M permutations) are hashed on several host threads.
+void section_digests_host(const uint32_t* sw, size_t sl, uint32_t* dg) {
+  const size_t n_chunks = (sl + 511) / 512;
+  hashcall::for_calls(n_chunks, hashcall::parts_for(n_chunks / 8), [&](unsigned, size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; k++) hash_elems(sw + 512 * k, sl - 512 * k < 512 ? sl - 512 * k : 512, dg + 4 * k);
+  });
+}
+int host_digests(void*, int, const uint32_t* sw, size_t sl, uint32_t* dg) { section_digests_host(sw, sl, dg); return 0; }
+// The digest inside the new bytes is computed HERE (hashcall::new_bytes).
+int host_hash_side(void* self, const uint32_t* lk_m, uint32_t T[4]) {
+  const std::vector<hashcall::Call>& hcalls = static_cast<zkir::HostTapes*>(self)->hcalls;
+  E4 T_hash = bb::e_zero();
+  if (!hcalls.empty()) {
+    const E4 alpha_l = lk_e4(lk_m, air::LK_ALPHA);
+    E4 lam[air::N_TUPLE + 1];
+    for (int j = 0; j <= air::N_TUPLE; j++) lam[j] = lk_e4(lk_m, air::LK_LAM + 4 * j);
+    auto mem_d = [&](uint64_t addr, uint32_t t, uint64_t bytes) {
+      E4 fp = bb::e_mul_fm(lam[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_MEM));
+      fp.c[0] = bb::add(fp.c[0], bb::to_mont((uint32_t)(addr & 0xFFFFF)));
+      fp = bb::e_add(fp, bb::e_mul_fm(lam[1], bb::to_mont((uint32_t)((addr >> 20) & 0xFFFFF))));
+      fp = bb::e_add(fp, bb::e_mul_fm(lam[2], bb::to_mont(t)));
+      for (int k = 0; k < 8; k++) fp = bb::e_add(fp, bb::e_mul_fm(lam[3 + k], bb::to_mont((uint32_t)((bytes >> (8 * k)) & 0xFF))));
+      return bb::e_sub(alpha_l, fp);
+    };
+    const unsigned parts = hashcall::parts_for(hcalls.size());
+    std::vector<E4> Tpart(parts, bb::e_zero());
+    hashcall::for_calls(hcalls.size(), parts, [&](unsigned part, size_t lo, size_t hi) {      // (host threads; each part inverts its own batch)
+      std::vector<E4> hd; std::vector<int8_t> hsign; std::vector<uint64_t> nb;
+      for (size_t ci = lo; ci < hi; ci++) {
+        const hashcall::Call& c = hcalls[ci];
+        const uint32_t e[11] = {(uint32_t)(c.cycle % bb::P), (uint32_t)(c.in_ptr & 0xFFFFF), (uint32_t)((c.in_ptr >> 20) & 0xFFFFF), (uint32_t)(c.in_ptr >> 40), (uint32_t)(c.len & 0xFFFFF),
+                                (uint32_t)((c.len >> 20) & 0xFFFFF), (uint32_t)(c.len >> 40), (uint32_t)(c.out_ptr & 0xFFFFF), (uint32_t)((c.out_ptr >> 20) & 0xFFFFF), (uint32_t)(c.out_ptr >> 40), c.kind};
+        E4 fp = bb::e_mul_fm(lam[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_HASH));
+        for (int j = 0; j < 11; j++) fp = bb::e_add(fp, bb::e_mul_fm(lam[j], bb::to_mont(e[j])));
+        hd.push_back(bb::e_sub(alpha_l, fp)); hsign.push_back(1);
+        hashcall::new_bytes(c, nb);
+        for (size_t k = 0; k < c.cells.size(); k++) {
+          hd.push_back(mem_d(c.cells[k].addr, c.cells[k].t, c.cells[k].bytes)); hsign.push_back(-1);
+          hd.push_back(mem_d(c.cells[k].addr, (uint32_t)((c.cycle + 1) % bb::P), nb[k])); hsign.push_back(1);
+        }
+      }
+      std::vector<E4> hpre(hd.size());
+      E4 hacc = bb::e_one_m();
+      for (size_t i = 0; i < hd.size(); i++) { hpre[i] = hacc; hacc = bb::e_mul_m(hacc, hd[i]); }
+      E4 hinv = bb::e_inv_m(hacc), Tp = bb::e_zero();
+      for (size_t i = hd.size(); i-- > 0;) {
+        const E4 di = bb::e_mul_m(hinv, hpre[i]);
+        hinv = bb::e_mul_m(hinv, hd[i]);
+        Tp = hsign[i] > 0 ? bb::e_add(Tp, di) : bb::e_sub(Tp, di);
+      }
+      Tpart[part] = Tp;
+    });
+    for (const E4& tp : Tpart) T_hash = bb::e_add(T_hash, tp);
+  }
+  memcpy(T, T_hash.c, 16);
+  return 0;
+}
+// The result is computed HERE (air::wide_result).
+int host_wide_side(void* self, const uint32_t* lk_m, uint32_t T[4]) {
+  const zkir::HostTapes& h = *static_cast<zkir::HostTapes*>(self);
+  const uint32_t* wide_words = h.wide; const size_t n_wide = h.n_wide;
+  E4 T_wide = bb::e_zero();
+  if (n_wide) {
+    const E4 alpha_l = lk_e4(lk_m, air::LK_ALPHA);
+    E4 lam[air::N_TUPLE + 1];
+    for (int j = 0; j <= air::N_TUPLE; j++) lam[j] = lk_e4(lk_m, air::LK_LAM + 4 * j);
+    const unsigned parts = hashcall::parts_for(n_wide / 4);
+    std::vector<E4> Tpart(parts, bb::e_zero());
+    hashcall::for_calls(n_wide, parts, [&](unsigned part, size_t lo, size_t hi) {             // (host threads; each part inverts its own batch)
+      std::vector<E4> wd(hi - lo), wpre(hi - lo);
+      for (size_t k = lo; k < hi; k++) {
+        const uint32_t* r = wide_words + 1 + 8 * k;
+        const uint64_t a = (uint64_t)r[1] | ((uint64_t)r[2] << 20) | ((uint64_t)r[3] << 40), b = (uint64_t)r[4] | ((uint64_t)r[5] << 20) | ((uint64_t)r[6] << 40);
+        const uint64_t y = air::wide_result(r[7], a, b);
+        const uint32_t e[11] = {r[0] % bb::P, r[1], r[2], r[3], r[4], r[5], r[6], (uint32_t)(y & 0xFFFFF), (uint32_t)((y >> 20) & 0xFFFFF), (uint32_t)(y >> 40), r[7]};
+        E4 fp = bb::e_mul_fm(lam[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_WIDE));
+        for (int j = 0; j < 11; j++) fp = bb::e_add(fp, bb::e_mul_fm(lam[j], bb::to_mont(e[j])));
+        wd[k - lo] = bb::e_sub(alpha_l, fp);
+      }
+      E4 wacc = bb::e_one_m(), Tp = bb::e_zero();
+      for (size_t k = 0; k < wd.size(); k++) { wpre[k] = wacc; wacc = bb::e_mul_m(wacc, wd[k]); }
+      E4 winv = bb::e_inv_m(wacc);
+      for (size_t k = wd.size(); k-- > 0;) { Tp = bb::e_add(Tp, bb::e_mul_m(winv, wpre[k])); winv = bb::e_mul_m(winv, wd[k]); }
+      Tpart[part] = Tp;
+    });
+    for (const E4& tp : Tpart) T_wide = bb::e_add(T_wide, tp);
+  }
+  memcpy(T, T_wide.c, 16);
+  return 0;
+}
+
 }  // namespace
+
+namespace zkir {
+TapeStages host_tape_stages(HostTapes* h) { return TapeStages{h, host_hash_check, host_wide_check, host_digests, host_hash_side, host_wide_side}; }
+int verify_with_stages(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, const TapeStages& stages) {
+  return verify_impl(proof, proof_words, expect, true, nullptr, nullptr, &stages);
+}
+void verify_note_device_stages(uint32_t n) { last_stages.device_stages = n; }
+}  // namespace zkir
 
 extern "C" {
 
@@ -234,6 +369,12 @@ uint64_t zkir_hash_call_cells_host(uint64_t in_ptr, uint64_t len, uint64_t out_p
 }
 
 int zkir_verify(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect) { return verify_impl(w, len, expect, true, nullptr); }
+int zkir_verify_last_stages(double ms[5], uint32_t* device_stages) {
+  if (!last_stages.valid) return ZKIR_ERR_ARGUMENT;
+  if (ms) for (int k = 0; k < 5; k++) ms[k] = last_stages.ms[k];
+  if (device_stages) *device_stages = last_stages.device_stages;
+  return ZKIR_OK;
+}
 
 // ---- (mode 3) the memory witness: a sequential replay of the run's loads and stores over 8-byte cells (see include/zkir_amd.h) ----
 }  // extern "C"
@@ -478,7 +619,11 @@ int zkir_verify_chain_io(const uint32_t* const* proofs, const uint64_t* lens, ui
 
 namespace {
 
-int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out) {
+int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out, const zkir::TapeStages* stages) {
+  StageClock clk;                                                          // (diagnostics: the host wall time of the call's phases, kept for zkir_verify_last_stages)
+  zkir::HostTapes host_tapes;
+  const zkir::TapeStages host_stages = zkir::host_tape_stages(&host_tapes);
+  const zkir::TapeStages& S = stages ? *stages : host_stages;
   if (!w) return 1;
   size_t p = 0;
   auto need = [&](size_t k) { return p + k <= len; };
@@ -577,16 +722,15 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     p += mem_len;
   }
   // (mode 4) the hash calls: records in increasing cycle order, ranges in the clear, every touched cell's previous access before the call (56); no output on code bytes (55)
-  std::vector<hashcall::Call> hcalls;
+  // (the record checks, the sections' chunk digests and their shares of the table side are the three stages behind zkir::TapeStages: verify_stages.h)
   const uint32_t* hash_words = nullptr; size_t hash_len = 0;
   if (mode == 4) {
     hash_words = w + p;
-    const int hrc = hashcall::parse_section(w + p, (size_t)(len - p), pub.n_real, air::CODE_BASE + 4 * (uint64_t)n_code, hcalls, &hash_len);
+    const int hrc = S.hash_check(S.self, w + p, (size_t)(len - p), pub.n_real, air::CODE_BASE + 4 * (uint64_t)n_code, &hash_len);
     if (hrc) return hrc;
     p += hash_len;
   }
   // (mode 4 d) the wide tape: records in increasing cycle order, limbs in range, an opcode 3..7, no zero divisor (57)
-  struct WideRec { uint32_t w[8]; };
   const uint32_t* wide_words = nullptr; size_t wide_len = 0, n_wide = 0;
   if (mode == 4) {
     if (!need(1)) return 4;
@@ -594,11 +738,8 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     if (n_wide > pub.n_real) return 57;
     if (!need(1 + 8 * n_wide)) return 4;
     wide_words = w + p; wide_len = 1 + 8 * n_wide;
-    for (size_t k = 0; k < n_wide; k++) {
-      const uint32_t* c = wide_words + 1 + 8 * k;
-      if (c[1] >= (1u << 20) || c[2] >= (1u << 20) || c[3] >= (1u << 24) || c[4] >= (1u << 20) || c[5] >= (1u << 20) || c[6] >= (1u << 24) || c[7] < 3 || c[7] > 7) return 57;
-      if (c[0] >= pub.n_real || (k && c[0] <= c[-8]) || (c[7] >= 4 && !(c[4] | c[5] | c[6]))) return 57;
-    }
+    const int wrc = S.wide_check(S.self, wide_words, n_wide, pub.n_real);
+    if (wrc) return wrc;
     p += wide_len;
   }
   if (!need(n_code + air::RC_TABLE + (mode >= 3 ? air::MEM_MULT : 0))) return 4;
@@ -626,6 +767,7 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   std::vector<E4> fin(n_fin);
   for (size_t i = 0; i < n_fin; i++) { fin[i] = get_m(p); p += 4; }
   const uint32_t pow_nonce = w[p++];
+  clk.lap(0);
   // ---- transcript ----
   Challenger ch;
   ch.observe_n(w + 2, (size_t)HW - 2);
@@ -633,17 +775,24 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   if (mode >= 2)                                                           // (v11) the tapes and the halt reason, fixed before the lookup challenges (a segment's too) — so::observe_section
     for (size_t at = 0; at < io.words; at += 512) { uint32_t dg[4]; hash_elems(io_words + at, io.words - at < 512 ? io.words - at : 512, dg); ch.observe_n(dg, 4); }
   // the touched cells enter through a two-level sponge: chunks of 512 words hashed on their own, the digests observed (so::observe_section); (mode 4) the hash calls likewise.
-  // The chunks are independent: long sections (a 2^22-cycle hash chain's tape is 34 M words = 4 M permutations) are hashed on several host threads.
   auto observe_section = [&](const uint32_t* sw, size_t sl) {
-    const size_t n_chunks = (sl + 511) / 512;
-    std::vector<uint32_t> dg(4 * n_chunks);
-    hashcall::for_calls(n_chunks, hashcall::parts_for(n_chunks / 8), [&](unsigned, size_t lo, size_t hi) {
-      for (size_t k = lo; k < hi; k++) hash_elems(sw + 512 * k, sl - 512 * k < 512 ? sl - 512 * k : 512, dg.data() + 4 * k);
-    });
+    std::vector<uint32_t> dg(4 * ((sl + 511) / 512));
+    section_digests_host(sw, sl, dg.data());
     ch.observe_n(dg.data(), dg.size());
   };
+  clk.lap(4);
   if (mode >= 3) observe_section(mem_words, mem_len);
-  if (mode == 4) { observe_section(hash_words, hash_len); observe_section(wide_words, wide_len); }
+  if (mode == 4) {
+    std::vector<uint32_t> dg;
+    for (int which = 0; which < 2; which++) {
+      const uint32_t* sw = which ? wide_words : hash_words; const size_t sl = which ? wide_len : hash_len;
+      dg.resize(4 * ((sl + 511) / 512));
+      const int drc = S.digests(S.self, which, sw, sl, dg.data());
+      if (drc) return drc;
+      ch.observe_n(dg.data(), dg.size());
+    }
+  }
+  clk.lap(1);
   ch.observe_n(rom_mult, n_code);
   ch.observe_n(rc_mult, air::RC_TABLE);
   if (mode >= 3) ch.observe_n(mem_mult, air::MEM_MULT);
@@ -682,61 +831,18 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
       };
       for (size_t k = 0; k < cells.size(); k++) { m[air::MEM_MULT + 2 * k] = mem_d(cells[k], 0, image_cell(blob.data(), blob_len, cells[k].addr)); m[air::MEM_MULT + 2 * k + 1] = mem_d(cells[k], cells[k].t, cells[k].bytes); }
       // (mode 4) the hash calls: + 1 / (alpha - fp(call)) per call (its ECALL row looks it up) and the call's memory accesses, which no row states: per touched cell
-      // - 1 / (alpha - fp(cell, told, old bytes)) + 1 / (alpha - fp(cell, cycle + 1, new bytes)).  The digest inside the new bytes is computed HERE (hashcall::new_bytes).
-      if (mode == 4 && !hcalls.empty()) {
-        const unsigned parts = hashcall::parts_for(hcalls.size());
-        std::vector<E4> Tpart(parts, bb::e_zero());
-        hashcall::for_calls(hcalls.size(), parts, [&](unsigned part, size_t lo, size_t hi) {      // (host threads; each part inverts its own batch)
-          std::vector<E4> hd; std::vector<int8_t> hsign; std::vector<uint64_t> nb;
-          for (size_t ci = lo; ci < hi; ci++) {
-            const hashcall::Call& c = hcalls[ci];
-            const uint32_t e[11] = {(uint32_t)(c.cycle % bb::P), (uint32_t)(c.in_ptr & 0xFFFFF), (uint32_t)((c.in_ptr >> 20) & 0xFFFFF), (uint32_t)(c.in_ptr >> 40), (uint32_t)(c.len & 0xFFFFF),
-                                    (uint32_t)((c.len >> 20) & 0xFFFFF), (uint32_t)(c.len >> 40), (uint32_t)(c.out_ptr & 0xFFFFF), (uint32_t)((c.out_ptr >> 20) & 0xFFFFF), (uint32_t)(c.out_ptr >> 40), c.kind};
-            E4 fp = bb::e_mul_fm(lam[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_HASH));
-            for (int j = 0; j < 11; j++) fp = bb::e_add(fp, bb::e_mul_fm(lam[j], bb::to_mont(e[j])));
-            hd.push_back(bb::e_sub(alpha_l, fp)); hsign.push_back(1);
-            hashcall::new_bytes(c, nb);
-            for (size_t k = 0; k < c.cells.size(); k++) {
-              const Cell cc{c.cells[k].addr, 0, 0};
-              hd.push_back(mem_d(cc, c.cells[k].t, c.cells[k].bytes)); hsign.push_back(-1);
-              hd.push_back(mem_d(cc, (uint32_t)((c.cycle + 1) % bb::P), nb[k])); hsign.push_back(1);
-            }
-          }
-          std::vector<E4> hpre(hd.size());
-          E4 hacc = bb::e_one_m();
-          for (size_t i = 0; i < hd.size(); i++) { hpre[i] = hacc; hacc = bb::e_mul_m(hacc, hd[i]); }
-          E4 hinv = bb::e_inv_m(hacc), Tp = bb::e_zero();
-          for (size_t i = hd.size(); i-- > 0;) {
-            const E4 di = bb::e_mul_m(hinv, hpre[i]);
-            hinv = bb::e_mul_m(hinv, hd[i]);
-            Tp = hsign[i] > 0 ? bb::e_add(Tp, di) : bb::e_sub(Tp, di);
-          }
-          Tpart[part] = Tp;
-        });
-        for (const E4& tp : Tpart) T_hash = bb::e_add(T_hash, tp);
-      }
-      // (mode 4 d) the wide tape: + 1 / (alpha - fp(cycle, rs1, rs2, what the reference writes, opcode)) per record — the result is computed HERE (air::wide_result)
-      if (mode == 4 && n_wide) {
-        const unsigned parts = hashcall::parts_for(n_wide / 4);
-        std::vector<E4> Tpart(parts, bb::e_zero());
-        hashcall::for_calls(n_wide, parts, [&](unsigned part, size_t lo, size_t hi) {             // (host threads; each part inverts its own batch)
-          std::vector<E4> wd(hi - lo), wpre(hi - lo);
-          for (size_t k = lo; k < hi; k++) {
-            const uint32_t* r = wide_words + 1 + 8 * k;
-            const uint64_t a = (uint64_t)r[1] | ((uint64_t)r[2] << 20) | ((uint64_t)r[3] << 40), b = (uint64_t)r[4] | ((uint64_t)r[5] << 20) | ((uint64_t)r[6] << 40);
-            const uint64_t y = air::wide_result(r[7], a, b);
-            const uint32_t e[11] = {r[0] % bb::P, r[1], r[2], r[3], r[4], r[5], r[6], (uint32_t)(y & 0xFFFFF), (uint32_t)((y >> 20) & 0xFFFFF), (uint32_t)(y >> 40), r[7]};
-            E4 fp = bb::e_mul_fm(lam[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_WIDE));
-            for (int j = 0; j < 11; j++) fp = bb::e_add(fp, bb::e_mul_fm(lam[j], bb::to_mont(e[j])));
-            wd[k - lo] = bb::e_sub(alpha_l, fp);
-          }
-          E4 wacc = bb::e_one_m(), Tp = bb::e_zero();
-          for (size_t k = 0; k < wd.size(); k++) { wpre[k] = wacc; wacc = bb::e_mul_m(wacc, wd[k]); }
-          E4 winv = bb::e_inv_m(wacc);
-          for (size_t k = wd.size(); k-- > 0;) { Tp = bb::e_add(Tp, bb::e_mul_m(winv, wpre[k])); winv = bb::e_mul_m(winv, wd[k]); }
-          Tpart[part] = Tp;
-        });
-        for (const E4& tp : Tpart) T_hash = bb::e_add(T_hash, tp);
+      // - 1 / (alpha - fp(cell, told, old bytes)) + 1 / (alpha - fp(cell, cycle + 1, new bytes)), the digest inside the new bytes computed by the verifier; (mode 4 d) the
+      // wide tape: + 1 / (alpha - fp(cycle, rs1, rs2, what the reference writes, opcode)) per record, the result computed by the verifier
+      if (mode == 4) {
+        E4 Th = bb::e_zero(), Tw = bb::e_zero();
+        clk.lap(4);
+        const int hs = S.hash_side(S.self, lk_m, Th.c);
+        clk.lap(2);
+        if (hs) return hs;
+        const int ws = S.wide_side(S.self, lk_m, Tw.c);
+        clk.lap(3);
+        if (ws) return ws;
+        T_hash = bb::e_add(Th, Tw);
       }
     }
     for (size_t u = 0; u < n_code; u++) {

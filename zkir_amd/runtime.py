@@ -242,6 +242,23 @@ def tape_table_side(hash_section, new_bytes, wide_section, alpha, lam, device: b
     return out
 
 
+def hash_tape_new_bytes(hash_section, device: bool = True, stream=None) -> np.ndarray:
+    """zkir_hash_tape_new_bytes_launch / _host: per touched cell of a hash section, in the section's order, the cell's bytes AFTER its call — the message rebuilt from the
+    old bytes, hashed (SHA-256 / Keccak-256 / BLAKE3), the 32 output bytes laid over the old ones.  device=False: hashcall::new_bytes on the host."""
+    hs = np.ascontiguousarray(hash_section if hash_section is not None and len(hash_section) else [0], dtype=np.uint32)
+    n_calls, q, cells = int(hs[0]), 1, 0                          # the output is sized by the section's own counts: walked here, checked by the call
+    for _ in range(n_calls):
+        if q + 8 > len(hs):
+            break
+        k = int(hs[q + 7]); cells += k; q += 8 + 5 * k
+    out = np.zeros(min(cells, len(hs)), np.uint64)
+    args = [hs.ctypes.data, len(hs), out.ctypes.data if len(out) else None]
+    rc = lib().zkir_hash_tape_new_bytes_launch(*args, stream) if device else lib().zkir_hash_tape_new_bytes_host(*args)
+    if rc != ZKIR_OK:
+        _raise(rc)
+    return out
+
+
 def hash_tape_check(hash_section, n_real: int, code_end: int, device: bool = True, stream=None) -> int:
     """zkir_hash_tape_check_launch / _host: hashcall::parse_section's checks of a hash section — 0 well-formed, 4 truncated, 55 a call's output on code bytes, 56 a malformed
     record; of the lowest failing record.  device=False: parse_section itself."""
@@ -382,6 +399,11 @@ def lib() -> C.CDLL:
         L.zkir_tape_table_side_host.restype = C.c_int; L.zkir_tape_table_side_host.argtypes = [V, U64, V, V, U64, V, V, V, V, V]
         L.zkir_hash_tape_check_launch.restype = C.c_int; L.zkir_hash_tape_check_launch.argtypes = [V, U64, U64, U64, C.POINTER(C.c_int), V]
         L.zkir_hash_tape_check_host.restype = C.c_int; L.zkir_hash_tape_check_host.argtypes = [V, U64, U64, U64, C.POINTER(C.c_int)]
+    if hasattr(L, "zkir_verify_device"):
+        L.zkir_hash_tape_new_bytes_launch.restype = C.c_int; L.zkir_hash_tape_new_bytes_launch.argtypes = [V, U64, V, V]
+        L.zkir_hash_tape_new_bytes_host.restype = C.c_int; L.zkir_hash_tape_new_bytes_host.argtypes = [V, U64, V]
+        L.zkir_verify_device.restype = C.c_int; L.zkir_verify_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
+        L.zkir_verify_last_stages.restype = C.c_int; L.zkir_verify_last_stages.argtypes = [V, C.POINTER(C.c_uint32)]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -584,10 +606,25 @@ def verify_chain_io(proofs, expect: Optional[PublicInputsC], inputs, outputs, ha
     return L.zkir_verify_chain_io(ptrs, lens, len(ps), C.byref(expect) if expect is not None else None, i.ctypes.data, len(i), o.ctypes.data, len(o), int(kind), int(code or 0))
 
 
-def verify(proof: np.ndarray, expect: Optional[PublicInputsC] = None) -> int:
-    """zkir_verify (host only): 0 = accepted, otherwise the number of the failed check."""
+def verify(proof: np.ndarray, expect: Optional[PublicInputsC] = None, device: bool = False, stream=None) -> int:
+    """zkir_verify (host only): 0 = accepted, otherwise the number of the failed check.  device=True: zkir_verify_device — the same verdict, a mode-4 proof's tape stages
+    (record checks, chunk digests, the table side with every hash call's digest) on the GPU; a negative result is a device failure, not a verdict (raised)."""
     proof = np.ascontiguousarray(proof, dtype=np.uint32)
-    return lib().zkir_verify(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None)
+    if not device:
+        return lib().zkir_verify(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None)
+    rc = lib().zkir_verify_device(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None, stream)
+    if rc < 0:
+        _raise(-rc)
+    return rc
+
+
+def verify_last_stages() -> dict:
+    """zkir_verify_last_stages: the host clocks (ms) of this thread's last verification and how many of its stages ran on the device."""
+    ms, n = (C.c_double * 5)(), C.c_uint32(0)
+    rc = lib().zkir_verify_last_stages(ms, C.byref(n))
+    if rc != ZKIR_OK:
+        raise RuntimeError(rc, "no verification has run on this thread")
+    return {"parse": ms[0], "section_digests": ms[1], "hash_table_side": ms[2], "wide_table_side": ms[3], "rest": ms[4], "device_stages": int(n.value)}
 
 
 def interpret(program: Program | bytes, inputs: Sequence[int] = (), config: Optional[VMConfig] = None, tile_rows: int = 0,
