@@ -289,7 +289,12 @@ int zkir_sha256_chip_launch(const zkir_sha_block* blocks, uint64_t n, uint32_t* 
  * capacity 4 (~62-bit collisions).  What the AIR does and does not constrain is stated in zkir_amd/csrc/air.h. */
 typedef struct zkir_stark_ctx zkir_stark_ctx;     /* device tables (twiddles, coset powers, Poseidon2 constants) + workspace for 2^log_n rows.
                                                      One proof at a time per context; different contexts are independent (no process-wide state). */
-int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup /* must be 1 */, zkir_stark_ctx** out);
+/* log_blowup in {1, 2, 3} (rate 1/2, 1/4, 1/8) with log_n <= 26 and log_n + log_blowup <= 27, the field's two-adicity; anything else is ZKIR_ERR_ARGUMENT before anything is
+ * allocated.  A context of log_blowup 2 / 3 serves the COMMITMENT: zkir_lde_launch and the zkir_merkle_* calls.  The prover (zkir_prove; zkir_prove_result always makes its own
+ * context of log_blowup 1) and the experiments built on its LDE (zkir_amd_experimental.h) are defined at blow-up 2 only and refuse such a context with ZKIR_ERR_ARGUMENT
+ * before any launch: the proof format, AIR and verifier are blow-up 2. */
+int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** out);
+uint32_t zkir_stark_ctx_log_blowup(const zkir_stark_ctx* ctx);   /* what the context was created with (0 for NULL) */
 void zkir_stark_ctx_free(zkir_stark_ctx* ctx);
 uint32_t zkir_main_trace_width(void);             /* 152: COMMITTED main-trace columns of a default-mode run (the AIR's 172 logical columns minus the ones that
                                                      are identically zero there: R0's limbs and the 16 storage states; zkir_amd/csrc/air.h) */
@@ -333,10 +338,12 @@ void zkir_air_eval_host(const uint32_t* loc, const uint32_t* nxt, const uint32_t
                         const uint32_t* cnt4 /* mode 2: (oc, ic) of the first and of the last row; else NULL */, uint32_t* out4);
 int zkir_air_check_bounds(uint32_t deferred, char* why, size_t why_len);
 /* per-column low-degree extension: in = B8 matrix with N rows (evaluations over <w_N>, natural order; CLOBBERED as scratch when N >= 1024)
- * -> out = B8 matrix with 2N rows = evaluations over the coset 31*<w_2N>, natural order.  All 8 columns of every block are transformed. */
+ * -> out = B8 matrix with M = N << log_blowup rows (the context's: 2N, 4N or 8N) = evaluations over the coset 31*<w_M>, natural order, canonical words.  All 8 columns of
+ * every block are transformed (zero columns of a ragged last block stay zero).  The extensions nest: row 2j at log_blowup b is row j at b - 1. */
 int zkir_lde_launch(const zkir_stark_ctx* ctx, uint32_t* in, uint32_t width, uint32_t* out, void* hip_stream);
 /* Poseidon2-12 Merkle tree over the n_leaves rows of the B8 matrix `mat` (leaf j = sponge over the `width` real columns of row j);
- * tree = 4*(2*n_leaves-1) words, leaf digests first, root = last 4 words */
+ * tree = 4*(2*n_leaves-1) words, leaf digests first, root = last 4 words.  This call, _leaves_ and _cap_ take the leaf count from the caller and use nothing of the
+ * context that depends on its rate: n_leaves = N << log_blowup, up to 2^27, needs nothing else (64-bit leaf indices, at most 2^19 workgroups a launch). */
 int zkir_merkle_commit_launch(const zkir_stark_ctx* ctx, const uint32_t* mat, uint32_t width, uint64_t n_leaves, uint32_t* tree, void* hip_stream);
 
 /* The two halves of zkir_merkle_commit_launch, for callers that time or schedule them separately: the leaf digests (tree[0..4n), one

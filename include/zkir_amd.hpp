@@ -360,12 +360,14 @@ namespace zkir_prover {
 
 class StarkContext {                                            // device tables + workspace for traces of 2^log_n rows
  public:
-  explicit StarkContext(uint32_t log_n) : log_n_(log_n) { const int rc = zkir_stark_ctx_create(log_n, 1, &h_); if (rc != ZKIR_OK) zkir_runtime::detail::raise(rc); }
+  // log_blowup 2 / 3: a context for COMMITMENTS at rate 1/4 / 1/8 (zkir_lde_launch, zkir_merkle_*); proofs are blow-up 2 and refuse it
+  explicit StarkContext(uint32_t log_n, uint32_t log_blowup = 1) : log_n_(log_n) { const int rc = zkir_stark_ctx_create(log_n, log_blowup, &h_); if (rc != ZKIR_OK) zkir_runtime::detail::raise(rc); }
   ~StarkContext() { zkir_stark_ctx_free(h_); }
   StarkContext(const StarkContext&) = delete;
   StarkContext& operator=(const StarkContext&) = delete;
   const zkir_stark_ctx* handle() const { return h_; }
   uint32_t log_n() const { return log_n_; }
+  uint32_t log_blowup() const { return zkir_stark_ctx_log_blowup(h_); }
 
  private:
   zkir_stark_ctx* h_ = nullptr;

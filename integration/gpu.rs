@@ -90,6 +90,7 @@ extern "C" {
     fn zkir_last_error() -> *const c_char;
     // proving (self-defined stages: the reference has none — DESIGN.md §8)
     fn zkir_stark_ctx_create(log_n: u32, log_blowup: u32, out: *mut *mut ZkirStarkCtx) -> c_int;
+    fn zkir_stark_ctx_log_blowup(ctx: *const ZkirStarkCtx) -> u32;
     fn zkir_stark_ctx_free(ctx: *mut ZkirStarkCtx);
     fn zkir_padded_log_n(n_real: u64) -> u32;
     fn zkir_public_inputs_of(log: *const ZkirDeltaLog, blob: *const u8, len: usize, inputs: *const u64, n_inputs: usize, deferred: u32, out: *mut ZkirPublicInputs) -> c_int;

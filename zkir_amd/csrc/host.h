@@ -199,11 +199,12 @@ int memcheck_device_hash(const zkir_trace_columns* trace, uint64_t n_real, const
 struct LdeTables {
   int log_n;
   const uint32_t* tw_inv;     // w_N^-k, k < N/2
-  const uint32_t* tw_fwd;     // w_{2N}^k, k < N
+  const uint32_t* tw_fwd;     // w_M^k, k < M/2, M = N << log_blowup   (blow-up 2: w_{2N}^k, k < N)
   const uint32_t* g_lo;       // g^k / N, k < 1024
   const uint32_t* g_hi;       // g^(1024 k)
   const uint32_t* small_inv;  // w_{2^Bm}^-k, k < 2^(Bm-1)      (Bm = min(log_n, 10))
-  const uint32_t* small_fwd;  // w_{2^(Bm+1)}^k, k < 2^Bm
+  const uint32_t* small_fwd;  // w_{2^(Bm+b)}^k, k < 2^(Bm+b-1), b = log_blowup   (blow-up 2: w_{2^(Bm+1)}^k, k < 2^Bm)
+  int log_blowup = 1;         // 1, 2, 3: rows of `out` = N << log_blowup
 };
 void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out, void* hip_stream);   // matrices in the B8 layout: n_blocks x [rows][8]
 bool strided_variant_run(const LdeTables& t, uint32_t* data, uint32_t n_blocks, int variant, bool dit, void* hip_stream);   // experiment: one strided pass, chosen tile geometry (timing only)

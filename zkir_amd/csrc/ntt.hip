@@ -584,11 +584,176 @@ __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   }
 }
 
+
+// ---- blow-up 4 and 8 (log_blowup b = 2, 3): the same pass structure with M = N 2^b output rows.  Coefficient k of the padded input sits at position brv_L(k) << b of the
+// bit-reversed size-M array, so forward stages 0 .. b-1 only replicate every coefficient 2^b times and stages b .. b+9 stay inside a chunk of 1024 * 2^b output positions.
+// For a fixed residue r of the output position mod 2^b those ten stages touch only positions of that residue: the chunk is 2^b INDEPENDENT 1024-point transforms of the SAME
+// 1024 scaled coefficients, one per coset 31 w_M^r <w_N>, and the twiddle of local stage s at position c of residue r is w_(2^(s+1))^(c mod 2^s) * w_(2^(s+b+1))^r.
+//
+// lde_middle_blowup_kernel<LB>: the inverse half is that of lde_middle_r4_kernel (A = both column planes of the chunk, 32 KiB) except for the hand-off after its last round: a
+// wave-local wait where the shipped kernel has a workgroup barrier, because forward round 0 here reads only the lane's own positions 4q .. 4q + 3.  The
+// forward half then runs ONE RESIDUE AT A TIME, both planes together, in F (32 KiB): 64 KiB per workgroup and two workgroups per CU at every b, where a whole b = 3 chunk
+// (2 x 128 KiB) could not be resident at all.  A lane owns (quad q, plane h) as on the inverse side; round 0 reads A (which every residue needs again) and writes F.  A lane's
+// twiddle of round rho for residue r is its residue-0 twiddle times w_(2^(2 rho + b + 2))^r: a running product, five multiplications per lane and residue, no table read
+// inside the chunk loop (the prefetch discipline of the strided kernel: nothing is read from global memory between the issue of the next chunk's prefetch and its use).
+// Rounds 0 .. 3 (spans up to 64) stay inside a wave's own 256 positions of its plane; only round 4 crosses waves.
+// Stores: output position (c << b) | r takes both planes from one lane, 32 contiguous bytes = one full sector per lane (half-filled sectors reach HBM twice: see the
+// comment in lde_middle_r4_kernel); the lanes of a wave are 32 << b bytes apart, and the 2^b residues of a 128-byte line are written within one chunk's time.
+template <int LB>
+__global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void lde_middle_blowup_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, uint32_t chunks_per_block, uint32_t total, int L,
+                                                                const uint32_t* __restrict__ tw_inv, const uint32_t* __restrict__ small_inv, const uint32_t* __restrict__ small_fwd,
+                                                                const uint32_t* __restrict__ g_lo, const uint32_t* __restrict__ g_hi, uint32_t j4_inv_m, uint32_t j4_fwd_m, int canon) {
+  static_assert(LB == 2 || LB == 3, "blow-up 4 or 8 (blow-up 2: lde_middle_r4_kernel)");
+  constexpr int Bm = 10;
+  constexpr uint32_t APL = 1024;
+  __shared__ uint4 A[2 * APL];
+  __shared__ uint4 F[2 * APL];
+  const uint32_t n = 1u << L, t = threadIdx.x;
+  uint32_t w = blockIdx.x;
+  if (w >= total) return;
+  uint32_t tw_i[5], tw_f[5], step[5];
+#pragma unroll
+  for (int r = 0; r < 5; r++) {
+    const int lg = 8 - 2 * r;
+    tw_i[r] = small_inv[bitrev((t & 255) >> lg, 2 * r) << lg];                 // w_(2^(2r+2))^-brv_2r(block inside the chunk)
+    const int s = 2 * r;                                                       // forward round r = local stages (s, s + 1); small_fwd has order 2^(10 + LB)
+    tw_f[r] = small_fwd[((t & 255) & ((1u << s) - 1)) << (LB + lg)];           // w_(2^(s+2))^lo: stage s + 1 at residue 0
+    step[r] = small_fwd[1u << lg];                                             // w_(2^(s+LB+2)): from one residue to the next
+  }
+  u32x4 pre[4];
+  uint32_t cf_next[5];                                         // tw_inv[brv_(L-10)(chunk) << (8 - 2r)]: the chunk's factor of inverse round r
+  uint32_t glo[4], ghi[4];                                     // factors of g^k / N for the lane's four positions 4q .. 4q + 3 of the last inverse round, k = bitrev_L(position)
+  auto fetch = [&](uint32_t ww) {                              // one chunk's loads, in the order they are consumed: the 1024 positions, then the scale factors
+    const uint4* x = in + ((uint64_t)(ww / chunks_per_block) * n + ((uint64_t)(ww % chunks_per_block) << Bm)) * 2;
+#pragma unroll
+    for (int k = 0; k < 4; k++) pre[k] = ld4(&x[t + k * MID_NT]);
+    const uint32_t p0 = ((ww % chunks_per_block) << Bm) + 4 * (t & 255);
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const uint32_t k = bitrev(p0 + i, L); glo[i] = g_lo[k & 1023]; ghi[i] = g_hi[k >> 10]; }
+    const uint32_t ce = bitrev(ww % chunks_per_block, L - Bm);
+#pragma unroll
+    for (int r = 0; r < 5; r++) cf_next[r] = tw_inv[ce << (8 - 2 * r)];
+  };
+  fetch(w);
+  const uint32_t q = t & 255;
+  uint4* a = A + (t >> 8) * APL;                               // the lane's plane, both sides
+  uint4* f = F + (t >> 8) * APL;
+  for (;;) {
+    const uint32_t base = (w % chunks_per_block) << Bm;
+    uint4* y = out + ((uint64_t)(w / chunks_per_block) * n << (LB + 1));
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const uint32_t e = t + k * MID_NT; st4(&A[(e & 1) * APL + (e >> 1)], pre[k]); }
+    uint32_t gs[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) gs[i] = bb::mont_mul(glo[i], ghi[i]);
+    uint32_t cf[5];
+#pragma unroll
+    for (int r = 0; r < 5; r++) cf[r] = cf_next[r];
+    __syncthreads();
+    const uint32_t wn = w + gridDim.x;
+    if (wn < total) fetch(wn);
+    // ---- inverse, rounds r = 0..4 (lde_middle_r4_kernel) ----
+#pragma unroll
+    for (int r = 0; r < 5; r++) {
+      const int lg = 8 - 2 * r;                                // log2(h2)
+      const uint32_t h2 = 1u << lg, lo = q & (h2 - 1), hi = q >> lg;
+      const uint32_t i0 = (hi << (lg + 2)) | lo;
+      WTw c1, c2, c2i;
+      ct_twiddles(tw_i[r], cf[r], false, j4_inv_m, c1, c2, c2i);
+      uint4 x0 = a[i0], x1 = a[i0 + h2], x2 = a[i0 + 2 * h2], x3 = a[i0 + 3 * h2];
+      ct4w4(x0, x1, x2, x3, c1, c2, c2i);
+      if (r == 4) { x0 = scale4(x0, gs[0]); x1 = scale4(x1, gs[1]); x2 = scale4(x2, gs[2]); x3 = scale4(x3, gs[3]); }
+      a[i0] = x0; a[i0 + h2] = x1; a[i0 + 2 * h2] = x2; a[i0 + 3 * h2] = x3;
+      // rounds 1..4 stay inside the wave's own 256 positions of its plane; round 4's results are read next by forward round 0 of the SAME wave (positions 4q .. 4q + 3)
+      if (r >= 1) wave_sync_lds(); else __syncthreads();
+    }
+    // ---- forward, one residue at a time: the 1024-point DIT of A on the coset of residue res, both planes, in F ----
+    uint32_t twl[5];                                           // the lane's twiddle of round r at the current residue
+#pragma unroll
+    for (int r = 0; r < 5; r++) twl[r] = tw_f[r];
+#pragma unroll 1
+    for (uint32_t res = 0; res < (1u << LB); res++) {
+#pragma unroll
+      for (int r = 0; r < 5; r++) {
+        const int s = 2 * r;
+        const uint32_t lo = q & ((1u << s) - 1), hi = q >> s;
+        const uint32_t i0 = (hi << (s + 2)) | lo, d = 1u << s;
+        const uint32_t w2 = twl[r];
+        const WTw c2 = wtw(bb::centre(w2)), c1 = wtw(bb::mont_mul_centred(w2, w2)), c2i = wtw(bb::mont_mul_centred(w2, j4_fwd_m));
+        twl[r] = bb::mont_mul(w2, step[r]);
+        uint4 x0, x1, x2, x3;
+        if (r == 0) { x0 = a[i0]; x1 = a[i0 + 1]; x2 = a[i0 + 2]; x3 = a[i0 + 3]; }           // the replicated coefficients: every residue starts from A
+        else { x0 = f[i0]; x1 = f[i0 + d]; x2 = f[i0 + 2 * d]; x3 = f[i0 + 3 * d]; }
+        dit4w4(x0, x1, x2, x3, c1, c2, c2i);
+        f[i0] = x0; f[i0 + d] = x1; f[i0 + 2 * d] = x2; f[i0 + 3 * d] = x3;
+        // rounds 0..3 (spans up to 64) stay inside the wave's own 256 positions [256 v, 256 v + 256) of its plane of F; round 4 crosses waves
+        if (r < 3) wave_sync_lds(); else __syncthreads();
+      }
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const uint32_t c = t + k * MID_NT;
+        uint4 v0 = F[c], v1 = F[APL + c];
+        if (canon) { v0 = canon4(v0); v1 = canon4(v1); }      // log_n = 10: no strided forward pass follows
+        const uint64_t o = ((((uint64_t)base + c) << LB) | res) * 2;
+        y[o] = v0; y[o + 1] = v1;
+      }
+      __syncthreads();                                         // F is rewritten by the next residue's round 0, A by the next chunk
+    }
+    if (wn >= total) break;
+    w = wn;
+  }
+}
+
+// ---- N < 1024 at blow-up 2^b, b = 2, 3: lde_small_kernel with 2^b copies of every scaled coefficient and forward stages b .. L+b-1 of the size-M transform
+//      (small_fwd: w_(2^(L+b))^k, k < 2^(L+b-1); LDS: M words, at most 16 KiB) ----
+__global__ __launch_bounds__(NT) void lde_small_blowup_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int L, int lb, const uint32_t* __restrict__ small_inv,
+                                                               const uint32_t* __restrict__ small_fwd, const uint32_t* __restrict__ g_lo, const uint32_t* __restrict__ g_hi) {
+  extern __shared__ uint32_t lds[];                            // M words
+  const uint32_t n = 1u << L, m = n << lb;
+  const uint32_t* x = in + (uint64_t)blockIdx.x * n * 8;
+  uint32_t* y = out + (uint64_t)blockIdx.x * m * 8;
+  for (int c = 0; c < 8; c++) {
+    for (uint32_t e = threadIdx.x; e < n; e += NT) lds[e] = x[(uint64_t)e * 8 + c];
+    __syncthreads();
+    for (int b = 0; b < L; b++) {                              // inverse DIF stages, half = 2^(L-1-b)
+      const int hb = L - 1 - b;
+      const uint32_t half = 1u << hb;
+      for (uint32_t q = threadIdx.x; q < (n >> 1); q += NT) {
+        const uint32_t r_lo = q & (half - 1), r_hi = q >> hb;
+        const uint32_t ia = (r_hi << (hb + 1)) | r_lo, ib = ia + half;
+        const uint32_t a = lds[ia], bv = lds[ib];
+        lds[ia] = bb::add(a, bv); lds[ib] = bb::mont_mul(bb::sub(a, bv), small_inv[r_lo << b]);
+      }
+      __syncthreads();
+    }
+    // scale + replicate: position p holds coefficient k = bitrev_L(p); DIT stages 0 .. lb-1 copy it to positions (p << lb) .. (p << lb) + 2^lb - 1
+    uint32_t v[2];                                             // n <= 512: at most two positions per lane
+    int cnt = 0;
+    for (uint32_t e = threadIdx.x; e < n; e += NT) { const uint32_t k = bitrev(e, L); v[cnt++] = bb::mont_mul(bb::mont_mul(lds[e], g_lo[k & 1023]), g_hi[k >> 10]); }
+    __syncthreads();
+    cnt = 0;
+    for (uint32_t e = threadIdx.x; e < n; e += NT) { for (uint32_t i = 0; i < (1u << lb); i++) lds[(e << lb) + i] = v[cnt]; cnt++; }
+    __syncthreads();
+    for (int s = lb; s < L + lb; s++) {                        // forward DIT stages lb .. L+lb-1 of the size-M transform
+      const uint32_t half = 1u << s;
+      for (uint32_t q = threadIdx.x; q < (m >> 1); q += NT) {
+        const uint32_t r_lo = q & (half - 1), r_hi = q >> s;
+        const uint32_t ia = (r_hi << (s + 1)) | r_lo, ib = ia + half;
+        const uint32_t a = lds[ia], tt = bb::mont_mul(lds[ib], small_fwd[r_lo << (L + lb - 1 - s)]);
+        lds[ia] = bb::add(a, tt); lds[ib] = bb::sub(a, tt);
+      }
+      __syncthreads();
+    }
+    for (uint32_t e = threadIdx.x; e < m; e += NT) y[(uint64_t)e * 8 + c] = lds[e];
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 namespace zkir {
 
-// in: n_blocks x [N][8] canonical evaluations over H (natural order; used as scratch and overwritten!), out: n_blocks x [2N][8]
+// in: n_blocks x [N][8] canonical evaluations over H (natural order; used as scratch and overwritten!), out: n_blocks x [N << t.log_blowup][8]
 void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int L = t.log_n;
@@ -597,6 +762,22 @@ void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out,
   static const uint32_t r8_fwd = bb::root_of_unity(3), r8_inv = bb::inv(r8_fwd);
   static const uint32_t r8_inv_m = bb::to_mont(r8_inv), r8_inv3_m = bb::to_mont(bb::mul(bb::mul(r8_inv, r8_inv), r8_inv));
   static const uint32_t r8_fwd_m = bb::to_mont(r8_fwd), r8_fwd3_m = bb::to_mont(bb::mul(bb::mul(r8_fwd, r8_fwd), r8_fwd));
+  const int LB = t.log_blowup;
+  if (LB != 1) {                                                 // blow-up 4 / 8: the same three steps with their own middle (and small) kernel; the strided kernels are generic
+    if (L < 10) {
+      hipLaunchKernelGGL(lde_small_blowup_kernel, dim3(n_blocks), dim3(NT), (4u << (L + LB)), s, in, out, L, LB, t.small_inv, t.small_fwd, t.g_lo, t.g_hi);
+      return;
+    }
+    run_strided_stages<false>(in, N, n_blocks, L, 0, L - 10, t.tw_inv, t.small_inv, 10, j4_inv_m, r8_inv_m, r8_inv3_m, s);
+    const uint32_t chunks = N >> 10, total = chunks * n_blocks;
+    unsigned grid = persist() ? cu_count() * 2 : total;                     // 64 KiB of LDS: two workgroups per CU
+    if (grid > total) grid = total;
+    auto mid = LB == 2 ? lde_middle_blowup_kernel<2> : lde_middle_blowup_kernel<3>;
+    hipLaunchKernelGGL(mid, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.tw_inv, t.small_inv, t.small_fwd, t.g_lo, t.g_hi, j4_inv_m, j4_fwd_m, L == 10);
+    // forward DIT strided stages 10 + b .. L + b - 1 of the size-M transform (tw_fwd: w_M^k, small_fwd: order 2^(10 + b))
+    run_strided_stages<true>(out, (uint64_t)N << LB, n_blocks, L + LB, 10 + LB, L - 10, t.tw_fwd, t.small_fwd, 10 + LB, j4_fwd_m, r8_fwd_m, r8_fwd3_m, s);
+    return;
+  }
   if (L < 10) {
     hipLaunchKernelGGL(lde_small_kernel, dim3(n_blocks), dim3(NT), (8u << L), s, in, out, L, t.small_inv, t.small_fwd, t.g_lo, t.g_hi);
     return;

@@ -737,13 +737,13 @@ void launch_tree_levels(const p2::Consts* cp, uint32_t* leaf_digests, uint64_t n
 struct zkir_stark_ctx {
   uint32_t log_n = 0, log_blowup = 1;
   uint32_t* d_tw_inv = nullptr;   // w_N^-k, k < N/2
-  uint32_t* d_tw_fwd = nullptr;   // w_{2N}^k, k < N
+  uint32_t* d_tw_fwd = nullptr;   // w_M^k, k < M/2, M = N << log_blowup   (blow-up 2: w_{2N}^k, k < N — the form the prover's kernels read)
   uint32_t* d_g_lo = nullptr;     // g^k / N, k < 1024
   uint32_t* d_g_lo_m = nullptr;   // R g^k / N: the same scale with the Montgomery factor folded in — the LDE then leaves its output in Montgomery form (zkir_prove)
-  uint32_t* d_inv_xm1 = nullptr;  // 1 / (x_j - 1), j < 2N, over the LDE coset (Montgomery): the row selectors of the quotient (stark_prove.inl)
+  uint32_t* d_inv_xm1 = nullptr;  // 1 / (x_j - 1), j < 2N, over the blow-up-2 LDE coset (Montgomery): the row selectors of the quotient (stark_prove.inl); filled at log_blowup 1 only
   uint32_t* d_g_hi = nullptr;     // g^(1024 k)
   uint32_t* d_small_inv = nullptr;  // w_{2^Bm}^-k, k < 2^(Bm-1)      (Bm = min(log_n, 10))
-  uint32_t* d_small_fwd = nullptr;  // w_{2^(Bm+1)}^k, k < 2^Bm
+  uint32_t* d_small_fwd = nullptr;  // w_{2^(Bm+b)}^k, k < 2^(Bm+b-1), b = log_blowup   (blow-up 2: w_{2^(Bm+1)}^k, k < 2^Bm)
   p2::Consts consts;              // host copy (transcript, verifier side)
   p2::Consts* d_p2 = nullptr;     // device copy: every hash kernel takes the pointer (no process-wide __constant__ state)
   // zkir_commit_overlapped_launch (experiment): a second stream, two events and the per-leaf sponge states, made on first use
@@ -757,10 +757,17 @@ struct zkir_stark_ctx {
 };
 
 namespace {
+// What is defined at blow-up 2 only (the prover and the experiments built on its LDE) refuses a context of another rate BEFORE any launch
+const char* const BLOWUP2_ONLY = ": the context has log_blowup != 1; the prover's quotient, DEEP and FRI stages (and the experiments built on its LDE) are blow-up 2 — contexts of log_blowup 2 / 3 serve zkir_lde_launch and the zkir_merkle_* calls";
+bool blowup2_only(const zkir_stark_ctx* c, const char* who) {
+  if (c->log_blowup == 1) return true;
+  zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + BLOWUP2_ONLY});
+  return false;
+}
 // The LDE with the scale table chosen by the form its output is to rest in: mont_out = the words of `out` carry the Montgomery factor R (the
 // prover's matrices; the scale g^k / N of the fused middle pass comes from the table that has R folded in — same kernels, same instruction count).
 int lde_launch(const zkir_stark_ctx* c, uint32_t* in, uint32_t width, uint32_t* out, bool mont_out, hipStream_t s) {
-  const zkir::LdeTables t{(int)c->log_n, c->d_tw_inv, c->d_tw_fwd, mont_out ? c->d_g_lo_m : c->d_g_lo, c->d_g_hi, c->d_small_inv, c->d_small_fwd};
+  const zkir::LdeTables t{(int)c->log_n, c->d_tw_inv, c->d_tw_fwd, mont_out ? c->d_g_lo_m : c->d_g_lo, c->d_g_hi, c->d_small_inv, c->d_small_fwd, (int)c->log_blowup};
   zkir::lde_run(t, in, (width + 7) / 8, out, s);               // ntt.hip
   return check_launch("lde");
 }
@@ -859,37 +866,42 @@ double zkir_modmul_peak_per_s(void* stream) {
 }
 
 int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** out) {
-  if (!out || log_n < 1 || log_n > 26 || log_blowup != 1) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_stark_ctx_create: need 1 <= log_n <= 26 and log_blowup == 1"}); return ZKIR_ERR_ARGUMENT; }
+  // (log_n + log_blowup <= 27 is Baby Bear's 2-adicity: the extension's domain has to exist — not a memory bound)
+  if (!out || log_n < 1 || log_n > 26 || log_blowup < 1 || log_blowup > 3 || log_n + log_blowup > 27) {
+    zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_stark_ctx_create: need 1 <= log_n <= 26, log_blowup in {1, 2, 3} and log_n + log_blowup <= 27 (the field's two-adicity)"});
+    return ZKIR_ERR_ARGUMENT;
+  }
   *out = nullptr;
   zkir_stark_ctx* c = new zkir_stark_ctx();
   c->log_n = log_n; c->log_blowup = log_blowup;
   const uint32_t N = 1u << log_n;
   const uint32_t n_inv = N >= 2 ? N / 2 : 1, n_hi = (N >> 10) + 1;
+  const uint32_t n_fwd = N << (log_blowup - 1);                  // M / 2
   p2::generate(c->consts);
   hipError_t e = hipMalloc((void**)&c->d_p2, sizeof(p2::Consts));
   if (e == hipSuccess) e = hipMemcpy(c->d_p2, &c->consts, sizeof(p2::Consts), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&c->sync.d_slots, SYNC_SLOTS * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(c->sync.d_slots, 0, SYNC_SLOTS * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&c->d_tw_inv, (size_t)n_inv * 4);
-  if (e == hipSuccess) e = hipMalloc(&c->d_tw_fwd, (size_t)N * 4);
+  if (e == hipSuccess) e = hipMalloc(&c->d_tw_fwd, (size_t)n_fwd * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_g_lo, 1024 * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_g_hi, (size_t)n_hi * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_g_lo_m, 1024 * 4);
-  if (e == hipSuccess) e = hipMalloc(&c->d_inv_xm1, (size_t)2 * N * 4);
+  if (e == hipSuccess && log_blowup == 1) e = hipMalloc(&c->d_inv_xm1, (size_t)2 * N * 4);        // the prover's: it refuses any other rate
   const int Bm = log_n < 10 ? (int)log_n : 10;
-  const uint32_t n_si = Bm >= 1 ? (1u << (Bm - 1)) : 1, n_sf = 1u << Bm;
+  const uint32_t n_si = Bm >= 1 ? (1u << (Bm - 1)) : 1, n_sf = 1u << (Bm + log_blowup - 1);
   if (e == hipSuccess) e = hipMalloc(&c->d_small_inv, (size_t)n_si * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_small_fwd, (size_t)n_sf * 4);
   if (e != hipSuccess) { zkir::set_last_error({ZKIR_ERR_DEVICE, std::string("zkir_stark_ctx_create: ") + hipGetErrorString(e)}); zkir_stark_ctx_free(c); return ZKIR_ERR_DEVICE; }
-  const uint32_t wN = bb::root_of_unity(log_n), w2N = bb::root_of_unity(log_n + 1);
+  const uint32_t wN = bb::root_of_unity(log_n), wM = bb::root_of_unity(log_n + log_blowup);
   hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_inv)), dim3(NT), 0, 0, bb::inv(wN), bb::R1, c->d_tw_inv, n_inv);
-  hipLaunchKernelGGL(powers_kernel, dim3(grid_for(N)), dim3(NT), 0, 0, w2N, bb::R1, c->d_tw_fwd, N);
+  hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_fwd)), dim3(NT), 0, 0, wM, bb::R1, c->d_tw_fwd, n_fwd);
   hipLaunchKernelGGL(powers_kernel, dim3(4), dim3(NT), 0, 0, bb::GEN, bb::to_mont(bb::inv(N % bb::P)), c->d_g_lo, 1024u);
   hipLaunchKernelGGL(powers_kernel, dim3(4), dim3(NT), 0, 0, bb::GEN, bb::to_mont(bb::to_mont(bb::inv(N % bb::P))), c->d_g_lo_m, 1024u);
   hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_hi)), dim3(NT), 0, 0, bb::pow(bb::GEN, 1024), bb::R1, c->d_g_hi, n_hi);
-  hipLaunchKernelGGL(selector_inverse_kernel, dim3(grid_for((2ull * N + 7) / 8)), dim3(NT), 0, 0, log_n, c->d_tw_fwd, c->d_inv_xm1);
+  if (log_blowup == 1) hipLaunchKernelGGL(selector_inverse_kernel, dim3(grid_for((2ull * N + 7) / 8)), dim3(NT), 0, 0, log_n, c->d_tw_fwd, c->d_inv_xm1);
   hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_si)), dim3(NT), 0, 0, bb::inv(bb::root_of_unity(Bm)), bb::R1, c->d_small_inv, n_si);
-  hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_sf)), dim3(NT), 0, 0, bb::root_of_unity(Bm + 1), bb::R1, c->d_small_fwd, n_sf);
+  hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_sf)), dim3(NT), 0, 0, bb::root_of_unity(Bm + log_blowup), bb::R1, c->d_small_fwd, n_sf);
   if (hipDeviceSynchronize() != hipSuccess || check_launch("stark ctx tables") != ZKIR_OK) { zkir_stark_ctx_free(c); return ZKIR_ERR_DEVICE; }
   *out = c;
   return ZKIR_OK;
@@ -906,6 +918,8 @@ void zkir_stark_ctx_free(zkir_stark_ctx* c) {
   if (c->arena) (void)hipFree(c->arena);
   delete c;
 }
+
+uint32_t zkir_stark_ctx_log_blowup(const zkir_stark_ctx* c) { return c ? c->log_blowup : 0; }
 
 uint32_t zkir_padded_log_n(uint64_t n_real) { uint32_t k = 3; while (((uint64_t)1 << k) < n_real) k++; return k; }
 
@@ -1004,6 +1018,7 @@ int zkir_main_trace_io_host(const zkir_trace_columns* trace, uint64_t n_real, co
 // does not apply (log_n < 20 or = 21, deferred mode).
 int zkir_commit_fused01_launch(const zkir_stark_ctx* c, const zkir_trace_columns* trace, uint64_t n_real, uint32_t* m, uint32_t width, uint32_t* out, void* stream) {
   if (!c || !trace || !m || !out || n_real == 0 || zkir_padded_log_n(n_real) != c->log_n) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_commit_fused01_launch: bad argument"}); return ZKIR_ERR_ARGUMENT; }
+  if (!blowup2_only(c, "zkir_commit_fused01_launch")) return ZKIR_ERR_ARGUMENT;
   const uint64_t N = (uint64_t)1 << c->log_n;
   hipLaunchKernelGGL((main_trace_kernel<0, 2>), dim3(grid_for(N)), dim3(NT), 0, (hipStream_t)stream, *trace, n_real, N, m, IoRowArgs{});
   const zkir::LdeTables t{(int)c->log_n, c->d_tw_inv, c->d_tw_fwd, c->d_g_lo, c->d_g_hi, c->d_small_inv, c->d_small_fwd};
@@ -1013,6 +1028,7 @@ int zkir_commit_fused01_launch(const zkir_stark_ctx* c, const zkir_trace_columns
 
 // EXPERIMENT: one strided NTT pass with a chosen tile geometry over `width` columns of 2^log_n (inverse) / 2^(log_n + 1) (forward) rows: timing only (ntt.hip: strided_variant_run)
 int zkir_ntt_strided_variant_launch(const zkir_stark_ctx* c, uint32_t* data, uint32_t width, int variant, int forward, void* stream) {
+  if (!c || !blowup2_only(c, "zkir_ntt_strided_variant_launch")) { if (!c) zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_ntt_strided_variant_launch: null context"}); return ZKIR_ERR_ARGUMENT; }
   const zkir::LdeTables t{(int)c->log_n, c->d_tw_inv, c->d_tw_fwd, c->d_g_lo, c->d_g_hi, c->d_small_inv, c->d_small_fwd};
   if (!zkir::strided_variant_run(t, data, (width + 7) / 8, variant, forward != 0, stream)) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_ntt_strided_variant_launch: log_n < 20 or unknown variant"}); return ZKIR_ERR_ARGUMENT; }
   return check_launch("ntt_strided_variant");
@@ -1035,6 +1051,7 @@ int zkir_main_trace_host(const zkir_trace_columns* trace, uint64_t n_real, uint3
 int zkir_commit_overlapped_launch(const zkir_stark_ctx* c, uint32_t* in, uint32_t width, uint32_t* out, uint32_t* tree, uint32_t group, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!c || !in || !out || !tree || width == 0 || group == 0) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_commit_overlapped_launch: bad argument"}); return ZKIR_ERR_ARGUMENT; }
+  if (!blowup2_only(c, "zkir_commit_overlapped_launch")) return ZKIR_ERR_ARGUMENT;
   std::lock_guard<std::mutex> lk(c->mu);
   const uint64_t N = (uint64_t)1 << c->log_n, N2 = N << c->log_blowup;
   const uint32_t nb = (width + 7) / 8, n_groups = (nb + group - 1) / group;
@@ -1057,7 +1074,7 @@ int zkir_commit_overlapped_launch(const zkir_stark_ctx* c, uint32_t* in, uint32_
   return check_launch("commit_overlapped");
 }
 
-// in: ceil(width/8) blocks [N][8] of canonical evaluations over H (natural order; used as scratch and overwritten!), out: blocks [2N][8]
+// in: ceil(width/8) blocks [N][8] of canonical evaluations over H (natural order; used as scratch and overwritten!), out: blocks [N << log_blowup][8]
 int zkir_lde_launch(const zkir_stark_ctx* c, uint32_t* in, uint32_t width, uint32_t* out, void* stream) { return lde_launch(c, in, width, out, false, (hipStream_t)stream); }
 
 // mat: B8 layout, ceil(width/8) blocks [n_leaves][8]; tree = [leaf digests (4*n)] [layer 1 (4*n/2)] ... [root (4)] = 4*(2n-1) words; n_leaves a power of two

@@ -359,6 +359,8 @@ def lib() -> C.CDLL:
         f.argtypes = args
     L.zkir_stark_ctx_create.restype = C.c_int
     L.zkir_stark_ctx_create.argtypes = [U32, U32, C.POINTER(V)]
+    if hasattr(L, "zkir_stark_ctx_log_blowup"):               # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_stark_ctx_log_blowup.restype = U32; L.zkir_stark_ctx_log_blowup.argtypes = [V]
     L.zkir_stark_ctx_free.restype = None
     L.zkir_stark_ctx_free.argtypes = [V]
     L.zkir_main_trace_width.restype = U32

@@ -65,16 +65,21 @@ class PipelineReport:
 
 
 def prove_many(jobs: Iterable[Job], log2_rows: int, producers: int = 3, ctx: Optional[stark.StarkContext] = None,
-               keep_proofs: bool = True, commit_only: bool = False, provers: int = 2) -> PipelineReport:
+               keep_proofs: bool = True, commit_only: bool = False, provers: int = 2, log_blowup: int = 1) -> PipelineReport:
     """Prove every job (program blob, inputs, VMConfig with enable_execution_trace; the run's row count must pad to 2^log2_rows,
     i.e. 2^(log2_rows-1) < rows <= 2^log2_rows).  Proofs come back in job order.  commit_only: stop after the trace commitment
-    (trace fill + main trace + LDE + Merkle); `proofs` then holds the 4-word roots.
+    (trace fill + main trace + LDE + Merkle); `proofs` then holds the 4-word roots.  log_blowup (1, 2, 3; a given `ctx` brings its own): the rate of that
+    commitment — full proofs are blow-up 2, so anything else needs commit_only.
     provers: a proof makes ~13 host round trips (Fiat-Shamir on the host) during which ITS stream is idle; with two proving threads,
     each with its own context (workspace) and stream, the GPU works on one proof while the other waits for its transcript."""
     pl._require_gpu()
     jobs = list(jobs)
     own_ctx = ctx is None
-    ctx = ctx or stark.StarkContext(log2_rows)
+    ctx = ctx or stark.StarkContext(log2_rows, log_blowup)
+    if ctx.log_blowup != 1 and not commit_only:
+        if own_ctx:
+            ctx.close()
+        raise rt.RuntimeError(rt.ERR_ARGUMENT, f"prove_many: proofs are blow-up 2; log_blowup {ctx.log_blowup} serves commit_only")
     ready: "queue.Queue" = queue.Queue(maxsize=max(2, producers))
     todo = list(enumerate(jobs))[::-1]
     lock = threading.Lock()

@@ -66,7 +66,8 @@ def trace_root(proof) -> list:
 
 
 class StarkContext:
-    """zkir_stark_ctx: device tables for traces of 2^log_n rows (blow-up 2)."""
+    """zkir_stark_ctx: device tables for traces of 2^log_n rows, extended to 2^(log_n + log_blowup) (log_blowup 1, 2, 3: blow-up 2, 4, 8; log_n + log_blowup <= 27).
+    Contexts of log_blowup 2 / 3 serve the commitment (lde, merkle_commit, commit_trace); proofs are blow-up 2: prove() raises on them."""
 
     def __init__(self, log_n: int, log_blowup: int = 1):
         pl._require_gpu()
@@ -76,6 +77,8 @@ class StarkContext:
         if rc != rt.ZKIR_OK:
             rt._raise(rc)
         self._h = h
+        if hasattr(rt.lib(), "zkir_stark_ctx_log_blowup"):
+            self.log_blowup = int(rt.lib().zkir_stark_ctx_log_blowup(h))     # what the library holds
 
     @property
     def handle(self):
@@ -132,11 +135,11 @@ def main_trace(trace: pl.DeviceTrace, stream=None, deferred: bool = False) -> to
 
 
 def lde(ctx: StarkContext, mat: torch.Tensor, stream=None, clobber: bool = False) -> torch.Tensor:
-    """Per-column LDE of a B8 matrix int32[nb][N][8] to int32[nb][2N][8] on the coset 31*<w_2N> (natural order)."""
+    """Per-column LDE of a B8 matrix int32[nb][N][8] to int32[nb][M][8], M = N << ctx.log_blowup, on the coset 31*<w_M> (natural order)."""
     nb, n, eight = mat.shape
     assert eight == 8 and n == 1 << ctx.log_n and mat.dtype == torch.int32 and mat.is_contiguous()
     src = mat if clobber else mat.clone()
-    out = torch.empty((nb, 2 * n, 8), dtype=torch.int32, device=mat.device)
+    out = torch.empty((nb, n << ctx.log_blowup, 8), dtype=torch.int32, device=mat.device)
     pl._check(rt.lib().zkir_lde_launch(ctx.handle, src.data_ptr(), nb * 8, out.data_ptr(), _sp(stream)))
     return out
 
@@ -162,7 +165,7 @@ def merkle_cap(ctx: StarkContext, digests: torch.Tensor, stream=None) -> torch.T
 
 
 def commit_trace(ctx: StarkContext, trace: pl.DeviceTrace, stream=None, deferred: bool = False):
-    """main trace -> LDE -> Merkle.  Returns (root np.uint32[4], lde matrix tensor (B8), tree tensor)."""
+    """main trace -> LDE (at the context's blow-up) -> Merkle.  Returns (root np.uint32[4], lde matrix tensor (B8), tree tensor)."""
     m = main_trace(trace, stream, deferred)
     L = lde(ctx, m, stream, clobber=True)
     tree = merkle_commit(ctx, L, main_width(deferred), stream)
@@ -172,7 +175,8 @@ def commit_trace(ctx: StarkContext, trace: pl.DeviceTrace, stream=None, deferred
 
 def prove(ctx: StarkContext, trace, pub: rt.PublicInputsC, stream=None, want_stage_ms: bool = False):
     """zkir_prove: full ZKIR-STARK v1 proof of a device trace (`trace`: pl.DeviceTrace or zkir_trace_columns) bound to the public
-    inputs `pub` (rt.public_inputs / ExecutionResult.public_inputs).  Returns np.uint32 proof words (and stage ms)."""
+    inputs `pub` (rt.public_inputs / ExecutionResult.public_inputs).  Returns np.uint32 proof words (and stage ms).  Proofs are blow-up 2: a context of
+    log_blowup != 1 is refused by the library (rt.RuntimeError, ERR_ARGUMENT)."""
     cols = trace.c if hasattr(trace, "c") else trace
     out = C.POINTER(C.c_uint32)()
     n_words = C.c_uint64()
