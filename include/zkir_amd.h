@@ -355,6 +355,34 @@ int zkir_merkle_leaves_launch(const zkir_stark_ctx* ctx, const uint32_t* mat, ui
  * shards, in rank order — and the call appends the log2(n) upper levels; root = last 4 words of the 4*(2n-1)-word buffer. */
 int zkir_merkle_cap_launch(const zkir_stark_ctx* ctx, uint32_t* tree, uint64_t n_digests, void* hip_stream);
 
+/* ---- openings of a commitment: "row j of what I committed is these words" ----
+ * An opening RECORD of a tree with n_leaves = 2^d leaves over a matrix of `width` columns is width + 4 d words: the row's `width` canonical words in column order (the zero
+ * padding of a ragged last block dropped), then the sibling digest of every level, leaf level first, four words each — the per-position record a proof's query section carries.
+ * With ZKIR_OPEN_LEAF_DIGEST the tree's leaves are digests with no matrix behind them (the cap tree over shard roots): the record is the leaf digest itself, then the path,
+ * 4 + 4 d words; `width` is 0 there.  Sharded commitments compose: a shard's record followed by the cap tree's digest-form PATH of that shard's root (its record without the
+ * leading digest) is an opening of the capped root at index g n_local + j with n_leaves = G n_local.
+ * zkir_merkle_opening_words: the record length, 0 for an n_leaves that is zero or not a power of two. */
+#define ZKIR_OPEN_LEAF_DIGEST 1u
+#define ZKIR_VERIFY_FORM_LANE 2u      /* zkir_merkle_verify_launch: run the one-lane-per-record kernel whatever the batch size (tests, measurements) */
+#define ZKIR_VERIFY_FORM_ROW16 4u     /* .. the 16-lanes-per-record kernel.  Neither: the library's rule (by n_idx) */
+uint64_t zkir_merkle_opening_words(uint32_t width, uint64_t n_leaves, uint32_t flags);
+/* out[i] = the record of row indices[i], i < n_idx.  mat: B8, canonical words, as zkir_lde_launch writes it; tree: as zkir_merkle_commit_launch / _cap_launch wrote it;
+ * indices, out: DEVICE pointers (out: n_idx records back to back).  mat == NULL selects the digest form (width must be 0).  Asynchronous on the stream, no synchronisation;
+ * uses nothing of the context that depends on its rate: any context serves any n_leaves up to 2^27.  An index >= n_leaves reads nothing: its record is filled with
+ * 0xFFFFFFFF.  n_idx == 0 is ZKIR_OK without a launch.  A null context, tree, indices or out, an n_leaves that is zero or not a power of two, or mat == NULL with width != 0:
+ * ZKIR_ERR_ARGUMENT before any launch. */
+int zkir_merkle_open_launch(const zkir_stark_ctx* ctx, const uint32_t* mat, uint32_t width, uint64_t n_leaves, const uint32_t* tree, const uint64_t* indices, uint64_t n_idx,
+                            uint32_t* out, void* hip_stream);
+/* verdicts[i] of record i (of `openings`, n_idx records back to back) for index indices[i] against `root` (all DEVICE pointers; root may be tree + 4 (2 n_leaves - 2)):
+ * 0 the record hashes to root, 1 it does not, 2 a word of the record is >= p (the record is not hashed), 3 the index is >= n_leaves; 3 wins over 2 over 1.
+ * summary (may be NULL): summary[0] = the number of non-zero verdicts, summary[1] = the smallest failing position i, 0xFFFFFFFF when there is none; the launch initialises both.
+ * flags: ZKIR_OPEN_LEAF_DIGEST (width 0), ZKIR_VERIFY_FORM_*. */
+int zkir_merkle_verify_launch(const zkir_stark_ctx* ctx, const uint32_t* root, uint32_t width, uint64_t n_leaves, const uint64_t* indices, uint64_t n_idx, const uint32_t* openings,
+                              uint32_t flags, uint32_t* verdicts, uint32_t* summary, void* hip_stream);
+/* The same verdicts on the HOST (host pointers everywhere, no device): part of the product, like zkir_verify. */
+int zkir_merkle_verify_host(const uint32_t root[4], uint32_t width, uint64_t n_leaves, const uint64_t* indices, uint64_t n_idx, const uint32_t* openings, uint32_t flags,
+                            uint32_t* verdicts, uint32_t summary[2]);
+
 /* Public inputs of a proof: absorbed by the Fiat-Shamir transcript before the first commitment and carried in the proof header. */
 typedef struct zkir_public_inputs {
   uint64_t n_real;             /* executed rows = ExecutionResult.cycles */

@@ -105,6 +105,14 @@ extern "C" {
     fn zkir_prove_result(result: *const ZkirResult, params: *const ZkirProverParams, proof: *mut *mut u8, len: *mut usize) -> c_int;
     fn zkir_proof_bytes_free(proof: *mut u8);
     fn zkir_abi_version() -> u32;
+    // openings of a commitment (rows of a committed B8 matrix + their Merkle paths) and their check: device pointers throughout, _host takes host pointers and needs no device
+    pub fn zkir_merkle_opening_words(width: u32, n_leaves: u64, flags: u32) -> u64;
+    pub fn zkir_merkle_open_launch(ctx: *const ZkirStarkCtx, mat: *const u32, width: u32, n_leaves: u64, tree: *const u32, indices: *const u64, n_idx: u64, out: *mut u32,
+                                   stream: *mut c_void) -> c_int;
+    pub fn zkir_merkle_verify_launch(ctx: *const ZkirStarkCtx, root: *const u32, width: u32, n_leaves: u64, indices: *const u64, n_idx: u64, openings: *const u32, flags: u32,
+                                     verdicts: *mut u32, summary: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn zkir_merkle_verify_host(root: *const u32, width: u32, n_leaves: u64, indices: *const u64, n_idx: u64, openings: *const u32, flags: u32, verdicts: *mut u32,
+                                   summary: *mut u32) -> c_int;
     // (mode 4) the tapes' share of the lookup table side and the hash tape's record checks as calls of their own (host arrays in, host arrays out)
     pub fn zkir_tape_table_side_launch(hash_words: *const u32, n_hash_words: u64, new_bytes: *const u64, wide_words: *const u32, n_wide_words: u64, alpha: *const u32, lambda: *const u32,
                                        sum: *mut u32, hh: *mut u32, ww: *mut u32, stream: *mut c_void) -> c_int;

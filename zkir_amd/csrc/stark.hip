@@ -1104,3 +1104,4 @@ int zkir_merkle_cap_launch(const zkir_stark_ctx* c, uint32_t* tree, uint64_t n_d
 }  // extern "C"
 
 #include "stark_prove.inl"
+#include "merkle_open.inl"

@@ -369,6 +369,35 @@ uint64_t zkir_hash_call_cells_host(uint64_t in_ptr, uint64_t len, uint64_t out_p
 }
 
 int zkir_verify(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect) { return verify_impl(w, len, expect, true, nullptr); }
+// zkir_merkle_verify_launch's verdicts on the host: hash_elems over the record's row (or its leaf digest as it stands), check_path over its siblings
+int zkir_merkle_verify_host(const uint32_t root[4], uint32_t width, uint64_t n_leaves, const uint64_t* indices, uint64_t n_idx, const uint32_t* openings, uint32_t flags, uint32_t* verdicts,
+                            uint32_t summary[2]) {
+  if (!root || !verdicts || (n_idx && (!indices || !openings))) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_merkle_verify_host: null root, indices, openings or verdicts"}); return ZKIR_ERR_ARGUMENT; }
+  if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_merkle_verify_host: n_leaves must be a power of two"}); return ZKIR_ERR_ARGUMENT; }
+  const bool digest_form = flags & ZKIR_OPEN_LEAF_DIGEST;
+  if (digest_form && width != 0) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_merkle_verify_host: the digest form has width 0"}); return ZKIR_ERR_ARGUMENT; }
+  int depth = 0;
+  while (((uint64_t)1 << depth) < n_leaves) depth++;
+  const size_t lead = digest_form ? 4 : width, rec = lead + 4 * (size_t)depth;
+  uint32_t failed = 0, first = 0xFFFFFFFFu;
+  for (uint64_t i = 0; i < n_idx; i++) {
+    const uint32_t* r = openings + i * rec;
+    uint32_t v = 0;
+    if (indices[i] >= n_leaves) v = 3;
+    else {
+      for (size_t k = 0; k < rec && !v; k++) if (r[k] >= bb::P) v = 2;
+      if (!v) {
+        uint32_t dg[4];
+        if (digest_form) memcpy(dg, r, 16); else hash_elems(r, width, dg);
+        if (!check_path(dg, (size_t)indices[i], r + lead, depth, root)) v = 1;
+      }
+    }
+    verdicts[i] = v;
+    if (v) { failed++; if (first == 0xFFFFFFFFu) first = (uint32_t)i; }
+  }
+  if (summary) { summary[0] = failed; summary[1] = first; }
+  return ZKIR_OK;
+}
 int zkir_verify_last_stages(double ms[5], uint32_t* device_stages) {
   if (!last_stages.valid) return ZKIR_ERR_ARGUMENT;
   if (ms) for (int k = 0; k < 5; k++) ms[k] = last_stages.ms[k];

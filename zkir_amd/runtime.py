@@ -406,6 +406,11 @@ def lib() -> C.CDLL:
         L.zkir_hash_tape_new_bytes_host.restype = C.c_int; L.zkir_hash_tape_new_bytes_host.argtypes = [V, U64, V]
         L.zkir_verify_device.restype = C.c_int; L.zkir_verify_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
         L.zkir_verify_last_stages.restype = C.c_int; L.zkir_verify_last_stages.argtypes = [V, C.POINTER(C.c_uint32)]
+    if hasattr(L, "zkir_merkle_open_launch"):                 # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_merkle_opening_words.restype = U64; L.zkir_merkle_opening_words.argtypes = [U32, U64, U32]
+        L.zkir_merkle_open_launch.restype = C.c_int; L.zkir_merkle_open_launch.argtypes = [V, V, U32, U64, V, V, U64, V, V]
+        L.zkir_merkle_verify_launch.restype = C.c_int; L.zkir_merkle_verify_launch.argtypes = [V, V, U32, U64, V, U64, V, U32, V, V, V]
+        L.zkir_merkle_verify_host.restype = C.c_int; L.zkir_merkle_verify_host.argtypes = [V, U32, U64, V, U64, V, U32, V, V]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -618,6 +623,33 @@ def verify(proof: np.ndarray, expect: Optional[PublicInputsC] = None, device: bo
     if rc < 0:
         _raise(-rc)
     return rc
+
+
+OPEN_LEAF_DIGEST, VERIFY_FORM_LANE, VERIFY_FORM_ROW16 = 1, 2, 4      # zkir_amd.h: ZKIR_OPEN_LEAF_DIGEST, ZKIR_VERIFY_FORM_*
+
+
+def opening_words(width: int, n_leaves: int, flags: int = 0) -> int:
+    """Words of one opening record (zkir_merkle_opening_words): width + 4 log2(n_leaves), 4 + 4 log2(n_leaves) in the digest form; 0 for a bad n_leaves."""
+    return int(lib().zkir_merkle_opening_words(int(width), int(n_leaves) & (2**64 - 1), int(flags)))
+
+
+def merkle_verify_host(root, width: int, n_leaves: int, indices, openings, flags: int = 0):
+    """zkir_merkle_verify_host: the verdicts (0 ok, 1 wrong, 2 non-canonical word, 3 index out of range) of opening records against a root, on the host — no GPU.
+    Returns (verdicts np.uint32[n_idx], summary np.uint32[2] = failures, smallest failing position or 0xFFFFFFFF)."""
+    root = np.ascontiguousarray(root, dtype=np.uint32)
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+    rec = np.ascontiguousarray(openings, dtype=np.uint32).reshape(-1)
+    words = opening_words(width, n_leaves, flags)
+    if words == 0 and len(idx) and n_leaves and not (n_leaves & (n_leaves - 1)):
+        rec = np.zeros(1, np.uint32)                            # (a record of no words: one leaf, no columns)
+    elif words:
+        assert len(rec) == len(idx) * words, f"{len(idx)} records of {words} words expected, got {len(rec)} words"
+    verdicts, summary = np.zeros(max(len(idx), 1), np.uint32), np.zeros(2, np.uint32)
+    rc = lib().zkir_merkle_verify_host(root.ctypes.data, int(width), int(n_leaves), idx.ctypes.data if len(idx) else None, len(idx), rec.ctypes.data if len(idx) else None, int(flags),
+                                       verdicts.ctypes.data, summary.ctypes.data)
+    if rc != ZKIR_OK:
+        _raise(rc)
+    return verdicts[:len(idx)], summary
 
 
 def verify_last_stages() -> dict:

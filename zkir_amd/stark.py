@@ -164,6 +164,51 @@ def merkle_cap(ctx: StarkContext, digests: torch.Tensor, stream=None) -> torch.T
     return tree[-4:]
 
 
+opening_words = rt.opening_words
+OPEN_LEAF_DIGEST, VERIFY_FORM_LANE, VERIFY_FORM_ROW16 = rt.OPEN_LEAF_DIGEST, rt.VERIFY_FORM_LANE, rt.VERIFY_FORM_ROW16
+
+
+def _indices(indices, device) -> torch.Tensor:
+    """Row indices as the C ABI takes them: uint64 words on the device (torch has no arithmetic on uint64: they travel as int64 bit patterns)."""
+    if isinstance(indices, torch.Tensor):
+        assert indices.dtype == torch.int64
+        return indices.to(device).contiguous().reshape(-1)
+    return torch.from_numpy(np.asarray(indices, dtype=np.uint64).reshape(-1).view(np.int64).copy()).to(device)
+
+
+def merkle_open(ctx: StarkContext, mat: Optional[torch.Tensor], tree: torch.Tensor, indices, width: Optional[int] = None, stream=None) -> torch.Tensor:
+    """zkir_merkle_open_launch: the opening records int32[n_idx][width + 4 d] of the rows `indices` of the committed B8 matrix `mat` (`width` real columns, default all)
+    under `tree` (merkle_commit's); mat=None: the digest form int32[n_idx][4 + 4 d] of a tree over digests (merkle_cap's full buffer).  An index >= n_leaves gives a record
+    of 0xFFFFFFFF words."""
+    assert tree.dtype == torch.int32 and tree.is_contiguous() and tree.numel() % 4 == 0
+    n = (tree.numel() // 4 + 1) // 2
+    if mat is None:
+        assert width in (None, 0)
+        width, flags = 0, OPEN_LEAF_DIGEST
+    else:
+        nb, rows, eight = mat.shape
+        assert eight == 8 and rows == n and mat.dtype == torch.int32 and mat.is_contiguous()
+        width, flags = (nb * 8 if width is None else width), 0
+    idx = _indices(indices, tree.device)
+    words = opening_words(width, n, flags)
+    out = torch.empty((idx.numel(), words), dtype=torch.int32, device=tree.device)
+    pl._check(rt.lib().zkir_merkle_open_launch(ctx.handle, mat.data_ptr() if mat is not None else None, width, n, tree.data_ptr(), idx.data_ptr(), idx.numel(), out.data_ptr(), _sp(stream)))
+    return out
+
+
+def merkle_verify(ctx: StarkContext, root: torch.Tensor, width: int, n_leaves: int, indices, openings: torch.Tensor, flags: int = 0, stream=None):
+    """zkir_merkle_verify_launch: (verdicts int32[n_idx], summary int32[2]) of the opening records against `root` (a device tensor of four words, e.g. tree[-4:]):
+    0 ok, 1 wrong, 2 a word >= p, 3 index >= n_leaves; summary = (failures, smallest failing position or -1 = 0xFFFFFFFF)."""
+    assert root.dtype == torch.int32 and root.numel() == 4 and openings.dtype == torch.int32 and openings.is_contiguous()
+    root = root.contiguous()
+    idx = _indices(indices, openings.device)
+    assert openings.numel() == idx.numel() * opening_words(width, n_leaves, flags)
+    verdicts = torch.empty(idx.numel(), dtype=torch.int32, device=openings.device)
+    summary = torch.empty(2, dtype=torch.int32, device=openings.device)
+    pl._check(rt.lib().zkir_merkle_verify_launch(ctx.handle, root.data_ptr(), width, n_leaves, idx.data_ptr(), idx.numel(), openings.data_ptr(), flags, verdicts.data_ptr(), summary.data_ptr(), _sp(stream)))
+    return verdicts, summary
+
+
 def commit_trace(ctx: StarkContext, trace: pl.DeviceTrace, stream=None, deferred: bool = False):
     """main trace -> LDE (at the context's blow-up) -> Merkle.  Returns (root np.uint32[4], lde matrix tensor (B8), tree tensor)."""
     m = main_trace(trace, stream, deferred)
