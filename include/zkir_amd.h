@@ -383,6 +383,26 @@ int zkir_merkle_verify_launch(const zkir_stark_ctx* ctx, const uint32_t* root, u
 int zkir_merkle_verify_host(const uint32_t root[4], uint32_t width, uint64_t n_leaves, const uint64_t* indices, uint64_t n_idx, const uint32_t* openings, uint32_t flags,
                             uint32_t* verdicts, uint32_t summary[2]);
 
+/* ---- a low-degree proof of a commitment, at any rate a context serves (log_blowup 1, 2, 3) ----
+ * Statement: every column of the B8 matrix committed under `tree` (lde_mat = zkir_lde_launch's output on this context, M = N << log_blowup rows; tree =
+ * zkir_merkle_commit_launch's over its `width` columns) is close to a polynomial of degree < N = 2^log_n.  Batched FRI over C(x) = sum_k gamma^k col_k(x), gamma drawn after
+ * the root.  It states NO constraint and NO opening at a point: it is what lets a holder of the root alone trust that the rows opened under it (zkir_merkle_open_launch) are
+ * rows of a low-degree extension.  Conjectured soundness: about log_blowup bits per query plus pow_bits, under the sponge's ~62-bit cap.
+ * Proof words (all canonical): [0..8) 'ZKLD' = 0x444C4B5A, version 1, log_n, log_blowup, width, num_queries, pow_bits, n_layers | [8..12) the root | n_layers x 4 layer roots |
+ * (4 << log_blowup) x 4 final layer | the grinding nonce (the smallest that passes) | per query: q < M/2, record(q), record(q + M/2) (zkir_merkle_open_launch's records:
+ * width + 4 (log_n + log_blowup) words each), then per layer 4 * 2^k values and 4 * depth sibling words.  A proof is a function of its inputs.
+ * zkir_lowdeg_proof_words: the proof's length; 0 unless 3 <= log_n <= 26, log_blowup in {1, 2, 3}, log_n + log_blowup <= 27, 1 <= width <= 512, 1 <= num_queries <= 128.
+ * zkir_lowdeg_prove: lde_mat, tree DEVICE pointers, proof_host a HOST buffer of cap_words words (nothing past *n_words is written); 0 <= pow_bits <= 24.  One proof at a time
+ * per context (its workspace arena, at most ~48 M bytes, shared with zkir_prove); synchronises the stream.  A null pointer, a context of log_n < 3, a width, num_queries or
+ * pow_bits outside its range, or cap_words below zkir_lowdeg_proof_words: ZKIR_ERR_ARGUMENT with a message, before anything is launched.
+ * zkir_lowdeg_verify: host only.  0 accepted; else the first failing check: 1 malformed (length not exactly the header's, magic, version, a range, n_layers), 2 not expect_root
+ * (NULL: any root), 3 a word >= p, 4 final layer not of degree < 4, 5 grinding, 6 a query's index word, 7 a matrix record does not hash to the root, 8 layer-0 values are not
+ * the combination of the rows, 9 a FRI leaf's path, 10 a carried value, 11 the final value; lowest query first. */
+uint64_t zkir_lowdeg_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t num_queries);
+int zkir_lowdeg_prove(zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host,
+                      uint64_t cap_words, uint64_t* n_words, void* hip_stream);
+int zkir_lowdeg_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root);
+
 /* Public inputs of a proof: absorbed by the Fiat-Shamir transcript before the first commitment and carried in the proof header. */
 typedef struct zkir_public_inputs {
   uint64_t n_real;             /* executed rows = ExecutionResult.cycles */

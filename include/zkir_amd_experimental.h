@@ -26,6 +26,13 @@ int zkir_ntt_strided_variant_launch(const zkir_stark_ctx* ctx, uint32_t* data, u
  * in / out as zkir_lde_launch, tree as zkir_merkle_commit_launch; same output as the two calls. */
 int zkir_commit_overlapped_launch(const zkir_stark_ctx* ctx, uint32_t* in, uint32_t width, uint32_t* out, uint32_t* tree, uint32_t group, void* hip_stream);
 
+/* MEASUREMENT: zkir_lowdeg_prove with the device time (ms, HIP events) of its four stages: combine | FRI commit phase | grinding | query section. */
+int zkir_lowdeg_prove_stages(zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host,
+                             uint64_t cap_words, uint64_t* n_words, float stage_ms[4], void* hip_stream);
+/* TEST / MEASUREMENT: the combine kernel of zkir_lowdeg_prove alone for a GIVEN canonical gamma: cw[t M + j] = coordinate t of sum_k gamma^k col_k(row j), M = N << log_blowup
+ * rows of the context.  gpow_scratch: DEVICE buffer of 32 ceil(width / 8) words for the gamma powers, uploaded with a synchronous copy. */
+int zkir_lowdeg_combine_launch(const zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t gamma[4], uint32_t* gpow_scratch, uint32_t* cw, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,11 @@ extern "C" {
                                      verdicts: *mut u32, summary: *mut u32, stream: *mut c_void) -> c_int;
     pub fn zkir_merkle_verify_host(root: *const u32, width: u32, n_leaves: u64, indices: *const u64, n_idx: u64, openings: *const u32, flags: u32, verdicts: *mut u32,
                                    summary: *mut u32) -> c_int;
+    // a low-degree proof of a commitment at the context's rate (log_blowup 1, 2, 3), and its host verifier
+    pub fn zkir_lowdeg_proof_words(log_n: u32, log_blowup: u32, width: u32, num_queries: u32) -> u64;
+    pub fn zkir_lowdeg_prove(ctx: *mut ZkirStarkCtx, lde_mat: *const u32, width: u32, tree: *const u32, num_queries: u32, pow_bits: u32, proof_host: *mut u32, cap_words: u64,
+                             n_words: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn zkir_lowdeg_verify(proof: *const u32, n_words: u64, expect_root: *const u32) -> c_int;
     // (mode 4) the tapes' share of the lookup table side and the hash tape's record checks as calls of their own (host arrays in, host arrays out)
     pub fn zkir_tape_table_side_launch(hash_words: *const u32, n_hash_words: u64, new_bytes: *const u64, wide_words: *const u32, n_wide_words: u64, alpha: *const u32, lambda: *const u32,
                                        sum: *mut u32, hh: *mut u32, ww: *mut u32, stream: *mut c_void) -> c_int;

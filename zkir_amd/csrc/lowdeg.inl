@@ -1,0 +1,292 @@
+// lowdeg.inl — zkir_lowdeg_prove (include/zkir_amd.h): a LOW-DEGREE PROOF OF A COMMITMENT at any rate the context serves (log_blowup 1, 2, 3).  Included by stark.hip at file
+// scope after stark_prove.inl and merkle_open.inl, whose FRI, gather and opening kernels it launches unchanged.
+//
+// Statement: the B8 matrix under `tree` (zkir_lde_launch's output: canonical words over 31 <w_M>, M = N << b; zkir_merkle_commit_launch's tree) has every column close to a
+// polynomial of degree < N.  Proof: batched FRI over C(x) = sum_k gamma^k col_k(x), gamma in E4 drawn after the root — no DEEP point, no quotient, no constraint.  Format,
+// transcript and verifier: verify.cpp (zkir_lowdeg_verify) and DESIGN.md; spec of every word: tests/lowdeg_ref.py.
+//
+// The one HBM-bound pass is lowdeg_combine_kernel (4 * 8 * ceil(width / 8) B read and 16 B written per row); everything after it is zkir_prove's FRI with log_2n = log_n + b.
+namespace {
+
+constexpr uint32_t LOWDEG_MAGIC = 0x444C4B5Au, LOWDEG_VERSION = 1;   // 'ZKLD'
+// Each of the four 96-bit sums of a row takes one product gamma^k[t] * v per column, both below p < 2^31: `width` terms stay below width * 2^62, so the sum's top word
+// stays below width / 4.  bb::acc96_div_R asks for a top word below 2^9: 2^9 terms (deep_kernel's static_assert) are a quarter of what the bound admits.
+constexpr uint32_t LOWDEG_MAX_WIDTH = 512;
+static_assert(bb::P < (1u << 31) && LOWDEG_MAX_WIDTH / 4 <= (1u << 9), "lowdeg_combine_kernel: a 96-bit sum's top word stays below 2^9");
+
+// Folds per committed layer: zkir_prove's fri_schedule with the rate as a parameter — the codeword of 2^(log_n + b) values is folded once (its leaves are the pairs
+// (q, q + M/2) the matrix openings determine), later layers LOG_ARITY times, the last one as needed; the final layer has 4 << b values of a word of degree < 4.
+std::vector<int> lowdeg_schedule(int log_n, int b) {
+  std::vector<int> ks;
+  const int log_fin = 2 + b;
+  for (int log_m = log_n + b; log_m > log_fin;) {
+    const int k = ks.empty() ? 1 : (LOG_ARITY < log_m - log_fin ? LOG_ARITY : log_m - log_fin);
+    ks.push_back(k); log_m -= k;
+  }
+  return ks;
+}
+
+// ---- C(x_j) = sum_k gamma^k col_k(x_j), one lane per row ------------------------------------------------------------------------------------------------------------------
+// The loads are deep_kernel's: the two 16-byte halves of (block, row), M4[(blk M + j) 2 + {0, 1}] — 64-bit offsets throughout (block 18 of 2^27 rows starts past 2^32 words);
+// the next block's pair is requested before the current one is multiplied in.  The words are CANONICAL (zkir_lde_launch), the gamma powers Montgomery (gpow: R gamma^k,
+// 8 * n_blocks entries, the columns a ragged last block does not have carry coefficient zero; uniform reads, scalar registers): each coordinate is an exact 96-bit sum
+// (bb::mad96_s) reduced once, and the reduction's division by R leaves the canonical coordinate.  Written column-wise, cw[t M + j]: what the fold and leaf-hash kernels read.
+__global__ __launch_bounds__(NT, DEEP_WAVES) void lowdeg_combine_kernel(const uint32_t* __restrict__ mat, uint32_t n_blocks, uint64_t M, const E4* __restrict__ gpow, uint32_t* __restrict__ cw) {
+  const uint64_t j = (uint64_t)blockIdx.x * NT + threadIdx.x;
+  if (j >= M) return;
+  const uint4* __restrict__ M4 = reinterpret_cast<const uint4*>(mat);
+  bb::Acc96 A[4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) A[t] = bb::acc96_zero();
+  uint4 nlo = M4[j * 2], nhi = M4[j * 2 + 1];
+#pragma unroll 1
+  for (uint32_t blk = 0; blk < n_blocks; blk++) {
+    const uint4 vlo = nlo, vhi = nhi;
+    if (blk + 1 < n_blocks) { nlo = M4[((uint64_t)(blk + 1) * M + j) * 2]; nhi = M4[((uint64_t)(blk + 1) * M + j) * 2 + 1]; }
+    const uint32_t v[8] = {vlo.x, vlo.y, vlo.z, vlo.w, vhi.x, vhi.y, vhi.z, vhi.w};
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      const E4 g = gpow[8 * blk + u];
+#pragma unroll
+      for (int t = 0; t < 4; t++) bb::mad96_s(A[t], g.c[t], v[u]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; t++) cw[(uint64_t)t * M + j] = bb::acc96_div_R(A[t]);
+}
+
+// R gamma^k for k < width, zero up to the next multiple of eight
+std::vector<E4> lowdeg_gamma_table(const E4& gamma, uint32_t width) {
+  std::vector<E4> t(8 * (size_t)((width + 7) / 8), bb::e_zero());
+  const E4 gamma_m = bb::e_to_mont(gamma);
+  E4 g = bb::e_one_m();
+  for (uint32_t k = 0; k < width; k++) { t[k] = g; g = bb::e_mul_m(g, gamma_m); }
+  return t;
+}
+
+int lowdeg_bad(const std::string& why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_lowdeg_prove: " + why}); return ZKIR_ERR_ARGUMENT; }
+
+// stage_ms (measurements; may be null): combine | FRI commit phase | grinding | query section
+int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words,
+                      uint64_t* n_words, float* stage_ms, hipStream_t s) {
+  // every argument is checked before anything is launched
+  if (n_words) *n_words = 0;
+  if (!c || !mat || !tree || !proof_host || !n_words) return lowdeg_bad("null context, matrix, tree, proof buffer or n_words");
+  const uint32_t log_n = c->log_n, b = c->log_blowup, log_M = log_n + b;
+  if (log_n < 3) return lowdeg_bad("the context's log_n must be at least 3: below that there is no layer to commit");
+  if (width < 1 || width > LOWDEG_MAX_WIDTH) return lowdeg_bad("width must be 1 .. 512 (terms per 96-bit sum of the combination)");
+  if (num_queries < 1 || num_queries > 128) return lowdeg_bad("num_queries must be 1 .. 128");
+  if (pow_bits > 24) return lowdeg_bad("pow_bits must be 0 .. 24");
+  const uint64_t total = zkir_lowdeg_proof_words(log_n, b, width, num_queries);
+  if (total == 0) return lowdeg_bad("the context's log_n / log_blowup are outside what a proof can state (log_n 3 .. 26, log_blowup 1 .. 3, their sum at most 27)");
+  if (cap_words < total) return lowdeg_bad("cap_words is below zkir_lowdeg_proof_words(log_n, log_blowup, width, num_queries)");
+
+  std::lock_guard<std::mutex> ctx_lock(c->mu);                   // one proof at a time per context: the workspace is its arena, as in zkir_prove
+  const uint64_t M = 1ull << log_M;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const int n_layers = (int)ks.size();
+  const uint32_t n_fin = 4u << b, rec = width + 4 * log_M, n_blocks = (width + 7) / 8;
+  const uint64_t head_words = 12 + 4 * (uint64_t)n_layers + 4 * (uint64_t)n_fin + 1, qsize = (total - head_words) / num_queries;
+
+  // workspace: the codeword (16 M bytes), the layers and their trees (at most 48 M bytes together at the schedules of log_n >= 5), the query section and its inputs
+  {
+    auto al = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    size_t want = al(16 * M) + al(n_blocks * 8 * sizeof(E4)) + 8 * 256 + al(16 * (size_t)(n_layers + 1) * 4);
+    { int lm = (int)log_M; for (int k : ks) { const uint64_t g = (1ull << lm) >> k; want += al(16 * (2 * g - 1)) + al(16 * g); lm -= k; } }
+    size_t n_jobs = 0;
+    for (int k : ks) n_jobs += ((size_t)1 << k) + 1;
+    n_jobs = (n_jobs + 1) * num_queries;
+    want += al(2 * (size_t)num_queries * 8) + al(2 * (size_t)num_queries * rec * 4) + al(n_jobs * sizeof(GatherJob)) + al((size_t)num_queries * qsize * 4);
+    if (c->arena_size < want) {
+      if (c->arena) (void)hipFree(c->arena);
+      c->arena = nullptr; c->arena_size = 0;
+      HIP_OK(hipMalloc((void**)&c->arena, want));
+      c->arena_size = want;
+    }
+    c->arena_off = 0;
+  }
+  Arena ar{c};
+  zkir::HostPin& pin = c->pin;
+  pin.reset();
+  auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    void* p = pin.take(bytes);
+    if (!p) return hipErrorOutOfMemory;
+    memcpy(p, src, bytes);
+    return hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
+  };
+  struct Staged { void* dst; const void* src; size_t n; };
+  std::vector<Staged> staged;
+  auto d2h = [&](void* dst, const void* dsrc, size_t bytes) -> hipError_t {
+    void* h = pin.take(bytes);
+    if (!h) return hipErrorOutOfMemory;
+    staged.push_back({dst, h, bytes});
+    return hipMemcpyAsync(h, dsrc, bytes, hipMemcpyDeviceToHost, s);
+  };
+  auto sync_d2h = [&]() -> hipError_t {
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) for (const Staged& x : staged) memcpy(x.dst, x.src, x.n);
+    staged.clear();
+    return e;
+  };
+  StageEvents se;
+  if (stage_ms) HIP_OK(se.create());
+  auto mark = [&](int i) { if (stage_ms) (void)hipEventRecord(se.ev[i], s); };
+
+  // ---- transcript up to gamma: header, root ------------------------------------------------------------------------------------------------------------------------------
+  std::vector<uint32_t> head = {LOWDEG_MAGIC, LOWDEG_VERSION, log_n, b, width, num_queries, pow_bits, (uint32_t)n_layers};
+  uint32_t root[4];
+  HIP_OK(d2h(root, tree + 4 * (2 * M - 2), 16));
+  HIP_OK(sync_d2h());
+  Challenger ch(c->consts);
+  ch.observe_n(head.data(), 8);
+  ch.observe_n(root, 4);
+  const E4 gamma = ch.sample_ext();
+  head.insert(head.end(), root, root + 4);
+
+  // ---- 1. the codeword --------------------------------------------------------------------------------------------------------------------------------------------------------
+  E4* dGpow; uint32_t *dState, *dBest, *dChSt, *dFri;
+  std::vector<uint32_t*> fri_trees(n_layers), fri_layers(n_layers + 1);
+  HIP_OK(ar.take(&dGpow, (size_t)n_blocks * 8)); HIP_OK(ar.take(&dState, 16)); HIP_OK(ar.take(&dBest, 4)); HIP_OK(ar.take(&dChSt, 16)); HIP_OK(ar.take(&dFri, 16 * (size_t)(n_layers + 1)));
+  HIP_OK(ar.take(&fri_layers[0], 4 * M));
+  {
+    const std::vector<E4> gp = lowdeg_gamma_table(gamma, width);
+    HIP_OK(h2d(dGpow, gp.data(), gp.size() * sizeof(E4)));
+  }
+  mark(0);
+  hipLaunchKernelGGL(lowdeg_combine_kernel, dim3(grid_for(M)), dim3(NT), 0, s, mat, n_blocks, M, dGpow, fri_layers[0]);
+  mark(1);
+
+  // ---- 2. FRI commit phase, enqueued as a whole (zkir_prove's, with log_2n = log_n + b): nothing is pending in the transcript once gamma is drawn ---------------------------
+  if (!ch.in.empty()) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: the transcript has pending input at the FRI commit phase"}); return ZKIR_ERR_OTHER; }
+  HIP_OK(h2d(dChSt, ch.st, sizeof(ch.st)));
+  {
+    uint32_t shift = bb::GEN;
+    int log_m = (int)log_M;
+    for (int j = 0; j < n_layers; j++) {
+      const int k = ks[j];
+      const uint64_t m = 1ull << log_m, g = m >> k;
+      HIP_OK(ar.take(&fri_trees[j], 4 * (2 * g - 1)));
+      uint32_t* ltree = fri_trees[j];
+      if (g <= (1u << 11)) hipLaunchKernelGGL(fri_leaf_hash_row16_kernel, dim3(grid_for(16 * g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, ltree);
+      else if (g <= (1u << 14)) hipLaunchKernelGGL(fri_leaf_hash_quad_kernel, dim3(grid_for(4 * g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, ltree);
+      else hipLaunchKernelGGL(fri_leaf_hash_kernel, dim3(grid_for(g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, ltree);
+      launch_tree_levels(c->d_p2, ltree, g, c->sync, s);
+      hipLaunchKernelGGL(fri_transcript_kernel, dim3(1), dim3(16), 0, s, c->d_p2, dChSt, ltree + 4 * (2 * g - 2), dFri + 16 * j);
+      FoldParams fp{};
+      for (int f = 0; f < k; f++) {
+        fp.half_shift_inv_m[f] = bb::to_mont(bb::inv(bb::mul(2, shift)));
+        shift = bb::mul(shift, shift);
+      }
+      uint32_t* dst;
+      HIP_OK(ar.take(&dst, 4 * g));
+      const E4* dBeta = reinterpret_cast<const E4*>(dFri + 16 * j + 4);
+      if (k == 1) hipLaunchKernelGGL(fri_fold_k_kernel<1>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, dst);
+      else if (k == 2) hipLaunchKernelGGL(fri_fold_k_kernel<2>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, dst);
+      else hipLaunchKernelGGL(fri_fold_k_kernel<3>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, dst);
+      fri_layers[j + 1] = dst;
+      log_m -= k;
+    }
+  }
+  uint32_t fin_cols[4 * 32];                                                   // n_fin <= 32
+  std::vector<uint32_t> fri_out(16 * (size_t)n_layers);
+  HIP_OK(d2h(fri_out.data(), dFri, fri_out.size() * 4));
+  HIP_OK(d2h(fin_cols, fri_layers[n_layers], 4 * (size_t)n_fin * 4));
+  HIP_OK(sync_d2h());
+  if (check_launch("zkir_lowdeg_prove") != ZKIR_OK) return ZKIR_ERR_DEVICE;
+  for (int j = 0; j < n_layers; j++) {                                         // the host's replay of the device's transcript steps
+    ch.observe_n(&fri_out[16 * (size_t)j], 4);
+    const E4 bm = bb::e_to_mont(ch.sample_ext());
+    if (memcmp(bm.c, &fri_out[16 * (size_t)j + 4], 16)) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: the device's FRI transcript diverged from the host's"}); return ZKIR_ERR_OTHER; }
+    head.insert(head.end(), &fri_out[16 * (size_t)j], &fri_out[16 * (size_t)j] + 4);
+  }
+  for (uint32_t i = 0; i < n_fin; i++) for (int t = 0; t < 4; t++) { ch.observe(fin_cols[t * n_fin + i]); head.push_back(fin_cols[t * n_fin + i]); }
+  mark(2);
+
+  // ---- 3. grinding: the SMALLEST nonce that passes (batches in rising order, the smallest hit of a batch) -------------------------------------------------------------------
+  uint32_t pow_nonce = 0xFFFFFFFFu;
+  {
+    ch.flush();
+    HIP_OK(h2d(dState, ch.st, sizeof(ch.st)));
+    const uint32_t batch = 1u << 18;
+    for (uint64_t base = 0; base < bb::P && pow_nonce == 0xFFFFFFFFu; base += batch) {
+      HIP_OK(hipMemsetAsync(dBest, 0xFF, 4, s));
+      hipLaunchKernelGGL(pow_grind_kernel, dim3(batch / NT), dim3(NT), 0, s, c->d_p2, dState, (uint32_t)base, pow_bits, dBest);
+      HIP_OK(d2h(&pow_nonce, dBest, 4));
+      HIP_OK(sync_d2h());
+    }
+    if (pow_nonce == 0xFFFFFFFFu || !ch.check_pow(pow_nonce, (int)pow_bits)) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: proof-of-work search failed"}); return ZKIR_ERR_OTHER; }
+  }
+  head.push_back(pow_nonce);
+  mark(3);
+  if (head.size() != head_words) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: header length"}); return ZKIR_ERR_OTHER; }
+
+  // ---- 4. queries: the matrix records by merkle_open_kernel from a device index array, copied next to the FRI leaves and paths by gather_kernel; one download --------------
+  std::vector<uint32_t> queries(num_queries);
+  std::vector<uint64_t> idx(2 * (size_t)num_queries);
+  for (uint32_t t = 0; t < num_queries; t++) { queries[t] = ch.sample_bits((int)log_M - 1); idx[2 * t] = queries[t]; idx[2 * t + 1] = (uint64_t)queries[t] + M / 2; }
+  uint64_t* dIdx; uint32_t *dRec, *dOut; GatherJob* dJobs;
+  HIP_OK(ar.take(&dIdx, idx.size())); HIP_OK(ar.take(&dRec, idx.size() * rec));
+  HIP_OK(h2d(dIdx, idx.data(), idx.size() * 8));
+  hipLaunchKernelGGL(merkle_open_kernel, dim3(grid_for(idx.size() * OPEN_LANES)), dim3(NT), 0, s, mat, width, M, log_M, tree, dIdx, (uint64_t)idx.size(), dRec);
+  std::vector<GatherJob> jobs;
+  uint32_t off = 0;
+  for (uint32_t t = 0; t < num_queries; t++) {
+    const uint32_t q = queries[t];
+    off += 1;                                                                // the index word: written by the host below
+    jobs.push_back({dRec + 2 * (size_t)t * rec, 1, 2 * rec, off, 0u, 0u}); off += 2 * rec;      // record(q), record(q + M/2)
+    int log_m = (int)log_M;
+    for (int j = 0; j < n_layers; log_m -= ks[j], j++) {
+      const uint64_t m = 1ull << log_m, g = m >> ks[j], li = q & (g - 1);
+      for (uint64_t u = 0; u < (1ull << ks[j]); u++) { jobs.push_back({fri_layers[j] + li + u * g, m, 4, off, 0u, 0u}); off += 4; }
+      jobs.push_back({fri_trees[j], g, (uint32_t)li, off, 0u, 2u}); off += 4 * (uint32_t)(log_m - ks[j]);
+    }
+  }
+  if ((uint64_t)off != qsize * num_queries) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: query section length"}); return ZKIR_ERR_OTHER; }
+  HIP_OK(ar.take(&dJobs, jobs.size())); HIP_OK(ar.take(&dOut, (size_t)off));
+  HIP_OK(h2d(dJobs, jobs.data(), jobs.size() * sizeof(GatherJob)));
+  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)jobs.size()), dim3(64), 0, s, dJobs, (uint32_t)jobs.size(), dOut);
+  uint32_t* h_out = pin.take_n<uint32_t>((size_t)off);
+  if (!h_out) { zkir::set_last_error({ZKIR_ERR_DEVICE, "zkir_lowdeg_prove: no pinned host memory for the query section"}); return ZKIR_ERR_DEVICE; }
+  HIP_OK(hipMemcpyAsync(h_out, dOut, (size_t)off * 4, hipMemcpyDeviceToHost, s));
+  mark(4);
+  HIP_OK(hipStreamSynchronize(s));
+  if (check_launch("zkir_lowdeg_prove") != ZKIR_OK) return ZKIR_ERR_DEVICE;
+  for (uint32_t t = 0; t < num_queries; t++) h_out[(size_t)t * qsize] = queries[t];
+  memcpy(proof_host, head.data(), head_words * 4);
+  memcpy(proof_host + head_words, h_out, (size_t)off * 4);
+  if (stage_ms) {
+    (void)hipEventSynchronize(se.ev[4]);
+    for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&stage_ms[i], se.ev[i], se.ev[i + 1]);
+  }
+  *n_words = total;
+  return ZKIR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkir_lowdeg_prove(zkir_stark_ctx* c, const uint32_t* lde_mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words,
+                      uint64_t* n_words, void* stream) {
+  return lowdeg_prove_impl(c, lde_mat, width, tree, num_queries, pow_bits, proof_host, cap_words, n_words, nullptr, (hipStream_t)stream);
+}
+
+// (zkir_amd_experimental.h) the same proof with the device time of its four stages: combine | FRI commit phase | grinding | query section
+int zkir_lowdeg_prove_stages(zkir_stark_ctx* c, const uint32_t* lde_mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words,
+                             uint64_t* n_words, float stage_ms[4], void* stream) {
+  return lowdeg_prove_impl(c, lde_mat, width, tree, num_queries, pow_bits, proof_host, cap_words, n_words, stage_ms, (hipStream_t)stream);
+}
+
+// (zkir_amd_experimental.h) lowdeg_combine_kernel alone for a GIVEN gamma (canonical E4): cw[t M + j] = coordinate t of sum_k gamma^k col_k(x_j), M = N << log_blowup rows.
+// The gamma table is uploaded with a synchronous copy: a test and measurement entry, not a stage of a pipeline.
+int zkir_lowdeg_combine_launch(const zkir_stark_ctx* c, const uint32_t* lde_mat, uint32_t width, const uint32_t gamma[4], uint32_t* gpow_scratch, uint32_t* cw, void* stream) {
+  if (!c || !lde_mat || !gamma || !gpow_scratch || !cw || width < 1 || width > LOWDEG_MAX_WIDTH) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_lowdeg_combine_launch: null argument, or width outside 1 .. 512"}); return ZKIR_ERR_ARGUMENT; }
+  for (int t = 0; t < 4; t++) if (gamma[t] >= bb::P) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_lowdeg_combine_launch: gamma must be canonical"}); return ZKIR_ERR_ARGUMENT; }
+  const std::vector<E4> gp = lowdeg_gamma_table(E4{{gamma[0], gamma[1], gamma[2], gamma[3]}}, width);
+  HIP_OK(hipMemcpy(gpow_scratch, gp.data(), gp.size() * sizeof(E4), hipMemcpyHostToDevice));
+  const uint64_t M = 1ull << (c->log_n + c->log_blowup);
+  hipLaunchKernelGGL(lowdeg_combine_kernel, dim3(grid_for(M)), dim3(NT), 0, (hipStream_t)stream, lde_mat, (width + 7) / 8, M, reinterpret_cast<const E4*>(gpow_scratch), cw);
+  return check_launch("lowdeg_combine");
+}
+
+}  // extern "C"

@@ -1067,3 +1067,136 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
 }
 
 }  // namespace
+
+// ================================================================================================
+// zkir_lowdeg_verify — the verifier of a LOW-DEGREE PROOF OF A COMMITMENT (zkir_lowdeg_prove, lowdeg.inl; spec: tests/lowdeg_ref.py).  Host only.
+//
+// The proof says: every column of the matrix committed under the root is close to a polynomial of degree < N = 2^log_n over the coset 31 <w_M>, M = N << b.  It says nothing
+// else — no constraint, no opening at a point.  Batched FRI over C(x) = sum_k gamma^k col_k(x); the schedule, the final-degree check and the query width follow b.
+//   [0..8)  'ZKLD', version 1, log_n, b, width, num_queries, pow_bits, n_layers | [8..12) the root | n_layers x 4 layer roots | n_fin x 4 final layer (n_fin = 4 << b) | nonce |
+//   per query: q (< M/2), record(q), record(q + M/2) (zkir_merkle_open_launch's records), per layer 4 * 2^k values (value t = c[idx + t g]) and 4 * depth sibling words
+// Transcript (the Challenger above): header, root, gamma; per layer root, beta; the final words; check_pow(nonce); q_t = sample_bits(log_n + b - 1).
+// Codes, first failing check in this order, lowest query first: 1 malformed (length not EXACTLY the header's, magic, version, a range, n_layers), 2 not the expected root,
+// 3 a word >= p (the whole proof is scanned before any product), 4 the final layer is not of degree < 4, 5 grinding, 6 a query's index word, 7 a matrix record does not hash to
+// the root, 8 layer-0 values are not sum gamma^k row at q / q + M/2 (checked BEFORE layer 0's path), 9 a FRI leaf's path, 10 carried value != v[slot], 11 final value.
+// ================================================================================================
+namespace {
+
+std::vector<int> lowdeg_schedule(int log_n, int b) {
+  std::vector<int> ks;
+  const int log_fin = 2 + b;
+  for (int log_m = log_n + b; log_m > log_fin;) { const int k = ks.empty() ? 1 : (LOG_ARITY < log_m - log_fin ? LOG_ARITY : log_m - log_fin); ks.push_back(k); log_m -= k; }
+  return ks;
+}
+bool lowdeg_params_ok(uint32_t log_n, uint32_t b, uint32_t width, uint32_t num_queries) {
+  return log_n >= 3 && log_n <= 26 && b >= 1 && b <= 3 && log_n + b <= 27 && width >= 1 && width <= 512 && num_queries >= 1 && num_queries <= 128;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t zkir_lowdeg_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t num_queries) {
+  if (!lowdeg_params_ok(log_n, log_blowup, width, num_queries)) return 0;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)log_blowup);
+  uint64_t qsize = 1 + 2 * ((uint64_t)width + 4 * (uint64_t)(log_n + log_blowup));
+  int lm = (int)(log_n + log_blowup);
+  for (int k : ks) { qsize += 4 * ((uint64_t)1 << k) + 4 * (uint64_t)(lm - k); lm -= k; }
+  return 12 + 4 * (uint64_t)ks.size() + 4 * ((uint64_t)4 << log_blowup) + 1 + (uint64_t)num_queries * qsize;
+}
+
+int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root) {
+  // ---- 1: shape ----
+  if (!w || len < 12 || w[0] != 0x444C4B5Au || w[1] != 1) return 1;
+  const uint32_t log_n = w[2], b = w[3], width = w[4], num_queries = w[5], pow_bits = w[6];
+  if (!lowdeg_params_ok(log_n, b, width, num_queries) || pow_bits > 24) return 1;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const int n_layers = (int)ks.size();
+  if (w[7] != (uint32_t)n_layers || len != zkir_lowdeg_proof_words(log_n, b, width, num_queries)) return 1;
+  // ---- 2: the root ----
+  const uint32_t* root = w + 8;
+  if (expect_root && memcmp(root, expect_root, 16)) return 2;
+  // ---- 3: canonical words ----
+  for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
+  const int log_M = (int)(log_n + b);
+  const size_t M = (size_t)1 << log_M, n_fin = (size_t)4 << b;
+  const uint32_t* lroots = w + 12;
+  const size_t at_fin = 12 + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1;
+  auto get_m = [&](size_t at) { return bb::e_to_mont(E4{{w[at], w[at + 1], w[at + 2], w[at + 3]}}); };
+  std::vector<E4> fin(n_fin);
+  for (size_t i = 0; i < n_fin; i++) fin[i] = get_m(at_fin + 4 * i);
+  // ---- 4: the final layer has degree < 4: coefficients 4 .. n_fin - 1 of its interpolant vanish (a plain inverse DFT decides: the coset shift scales coefficient k by
+  //         shift^-k and cannot make a non-zero one vanish) ----
+  {
+    const uint32_t winv_m = bb::to_mont(bb::inv(bb::root_of_unity(2 + (int)b)));
+    for (size_t k = 4; k < n_fin; k++) {
+      E4 c = bb::e_zero();
+      uint32_t tw = bb::R1, step = bb::R1;
+      for (size_t t = 0; t < k; t++) step = bb::mont_mul(step, winv_m);     // w^-k
+      for (size_t i = 0; i < n_fin; i++) { c = bb::e_add(c, bb::e_mul_fm(fin[i], tw)); tw = bb::mont_mul(tw, step); }
+      if (c.c[0] | c.c[1] | c.c[2] | c.c[3]) return 4;
+    }
+  }
+  // ---- the transcript ----
+  Challenger ch;
+  ch.observe_n(w, 8);
+  ch.observe_n(root, 4);
+  const E4 gamma = bb::e_to_mont(ch.sample_ext());
+  std::vector<E4> betas(n_layers);
+  for (int j = 0; j < n_layers; j++) { ch.observe_n(lroots + 4 * j, 4); betas[j] = bb::e_to_mont(ch.sample_ext()); }
+  ch.observe_n(w + at_fin, 4 * n_fin);
+  // ---- 5: grinding ----
+  if (!ch.check_pow(w[at_nonce], (int)pow_bits)) return 5;
+  std::vector<uint32_t> qs(num_queries);
+  for (auto& q : qs) q = ch.sample_bits(log_M - 1);
+  // ---- 6 .. 11: queries ----
+  std::vector<E4> gp(width);
+  gp[0] = bb::e_one_m();
+  for (size_t k = 1; k < width; k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
+  const size_t rec = (size_t)width + 4 * (size_t)log_M, qsize = (len - at_queries) / num_queries;
+  auto check_query = [&](int t) -> int {
+    size_t p = at_queries + (size_t)t * qsize;
+    const uint32_t q = qs[t];
+    if (w[p++] != q) return 6;
+    E4 comb[2];
+    for (int s2 = 0; s2 < 2; s2++) {
+      const size_t pos = (size_t)q + (s2 ? M / 2 : 0);
+      const uint32_t* row = w + p;
+      uint32_t dg[4]; hash_elems(row, width, dg);
+      if (!check_path(dg, pos, row + width, log_M, root)) return 7;
+      E4 A = bb::e_zero();                                                  // canonical word x Montgomery gamma^k = canonical; lifted to Montgomery at the end
+      for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[k], row[k]));
+      comb[s2] = bb::e_to_mont(A);
+      p += rec;
+    }
+    E4 carried = bb::e_zero(); size_t carried_idx = q;
+    uint32_t shift = bb::GEN; int log_m = log_M;
+    for (int j = 0; j < n_layers; j++) {
+      const int k = ks[j], depth = log_m - k;
+      const size_t nv = (size_t)1 << k, g = (size_t)1 << depth, idx = carried_idx & (g - 1), slot = carried_idx >> depth;
+      std::vector<E4> v(nv);
+      for (size_t t2 = 0; t2 < nv; t2++) v[t2] = get_m(p + 4 * t2);
+      if (j == 0 && (!e_eq(v[0], comb[0]) || !e_eq(v[1], comb[1]))) return 8;
+      uint32_t dg[4]; hash_elems(w + p, 4 * nv, dg);
+      p += 4 * nv;
+      if (!check_path(dg, idx, w + p, depth, lroots + 4 * j)) return 9;
+      p += 4 * (size_t)depth;
+      if (j > 0 && !e_eq(v[slot], carried)) return 10;
+      E4 beta = betas[j];
+      for (int f = 0; f < k; f++) {
+        const size_t half = nv >> (f + 1);
+        const uint32_t wm = bb::root_of_unity(log_m);
+        for (size_t t2 = 0; t2 < half; t2++) v[t2] = fold_pair(v[t2], v[t2 + half], bb::to_mont(bb::mul(shift, bb::pow(wm, idx + t2 * g))), beta);
+        shift = bb::mul(shift, shift); log_m--; beta = bb::e_mul_m(beta, beta);
+      }
+      carried = v[0]; carried_idx = idx;
+    }
+    if (!e_eq(fin[carried_idx & (n_fin - 1)], carried)) return 11;
+    return 0;
+  };
+  // (the queries are independent; checked one after the other: a proof has at most 128 of them and its verdict is this loop's)
+  for (int t = 0; t < (int)num_queries; t++) { const int code = check_query(t); if (code) return code; }
+  return 0;
+}
+
+}  // extern "C"

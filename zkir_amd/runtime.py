@@ -411,6 +411,12 @@ def lib() -> C.CDLL:
         L.zkir_merkle_open_launch.restype = C.c_int; L.zkir_merkle_open_launch.argtypes = [V, V, U32, U64, V, V, U64, V, V]
         L.zkir_merkle_verify_launch.restype = C.c_int; L.zkir_merkle_verify_launch.argtypes = [V, V, U32, U64, V, U64, V, U32, V, V, V]
         L.zkir_merkle_verify_host.restype = C.c_int; L.zkir_merkle_verify_host.argtypes = [V, U32, U64, V, U64, V, U32, V, V]
+    if hasattr(L, "zkir_lowdeg_prove"):                       # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_lowdeg_proof_words.restype = U64; L.zkir_lowdeg_proof_words.argtypes = [U32, U32, U32, U32]
+        L.zkir_lowdeg_prove.restype = C.c_int; L.zkir_lowdeg_prove.argtypes = [V, V, U32, V, U32, U32, V, U64, C.POINTER(U64), V]
+        L.zkir_lowdeg_verify.restype = C.c_int; L.zkir_lowdeg_verify.argtypes = [V, U64, V]
+        L.zkir_lowdeg_prove_stages.restype = C.c_int; L.zkir_lowdeg_prove_stages.argtypes = [V, V, U32, V, U32, U32, V, U64, C.POINTER(U64), V, V]
+        L.zkir_lowdeg_combine_launch.restype = C.c_int; L.zkir_lowdeg_combine_launch.argtypes = [V, V, U32, V, V, V, V]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -650,6 +656,20 @@ def merkle_verify_host(root, width: int, n_leaves: int, indices, openings, flags
     if rc != ZKIR_OK:
         _raise(rc)
     return verdicts[:len(idx)], summary
+
+
+def lowdeg_proof_words(log_n: int, log_blowup: int, width: int, num_queries: int) -> int:
+    """Words of a low-degree proof of a commitment (zkir_lowdeg_proof_words); 0 for parameters no proof can state."""
+    return int(lib().zkir_lowdeg_proof_words(int(log_n), int(log_blowup), int(width), int(num_queries)))
+
+
+def lowdeg_verify(proof, root=None) -> int:
+    """zkir_lowdeg_verify, on the host — no GPU: 0 = the proof convinces a holder of its root (or of `root`, four words, when given) that every committed column is close to a
+    polynomial of degree < 2^log_n; else the code of the first failing check (include/zkir_amd.h lists them)."""
+    w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
+    r = None if root is None else np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
+    assert r is None or len(r) == 4
+    return int(lib().zkir_lowdeg_verify(w.ctypes.data if len(w) else None, len(w), r.ctypes.data if r is not None else None))
 
 
 def verify_last_stages() -> dict:

@@ -67,7 +67,8 @@ def trace_root(proof) -> list:
 
 class StarkContext:
     """zkir_stark_ctx: device tables for traces of 2^log_n rows, extended to 2^(log_n + log_blowup) (log_blowup 1, 2, 3: blow-up 2, 4, 8; log_n + log_blowup <= 27).
-    Contexts of log_blowup 2 / 3 serve the commitment (lde, merkle_commit, commit_trace); proofs are blow-up 2: prove() raises on them."""
+    Contexts of log_blowup 2 / 3 serve the commitment (lde, merkle_commit, commit_trace); and lowdeg_prove (a low-degree proof of such a
+    commitment, at the context's rate); zkir_prove's proofs are blow-up 2: prove() raises on them."""
 
     def __init__(self, log_n: int, log_blowup: int = 1):
         pl._require_gpu()
@@ -207,6 +208,51 @@ def merkle_verify(ctx: StarkContext, root: torch.Tensor, width: int, n_leaves: i
     summary = torch.empty(2, dtype=torch.int32, device=openings.device)
     pl._check(rt.lib().zkir_merkle_verify_launch(ctx.handle, root.data_ptr(), width, n_leaves, idx.data_ptr(), idx.numel(), openings.data_ptr(), flags, verdicts.data_ptr(), summary.data_ptr(), _sp(stream)))
     return verdicts, summary
+
+
+lowdeg_proof_words = rt.lowdeg_proof_words
+
+
+def lowdeg_prove(ctx: StarkContext, lde_mat: torch.Tensor, tree: torch.Tensor, width: Optional[int] = None, num_queries: int = 50, pow_bits: int = 12, stream=None,
+                 want_stage_ms: bool = False):
+    """zkir_lowdeg_prove: the low-degree proof (np.uint32 words) of the commitment `tree` (merkle_commit's) to the B8 matrix `lde_mat` (lde's output on `ctx`, `width` real
+    columns, default all): every column is close to a polynomial of degree < 2^ctx.log_n — no constraint, no opening at a point.  Works at every rate a context serves.
+    A matrix or tree that is not of the context's size raises ValueError; the library refuses bad parameters with ERR_ARGUMENT before any launch.
+    want_stage_ms: also the device ms of (combine, FRI commit phase, grinding, query section)."""
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    if lde_mat.dim() != 3 or lde_mat.shape[1] != m or lde_mat.shape[2] != 8 or lde_mat.dtype != torch.int32 or not lde_mat.is_contiguous():
+        raise ValueError(f"lowdeg_prove: the matrix must be contiguous int32[blocks][{m}][8], the context's extension size")
+    if tree.dtype != torch.int32 or not tree.is_contiguous() or tree.numel() != 4 * (2 * m - 1):
+        raise ValueError(f"lowdeg_prove: the tree must be contiguous int32[{4 * (2 * m - 1)}], merkle_commit's over {m} leaves")
+    width = lde_mat.shape[0] * 8 if width is None else int(width)
+    if width > lde_mat.shape[0] * 8:
+        raise ValueError("lowdeg_prove: width exceeds the matrix's columns")
+    cap = lowdeg_proof_words(ctx.log_n, ctx.log_blowup, width, num_queries)
+    out = np.zeros(max(cap, 1), np.uint32)
+    n_words = C.c_uint64()
+    if want_stage_ms:
+        ms = (C.c_float * 4)()
+        pl._check(rt.lib().zkir_lowdeg_prove_stages(ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words), ms, _sp(stream)))
+        return out[:n_words.value], [float(x) for x in ms]
+    pl._check(rt.lib().zkir_lowdeg_prove(ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words), _sp(stream)))
+    return out[:n_words.value]
+
+
+lowdeg_verify = rt.lowdeg_verify
+
+
+def lowdeg_combine(ctx: StarkContext, lde_mat: torch.Tensor, gamma, width: Optional[int] = None, stream=None) -> torch.Tensor:
+    """(tests, measurements) zkir_lowdeg_combine_launch: the codeword int32[4][M] of lowdeg_prove's first stage for a GIVEN canonical gamma (four words):
+    row t = coordinate t of sum_k gamma^k col_k."""
+    nb, m, eight = lde_mat.shape
+    assert eight == 8 and m == 1 << (ctx.log_n + ctx.log_blowup) and lde_mat.dtype == torch.int32 and lde_mat.is_contiguous()
+    width = nb * 8 if width is None else int(width)
+    assert 1 <= width <= nb * 8
+    g = np.ascontiguousarray(gamma, dtype=np.uint32).reshape(4)
+    scratch = torch.empty(32 * ((width + 7) // 8), dtype=torch.int32, device=lde_mat.device)
+    cw = torch.empty((4, m), dtype=torch.int32, device=lde_mat.device)
+    pl._check(rt.lib().zkir_lowdeg_combine_launch(ctx.handle, lde_mat.data_ptr(), width, g.ctypes.data, scratch.data_ptr(), cw.data_ptr(), _sp(stream)))
+    return cw
 
 
 def commit_trace(ctx: StarkContext, trace: pl.DeviceTrace, stream=None, deferred: bool = False):
