@@ -109,7 +109,7 @@ void sha256(const uint8_t* data, size_t len, uint32_t out[8]) {
   for (; off + 64 <= len; off += 64) sha256_block(h, data + off);
   uint8_t tail[128] = {0};
   const size_t rem = len - off;
-  memcpy(tail, data + off, rem);
+  if (rem) memcpy(tail, data + off, rem);                          // (an empty message may come as a null pointer: memcpy's arguments must not be null even for 0 bytes)
   tail[rem] = 0x80;
   const size_t tl = rem < 56 ? 64 : 128;
   const uint64_t bits = (uint64_t)len * 8;
@@ -129,7 +129,7 @@ void keccak256(const uint8_t* data, size_t len, uint8_t out[32]) {
   size_t off = 0;
   for (; off + RATE <= len; off += RATE) absorb(data + off);
   uint8_t last[RATE] = {0};
-  memcpy(last, data + off, len - off);
+  if (len - off) memcpy(last, data + off, len - off);
   last[len - off] ^= 0x01;
   last[RATE - 1] ^= 0x80;
   absorb(last);
@@ -153,7 +153,7 @@ void blake3(const uint8_t* data, size_t len, uint8_t out[32]) {
     for (size_t b = 0; b < nb; b++) {
       uint8_t blk[64] = {0};
       const size_t bl = clen == 0 ? 0 : ((b == nb - 1) ? clen - b * 64 : 64);
-      memcpy(blk, p + b * 64, bl);
+      if (bl) memcpy(blk, p + b * 64, bl);
       uint32_t m[16];
       for (int i = 0; i < 16; i++) m[i] = le32w(blk + 4 * i);
       uint32_t fl = (b == 0 ? CHUNK_START : 0) | (b == nb - 1 ? CHUNK_END : 0);

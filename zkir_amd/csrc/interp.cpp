@@ -39,7 +39,9 @@ namespace zkir {
 // ---- block pool (host.h) --------------------------------------------------------------------------------------------------
 namespace {
 std::mutex g_pool_mu;
-std::vector<Block> g_pool;
+// Never destroyed: a static vector's destructor would drop the parked blocks at exit without freeing them (LeakSanitizer calls that a leak, rightly), and to free them there
+// is no option: a pinned block cannot be given back once the device runtime has begun to shut down.  So the pool owns its blocks until the process ends.
+std::vector<Block>& pool() { static std::vector<Block>* const p = new std::vector<Block>; return *p; }
 size_t g_pool_bytes = 0;
 constexpr size_t POOL_MAX_BLOCKS = 8, POOL_MAX_BYTES = 4ull << 30;
 void block_free(const Block& b) { if (b.pinned) pinned_free(b.p); else free(b.p); }
@@ -48,6 +50,7 @@ void block_free(const Block& b) { if (b.pinned) pinned_free(b.p); else free(b.p)
 Block block_acquire(size_t min_bytes) {
   {
     std::lock_guard<std::mutex> lk(g_pool_mu);
+    std::vector<Block>& g_pool = pool();
     int best = -1;
     for (int i = 0; i < (int)g_pool.size(); i++)
       if (g_pool[i].bytes >= min_bytes && g_pool[i].bytes <= 4 * min_bytes && (best < 0 || g_pool[i].bytes < g_pool[best].bytes)) best = i;
@@ -72,6 +75,7 @@ void block_release(const Block& b) {
   std::vector<Block> drop;
   {
     std::lock_guard<std::mutex> lk(g_pool_mu);
+    std::vector<Block>& g_pool = pool();
     if (b.bytes > POOL_MAX_BYTES) drop.push_back(b);
     else {
       g_pool.push_back(b);
@@ -587,7 +591,8 @@ bool Machine::hash_syscall(int which) {
     wr_bound(14, BoundT{32, ZKIR_BOUND_CRYPTO_OUTPUT, 0});                                        // syscall.rs:135
     if (tracing_ && il < 56) {                                                                    // single-block message -> SHA chip input (crypto.rs:108-139)
       zkir_sha_block blk; uint8_t raw[64] = {0};
-      memcpy(raw, in.data(), in.size()); raw[in.size()] = 0x80;
+      if (!in.empty()) memcpy(raw, in.data(), in.size());
+      raw[in.size()] = 0x80;
       const uint64_t bits = il * 8;
       for (int i = 0; i < 8; i++) raw[56 + i] = (uint8_t)(bits >> (8 * (7 - i)));
       for (int i = 0; i < 16; i++) blk.message_block[i] = ((uint32_t)raw[4 * i] << 24) | ((uint32_t)raw[4 * i + 1] << 16) | ((uint32_t)raw[4 * i + 2] << 8) | raw[4 * i + 3];
