@@ -403,6 +403,35 @@ int zkir_lowdeg_prove(zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t wid
                       uint64_t cap_words, uint64_t* n_words, void* hip_stream);
 int zkir_lowdeg_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root);
 
+/* ---- an evaluation proof of a commitment: opening it at out-of-domain points, at any rate a context serves ----
+ * Statement: every column k of the committed B8 matrix (lde_mat, tree: as for zkir_lowdeg_prove) is close to a polynomial p_k of degree < N = 2^log_n, and p_k(z_i) = y[i][k]
+ * at the n_points (1 or 2) points z_i the caller supplies: E4 elements, four canonical words each.  A point must lie OUTSIDE the base field (one of its coordinates 1 .. 3 is
+ * not zero: then z - x is invertible for every x of the domain and (z / 31)^N != 1), and two points must differ.  The points MUST BE CHOSEN AFTER THE ROOT (drawn from a
+ * transcript that has observed it): that is the caller's protocol; a point known before the commitment proves nothing.
+ * The evaluations are DEFINED as the barycentric sums over the rows j 2^log_blowup (the sub-coset 31 <w_N>):
+ *     y[i][k] = ((z_i / 31)^N - 1) / N * sum_j mat[k][j 2^log_blowup] x_j / (z_i - x_j),   x_j = 31 w_N^j
+ * whatever the matrix holds: on a matrix that is not low-degree the prover follows the same procedure and its proof is refused.
+ * Proof: batched FRI over F(x) = sum_i (a_i - A_i(x)) / (z_i - x) on all M rows, A_i(x) = sum_k gamma^(i width + k) col_k(x), a_i = sum_k gamma^(i width + k) y[i][k],
+ * gamma drawn after the header, the root, the points and the evaluations.  Conjectured soundness as for the low-degree proof.
+ * Proof words (all canonical): [0..9) 'ZKEV' = 0x56454B5A, version 1, log_n, log_blowup, width, n_points, num_queries, pow_bits, n_layers | [9..13) the root | the points
+ * (4 n_points words) | the evaluations (4 n_points width words, point-major: y[i][k] at 4 (i width + k)) | from there on the low-degree proof's layout: layer roots, final
+ * layer, nonce, queries.  A proof is a function of its inputs.
+ * zkir_eval_proof_words: the proof's length; 0 outside the low-degree proof's ranges or n_points 1 .. 2.
+ * zkir_eval_prove: lde_mat, tree DEVICE pointers; points, proof_host HOST (nothing past *n_words is written).  One proof at a time per context (its workspace arena: the
+ * low-degree proof's plus 16 n_points (M + N) bytes of inverses and weights); synchronises the stream.  A null pointer, a context of log_n < 3, a width, n_points,
+ * num_queries or pow_bits outside its range, a word of points >= p, a point in the base field, two equal points, or cap_words below zkir_eval_proof_words:
+ * ZKIR_ERR_ARGUMENT with a message naming the argument, before anything is launched.
+ * zkir_eval_verify: host only.  0 accepted; else the first failing check, in this order: 1 malformed (length not exactly the header's, magic, version, a range, n_points,
+ * n_layers), 2 not expect_root (NULL: any root), 13 not expect_points (4 n_points words) or not expect_evals (4 n_points width words; NULL: any), 3 a word >= p, 12 a point in
+ * the base field or two equal points, 4 final layer not of degree < 4, 5 grinding, 6 a query's index word, 7 a matrix record does not hash to the root, 8 layer-0 values are
+ * not F at the two rows, recomputed from the opened records, the points and the evaluations, 9 a FRI leaf's path, 10 a carried value, 11 the final value; lowest query first.
+ * expect_points / expect_evals are read at the sizes the PROOF's header states (4 proof[5] and 4 proof[5] proof[4] words) once check 1 has passed: a caller that expects
+ * certain sizes compares proof[4] and proof[5] with them before the call. */
+uint64_t zkir_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t n_points, uint32_t num_queries);
+int zkir_eval_prove(zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t* tree, const uint32_t* points, uint32_t n_points, uint32_t num_queries,
+                    uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words, void* hip_stream);
+int zkir_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals);
+
 /* Public inputs of a proof: absorbed by the Fiat-Shamir transcript before the first commitment and carried in the proof header. */
 typedef struct zkir_public_inputs {
   uint64_t n_real;             /* executed rows = ExecutionResult.cycles */

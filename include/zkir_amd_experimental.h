@@ -33,6 +33,20 @@ int zkir_lowdeg_prove_stages(zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint3
  * rows of the context.  gpow_scratch: DEVICE buffer of 32 ceil(width / 8) words for the gamma powers, uploaded with a synchronous copy. */
 int zkir_lowdeg_combine_launch(const zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t gamma[4], uint32_t* gpow_scratch, uint32_t* cw, void* hip_stream);
 
+/* MEASUREMENT: zkir_eval_prove with the device time (ms, HIP events) of its six stages: weights | evaluations | quotient | FRI commit phase | grinding | query section. */
+int zkir_eval_prove_stages(zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t* tree, const uint32_t* points, uint32_t n_points, uint32_t num_queries,
+                           uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words, float stage_ms[6], void* hip_stream);
+/* TEST / MEASUREMENT: the evaluations of zkir_eval_prove alone (weights, dot and sum kernels) for GIVEN points (HOST, canonical, as zkir_eval_prove takes them):
+ * evals = n_points x width canonical E4 words on the DEVICE, point-major.  scratch: DEVICE buffer of zkir_eval_at_scratch_words(log_n, width, n_points) words. */
+uint64_t zkir_eval_at_scratch_words(uint32_t log_n, uint32_t width, uint32_t n_points);
+int zkir_eval_at_launch(const zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t* points, uint32_t n_points, uint32_t* scratch, uint32_t* evals, void* hip_stream);
+/* TEST / MEASUREMENT: the codeword of zkir_eval_prove alone (inverse table and quotient kernel) for GIVEN gamma, points and evaluations (HOST, canonical):
+ * cw[t M + j] = coordinate t of F at row j, M = N << log_blowup.  scratch: DEVICE buffer of zkir_eval_quotient_scratch_words(log_n + log_blowup, width, n_points) words;
+ * the gamma table is uploaded with a synchronous copy. */
+uint64_t zkir_eval_quotient_scratch_words(uint32_t log_m, uint32_t width, uint32_t n_points);
+int zkir_eval_quotient_launch(const zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t gamma[4], const uint32_t* points, uint32_t n_points,
+                              const uint32_t* evals, uint32_t* scratch, uint32_t* cw, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,12 @@ extern "C" {
     pub fn zkir_lowdeg_prove(ctx: *mut ZkirStarkCtx, lde_mat: *const u32, width: u32, tree: *const u32, num_queries: u32, pow_bits: u32, proof_host: *mut u32, cap_words: u64,
                              n_words: *mut u64, stream: *mut c_void) -> c_int;
     pub fn zkir_lowdeg_verify(proof: *const u32, n_words: u64, expect_root: *const u32) -> c_int;
+    // an evaluation proof of a commitment at 1 or 2 points of E4 chosen AFTER the root (points: 4 n_points canonical words, host), and its host verifier
+    // (expect_* null = any; expect_points holds 4 proof[5] words, expect_evals 4 proof[5] proof[4] words)
+    pub fn zkir_eval_proof_words(log_n: u32, log_blowup: u32, width: u32, n_points: u32, num_queries: u32) -> u64;
+    pub fn zkir_eval_prove(ctx: *mut ZkirStarkCtx, lde_mat: *const u32, width: u32, tree: *const u32, points: *const u32, n_points: u32, num_queries: u32, pow_bits: u32,
+                           proof_host: *mut u32, cap_words: u64, n_words: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn zkir_eval_verify(proof: *const u32, n_words: u64, expect_root: *const u32, expect_points: *const u32, expect_evals: *const u32) -> c_int;
     // (mode 4) the tapes' share of the lookup table side and the hash tape's record checks as calls of their own (host arrays in, host arrays out)
     pub fn zkir_tape_table_side_launch(hash_words: *const u32, n_hash_words: u64, new_bytes: *const u64, wide_words: *const u32, n_wide_words: u64, alpha: *const u32, lambda: *const u32,
                                        sum: *mut u32, hh: *mut u32, ww: *mut u32, stream: *mut c_void) -> c_int;

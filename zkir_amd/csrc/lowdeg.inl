@@ -64,101 +64,92 @@ std::vector<E4> lowdeg_gamma_table(const E4& gamma, uint32_t width) {
   return t;
 }
 
-int lowdeg_bad(const std::string& why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_lowdeg_prove: " + why}); return ZKIR_ERR_ARGUMENT; }
-
-// stage_ms (measurements; may be null): combine | FRI commit phase | grinding | query section
-int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words,
-                      uint64_t* n_words, float* stage_ms, hipStream_t s) {
-  // every argument is checked before anything is launched
-  if (n_words) *n_words = 0;
-  if (!c || !mat || !tree || !proof_host || !n_words) return lowdeg_bad("null context, matrix, tree, proof buffer or n_words");
-  const uint32_t log_n = c->log_n, b = c->log_blowup, log_M = log_n + b;
-  if (log_n < 3) return lowdeg_bad("the context's log_n must be at least 3: below that there is no layer to commit");
-  if (width < 1 || width > LOWDEG_MAX_WIDTH) return lowdeg_bad("width must be 1 .. 512 (terms per 96-bit sum of the combination)");
-  if (num_queries < 1 || num_queries > 128) return lowdeg_bad("num_queries must be 1 .. 128");
-  if (pow_bits > 24) return lowdeg_bad("pow_bits must be 0 .. 24");
-  const uint64_t total = zkir_lowdeg_proof_words(log_n, b, width, num_queries);
-  if (total == 0) return lowdeg_bad("the context's log_n / log_blowup are outside what a proof can state (log_n 3 .. 26, log_blowup 1 .. 3, their sum at most 27)");
-  if (cap_words < total) return lowdeg_bad("cap_words is below zkir_lowdeg_proof_words(log_n, log_blowup, width, num_queries)");
-
-  std::lock_guard<std::mutex> ctx_lock(c->mu);                   // one proof at a time per context: the workspace is its arena, as in zkir_prove
-  const uint64_t M = 1ull << log_M;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
-  const int n_layers = (int)ks.size();
-  const uint32_t n_fin = 4u << b, rec = width + 4 * log_M, n_blocks = (width + 7) / 8;
-  const uint64_t head_words = 12 + 4 * (uint64_t)n_layers + 4 * (uint64_t)n_fin + 1, qsize = (total - head_words) / num_queries;
-
-  // workspace: the codeword (16 M bytes), the layers and their trees (at most 48 M bytes together at the schedules of log_n >= 5), the query section and its inputs
-  {
-    auto al = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-    size_t want = al(16 * M) + al(n_blocks * 8 * sizeof(E4)) + 8 * 256 + al(16 * (size_t)(n_layers + 1) * 4);
-    { int lm = (int)log_M; for (int k : ks) { const uint64_t g = (1ull << lm) >> k; want += al(16 * (2 * g - 1)) + al(16 * g); lm -= k; } }
-    size_t n_jobs = 0;
-    for (int k : ks) n_jobs += ((size_t)1 << k) + 1;
-    n_jobs = (n_jobs + 1) * num_queries;
-    want += al(2 * (size_t)num_queries * 8) + al(2 * (size_t)num_queries * rec * 4) + al(n_jobs * sizeof(GatherJob)) + al((size_t)num_queries * qsize * 4);
-    if (c->arena_size < want) {
-      if (c->arena) (void)hipFree(c->arena);
-      c->arena = nullptr; c->arena_size = 0;
-      HIP_OK(hipMalloc((void**)&c->arena, want));
-      c->arena_size = want;
-    }
-    c->arena_off = 0;
-  }
-  Arena ar{c};
-  zkir::HostPin& pin = c->pin;
-  pin.reset();
-  auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+// ---- what a proof in the context's arena needs on the host side: pinned staging for uploads and downloads, stage events (zkir_lowdeg_prove and zkir_eval_prove) -------------
+struct ProofRun {
+  zkir_stark_ctx* c; hipStream_t s; const char* who; bool timed;
+  Arena ar; zkir::HostPin& pin; StageEvents se;
+  struct Staged { void* dst; const void* src; size_t n; };
+  std::vector<Staged> staged;
+  ProofRun(zkir_stark_ctx* ctx, hipStream_t stream, const char* name, bool want_times) : c(ctx), s(stream), who(name), timed(want_times), ar{ctx}, pin(ctx->pin) { pin.reset(); }
+  int fail(int code, const std::string& why) const { zkir::set_last_error({code, std::string(who) + ": " + why}); return code; }
+  hipError_t h2d(void* dst, const void* src, size_t bytes) {
     void* p = pin.take(bytes);
     if (!p) return hipErrorOutOfMemory;
     memcpy(p, src, bytes);
     return hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
-  };
-  struct Staged { void* dst; const void* src; size_t n; };
-  std::vector<Staged> staged;
-  auto d2h = [&](void* dst, const void* dsrc, size_t bytes) -> hipError_t {
+  }
+  hipError_t d2h(void* dst, const void* dsrc, size_t bytes) {
     void* h = pin.take(bytes);
     if (!h) return hipErrorOutOfMemory;
     staged.push_back({dst, h, bytes});
     return hipMemcpyAsync(h, dsrc, bytes, hipMemcpyDeviceToHost, s);
-  };
-  auto sync_d2h = [&]() -> hipError_t {
+  }
+  hipError_t sync_d2h() {
     const hipError_t e = hipStreamSynchronize(s);
     if (e == hipSuccess) for (const Staged& x : staged) memcpy(x.dst, x.src, x.n);
     staged.clear();
     return e;
-  };
-  StageEvents se;
-  if (stage_ms) HIP_OK(se.create());
-  auto mark = [&](int i) { if (stage_ms) (void)hipEventRecord(se.ev[i], s); };
-
-  // ---- transcript up to gamma: header, root ------------------------------------------------------------------------------------------------------------------------------
-  std::vector<uint32_t> head = {LOWDEG_MAGIC, LOWDEG_VERSION, log_n, b, width, num_queries, pow_bits, (uint32_t)n_layers};
-  uint32_t root[4];
-  HIP_OK(d2h(root, tree + 4 * (2 * M - 2), 16));
-  HIP_OK(sync_d2h());
-  Challenger ch(c->consts);
-  ch.observe_n(head.data(), 8);
-  ch.observe_n(root, 4);
-  const E4 gamma = ch.sample_ext();
-  head.insert(head.end(), root, root + 4);
-
-  // ---- 1. the codeword --------------------------------------------------------------------------------------------------------------------------------------------------------
-  E4* dGpow; uint32_t *dState, *dBest, *dChSt, *dFri;
-  std::vector<uint32_t*> fri_trees(n_layers), fri_layers(n_layers + 1);
-  HIP_OK(ar.take(&dGpow, (size_t)n_blocks * 8)); HIP_OK(ar.take(&dState, 16)); HIP_OK(ar.take(&dBest, 4)); HIP_OK(ar.take(&dChSt, 16)); HIP_OK(ar.take(&dFri, 16 * (size_t)(n_layers + 1)));
-  HIP_OK(ar.take(&fri_layers[0], 4 * M));
-  {
-    const std::vector<E4> gp = lowdeg_gamma_table(gamma, width);
-    HIP_OK(h2d(dGpow, gp.data(), gp.size() * sizeof(E4)));
   }
-  mark(0);
-  hipLaunchKernelGGL(lowdeg_combine_kernel, dim3(grid_for(M)), dim3(NT), 0, s, mat, n_blocks, M, dGpow, fri_layers[0]);
-  mark(1);
+  void mark(int i) { if (timed) (void)hipEventRecord(se.ev[i], s); }
+  void times(float* stage_ms, int n) { (void)hipEventSynchronize(se.ev[n]); for (int i = 0; i < n; i++) (void)hipEventElapsedTime(&stage_ms[i], se.ev[i], se.ev[i + 1]); }
+};
 
-  // ---- 2. FRI commit phase, enqueued as a whole (zkir_prove's, with log_2n = log_n + b): nothing is pending in the transcript once gamma is drawn ---------------------------
-  if (!ch.in.empty()) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: the transcript has pending input at the FRI commit phase"}); return ZKIR_ERR_OTHER; }
-  HIP_OK(h2d(dChSt, ch.st, sizeof(ch.st)));
+inline size_t arena_al(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// words of one query: q, two matrix records, per layer its values and path
+uint64_t lowdeg_query_words(uint32_t log_M, uint32_t width, const std::vector<int>& ks) {
+  uint64_t q = 1 + 2 * ((uint64_t)width + 4 * log_M);
+  int lm = (int)log_M;
+  for (int k : ks) { q += 4 * ((uint64_t)1 << k) + 4 * (uint64_t)(lm - k); lm -= k; }
+  return q;
+}
+
+// workspace of everything from the codeword on: the codeword (16 M bytes), the layers and their trees (at most 48 M bytes together at the schedules of log_n >= 5), the
+// query section and its inputs
+size_t lowdeg_fri_bytes(uint32_t log_M, uint32_t width, const std::vector<int>& ks, uint32_t num_queries) {
+  const uint64_t M = 1ull << log_M, rec = width + 4 * (uint64_t)log_M;
+  size_t want = arena_al(16 * M) + 8 * 256 + arena_al(16 * (ks.size() + 1) * 4);
+  { int lm = (int)log_M; for (int k : ks) { const uint64_t g = (1ull << lm) >> k; want += arena_al(16 * (2 * g - 1)) + arena_al(16 * g); lm -= k; } }
+  size_t n_jobs = 0;
+  for (int k : ks) n_jobs += ((size_t)1 << k) + 1;
+  n_jobs = (n_jobs + 1) * num_queries;
+  return want + arena_al(2 * (size_t)num_queries * 8) + arena_al(2 * (size_t)num_queries * rec * 4) + arena_al(n_jobs * sizeof(GatherJob)) +
+         arena_al((size_t)num_queries * lowdeg_query_words(log_M, width, ks) * 4);
+}
+
+// the context's arena holds at least `want` bytes, and is empty
+int arena_reserve(zkir_stark_ctx* c, size_t want) {
+  if (c->arena_size < want) {
+    if (c->arena) (void)hipFree(c->arena);
+    c->arena = nullptr; c->arena_size = 0;
+    HIP_OK(hipMalloc((void**)&c->arena, want));
+    c->arena_size = want;
+  }
+  c->arena_off = 0;
+  return ZKIR_OK;
+}
+
+// Sections 2 - 4 of a proof over a codeword of M = 2^log_M values (cw[t M + j], canonical) under the matrix `mat` / `tree`: the FRI commit phase, grinding, the queries.
+// `ch` is the transcript as it stands once the codeword's challenge is drawn, `head` the proof words so far (the layer roots, the final layer and the nonce are appended),
+// `total` the proof's length.  Stage marks first_mark .. first_mark + 2 are recorded after the three sections.  Writes the whole proof to proof_host.
+int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& head, const uint32_t* mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits,
+                           const std::vector<int>& ks, uint32_t* codeword, uint64_t total, int first_mark, uint32_t* proof_host) {
+  zkir_stark_ctx* c = r.c;
+  hipStream_t s = r.s;
+  Arena& ar = r.ar;
+  const uint32_t log_M = c->log_n + c->log_blowup, b = c->log_blowup;
+  const uint64_t M = 1ull << log_M;
+  const int n_layers = (int)ks.size();
+  const uint32_t n_fin = 4u << b, rec = width + 4 * log_M;
+  const uint64_t qsize = lowdeg_query_words(log_M, width, ks), head_words = total - qsize * num_queries;
+  uint32_t *dState, *dBest, *dChSt, *dFri;
+  std::vector<uint32_t*> fri_trees(n_layers), fri_layers(n_layers + 1);
+  HIP_OK(ar.take(&dState, 16)); HIP_OK(ar.take(&dBest, 4)); HIP_OK(ar.take(&dChSt, 16)); HIP_OK(ar.take(&dFri, 16 * (size_t)(n_layers + 1)));
+  fri_layers[0] = codeword;
+
+  // ---- 2. FRI commit phase, enqueued as a whole (zkir_prove's, with log_2n = log_n + b): nothing is pending in the transcript once the challenge is drawn -------------------
+  if (!ch.in.empty()) return r.fail(ZKIR_ERR_OTHER, "the transcript has pending input at the FRI commit phase");
+  HIP_OK(r.h2d(dChSt, ch.st, sizeof(ch.st)));
   {
     uint32_t shift = bb::GEN;
     int log_m = (int)log_M;
@@ -189,36 +180,36 @@ int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, co
   }
   uint32_t fin_cols[4 * 32];                                                   // n_fin <= 32
   std::vector<uint32_t> fri_out(16 * (size_t)n_layers);
-  HIP_OK(d2h(fri_out.data(), dFri, fri_out.size() * 4));
-  HIP_OK(d2h(fin_cols, fri_layers[n_layers], 4 * (size_t)n_fin * 4));
-  HIP_OK(sync_d2h());
-  if (check_launch("zkir_lowdeg_prove") != ZKIR_OK) return ZKIR_ERR_DEVICE;
+  HIP_OK(r.d2h(fri_out.data(), dFri, fri_out.size() * 4));
+  HIP_OK(r.d2h(fin_cols, fri_layers[n_layers], 4 * (size_t)n_fin * 4));
+  HIP_OK(r.sync_d2h());
+  if (check_launch(r.who) != ZKIR_OK) return ZKIR_ERR_DEVICE;
   for (int j = 0; j < n_layers; j++) {                                         // the host's replay of the device's transcript steps
     ch.observe_n(&fri_out[16 * (size_t)j], 4);
     const E4 bm = bb::e_to_mont(ch.sample_ext());
-    if (memcmp(bm.c, &fri_out[16 * (size_t)j + 4], 16)) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: the device's FRI transcript diverged from the host's"}); return ZKIR_ERR_OTHER; }
+    if (memcmp(bm.c, &fri_out[16 * (size_t)j + 4], 16)) return r.fail(ZKIR_ERR_OTHER, "the device's FRI transcript diverged from the host's");
     head.insert(head.end(), &fri_out[16 * (size_t)j], &fri_out[16 * (size_t)j] + 4);
   }
   for (uint32_t i = 0; i < n_fin; i++) for (int t = 0; t < 4; t++) { ch.observe(fin_cols[t * n_fin + i]); head.push_back(fin_cols[t * n_fin + i]); }
-  mark(2);
+  r.mark(first_mark);
 
   // ---- 3. grinding: the SMALLEST nonce that passes (batches in rising order, the smallest hit of a batch) -------------------------------------------------------------------
   uint32_t pow_nonce = 0xFFFFFFFFu;
   {
     ch.flush();
-    HIP_OK(h2d(dState, ch.st, sizeof(ch.st)));
+    HIP_OK(r.h2d(dState, ch.st, sizeof(ch.st)));
     const uint32_t batch = 1u << 18;
     for (uint64_t base = 0; base < bb::P && pow_nonce == 0xFFFFFFFFu; base += batch) {
       HIP_OK(hipMemsetAsync(dBest, 0xFF, 4, s));
       hipLaunchKernelGGL(pow_grind_kernel, dim3(batch / NT), dim3(NT), 0, s, c->d_p2, dState, (uint32_t)base, pow_bits, dBest);
-      HIP_OK(d2h(&pow_nonce, dBest, 4));
-      HIP_OK(sync_d2h());
+      HIP_OK(r.d2h(&pow_nonce, dBest, 4));
+      HIP_OK(r.sync_d2h());
     }
-    if (pow_nonce == 0xFFFFFFFFu || !ch.check_pow(pow_nonce, (int)pow_bits)) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: proof-of-work search failed"}); return ZKIR_ERR_OTHER; }
+    if (pow_nonce == 0xFFFFFFFFu || !ch.check_pow(pow_nonce, (int)pow_bits)) return r.fail(ZKIR_ERR_OTHER, "proof-of-work search failed");
   }
   head.push_back(pow_nonce);
-  mark(3);
-  if (head.size() != head_words) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: header length"}); return ZKIR_ERR_OTHER; }
+  r.mark(first_mark + 1);
+  if (head.size() != head_words) return r.fail(ZKIR_ERR_OTHER, "header length");
 
   // ---- 4. queries: the matrix records by merkle_open_kernel from a device index array, copied next to the FRI leaves and paths by gather_kernel; one download --------------
   std::vector<uint32_t> queries(num_queries);
@@ -226,7 +217,7 @@ int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, co
   for (uint32_t t = 0; t < num_queries; t++) { queries[t] = ch.sample_bits((int)log_M - 1); idx[2 * t] = queries[t]; idx[2 * t + 1] = (uint64_t)queries[t] + M / 2; }
   uint64_t* dIdx; uint32_t *dRec, *dOut; GatherJob* dJobs;
   HIP_OK(ar.take(&dIdx, idx.size())); HIP_OK(ar.take(&dRec, idx.size() * rec));
-  HIP_OK(h2d(dIdx, idx.data(), idx.size() * 8));
+  HIP_OK(r.h2d(dIdx, idx.data(), idx.size() * 8));
   hipLaunchKernelGGL(merkle_open_kernel, dim3(grid_for(idx.size() * OPEN_LANES)), dim3(NT), 0, s, mat, width, M, log_M, tree, dIdx, (uint64_t)idx.size(), dRec);
   std::vector<GatherJob> jobs;
   uint32_t off = 0;
@@ -241,23 +232,72 @@ int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, co
       jobs.push_back({fri_trees[j], g, (uint32_t)li, off, 0u, 2u}); off += 4 * (uint32_t)(log_m - ks[j]);
     }
   }
-  if ((uint64_t)off != qsize * num_queries) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_lowdeg_prove: query section length"}); return ZKIR_ERR_OTHER; }
+  if ((uint64_t)off != qsize * num_queries) return r.fail(ZKIR_ERR_OTHER, "query section length");
   HIP_OK(ar.take(&dJobs, jobs.size())); HIP_OK(ar.take(&dOut, (size_t)off));
-  HIP_OK(h2d(dJobs, jobs.data(), jobs.size() * sizeof(GatherJob)));
+  HIP_OK(r.h2d(dJobs, jobs.data(), jobs.size() * sizeof(GatherJob)));
   hipLaunchKernelGGL(gather_kernel, dim3((unsigned)jobs.size()), dim3(64), 0, s, dJobs, (uint32_t)jobs.size(), dOut);
-  uint32_t* h_out = pin.take_n<uint32_t>((size_t)off);
-  if (!h_out) { zkir::set_last_error({ZKIR_ERR_DEVICE, "zkir_lowdeg_prove: no pinned host memory for the query section"}); return ZKIR_ERR_DEVICE; }
+  uint32_t* h_out = r.pin.take_n<uint32_t>((size_t)off);
+  if (!h_out) return r.fail(ZKIR_ERR_DEVICE, "no pinned host memory for the query section");
   HIP_OK(hipMemcpyAsync(h_out, dOut, (size_t)off * 4, hipMemcpyDeviceToHost, s));
-  mark(4);
+  r.mark(first_mark + 2);
   HIP_OK(hipStreamSynchronize(s));
-  if (check_launch("zkir_lowdeg_prove") != ZKIR_OK) return ZKIR_ERR_DEVICE;
+  if (check_launch(r.who) != ZKIR_OK) return ZKIR_ERR_DEVICE;
   for (uint32_t t = 0; t < num_queries; t++) h_out[(size_t)t * qsize] = queries[t];
   memcpy(proof_host, head.data(), head_words * 4);
   memcpy(proof_host + head_words, h_out, (size_t)off * 4);
-  if (stage_ms) {
-    (void)hipEventSynchronize(se.ev[4]);
-    for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&stage_ms[i], se.ev[i], se.ev[i + 1]);
+  return ZKIR_OK;
+}
+
+int lowdeg_bad(const std::string& why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_lowdeg_prove: " + why}); return ZKIR_ERR_ARGUMENT; }
+
+// stage_ms (measurements; may be null): combine | FRI commit phase | grinding | query section
+int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words,
+                      uint64_t* n_words, float* stage_ms, hipStream_t s) {
+  // every argument is checked before anything is launched
+  if (n_words) *n_words = 0;
+  if (!c || !mat || !tree || !proof_host || !n_words) return lowdeg_bad("null context, matrix, tree, proof buffer or n_words");
+  const uint32_t log_n = c->log_n, b = c->log_blowup, log_M = log_n + b;
+  if (log_n < 3) return lowdeg_bad("the context's log_n must be at least 3: below that there is no layer to commit");
+  if (width < 1 || width > LOWDEG_MAX_WIDTH) return lowdeg_bad("width must be 1 .. 512 (terms per 96-bit sum of the combination)");
+  if (num_queries < 1 || num_queries > 128) return lowdeg_bad("num_queries must be 1 .. 128");
+  if (pow_bits > 24) return lowdeg_bad("pow_bits must be 0 .. 24");
+  const uint64_t total = zkir_lowdeg_proof_words(log_n, b, width, num_queries);
+  if (total == 0) return lowdeg_bad("the context's log_n / log_blowup are outside what a proof can state (log_n 3 .. 26, log_blowup 1 .. 3, their sum at most 27)");
+  if (cap_words < total) return lowdeg_bad("cap_words is below zkir_lowdeg_proof_words(log_n, log_blowup, width, num_queries)");
+
+  std::lock_guard<std::mutex> ctx_lock(c->mu);                   // one proof at a time per context: the workspace is its arena, as in zkir_prove
+  const uint64_t M = 1ull << log_M;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const uint32_t n_blocks = (width + 7) / 8;
+  if (const int rc = arena_reserve(c, lowdeg_fri_bytes(log_M, width, ks, num_queries) + arena_al(n_blocks * 8 * sizeof(E4)))) return rc;
+  ProofRun r(c, s, "zkir_lowdeg_prove", stage_ms != nullptr);
+  if (stage_ms) HIP_OK(r.se.create());
+
+  // ---- transcript up to gamma: header, root ------------------------------------------------------------------------------------------------------------------------------
+  std::vector<uint32_t> head = {LOWDEG_MAGIC, LOWDEG_VERSION, log_n, b, width, num_queries, pow_bits, (uint32_t)ks.size()};
+  uint32_t root[4];
+  HIP_OK(r.d2h(root, tree + 4 * (2 * M - 2), 16));
+  HIP_OK(r.sync_d2h());
+  Challenger ch(c->consts);
+  ch.observe_n(head.data(), 8);
+  ch.observe_n(root, 4);
+  const E4 gamma = ch.sample_ext();
+  head.insert(head.end(), root, root + 4);
+
+  // ---- 1. the codeword --------------------------------------------------------------------------------------------------------------------------------------------------------
+  E4* dGpow; uint32_t* cw;
+  HIP_OK(r.ar.take(&dGpow, (size_t)n_blocks * 8)); HIP_OK(r.ar.take(&cw, 4 * M));
+  {
+    const std::vector<E4> gp = lowdeg_gamma_table(gamma, width);
+    HIP_OK(r.h2d(dGpow, gp.data(), gp.size() * sizeof(E4)));
   }
+  r.mark(0);
+  hipLaunchKernelGGL(lowdeg_combine_kernel, dim3(grid_for(M)), dim3(NT), 0, s, mat, n_blocks, M, dGpow, cw);
+  r.mark(1);
+
+  // ---- 2 - 4 ---------------------------------------------------------------------------------------------------------------------------------------------------------------------
+  if (const int rc = lowdeg_fri_and_queries(r, ch, head, mat, width, tree, num_queries, pow_bits, ks, cw, total, 2, proof_host)) return rc;
+  if (stage_ms) r.times(stage_ms, 4);
   *n_words = total;
   return ZKIR_OK;
 }

@@ -1092,36 +1092,17 @@ bool lowdeg_params_ok(uint32_t log_n, uint32_t b, uint32_t width, uint32_t num_q
   return log_n >= 3 && log_n <= 26 && b >= 1 && b <= 3 && log_n + b <= 27 && width >= 1 && width <= 512 && num_queries >= 1 && num_queries <= 128;
 }
 
-}  // namespace
-
-extern "C" {
-
-uint64_t zkir_lowdeg_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t num_queries) {
-  if (!lowdeg_params_ok(log_n, log_blowup, width, num_queries)) return 0;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)log_blowup);
-  uint64_t qsize = 1 + 2 * ((uint64_t)width + 4 * (uint64_t)(log_n + log_blowup));
-  int lm = (int)(log_n + log_blowup);
-  for (int k : ks) { qsize += 4 * ((uint64_t)1 << k) + 4 * (uint64_t)(lm - k); lm -= k; }
-  return 12 + 4 * (uint64_t)ks.size() + 4 * ((uint64_t)4 << log_blowup) + 1 + (uint64_t)num_queries * qsize;
-}
-
-int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root) {
-  // ---- 1: shape ----
-  if (!w || len < 12 || w[0] != 0x444C4B5Au || w[1] != 1) return 1;
-  const uint32_t log_n = w[2], b = w[3], width = w[4], num_queries = w[5], pow_bits = w[6];
-  if (!lowdeg_params_ok(log_n, b, width, num_queries) || pow_bits > 24) return 1;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+// What zkir_lowdeg_verify and zkir_eval_verify share: checks 4 .. 11 of a proof whose FRI part (layer roots | final layer | nonce | queries) starts at word `at_lroots`.
+// The caller has checked the shape and the words' range and hands over the transcript as it stands once gamma is drawn; layer0_want(pos, row) is the value (Montgomery E4)
+// the codeword has at row `pos` of the domain, computed from that row's `width` opened words — the one thing the two proofs disagree about.
+template <class Layer0>
+int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_lroots, uint32_t log_n, uint32_t b, uint32_t width, uint32_t num_queries, uint32_t pow_bits, const std::vector<int>& ks,
+                    const uint32_t* root, Challenger& ch, Layer0&& layer0_want) {
   const int n_layers = (int)ks.size();
-  if (w[7] != (uint32_t)n_layers || len != zkir_lowdeg_proof_words(log_n, b, width, num_queries)) return 1;
-  // ---- 2: the root ----
-  const uint32_t* root = w + 8;
-  if (expect_root && memcmp(root, expect_root, 16)) return 2;
-  // ---- 3: canonical words ----
-  for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
   const int log_M = (int)(log_n + b);
   const size_t M = (size_t)1 << log_M, n_fin = (size_t)4 << b;
-  const uint32_t* lroots = w + 12;
-  const size_t at_fin = 12 + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1;
+  const uint32_t* lroots = w + at_lroots;
+  const size_t at_fin = at_lroots + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1;
   auto get_m = [&](size_t at) { return bb::e_to_mont(E4{{w[at], w[at + 1], w[at + 2], w[at + 3]}}); };
   std::vector<E4> fin(n_fin);
   for (size_t i = 0; i < n_fin; i++) fin[i] = get_m(at_fin + 4 * i);
@@ -1137,11 +1118,7 @@ int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_r
       if (c.c[0] | c.c[1] | c.c[2] | c.c[3]) return 4;
     }
   }
-  // ---- the transcript ----
-  Challenger ch;
-  ch.observe_n(w, 8);
-  ch.observe_n(root, 4);
-  const E4 gamma = bb::e_to_mont(ch.sample_ext());
+  // ---- the transcript after gamma ----
   std::vector<E4> betas(n_layers);
   for (int j = 0; j < n_layers; j++) { ch.observe_n(lroots + 4 * j, 4); betas[j] = bb::e_to_mont(ch.sample_ext()); }
   ch.observe_n(w + at_fin, 4 * n_fin);
@@ -1150,9 +1127,6 @@ int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_r
   std::vector<uint32_t> qs(num_queries);
   for (auto& q : qs) q = ch.sample_bits(log_M - 1);
   // ---- 6 .. 11: queries ----
-  std::vector<E4> gp(width);
-  gp[0] = bb::e_one_m();
-  for (size_t k = 1; k < width; k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
   const size_t rec = (size_t)width + 4 * (size_t)log_M, qsize = (len - at_queries) / num_queries;
   auto check_query = [&](int t) -> int {
     size_t p = at_queries + (size_t)t * qsize;
@@ -1164,9 +1138,7 @@ int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_r
       const uint32_t* row = w + p;
       uint32_t dg[4]; hash_elems(row, width, dg);
       if (!check_path(dg, pos, row + width, log_M, root)) return 7;
-      E4 A = bb::e_zero();                                                  // canonical word x Montgomery gamma^k = canonical; lifted to Montgomery at the end
-      for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[k], row[k]));
-      comb[s2] = bb::e_to_mont(A);
+      comb[s2] = layer0_want(pos, row);
       p += rec;
     }
     E4 carried = bb::e_zero(); size_t carried_idx = q;
@@ -1197,6 +1169,114 @@ int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_r
   // (the queries are independent; checked one after the other: a proof has at most 128 of them and its verdict is this loop's)
   for (int t = 0; t < (int)num_queries; t++) { const int code = check_query(t); if (code) return code; }
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t zkir_lowdeg_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t num_queries) {
+  if (!lowdeg_params_ok(log_n, log_blowup, width, num_queries)) return 0;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)log_blowup);
+  uint64_t qsize = 1 + 2 * ((uint64_t)width + 4 * (uint64_t)(log_n + log_blowup));
+  int lm = (int)(log_n + log_blowup);
+  for (int k : ks) { qsize += 4 * ((uint64_t)1 << k) + 4 * (uint64_t)(lm - k); lm -= k; }
+  return 12 + 4 * (uint64_t)ks.size() + 4 * ((uint64_t)4 << log_blowup) + 1 + (uint64_t)num_queries * qsize;
+}
+
+int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root) {
+  // ---- 1: shape ----
+  if (!w || len < 12 || w[0] != 0x444C4B5Au || w[1] != 1) return 1;
+  const uint32_t log_n = w[2], b = w[3], width = w[4], num_queries = w[5], pow_bits = w[6];
+  if (!lowdeg_params_ok(log_n, b, width, num_queries) || pow_bits > 24) return 1;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  if (w[7] != (uint32_t)ks.size() || len != zkir_lowdeg_proof_words(log_n, b, width, num_queries)) return 1;
+  // ---- 2: the root ----
+  const uint32_t* root = w + 8;
+  if (expect_root && memcmp(root, expect_root, 16)) return 2;
+  // ---- 3: canonical words ----
+  for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
+  // ---- the transcript up to gamma ----
+  Challenger ch;
+  ch.observe_n(w, 8);
+  ch.observe_n(root, 4);
+  const E4 gamma = bb::e_to_mont(ch.sample_ext());
+  std::vector<E4> gp(width);
+  gp[0] = bb::e_one_m();
+  for (size_t k = 1; k < width; k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
+  // ---- 4 .. 11; 8: layer-0 values are sum gamma^k row ----
+  return fri_part_verify(w, len, 12, log_n, b, width, num_queries, pow_bits, ks, root, ch, [&](size_t, const uint32_t* row) {
+    E4 A = bb::e_zero();                                                    // canonical word x Montgomery gamma^k = canonical; lifted to Montgomery at the end
+    for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[k], row[k]));
+    return bb::e_to_mont(A);
+  });
+}
+
+// ================================================================================================
+// zkir_eval_verify — the verifier of an EVALUATION PROOF OF A COMMITMENT (zkir_eval_prove, eval_open.inl; spec: tests/eval_ref.py).  Host only.
+//
+// The proof says: every column k of the matrix committed under the root is close to a polynomial p_k of degree < N over the coset 31 <w_M>, M = N << b, and
+// p_k(z_i) = y[i][k] at the n_points (1 or 2) points z_i of E4 it carries.  Batched FRI over F(x) = sum_i (a_i - A_i(x)) / (z_i - x), A_i(x) = sum_k gamma^(i width + k) col_k(x),
+// a_i = sum_k gamma^(i width + k) y[i][k]: F is a polynomial of degree < N - 1 exactly when every claim holds.
+//   [0..9)  'ZKEV', version 1, log_n, b, width, n_points, num_queries, pow_bits, n_layers | [9..13) the root | 4 n_points point words | 4 n_points width evaluation words
+//   (point-major) | from there on the low-degree proof's layout: n_layers x 4 layer roots | n_fin x 4 final layer | nonce | the queries
+// Transcript: header, root, points, evaluations, gamma; per layer root, beta; the final words; check_pow(nonce); q_t = sample_bits(log_n + b - 1).
+// Codes, first failing check in this order, lowest query first: 1 malformed (length not EXACTLY the header's, magic, version, a range, n_points, n_layers), 2 not the expected
+// root, 13 not the expected points or not the expected evaluations (NULL: any), 3 a word >= p, 12 a point in the base field (coordinates 1 .. 3 all zero) or two equal points,
+// 4 the final layer is not of degree < 4, 5 grinding, 6 a query's index word, 7 a matrix record does not hash to the root, 8 layer-0 values are not F at rows q / q + M/2,
+// recomputed from the opened records, the points and the evaluations (checked BEFORE layer 0's path), 9 a FRI leaf's path, 10 carried value != v[slot], 11 final value.
+// ================================================================================================
+uint64_t zkir_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t n_points, uint32_t num_queries) {
+  const uint64_t ld = zkir_lowdeg_proof_words(log_n, log_blowup, width, num_queries);
+  if (ld == 0 || n_points < 1 || n_points > 2) return 0;
+  return ld + 1 + 4 * (uint64_t)n_points * (1 + (uint64_t)width);           // one more header word, the points, the evaluations
+}
+
+int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  // ---- 1: shape ----
+  if (!w || len < 9 || w[0] != 0x56454B5Au || w[1] != 1) return 1;
+  const uint32_t log_n = w[2], b = w[3], width = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
+  if (!lowdeg_params_ok(log_n, b, width, num_queries) || n_points < 1 || n_points > 2 || pow_bits > 24) return 1;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  if (w[8] != (uint32_t)ks.size() || len != zkir_eval_proof_words(log_n, b, width, n_points, num_queries)) return 1;
+  const uint32_t *root = w + 9, *pts = w + 13, *ys = pts + 4 * (size_t)n_points;
+  const size_t at_lroots = 13 + 4 * (size_t)n_points * (1 + (size_t)width);
+  // ---- 2, 13: what the caller expects ----
+  if (expect_root && memcmp(root, expect_root, 16)) return 2;
+  if (expect_points && memcmp(pts, expect_points, 16 * (size_t)n_points)) return 13;
+  if (expect_evals && memcmp(ys, expect_evals, 16 * (size_t)n_points * width)) return 13;
+  // ---- 3: canonical words ----
+  for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
+  // ---- 12: the points lie outside the base field (so z - x is invertible for every x of it) and differ ----
+  for (uint32_t i = 0; i < n_points; i++) if (!(pts[4 * i + 1] | pts[4 * i + 2] | pts[4 * i + 3])) return 12;
+  if (n_points == 2 && !memcmp(pts, pts + 4, 16)) return 12;
+  // ---- the transcript up to gamma ----
+  Challenger ch;
+  ch.observe_n(w, at_lroots);
+  const E4 gamma = bb::e_to_mont(ch.sample_ext());
+  auto get_m = [&](const uint32_t* at) { return bb::e_to_mont(E4{{at[0], at[1], at[2], at[3]}}); };
+  std::vector<E4> gp((size_t)n_points * width);
+  gp[0] = bb::e_one_m();
+  for (size_t k = 1; k < gp.size(); k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
+  E4 z[2], a[2];
+  for (uint32_t i = 0; i < n_points; i++) {
+    z[i] = get_m(pts + 4 * i);
+    a[i] = bb::e_zero();
+    for (size_t k = 0; k < width; k++) a[i] = bb::e_add(a[i], bb::e_mul_m(gp[(size_t)i * width + k], get_m(ys + 4 * ((size_t)i * width + k))));
+  }
+  const uint32_t wM = bb::root_of_unity((int)(log_n + b));
+  // ---- 4 .. 11; 8: layer-0 values are F at the two rows ----
+  return fri_part_verify(w, len, at_lroots, log_n, b, width, num_queries, pow_bits, ks, root, ch, [&](size_t pos, const uint32_t* row) {
+    const uint32_t x_m = bb::to_mont(bb::mul(bb::GEN, bb::pow(wM, pos)));
+    E4 F = bb::e_zero();
+    for (uint32_t i = 0; i < n_points; i++) {
+      E4 A = bb::e_zero();
+      for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[(size_t)i * width + k], row[k]));
+      E4 d = z[i]; d.c[0] = bb::sub(d.c[0], x_m);
+      F = bb::e_add(F, bb::e_mul_m(bb::e_sub(a[i], bb::e_to_mont(A)), bb::e_inv_m(d)));
+    }
+    return F;
+  });
 }
 
 }  // extern "C"

@@ -417,6 +417,15 @@ def lib() -> C.CDLL:
         L.zkir_lowdeg_verify.restype = C.c_int; L.zkir_lowdeg_verify.argtypes = [V, U64, V]
         L.zkir_lowdeg_prove_stages.restype = C.c_int; L.zkir_lowdeg_prove_stages.argtypes = [V, V, U32, V, U32, U32, V, U64, C.POINTER(U64), V, V]
         L.zkir_lowdeg_combine_launch.restype = C.c_int; L.zkir_lowdeg_combine_launch.argtypes = [V, V, U32, V, V, V, V]
+    if hasattr(L, "zkir_eval_prove"):                         # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_eval_proof_words.restype = U64; L.zkir_eval_proof_words.argtypes = [U32, U32, U32, U32, U32]
+        L.zkir_eval_prove.restype = C.c_int; L.zkir_eval_prove.argtypes = [V, V, U32, V, V, U32, U32, U32, V, U64, C.POINTER(U64), V]
+        L.zkir_eval_verify.restype = C.c_int; L.zkir_eval_verify.argtypes = [V, U64, V, V, V]
+        L.zkir_eval_prove_stages.restype = C.c_int; L.zkir_eval_prove_stages.argtypes = [V, V, U32, V, V, U32, U32, U32, V, U64, C.POINTER(U64), V, V]
+        L.zkir_eval_at_scratch_words.restype = U64; L.zkir_eval_at_scratch_words.argtypes = [U32, U32, U32]
+        L.zkir_eval_at_launch.restype = C.c_int; L.zkir_eval_at_launch.argtypes = [V, V, U32, V, U32, V, V, V]
+        L.zkir_eval_quotient_scratch_words.restype = U64; L.zkir_eval_quotient_scratch_words.argtypes = [U32, U32, U32]
+        L.zkir_eval_quotient_launch.restype = C.c_int; L.zkir_eval_quotient_launch.argtypes = [V, V, U32, V, V, U32, V, V, V, V]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -670,6 +679,33 @@ def lowdeg_verify(proof, root=None) -> int:
     r = None if root is None else np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
     assert r is None or len(r) == 4
     return int(lib().zkir_lowdeg_verify(w.ctypes.data if len(w) else None, len(w), r.ctypes.data if r is not None else None))
+
+
+def eval_proof_words(log_n: int, log_blowup: int, width: int, n_points: int, num_queries: int) -> int:
+    """Words of an evaluation proof of a commitment (zkir_eval_proof_words); 0 for parameters no proof can state."""
+    return int(lib().zkir_eval_proof_words(int(log_n), int(log_blowup), int(width), int(n_points), int(num_queries)))
+
+
+def eval_verify(proof, root=None, points=None, evals=None) -> int:
+    """zkir_eval_verify, on the host — no GPU: 0 = the proof convinces a holder of its root that every committed column is close to a polynomial of degree < 2^log_n that takes
+    the proof's evaluations at the proof's points; `root` (four words), `points` ([n_points][4]) and `evals` ([n_points][width][4]), when given, must be the proof's.  Else the
+    code of the first failing check (include/zkir_amd.h lists them).  The library reads as many expected words as the proof's header states: where the header is one a proof
+    can have, `points` / `evals` of another size raise ValueError."""
+    w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
+    r = None if root is None else np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
+    assert r is None or len(r) == 4
+    p = None if points is None else np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
+    e = None if evals is None else np.ascontiguousarray(evals, dtype=np.uint32).reshape(-1)
+    sane = len(w) >= 9 and 1 <= int(w[4]) <= 512 and 1 <= int(w[5]) <= 2
+    if sane:
+        if p is not None and len(p) != 4 * int(w[5]):
+            raise ValueError(f"eval_verify: points must hold {4 * int(w[5])} words, the proof's n_points x 4")
+        if e is not None and len(e) != 4 * int(w[5]) * int(w[4]):
+            raise ValueError(f"eval_verify: evals must hold {4 * int(w[5]) * int(w[4])} words, the proof's n_points x width x 4")
+    else:
+        p = e = None                                             # the proof is malformed (1) whatever is expected of it
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    return int(lib().zkir_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
 
 
 def verify_last_stages() -> dict:

@@ -255,6 +255,84 @@ def lowdeg_combine(ctx: StarkContext, lde_mat: torch.Tensor, gamma, width: Optio
     return cw
 
 
+eval_proof_words = rt.eval_proof_words
+eval_verify = rt.eval_verify
+
+
+def _eval_args(name: str, ctx: StarkContext, lde_mat: torch.Tensor, width: Optional[int], points):
+    """(width, points uint32[n_points][4]) of an evaluation call; ValueError for a matrix that is not of the context's size or points that are not rows of four words"""
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    if lde_mat.dim() != 3 or lde_mat.shape[1] != m or lde_mat.shape[2] != 8 or lde_mat.dtype != torch.int32 or not lde_mat.is_contiguous():
+        raise ValueError(f"{name}: the matrix must be contiguous int32[blocks][{m}][8], the context's extension size")
+    width = lde_mat.shape[0] * 8 if width is None else int(width)
+    if width > lde_mat.shape[0] * 8:
+        raise ValueError(f"{name}: width exceeds the matrix's columns")
+    pts = np.ascontiguousarray(points, dtype=np.uint32)
+    if pts.ndim != 2 or pts.shape[1] != 4:
+        raise ValueError(f"{name}: points must be [n_points][4] canonical words")
+    return width, pts
+
+
+def eval_prove(ctx: StarkContext, lde_mat: torch.Tensor, tree: torch.Tensor, width: Optional[int], points, num_queries: int = 50, pow_bits: int = 12, stream=None,
+               want_stage_ms: bool = False):
+    """zkir_eval_prove: the evaluation proof (np.uint32 words) of the commitment `tree` (merkle_commit's) to the B8 matrix `lde_mat` (lde's output on `ctx`, `width` real
+    columns, default all) at `points` ([1 or 2][4] canonical words, E4 elements outside the base field, CHOSEN AFTER THE ROOT): every column is close to a polynomial of
+    degree < 2^ctx.log_n with the proof's evaluations at the points (eval_layout finds them).  Works at every rate a context serves.  A matrix or tree that is not of the
+    context's size raises ValueError; the library refuses bad parameters and points with ERR_ARGUMENT before any launch.
+    want_stage_ms: also the device ms of (weights, evaluations, quotient, FRI commit phase, grinding, query section)."""
+    width, pts = _eval_args("eval_prove", ctx, lde_mat, width, points)
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    if tree.dtype != torch.int32 or not tree.is_contiguous() or tree.numel() != 4 * (2 * m - 1):
+        raise ValueError(f"eval_prove: the tree must be contiguous int32[{4 * (2 * m - 1)}], merkle_commit's over {m} leaves")
+    cap = eval_proof_words(ctx.log_n, ctx.log_blowup, width, len(pts), num_queries)
+    out = np.zeros(max(cap, 1), np.uint32)
+    n_words = C.c_uint64()
+    args = (ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), pts.ctypes.data, len(pts), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words))
+    if want_stage_ms:
+        ms = (C.c_float * 6)()
+        pl._check(rt.lib().zkir_eval_prove_stages(*args, ms, _sp(stream)))
+        return out[:n_words.value], [float(x) for x in ms]
+    pl._check(rt.lib().zkir_eval_prove(*args, _sp(stream)))
+    return out[:n_words.value]
+
+
+def eval_at(ctx: StarkContext, lde_mat: torch.Tensor, points, width: Optional[int] = None, stream=None) -> torch.Tensor:
+    """(tests, measurements) zkir_eval_at_launch: the evaluations int32[n_points][width][4] of eval_prove's first stages alone, for GIVEN points."""
+    width, pts = _eval_args("eval_at", ctx, lde_mat, width, points)
+    scratch = torch.empty(max(1, int(rt.lib().zkir_eval_at_scratch_words(ctx.log_n, width, len(pts)))), dtype=torch.int32, device=lde_mat.device)
+    out = torch.empty((len(pts), width, 4), dtype=torch.int32, device=lde_mat.device)
+    pl._check(rt.lib().zkir_eval_at_launch(ctx.handle, lde_mat.data_ptr(), width, pts.ctypes.data, len(pts), scratch.data_ptr(), out.data_ptr(), _sp(stream)))
+    return out
+
+
+def eval_quotient(ctx: StarkContext, lde_mat: torch.Tensor, gamma, points, evals, width: Optional[int] = None, stream=None) -> torch.Tensor:
+    """(tests, measurements) zkir_eval_quotient_launch: the codeword int32[4][M] of eval_prove's quotient stage for GIVEN canonical gamma (four words), points and
+    evaluations ([n_points][width][4]): row t = coordinate t of F."""
+    width, pts = _eval_args("eval_quotient", ctx, lde_mat, width, points)
+    g = np.ascontiguousarray(gamma, dtype=np.uint32).reshape(4)
+    y = np.ascontiguousarray(evals, dtype=np.uint32).reshape(-1)
+    if len(y) != 4 * len(pts) * width:
+        raise ValueError("eval_quotient: evals must be [n_points][width][4] words")
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    scratch = torch.empty(max(1, int(rt.lib().zkir_eval_quotient_scratch_words(ctx.log_n + ctx.log_blowup, width, len(pts)))), dtype=torch.int32, device=lde_mat.device)
+    cw = torch.empty((4, m), dtype=torch.int32, device=lde_mat.device)
+    pl._check(rt.lib().zkir_eval_quotient_launch(ctx.handle, lde_mat.data_ptr(), width, g.ctypes.data, pts.ctypes.data, len(pts), y.ctypes.data, scratch.data_ptr(), cw.data_ptr(), _sp(stream)))
+    return cw
+
+
+def eval_layout(proof) -> dict:
+    """Word offsets of a well-formed evaluation proof: the header's fields, root, points, evals ([n_points][width][4] from there), layer_roots, final, nonce, queries, and the
+    words of one query (qsize)."""
+    log_n, b, width, n_points, nq, _, n_layers = (int(x) for x in proof[2:9])
+    at = {"log_n": log_n, "log_blowup": b, "width": width, "n_points": n_points, "num_queries": nq, "n_layers": n_layers, "root": 9, "points": 13, "evals": 13 + 4 * n_points}
+    at["layer_roots"] = at["evals"] + 4 * n_points * width
+    at["final"] = at["layer_roots"] + 4 * n_layers
+    at["nonce"] = at["final"] + 4 * (4 << b)
+    at["queries"] = at["nonce"] + 1
+    at["qsize"] = (len(proof) - at["queries"]) // nq if nq else 0
+    return at
+
+
 def commit_trace(ctx: StarkContext, trace: pl.DeviceTrace, stream=None, deferred: bool = False):
     """main trace -> LDE (at the context's blow-up) -> Merkle.  Returns (root np.uint32[4], lde matrix tensor (B8), tree tensor)."""
     m = main_trace(trace, stream, deferred)
