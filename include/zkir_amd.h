@@ -432,6 +432,38 @@ int zkir_eval_prove(zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width
                     uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words, void* hip_stream);
 int zkir_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals);
 
+/* ---- a batched evaluation proof: several commitments of one height opened in ONE proof ----
+ * Statement: n_mats (1 .. 4) committed B8 matrices of the SAME context (the same log_n and log_blowup; lde_mats[m], trees[m]: as for zkir_lowdeg_prove, widths[m] columns
+ * each) have every column close to a polynomial of degree < N, and matrix m's columns take the proof's values at those of the n_points (1 or 2) shared points z_i that
+ * masks[m] selects (bit i: opened at z_i).  The points are checked as zkir_eval_prove checks them.  1 <= widths[m] <= 512 and the widths sum to at most 512 (one product per
+ * column per point in a 96-bit sum); 1 <= masks[m] < 2^n_points; every point is selected by some matrix.
+ * The evaluations are zkir_eval_prove's barycentric sums, taken for the (point, matrix) pairs the masks select and for no others.  One gamma is drawn after the header, the
+ * shape, all the roots, the points and all the evaluations; its exponent e runs consecutively: for i over the points, for m over the matrices with bit i of masks[m] set,
+ * in order, for k < widths[m].  Then
+ *     A_i(x) = sum gamma^e col_{m,k}(x),   a_i = sum gamma^e y[i][m][k]   (over the selected (m, k) of point i),   F(x_j) = sum_i (a_i - A_i(x_j)) / (z_i - x_j)
+ * over all M rows, and batched FRI over F as in the low-degree proof: one inverse table, one commit phase, one grind and one set of query rows for all the matrices.
+ * With n_mats = 1 and a full mask F is zkir_eval_prove's codeword; splitting a matrix at a multiple of 8 columns into two matrices with full masks leaves F unchanged.
+ * Proof words (all canonical): [0..9) 'ZKBE' = 0x45424B5A, version 1, log_n, log_blowup, n_mats, n_points, num_queries, pow_bits, n_layers | (widths[m], masks[m]) per matrix
+ * | the n_mats roots | the points (4 n_points words) | the evaluations in the exponent order, 4 words each | from there on the low-degree proof's layout: layer roots, final
+ * layer, nonce, queries.  A query: q, then for each matrix in order record_m(q), record_m(q + M/2) (zkir_merkle_open_launch's records, widths[m] + 4 (log_n + log_blowup)
+ * words each), then per layer the values and the path.
+ * Transcript: every word up to and including the evaluations, gamma; per layer root, beta; the final words; check_pow(nonce); q_t = sample_bits(log_n + log_blowup - 1).
+ * zkir_batch_eval_proof_words: the proof's length; 0 for a shape no proof can state.
+ * zkir_batch_eval_prove: lde_mats, trees, widths, masks HOST arrays of n_mats entries (the matrices and trees they name are DEVICE pointers); points, proof_host HOST (nothing
+ * past *n_words is written).  One proof at a time per context (its workspace arena: the low-degree proof's plus 16 n_points (M + N) bytes of inverses and weights and the
+ * matrices' partial sums); synchronises the stream.  ZKIR_ERR_ARGUMENT with *n_words = 0, nothing written and a message naming the cause, before anything is launched, for:
+ * a null pointer, n_mats outside 1 .. 4, a width outside 1 .. 512, widths summing above 512, a mask of 0 or with a bit at or above n_points, a point no matrix is opened at,
+ * and zkir_eval_prove's refusals of points, num_queries, pow_bits, the context's log_n and cap_words.
+ * zkir_batch_eval_verify: host only.  zkir_eval_verify's codes in its order of checks: 1 also covers n_mats, a width, the width total, a mask and an unused point; 2 compares
+ * all n_mats roots with expect_roots (4 n_mats words; NULL: any); 13 expect_points (4 n_points words) and expect_evals (the proof's evaluation words, in the exponent order);
+ * 7 a record of any matrix, lowest matrix first within a query; 8 recomputes F from all the matrices' records.  The expected arrays are read at the sizes the PROOF's header
+ * states, and only once check 1 has passed. */
+uint64_t zkir_batch_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t n_mats, const uint32_t* widths, const uint32_t* masks, uint32_t n_points, uint32_t num_queries);
+int zkir_batch_eval_prove(zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* const* lde_mats, const uint32_t* widths, const uint32_t* const* trees, const uint32_t* masks,
+                          const uint32_t* points, uint32_t n_points, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words,
+                          void* hip_stream);
+int zkir_batch_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals);
+
 /* Public inputs of a proof: absorbed by the Fiat-Shamir transcript before the first commitment and carried in the proof header. */
 typedef struct zkir_public_inputs {
   uint64_t n_real;             /* executed rows = ExecutionResult.cycles */

@@ -47,6 +47,17 @@ uint64_t zkir_eval_quotient_scratch_words(uint32_t log_m, uint32_t width, uint32
 int zkir_eval_quotient_launch(const zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t gamma[4], const uint32_t* points, uint32_t n_points,
                               const uint32_t* evals, uint32_t* scratch, uint32_t* cw, void* hip_stream);
 
+/* MEASUREMENT: zkir_batch_eval_prove with the device time (ms, HIP events) of its six stages: weights | evaluations | quotient | FRI commit phase | grinding | query section. */
+int zkir_batch_eval_prove_stages(zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* const* lde_mats, const uint32_t* widths, const uint32_t* const* trees, const uint32_t* masks,
+                                 const uint32_t* points, uint32_t n_points, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words,
+                                 float stage_ms[6], void* hip_stream);
+/* TEST / MEASUREMENT: the codeword of zkir_batch_eval_prove alone (inverse table and batch_quotient_kernel) for GIVEN gamma, points and evaluations (HOST, canonical; evals in
+ * the proof's exponent order, 4 words each): cw[t M + j] = coordinate t of F at row j.  scratch: DEVICE buffer of zkir_batch_eval_quotient_scratch_words words; the gamma
+ * table is uploaded with a synchronous copy. */
+uint64_t zkir_batch_eval_quotient_scratch_words(uint32_t log_m, uint32_t n_mats, const uint32_t* widths, uint32_t n_points);
+int zkir_batch_eval_quotient_launch(const zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* const* lde_mats, const uint32_t* widths, const uint32_t* masks, const uint32_t gamma[4],
+                                    const uint32_t* points, uint32_t n_points, const uint32_t* evals, uint32_t* scratch, uint32_t* cw, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,13 @@ extern "C" {
     pub fn zkir_eval_prove(ctx: *mut ZkirStarkCtx, lde_mat: *const u32, width: u32, tree: *const u32, points: *const u32, n_points: u32, num_queries: u32, pow_bits: u32,
                            proof_host: *mut u32, cap_words: u64, n_words: *mut u64, stream: *mut c_void) -> c_int;
     pub fn zkir_eval_verify(proof: *const u32, n_words: u64, expect_root: *const u32, expect_points: *const u32, expect_evals: *const u32) -> c_int;
+    // a batched evaluation proof: 1 .. 4 commitments of ONE context opened in one proof at a shared list of 1 or 2 points; masks[m] bit i = matrix m is opened at point i.
+    // lde_mats / trees / widths / masks are host arrays of n_mats entries (the matrices and trees they name: device pointers); the verifier is host only, zkir_eval_verify's codes
+    // (expect_* null = any; read at the sizes the proof's header states: 4 n_mats root words, 4 n_points point words, the proof's evaluation words)
+    pub fn zkir_batch_eval_proof_words(log_n: u32, log_blowup: u32, n_mats: u32, widths: *const u32, masks: *const u32, n_points: u32, num_queries: u32) -> u64;
+    pub fn zkir_batch_eval_prove(ctx: *mut ZkirStarkCtx, n_mats: u32, lde_mats: *const *const u32, widths: *const u32, trees: *const *const u32, masks: *const u32, points: *const u32,
+                                 n_points: u32, num_queries: u32, pow_bits: u32, proof_host: *mut u32, cap_words: u64, n_words: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn zkir_batch_eval_verify(proof: *const u32, n_words: u64, expect_roots: *const u32, expect_points: *const u32, expect_evals: *const u32) -> c_int;
     // (mode 4) the tapes' share of the lookup table side and the hash tape's record checks as calls of their own (host arrays in, host arrays out)
     pub fn zkir_tape_table_side_launch(hash_words: *const u32, n_hash_words: u64, new_bytes: *const u64, wide_words: *const u32, n_wide_words: u64, alpha: *const u32, lambda: *const u32,
                                        sum: *mut u32, hh: *mut u32, ww: *mut u32, stream: *mut c_void) -> c_int;

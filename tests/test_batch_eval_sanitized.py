@@ -1,0 +1,72 @@
+"""zkir_batch_eval_verify under AddressSanitizer + UndefinedBehaviorSanitizer on honest and malformed batched evaluation proofs.  The host sources
+(zkir_amd.build.HOST_SOURCES) and a stand-alone driver (tests/cpp/batch_eval_san_driver.cpp, its own main) are compiled with -fsanitize=address,undefined exactly as
+tests/test_eval_sanitized.py builds its driver, and the driver is run on test_batch_eval_verify's reference proofs and mutants, each copied into a heap block of exactly its
+length: no sanitizer report, and every verdict the one tests/batch_eval_ref.py gives.  CPU only; nothing is loaded into Python and nothing is preloaded."""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import batch_eval_ref as be
+import test_batch_eval_verify as tv
+from test_host_sanitized import SAN, SAN_FLAGS, Corpus, _check, _linker
+from zkir_amd import build as zbuild
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "batch_eval_san_driver.cpp")
+BIN = os.path.join(SAN, "batch_eval_san_driver")
+BATCH = 0
+
+
+@pytest.fixture(scope="module")
+def driver():
+    os.makedirs(SAN, exist_ok=True)
+    probe = os.path.join(SAN, "probe.cpp")
+    with open(probe, "w") as f:
+        f.write("#include <vector>\nint main() { std::vector<int> v(3, 1); return v[0] + v[2] - 2; }\n")
+    p = subprocess.run([zbuild.HIPCC, "-x", "c++", *SAN_FLAGS, probe, "-o", os.path.join(SAN, "probe")], capture_output=True, text=True)
+    if p.returncode != 0 or subprocess.run([os.path.join(SAN, "probe")], capture_output=True).returncode != 0:
+        pytest.skip("the compiler cannot link or run a program with the AddressSanitizer / UndefinedBehaviorSanitizer runtime: " + p.stderr[-300:])
+    deps = [os.path.normpath(os.path.join(zbuild.CSRC, h)) for h in zbuild.HEADERS]
+    objs, jobs = [], []
+    for src in [os.path.join(zbuild.CSRC, name) for name in zbuild.HOST_SOURCES] + [DRIVER_SRC]:
+        obj = os.path.join(SAN, os.path.basename(src) + ".o")
+        objs.append(obj)
+        if zbuild._newer(src, obj, deps):
+            jobs.append(subprocess.Popen([zbuild.HIPCC, "-x", "c++", "-std=c++17", *SAN_FLAGS, "-Wall", "-Wno-unused-function", "-c", src, "-o", obj]))
+    for j in jobs:
+        assert j.wait() == 0, "a sanitizer build of a host source failed"
+    if zbuild._newer(objs[0], BIN, objs[1:]):
+        subprocess.check_call([_linker(), "-fsanitize=address,undefined", *objs, "-o", BIN])
+    return BIN
+
+
+def test_batch_eval_verify(driver):
+    """zkir_batch_eval_verify with every combination of expectations on three reference proofs (one, two and three matrices) and their mutants"""
+    c = Corpus("batch_eval")
+    for shape in tv.SHAPES:
+        pr = tv.proof(shape)
+        rng = np.random.default_rng(199 + shape[0])
+        roots, pts, ys = tv.expectations(pr, pr)
+        assert be.verify_ref(pr, roots, pts, ys) == 0
+        base = c.base(pr)
+
+        def add(label, t, exp, mutant):
+            flags = sum(1 << k for k, e in enumerate(exp) if e is not None)
+            want = be.verify_ref(t, *exp)
+            c.add(label, BATCH, [flags], [(base, t)] + [np.ascontiguousarray(e, dtype=np.uint32) for e in exp if e is not None], f"rc {want}", mutant=mutant, accepted=want == 0)
+        for exp in ((None, None, None), (roots, None, None), (roots, pts, ys), (None, pts, None), (None, None, ys)):
+            add("honest", pr, exp, False)
+        for k, wrong in enumerate((roots, pts, ys)):
+            w = wrong.copy(); w[-1] ^= 1
+            add("honest, another expectation", pr, tuple(w if i == k else e for i, e in enumerate((roots, pts, ys))), True)
+        for i, (label, t) in enumerate(tv.batch_mutants(pr, rng)):
+            r2, p2, y2 = tv.expectations(t, pr)
+            add(f"log_n {shape[0]} {label}", t, [(None, None, None), (r2, None, None), (r2, p2, y2), (None, p2, y2)][i % 4], True)
+    assert len(c.cases) >= 900
+    codes = _check(driver, c, min_codes=5)
+    assert {"rc 1", "rc 2", "rc 7", "rc 8", "rc 12", "rc 13"} <= set(codes), codes
+    print(f"batch_eval: {len(c.cases)} cases, {codes}")

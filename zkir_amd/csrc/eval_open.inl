@@ -258,7 +258,7 @@ int eval_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, cons
   const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
   const uint32_t n_blocks = (width + 7) / 8, n_chunks = eval_chunks(N);
   const size_t n_gpow = (size_t)n_points * n_blocks * 8, n_part = n_gpow * n_chunks, n_y = (size_t)n_points * width;
-  if (const int rc = arena_reserve(c, lowdeg_fri_bytes(log_M, width, ks, num_queries) + arena_al(16 * n_gpow) + arena_al(16 * n_part) + arena_al(16 * n_y) +
+  if (const int rc = arena_reserve(c, lowdeg_fri_bytes(log_M, width + 4 * (uint64_t)log_M, 1, ks, num_queries) + arena_al(16 * n_gpow) + arena_al(16 * n_part) + arena_al(16 * n_y) +
                                           arena_al(16 * n_points * N) + arena_al(16 * n_points * M))) return rc;
   ProofRun r(c, s, "zkir_eval_prove", stage_ms != nullptr);
   if (stage_ms) HIP_OK(r.se.create());
@@ -292,7 +292,8 @@ int eval_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, cons
   r.mark(3);
 
   // ---- 2 - 4: the low-degree proof's, over this codeword --------------------------------------------------------------------------------------------------------------------------
-  if (const int rc = lowdeg_fri_and_queries(r, ch, head, mat, width, tree, num_queries, pow_bits, ks, cw, total, 4, proof_host)) return rc;
+  const OpenMat open{mat, width, tree};
+  if (const int rc = lowdeg_fri_and_queries(r, ch, head, &open, 1, num_queries, pow_bits, ks, cw, total, 4, proof_host)) return rc;
   if (stage_ms) r.times(stage_ms, 6);
   *n_words = total;
   return ZKIR_OK;

@@ -96,25 +96,36 @@ struct ProofRun {
 
 inline size_t arena_al(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-// words of one query: q, two matrix records, per layer its values and path
-uint64_t lowdeg_query_words(uint32_t log_M, uint32_t width, const std::vector<int>& ks) {
-  uint64_t q = 1 + 2 * ((uint64_t)width + 4 * log_M);
+// A matrix a proof's queries open: the B8 matrix, its real columns, its tree (DEVICE pointers).  A proof opens one (zkir_lowdeg_prove, zkir_eval_prove) or several of the
+// same height (zkir_batch_eval_prove); a query carries record_m(q), record_m(q + M/2) matrix by matrix.
+struct OpenMat { const uint32_t* mat; uint32_t width; const uint32_t* tree; };
+constexpr uint32_t OPEN_MAX_MATS = 4;
+// words of the records of ONE row across the matrices: sum of width_m + 4 log_M
+uint64_t open_rec_words(uint32_t log_M, const OpenMat* mats, uint32_t n_mats) {
+  uint64_t rec = 0;
+  for (uint32_t m = 0; m < n_mats; m++) rec += (uint64_t)mats[m].width + 4 * (uint64_t)log_M;
+  return rec;
+}
+
+// words of one query: q, two records per matrix (rec_words: open_rec_words), per layer its values and path
+uint64_t lowdeg_query_words(uint32_t log_M, uint64_t rec_words, const std::vector<int>& ks) {
+  uint64_t q = 1 + 2 * rec_words;
   int lm = (int)log_M;
   for (int k : ks) { q += 4 * ((uint64_t)1 << k) + 4 * (uint64_t)(lm - k); lm -= k; }
   return q;
 }
 
 // workspace of everything from the codeword on: the codeword (16 M bytes), the layers and their trees (at most 48 M bytes together at the schedules of log_n >= 5), the
-// query section and its inputs
-size_t lowdeg_fri_bytes(uint32_t log_M, uint32_t width, const std::vector<int>& ks, uint32_t num_queries) {
-  const uint64_t M = 1ull << log_M, rec = width + 4 * (uint64_t)log_M;
+// query section and its inputs (one record buffer per opened matrix)
+size_t lowdeg_fri_bytes(uint32_t log_M, uint64_t rec_words, uint32_t n_mats, const std::vector<int>& ks, uint32_t num_queries) {
+  const uint64_t M = 1ull << log_M;
   size_t want = arena_al(16 * M) + 8 * 256 + arena_al(16 * (ks.size() + 1) * 4);
   { int lm = (int)log_M; for (int k : ks) { const uint64_t g = (1ull << lm) >> k; want += arena_al(16 * (2 * g - 1)) + arena_al(16 * g); lm -= k; } }
   size_t n_jobs = 0;
   for (int k : ks) n_jobs += ((size_t)1 << k) + 1;
-  n_jobs = (n_jobs + 1) * num_queries;
-  return want + arena_al(2 * (size_t)num_queries * 8) + arena_al(2 * (size_t)num_queries * rec * 4) + arena_al(n_jobs * sizeof(GatherJob)) +
-         arena_al((size_t)num_queries * lowdeg_query_words(log_M, width, ks) * 4);
+  n_jobs = (n_jobs + n_mats) * num_queries;
+  return want + arena_al(2 * (size_t)num_queries * 8) + arena_al(2 * (size_t)num_queries * rec_words * 4) + 256 * (size_t)n_mats + arena_al(n_jobs * sizeof(GatherJob)) +
+         arena_al((size_t)num_queries * lowdeg_query_words(log_M, rec_words, ks) * 4);
 }
 
 // the context's arena holds at least `want` bytes, and is empty
@@ -129,10 +140,11 @@ int arena_reserve(zkir_stark_ctx* c, size_t want) {
   return ZKIR_OK;
 }
 
-// Sections 2 - 4 of a proof over a codeword of M = 2^log_M values (cw[t M + j], canonical) under the matrix `mat` / `tree`: the FRI commit phase, grinding, the queries.
+// Sections 2 - 4 of a proof over a codeword of M = 2^log_M values (cw[t M + j], canonical) under the n_mats (1 .. OPEN_MAX_MATS) matrices `mats`: the FRI commit phase,
+// grinding, the queries (one merkle_open_kernel launch per matrix from the one index array; a query's gather jobs: the records matrix by matrix, then the layers).
 // `ch` is the transcript as it stands once the codeword's challenge is drawn, `head` the proof words so far (the layer roots, the final layer and the nonce are appended),
 // `total` the proof's length.  Stage marks first_mark .. first_mark + 2 are recorded after the three sections.  Writes the whole proof to proof_host.
-int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& head, const uint32_t* mat, uint32_t width, const uint32_t* tree, uint32_t num_queries, uint32_t pow_bits,
+int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& head, const OpenMat* mats, uint32_t n_mats, uint32_t num_queries, uint32_t pow_bits,
                            const std::vector<int>& ks, uint32_t* codeword, uint64_t total, int first_mark, uint32_t* proof_host) {
   zkir_stark_ctx* c = r.c;
   hipStream_t s = r.s;
@@ -140,8 +152,9 @@ int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& h
   const uint32_t log_M = c->log_n + c->log_blowup, b = c->log_blowup;
   const uint64_t M = 1ull << log_M;
   const int n_layers = (int)ks.size();
-  const uint32_t n_fin = 4u << b, rec = width + 4 * log_M;
-  const uint64_t qsize = lowdeg_query_words(log_M, width, ks), head_words = total - qsize * num_queries;
+  const uint32_t n_fin = 4u << b;
+  if (n_mats < 1 || n_mats > OPEN_MAX_MATS) return r.fail(ZKIR_ERR_OTHER, "number of opened matrices");
+  const uint64_t qsize = lowdeg_query_words(log_M, open_rec_words(log_M, mats, n_mats), ks), head_words = total - qsize * num_queries;
   uint32_t *dState, *dBest, *dChSt, *dFri;
   std::vector<uint32_t*> fri_trees(n_layers), fri_layers(n_layers + 1);
   HIP_OK(ar.take(&dState, 16)); HIP_OK(ar.take(&dBest, 4)); HIP_OK(ar.take(&dChSt, 16)); HIP_OK(ar.take(&dFri, 16 * (size_t)(n_layers + 1)));
@@ -215,16 +228,22 @@ int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& h
   std::vector<uint32_t> queries(num_queries);
   std::vector<uint64_t> idx(2 * (size_t)num_queries);
   for (uint32_t t = 0; t < num_queries; t++) { queries[t] = ch.sample_bits((int)log_M - 1); idx[2 * t] = queries[t]; idx[2 * t + 1] = (uint64_t)queries[t] + M / 2; }
-  uint64_t* dIdx; uint32_t *dRec, *dOut; GatherJob* dJobs;
-  HIP_OK(ar.take(&dIdx, idx.size())); HIP_OK(ar.take(&dRec, idx.size() * rec));
+  uint64_t* dIdx; uint32_t *dRec[OPEN_MAX_MATS], *dOut; GatherJob* dJobs;
+  HIP_OK(ar.take(&dIdx, idx.size()));
   HIP_OK(r.h2d(dIdx, idx.data(), idx.size() * 8));
-  hipLaunchKernelGGL(merkle_open_kernel, dim3(grid_for(idx.size() * OPEN_LANES)), dim3(NT), 0, s, mat, width, M, log_M, tree, dIdx, (uint64_t)idx.size(), dRec);
+  for (uint32_t m = 0; m < n_mats; m++) {
+    HIP_OK(ar.take(&dRec[m], idx.size() * (mats[m].width + 4 * (size_t)log_M)));
+    hipLaunchKernelGGL(merkle_open_kernel, dim3(grid_for(idx.size() * OPEN_LANES)), dim3(NT), 0, s, mats[m].mat, mats[m].width, M, log_M, mats[m].tree, dIdx, (uint64_t)idx.size(), dRec[m]);
+  }
   std::vector<GatherJob> jobs;
   uint32_t off = 0;
   for (uint32_t t = 0; t < num_queries; t++) {
     const uint32_t q = queries[t];
     off += 1;                                                                // the index word: written by the host below
-    jobs.push_back({dRec + 2 * (size_t)t * rec, 1, 2 * rec, off, 0u, 0u}); off += 2 * rec;      // record(q), record(q + M/2)
+    for (uint32_t m = 0; m < n_mats; m++) {                                  // record_m(q), record_m(q + M/2)
+      const uint32_t rec = mats[m].width + 4 * log_M;
+      jobs.push_back({dRec[m] + 2 * (size_t)t * rec, 1, 2 * rec, off, 0u, 0u}); off += 2 * rec;
+    }
     int log_m = (int)log_M;
     for (int j = 0; j < n_layers; log_m -= ks[j], j++) {
       const uint64_t m = 1ull << log_m, g = m >> ks[j], li = q & (g - 1);
@@ -269,7 +288,7 @@ int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, co
   const uint64_t M = 1ull << log_M;
   const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
   const uint32_t n_blocks = (width + 7) / 8;
-  if (const int rc = arena_reserve(c, lowdeg_fri_bytes(log_M, width, ks, num_queries) + arena_al(n_blocks * 8 * sizeof(E4)))) return rc;
+  if (const int rc = arena_reserve(c, lowdeg_fri_bytes(log_M, width + 4 * (uint64_t)log_M, 1, ks, num_queries) + arena_al(n_blocks * 8 * sizeof(E4)))) return rc;
   ProofRun r(c, s, "zkir_lowdeg_prove", stage_ms != nullptr);
   if (stage_ms) HIP_OK(r.se.create());
 
@@ -296,7 +315,8 @@ int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, co
   r.mark(1);
 
   // ---- 2 - 4 ---------------------------------------------------------------------------------------------------------------------------------------------------------------------
-  if (const int rc = lowdeg_fri_and_queries(r, ch, head, mat, width, tree, num_queries, pow_bits, ks, cw, total, 2, proof_host)) return rc;
+  const OpenMat open{mat, width, tree};
+  if (const int rc = lowdeg_fri_and_queries(r, ch, head, &open, 1, num_queries, pow_bits, ks, cw, total, 2, proof_host)) return rc;
   if (stage_ms) r.times(stage_ms, 4);
   *n_words = total;
   return ZKIR_OK;

@@ -1092,12 +1092,14 @@ bool lowdeg_params_ok(uint32_t log_n, uint32_t b, uint32_t width, uint32_t num_q
   return log_n >= 3 && log_n <= 26 && b >= 1 && b <= 3 && log_n + b <= 27 && width >= 1 && width <= 512 && num_queries >= 1 && num_queries <= 128;
 }
 
-// What zkir_lowdeg_verify and zkir_eval_verify share: checks 4 .. 11 of a proof whose FRI part (layer roots | final layer | nonce | queries) starts at word `at_lroots`.
-// The caller has checked the shape and the words' range and hands over the transcript as it stands once gamma is drawn; layer0_want(pos, row) is the value (Montgomery E4)
-// the codeword has at row `pos` of the domain, computed from that row's `width` opened words — the one thing the two proofs disagree about.
+// What zkir_lowdeg_verify, zkir_eval_verify and zkir_batch_eval_verify share: checks 4 .. 11 of a proof whose FRI part (layer roots | final layer | nonce | queries) starts at
+// word `at_lroots`.  A query opens n_mats (1 .. FRI_PART_MAX_MATS) matrices of widths[m] columns under roots[4 m ..]: record_m(q), record_m(q + M/2) matrix by matrix.
+// The caller has checked the shape and the words' range and hands over the transcript as it stands once gamma is drawn; layer0_want(pos, rows) is the value (Montgomery E4)
+// the codeword has at row `pos` of the domain, computed from that row's opened words (rows[m]: matrix m's widths[m] words) — the one thing the proofs disagree about.
+constexpr uint32_t FRI_PART_MAX_MATS = 4;
 template <class Layer0>
-int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_lroots, uint32_t log_n, uint32_t b, uint32_t width, uint32_t num_queries, uint32_t pow_bits, const std::vector<int>& ks,
-                    const uint32_t* root, Challenger& ch, Layer0&& layer0_want) {
+int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_lroots, uint32_t log_n, uint32_t b, uint32_t n_mats, const uint32_t* widths, uint32_t num_queries, uint32_t pow_bits,
+                    const std::vector<int>& ks, const uint32_t* roots, Challenger& ch, Layer0&& layer0_want) {
   const int n_layers = (int)ks.size();
   const int log_M = (int)(log_n + b);
   const size_t M = (size_t)1 << log_M, n_fin = (size_t)4 << b;
@@ -1127,20 +1129,23 @@ int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_lroots, uint32_t 
   std::vector<uint32_t> qs(num_queries);
   for (auto& q : qs) q = ch.sample_bits(log_M - 1);
   // ---- 6 .. 11: queries ----
-  const size_t rec = (size_t)width + 4 * (size_t)log_M, qsize = (len - at_queries) / num_queries;
+  const size_t qsize = (len - at_queries) / num_queries;
   auto check_query = [&](int t) -> int {
     size_t p = at_queries + (size_t)t * qsize;
     const uint32_t q = qs[t];
     if (w[p++] != q) return 6;
+    const uint32_t* rows[2][FRI_PART_MAX_MATS];                            // a query's records: matrix by matrix, row q then row q + M/2
+    for (uint32_t m = 0; m < n_mats; m++)
+      for (int s2 = 0; s2 < 2; s2++) {
+        const size_t pos = (size_t)q + (s2 ? M / 2 : 0);
+        const uint32_t* row = w + p;
+        uint32_t dg[4]; hash_elems(row, widths[m], dg);
+        if (!check_path(dg, pos, row + widths[m], log_M, roots + 4 * m)) return 7;
+        rows[s2][m] = row;
+        p += (size_t)widths[m] + 4 * (size_t)log_M;
+      }
     E4 comb[2];
-    for (int s2 = 0; s2 < 2; s2++) {
-      const size_t pos = (size_t)q + (s2 ? M / 2 : 0);
-      const uint32_t* row = w + p;
-      uint32_t dg[4]; hash_elems(row, width, dg);
-      if (!check_path(dg, pos, row + width, log_M, root)) return 7;
-      comb[s2] = layer0_want(pos, row);
-      p += rec;
-    }
+    for (int s2 = 0; s2 < 2; s2++) comb[s2] = layer0_want((size_t)q + (s2 ? M / 2 : 0), rows[s2]);
     E4 carried = bb::e_zero(); size_t carried_idx = q;
     uint32_t shift = bb::GEN; int log_m = log_M;
     for (int j = 0; j < n_layers; j++) {
@@ -1205,7 +1210,8 @@ int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_r
   gp[0] = bb::e_one_m();
   for (size_t k = 1; k < width; k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
   // ---- 4 .. 11; 8: layer-0 values are sum gamma^k row ----
-  return fri_part_verify(w, len, 12, log_n, b, width, num_queries, pow_bits, ks, root, ch, [&](size_t, const uint32_t* row) {
+  return fri_part_verify(w, len, 12, log_n, b, 1, &width, num_queries, pow_bits, ks, root, ch, [&](size_t, const uint32_t* const* rows) {
+    const uint32_t* row = rows[0];
     E4 A = bb::e_zero();                                                    // canonical word x Montgomery gamma^k = canonical; lifted to Montgomery at the end
     for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[k], row[k]));
     return bb::e_to_mont(A);
@@ -1266,7 +1272,8 @@ int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roo
   }
   const uint32_t wM = bb::root_of_unity((int)(log_n + b));
   // ---- 4 .. 11; 8: layer-0 values are F at the two rows ----
-  return fri_part_verify(w, len, at_lroots, log_n, b, width, num_queries, pow_bits, ks, root, ch, [&](size_t pos, const uint32_t* row) {
+  return fri_part_verify(w, len, at_lroots, log_n, b, 1, &width, num_queries, pow_bits, ks, root, ch, [&](size_t pos, const uint32_t* const* rows) {
+    const uint32_t* row = rows[0];
     const uint32_t x_m = bb::to_mont(bb::mul(bb::GEN, bb::pow(wM, pos)));
     E4 F = bb::e_zero();
     for (uint32_t i = 0; i < n_points; i++) {
@@ -1274,6 +1281,113 @@ int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roo
       for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[(size_t)i * width + k], row[k]));
       E4 d = z[i]; d.c[0] = bb::sub(d.c[0], x_m);
       F = bb::e_add(F, bb::e_mul_m(bb::e_sub(a[i], bb::e_to_mont(A)), bb::e_inv_m(d)));
+    }
+    return F;
+  });
+}
+
+// ================================================================================================
+// zkir_batch_eval_verify — the verifier of a BATCHED EVALUATION PROOF (zkir_batch_eval_prove, batch_eval.inl; spec: tests/batch_eval_ref.py).  Host only.
+//
+// The proof says: n_mats (1 .. 4) matrices committed over the same coset 31 <w_M>, M = N << b, each under its own root, have every column close to a polynomial of degree
+// < N, and matrix m's columns take the proof's values at the points z_i (of the n_points shared ones) its mask_m selects.  ONE batched FRI over
+// F(x) = sum_i (a_i - A_i(x)) / (z_i - x), A_i(x) = sum gamma^e col_{m,k}(x), a_i = sum gamma^e y[i][m][k]; the exponent e runs consecutively for i over the points, for m
+// over the matrices with bit i of mask_m set, in order, for k < width_m.
+//   [0..9)  'ZKBE', version 1, log_n, b, n_mats, n_points, num_queries, pow_bits, n_layers | (width_m, mask_m) per matrix | the n_mats roots | 4 n_points point words | the
+//   evaluations in the exponent order, 4 words each | from there on the low-degree proof's layout: n_layers x 4 layer roots | n_fin x 4 final layer | nonce | the queries;
+//   a query: q, then for each matrix in order record_m(q), record_m(q + M/2) (width_m + 4 log_M words each), then per layer the values and the path
+// Transcript: every word up to and including the evaluations, gamma; per layer root, beta; the final words; check_pow(nonce); q_t = sample_bits(log_n + b - 1).
+// Codes: zkir_eval_verify's, in its order.  1 also covers n_mats, a width, the width total (at most 512: one product per column per point in a 96-bit sum), a mask (0, or a
+// bit at or above n_points) and a point no matrix is opened at; 2 compares all n_mats roots; 7 is a record of any matrix, lowest matrix first within a query; 8 recomputes
+// F from all the matrices' records.
+// ================================================================================================
+namespace {
+
+struct BatchShape { uint32_t n_mats, n_points, widths[4], masks[4]; uint64_t n_evals, sum_width; };
+// the (width, mask) pairs of a batch are ones a proof can state
+bool batch_shape_ok(uint32_t n_mats, uint32_t n_points, const uint32_t* widths, const uint32_t* masks, BatchShape* out) {
+  if (n_mats < 1 || n_mats > 4 || n_points < 1 || n_points > 2) return false;
+  BatchShape sh{};
+  sh.n_mats = n_mats; sh.n_points = n_points;
+  uint32_t used = 0;
+  for (uint32_t m = 0; m < n_mats; m++) {
+    if (widths[m] < 1 || widths[m] > 512 || masks[m] < 1 || masks[m] >= (1u << n_points)) return false;
+    sh.widths[m] = widths[m]; sh.masks[m] = masks[m];
+    sh.sum_width += widths[m]; used |= masks[m];
+    sh.n_evals += (uint64_t)widths[m] * (uint64_t)__builtin_popcount(masks[m]);
+  }
+  if (sh.sum_width > 512 || used != (1u << n_points) - 1) return false;
+  *out = sh;
+  return true;
+}
+
+}  // namespace
+
+uint64_t zkir_batch_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t n_mats, const uint32_t* widths, const uint32_t* masks, uint32_t n_points, uint32_t num_queries) {
+  BatchShape sh;
+  if (!widths || !masks || !batch_shape_ok(n_mats, n_points, widths, masks, &sh)) return 0;
+  const uint64_t ld = zkir_lowdeg_proof_words(log_n, log_blowup, 1, num_queries);      // one matrix of one column: 12 header and root words, 2 (1 + 4 log_M) record words a query
+  if (ld == 0) return 0;
+  const uint64_t log_M = (uint64_t)log_n + log_blowup;
+  return ld - 12 + 9 + 6 * (uint64_t)n_mats + 4 * (uint64_t)n_points + 4 * sh.n_evals + (uint64_t)num_queries * (2 * sh.sum_width - 2 + 8 * log_M * (n_mats - 1));
+}
+
+int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  // ---- 1: shape ----
+  if (!w || len < 9 || w[0] != 0x45424B5Au || w[1] != 1) return 1;
+  const uint32_t log_n = w[2], b = w[3], n_mats = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
+  if (n_mats < 1 || n_mats > 4 || n_points < 1 || n_points > 2 || len < 9 + 2 * (uint64_t)n_mats) return 1;
+  uint32_t widths[4], masks[4];
+  for (uint32_t m = 0; m < n_mats; m++) { widths[m] = w[9 + 2 * m]; masks[m] = w[10 + 2 * m]; }
+  BatchShape sh;
+  if (!batch_shape_ok(n_mats, n_points, widths, masks, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  if (w[8] != (uint32_t)ks.size() || len != zkir_batch_eval_proof_words(log_n, b, n_mats, widths, masks, n_points, num_queries)) return 1;
+  const uint32_t *roots = w + 9 + 2 * (size_t)n_mats, *pts = roots + 4 * (size_t)n_mats, *ys = pts + 4 * (size_t)n_points;
+  const size_t at_lroots = 9 + 6 * (size_t)n_mats + 4 * (size_t)n_points + 4 * (size_t)sh.n_evals;
+  // ---- 2, 13: what the caller expects, read at the sizes the header states ----
+  if (expect_roots && memcmp(roots, expect_roots, 16 * (size_t)n_mats)) return 2;
+  if (expect_points && memcmp(pts, expect_points, 16 * (size_t)n_points)) return 13;
+  if (expect_evals && memcmp(ys, expect_evals, 16 * (size_t)sh.n_evals)) return 13;
+  // ---- 3: canonical words ----
+  for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
+  // ---- 12: the points lie outside the base field and differ ----
+  for (uint32_t i = 0; i < n_points; i++) if (!(pts[4 * i + 1] | pts[4 * i + 2] | pts[4 * i + 3])) return 12;
+  if (n_points == 2 && !memcmp(pts, pts + 4, 16)) return 12;
+  // ---- the transcript up to gamma ----
+  Challenger ch;
+  ch.observe_n(w, at_lroots);
+  const E4 gamma = bb::e_to_mont(ch.sample_ext());
+  auto get_m = [&](const uint32_t* at) { return bb::e_to_mont(E4{{at[0], at[1], at[2], at[3]}}); };
+  std::vector<E4> gp((size_t)sh.n_evals);
+  gp[0] = bb::e_one_m();
+  for (size_t k = 1; k < gp.size(); k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
+  struct Sel { uint32_t i, m; size_t e; };                                  // the selected (point, matrix) pairs in the exponent order
+  std::vector<Sel> sel;
+  E4 z[2], a[2];
+  {
+    size_t e = 0;
+    for (uint32_t i = 0; i < n_points; i++) {
+      z[i] = get_m(pts + 4 * i);
+      a[i] = bb::e_zero();
+      for (uint32_t m = 0; m < n_mats; m++) {
+        if (!((masks[m] >> i) & 1)) continue;
+        sel.push_back({i, m, e});
+        for (size_t k = 0; k < widths[m]; k++, e++) a[i] = bb::e_add(a[i], bb::e_mul_m(gp[e], get_m(ys + 4 * e)));
+      }
+    }
+  }
+  const uint32_t wM = bb::root_of_unity((int)(log_n + b));
+  // ---- 4 .. 11; 8: layer-0 values are F at the two rows, from all the matrices' records ----
+  return fri_part_verify(w, len, at_lroots, log_n, b, n_mats, widths, num_queries, pow_bits, ks, roots, ch, [&](size_t pos, const uint32_t* const* rows) {
+    const uint32_t x_m = bb::to_mont(bb::mul(bb::GEN, bb::pow(wM, pos)));
+    E4 A[2] = {bb::e_zero(), bb::e_zero()};
+    for (const Sel& s : sel)
+      for (size_t k = 0; k < widths[s.m]; k++) A[s.i] = bb::e_add(A[s.i], bb::e_mul_fm(gp[s.e + k], rows[s.m][k]));
+    E4 F = bb::e_zero();
+    for (uint32_t i = 0; i < n_points; i++) {
+      E4 d = z[i]; d.c[0] = bb::sub(d.c[0], x_m);
+      F = bb::e_add(F, bb::e_mul_m(bb::e_sub(a[i], bb::e_to_mont(A[i])), bb::e_inv_m(d)));
     }
     return F;
   });

@@ -426,6 +426,13 @@ def lib() -> C.CDLL:
         L.zkir_eval_at_launch.restype = C.c_int; L.zkir_eval_at_launch.argtypes = [V, V, U32, V, U32, V, V, V]
         L.zkir_eval_quotient_scratch_words.restype = U64; L.zkir_eval_quotient_scratch_words.argtypes = [U32, U32, U32]
         L.zkir_eval_quotient_launch.restype = C.c_int; L.zkir_eval_quotient_launch.argtypes = [V, V, U32, V, V, U32, V, V, V, V]
+    if hasattr(L, "zkir_batch_eval_prove"):                   # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_batch_eval_proof_words.restype = U64; L.zkir_batch_eval_proof_words.argtypes = [U32, U32, U32, V, V, U32, U32]
+        L.zkir_batch_eval_prove.restype = C.c_int; L.zkir_batch_eval_prove.argtypes = [V, U32, V, V, V, V, V, U32, U32, U32, V, U64, C.POINTER(U64), V]
+        L.zkir_batch_eval_verify.restype = C.c_int; L.zkir_batch_eval_verify.argtypes = [V, U64, V, V, V]
+        L.zkir_batch_eval_prove_stages.restype = C.c_int; L.zkir_batch_eval_prove_stages.argtypes = [V, U32, V, V, V, V, V, U32, U32, U32, V, U64, C.POINTER(U64), V, V]
+        L.zkir_batch_eval_quotient_scratch_words.restype = U64; L.zkir_batch_eval_quotient_scratch_words.argtypes = [U32, U32, V, U32]
+        L.zkir_batch_eval_quotient_launch.restype = C.c_int; L.zkir_batch_eval_quotient_launch.argtypes = [V, U32, V, V, V, V, V, U32, V, V, V, V]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -706,6 +713,39 @@ def eval_verify(proof, root=None, points=None, evals=None) -> int:
         p = e = None                                             # the proof is malformed (1) whatever is expected of it
     ptr = lambda a: a.ctypes.data if a is not None else None
     return int(lib().zkir_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
+
+
+def batch_eval_proof_words(log_n: int, log_blowup: int, widths, masks, n_points: int, num_queries: int) -> int:
+    """Words of a batched evaluation proof (zkir_batch_eval_proof_words) of len(widths) matrices; 0 for a shape no proof can state."""
+    ws, ks = np.ascontiguousarray(widths, dtype=np.uint32).reshape(-1), np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+    if len(ws) != len(ks) or not 1 <= len(ws) <= 4:
+        return 0
+    return int(lib().zkir_batch_eval_proof_words(int(log_n), int(log_blowup), len(ws), ws.ctypes.data, ks.ctypes.data, int(n_points), int(num_queries)))
+
+
+def batch_eval_verify(proof, roots=None, points=None, evals=None) -> int:
+    """zkir_batch_eval_verify, on the host — no GPU: 0 = the proof convinces a holder of its roots that every column of every committed matrix is close to a polynomial of
+    degree < 2^log_n that takes the proof's evaluations at the points its matrix is opened at; `roots` ([n_mats][4]), `points` ([n_points][4]) and `evals` (the proof's
+    evaluation words, in its exponent order), when given, must be the proof's.  Else the code of the first failing check (include/zkir_amd.h lists them).  The library reads
+    as many expected words as the proof's header states: where the header is one a proof can have, expectations of another size raise ValueError."""
+    w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
+    r = None if roots is None else np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1)
+    p = None if points is None else np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
+    e = None if evals is None else np.ascontiguousarray(evals, dtype=np.uint32).reshape(-1)
+    sane = len(w) >= 9 and 1 <= int(w[4]) <= 4 and 1 <= int(w[5]) <= 2 and len(w) >= 9 + 2 * int(w[4])
+    if sane:
+        n_mats, n_points = int(w[4]), int(w[5])
+        shape = [(int(w[9 + 2 * m]), int(w[10 + 2 * m])) for m in range(n_mats)]
+        sane = all(1 <= wd <= 512 and 1 <= k < (1 << n_points) for wd, k in shape)
+    if sane:
+        n_evals = sum(wd * bin(k).count("1") for wd, k in shape)
+        for name, a, want in (("roots", r, 4 * n_mats), ("points", p, 4 * n_points), ("evals", e, 4 * n_evals)):
+            if a is not None and len(a) != want:
+                raise ValueError(f"batch_eval_verify: {name} must hold {want} words, what the proof's header states")
+    else:
+        r = p = e = None                                         # the proof is malformed (1) whatever is expected of it
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    return int(lib().zkir_batch_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
 
 
 def verify_last_stages() -> dict:

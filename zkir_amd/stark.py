@@ -333,6 +333,97 @@ def eval_layout(proof) -> dict:
     return at
 
 
+batch_eval_proof_words = rt.batch_eval_proof_words
+batch_eval_verify = rt.batch_eval_verify
+
+
+def _batch_args(name: str, ctx: StarkContext, mats, widths, masks, points):
+    """(widths uint32[n], masks uint32[n], points uint32[n_points][4], the matrices' device pointers as a C array) of a batched call; ValueError for lists of different
+    lengths, a matrix that is not of the context's size, a width its matrix does not have, or points that are not rows of four words"""
+    mats = list(mats)
+    widths = [m.shape[0] * 8 for m in mats] if widths is None else [int(w) for w in widths]
+    masks = [int(k) for k in masks]
+    if not (len(mats) == len(widths) == len(masks)):
+        raise ValueError(f"{name}: mats, widths and masks must have one entry per matrix")
+    if not mats or any(w < 0 for w in widths) or any(k < 0 for k in masks):
+        raise ValueError(f"{name}: at least one matrix, and no negative width or mask")
+    for m, w in zip(mats, widths):
+        _, pts = _eval_args(name, ctx, m, w, points)
+    ptrs = (C.c_void_p * max(len(mats), 1))(*[m.data_ptr() for m in mats])
+    return np.array(widths, np.uint32), np.array(masks, np.uint32), pts, ptrs
+
+
+def batch_eval_prove(ctx: StarkContext, mats, trees, widths, masks, points, num_queries: int = 50, pow_bits: int = 12, stream=None, want_stage_ms: bool = False):
+    """zkir_batch_eval_prove: ONE evaluation proof (np.uint32 words) opening the 1 .. 4 commitments `trees` (merkle_commit's) to the B8 matrices `mats` (lde's outputs on
+    `ctx`; `widths` real columns each, None: all) at the shared `points` ([1 or 2][4] canonical words, E4 elements outside the base field, CHOSEN AFTER THE ROOTS);
+    masks[m] bit i: matrix m is opened at point i.  One inverse table, one FRI commit phase, one grind and one set of query rows for all the matrices
+    (batch_eval_layout finds the sections).  Tensors of the wrong size raise ValueError; the library refuses bad parameters with ERR_ARGUMENT before any launch.
+    want_stage_ms: also the device ms of (weights, evaluations, quotient, FRI commit phase, grinding, query section)."""
+    ws, ks, pts, mat_ptrs = _batch_args("batch_eval_prove", ctx, mats, widths, masks, points)
+    trees = list(trees)
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    if len(trees) != len(ws):
+        raise ValueError("batch_eval_prove: trees must have one entry per matrix")
+    for tree in trees:
+        if tree.dtype != torch.int32 or not tree.is_contiguous() or tree.numel() != 4 * (2 * m - 1):
+            raise ValueError(f"batch_eval_prove: a tree must be contiguous int32[{4 * (2 * m - 1)}], merkle_commit's over {m} leaves")
+    tree_ptrs = (C.c_void_p * max(len(trees), 1))(*[t.data_ptr() for t in trees])
+    cap = batch_eval_proof_words(ctx.log_n, ctx.log_blowup, ws, ks, len(pts), num_queries)
+    out = np.zeros(max(cap, 1), np.uint32)
+    n_words = C.c_uint64()
+    args = (ctx.handle, len(ws), mat_ptrs, ws.ctypes.data, tree_ptrs, ks.ctypes.data, pts.ctypes.data, len(pts), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words))
+    if want_stage_ms:
+        ms = (C.c_float * 6)()
+        pl._check(rt.lib().zkir_batch_eval_prove_stages(*args, ms, _sp(stream)))
+        return out[:n_words.value], [float(x) for x in ms]
+    pl._check(rt.lib().zkir_batch_eval_prove(*args, _sp(stream)))
+    return out[:n_words.value]
+
+
+def batch_eval_quotient(ctx: StarkContext, mats, gamma, points, evals, widths, masks, stream=None) -> torch.Tensor:
+    """(tests, measurements) zkir_batch_eval_quotient_launch: the codeword int32[4][M] of batch_eval_prove's quotient stage for GIVEN canonical gamma (four words), points and
+    evaluations (4 words each, in the proof's exponent order: for each point, for each matrix opened at it, for each column): row t = coordinate t of F."""
+    ws, ks, pts, mat_ptrs = _batch_args("batch_eval_quotient", ctx, mats, widths, masks, points)
+    g = np.ascontiguousarray(gamma, dtype=np.uint32).reshape(4)
+    y = np.ascontiguousarray(evals, dtype=np.uint32).reshape(-1)
+    if len(y) != 4 * sum(int(w) * bin(int(k) & ((1 << len(pts)) - 1)).count("1") for w, k in zip(ws, ks)):
+        raise ValueError("batch_eval_quotient: evals must hold 4 words per selected (point, matrix, column)")
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    dev = mats[0].device
+    scratch = torch.empty(max(1, int(rt.lib().zkir_batch_eval_quotient_scratch_words(ctx.log_n + ctx.log_blowup, len(ws), ws.ctypes.data, len(pts)))), dtype=torch.int32, device=dev)
+    cw = torch.empty((4, m), dtype=torch.int32, device=dev)
+    pl._check(rt.lib().zkir_batch_eval_quotient_launch(ctx.handle, len(ws), mat_ptrs, ws.ctypes.data, ks.ctypes.data, g.ctypes.data, pts.ctypes.data, len(pts), y.ctypes.data,
+                                                       scratch.data_ptr(), cw.data_ptr(), _sp(stream)))
+    return cw
+
+
+def batch_eval_layout(proof) -> dict:
+    """Word offsets of a well-formed batched evaluation proof: the header's fields, widths, masks, shape, roots, points, evals (in the exponent order; evals_of[(i, m)] is where
+    y[i][m][0] stands), layer_roots, final, nonce, queries, the words of one query (qsize) and, relative to a query's start, records[m] = (record_m(q), record_m(q + M/2))."""
+    log_n, b, n_mats, n_points, nq, _, n_layers = (int(x) for x in proof[2:9])
+    widths, masks = [int(x) for x in proof[9:9 + 2 * n_mats:2]], [int(x) for x in proof[10:10 + 2 * n_mats:2]]
+    at = {"log_n": log_n, "log_blowup": b, "n_mats": n_mats, "n_points": n_points, "num_queries": nq, "n_layers": n_layers, "widths": widths, "masks": masks, "shape": 9,
+          "roots": 9 + 2 * n_mats, "points": 9 + 6 * n_mats, "evals": 9 + 6 * n_mats + 4 * n_points, "evals_of": {}}
+    e = 0
+    for i in range(n_points):
+        for m in range(n_mats):
+            if (masks[m] >> i) & 1:
+                at["evals_of"][(i, m)] = at["evals"] + 4 * e
+                e += widths[m]
+    at["n_evals"] = e
+    at["layer_roots"] = at["evals"] + 4 * e
+    at["final"] = at["layer_roots"] + 4 * n_layers
+    at["nonce"] = at["final"] + 4 * (4 << b)
+    at["queries"] = at["nonce"] + 1
+    at["qsize"] = (len(proof) - at["queries"]) // nq if nq else 0
+    rel, at["records"] = 1, []
+    for w in widths:
+        rec = w + 4 * (log_n + b)
+        at["records"].append((rel, rel + rec))
+        rel += 2 * rec
+    return at
+
+
 def commit_trace(ctx: StarkContext, trace: pl.DeviceTrace, stream=None, deferred: bool = False):
     """main trace -> LDE (at the context's blow-up) -> Merkle.  Returns (root np.uint32[4], lde matrix tensor (B8), tree tensor)."""
     m = main_trace(trace, stream, deferred)
