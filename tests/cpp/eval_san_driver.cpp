@@ -1,9 +1,12 @@
-// eval_san_driver.cpp — zkir_eval_verify (verify.cpp) called on a corpus of honest and malformed evaluation proofs from a stand-alone program built with AddressSanitizer and
-// UndefinedBehaviorSanitizer (tests/test_eval_sanitized.py builds it, writes the corpus and compares every verdict with tests/eval_ref.py's).  No HIP, no torch, no Python:
-// the host objects and this file.  What the library defines in its HIP translation units is stated here, as in host_san_driver.cpp.
+// eval_san_driver.cpp — zkir_eval_verify and zkir_batch_eval_verify (verify.cpp) called on a corpus of honest and malformed evaluation proofs from a stand-alone program built
+// with AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_eval_sanitized.py builds it; that file and tests/test_batch_eval_sanitized.py write the corpora and compare
+// every verdict with tests/eval_ref.py's and tests/batch_eval_ref.py's).  No HIP, no torch, no Python: the host objects and this file.  What the library defines in
+// its HIP translation units is stated here, as in host_san_driver.cpp.
 //
 // Corpus file: host_san_driver.cpp's format ('ZKSC', bases, cases; a buffer = a base's prefix + patches + inline elements).  Every buffer is handed to the verifier in a heap
-// block of EXACTLY its length.  One kind of case: args = [flags: 1 root, 2 points, 4 evals], bufs = proof [root] [points] [evals]; one line "<case index> rc <code>" each.
+// block of EXACTLY its length.  Case kind 0 is zkir_eval_verify (its root block has 4 words), kind 1 zkir_batch_eval_verify: args = [flags: 1 roots, 2 points, 4 evals],
+// bufs = proof [roots] [points] [evals], each expectation at the size the proof's header states (the verifier reads that many words of it once the header is one a proof can
+// have); one line "<case index> rc <code>" each.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,7 +89,8 @@ int main(int argc, char** argv) {
   for (Base& b : bases) { if (r.u32() != 4) die("base element size"); b.count = r.u64(); b.data = r.bytes((size_t)b.count * 4); }
   const uint32_t n_cases = r.u32();
   for (uint32_t i = 0; i < n_cases; i++) {
-    if (r.u32() != 0) die("case kind");
+    const uint32_t kind = r.u32();
+    if (kind > 1) die("case kind");
     if (r.u32() != 1) die("argument count");
     const uint64_t flags = r.u64();
     const uint32_t n_bufs = r.u32();
@@ -94,11 +98,11 @@ int main(int argc, char** argv) {
     for (uint32_t k = 0; k < n_bufs; k++) b.push_back(read_buf(r, bases));
     if (n_bufs != 1 + (flags & 1) + ((flags >> 1) & 1) + ((flags >> 2) & 1)) die("buffer count");
     size_t at = 1;
-    const uint32_t* root = (flags & 1) ? b[at++].p : nullptr;
+    const uint32_t* roots = (flags & 1) ? b[at++].p : nullptr;
     const uint32_t* points = (flags & 2) ? b[at++].p : nullptr;
     const uint32_t* evals = (flags & 4) ? b[at++].p : nullptr;
-    if ((flags & 1) && b[1].count != 4) die("root block");
-    printf("%u rc %d\n", i, zkir_eval_verify(b[0].p, b[0].count, root, points, evals));
+    if (kind == 0 && (flags & 1) && b[1].count != 4) die("root block");
+    printf("%u rc %d\n", i, (kind == 0 ? zkir_eval_verify : zkir_batch_eval_verify)(b[0].p, b[0].count, roots, points, evals));
   }
   return 0;
 }

@@ -1,47 +1,23 @@
-"""zkir_batch_eval_verify under AddressSanitizer + UndefinedBehaviorSanitizer on honest and malformed batched evaluation proofs.  The host sources
-(zkir_amd.build.HOST_SOURCES) and a stand-alone driver (tests/cpp/batch_eval_san_driver.cpp, its own main) are compiled with -fsanitize=address,undefined exactly as
-tests/test_eval_sanitized.py builds its driver, and the driver is run on test_batch_eval_verify's reference proofs and mutants, each copied into a heap block of exactly its
-length: no sanitizer report, and every verdict the one tests/batch_eval_ref.py gives.  CPU only; nothing is loaded into Python and nothing is preloaded."""
+"""zkir_batch_eval_verify under AddressSanitizer + UndefinedBehaviorSanitizer on honest and malformed batched evaluation proofs.  The stand-alone driver of
+tests/test_eval_sanitized.py (tests/cpp/eval_san_driver.cpp with the host sources, one build for both files; case kind 1 calls zkir_batch_eval_verify) is run on
+test_batch_eval_verify's reference proofs and mutants, each copied into a heap block of exactly its length: no sanitizer report, and every verdict the one
+tests/batch_eval_ref.py gives.  CPU only; nothing is loaded into Python and nothing is preloaded."""
 from __future__ import annotations
-
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import batch_eval_ref as be
 import test_batch_eval_verify as tv
-from test_host_sanitized import SAN, SAN_FLAGS, Corpus, _check, _linker
-from zkir_amd import build as zbuild
+from test_eval_sanitized import build_driver
+from test_host_sanitized import Corpus, _check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "batch_eval_san_driver.cpp")
-BIN = os.path.join(SAN, "batch_eval_san_driver")
-BATCH = 0
+BATCH = 1
 
 
 @pytest.fixture(scope="module")
 def driver():
-    os.makedirs(SAN, exist_ok=True)
-    probe = os.path.join(SAN, "probe.cpp")
-    with open(probe, "w") as f:
-        f.write("#include <vector>\nint main() { std::vector<int> v(3, 1); return v[0] + v[2] - 2; }\n")
-    p = subprocess.run([zbuild.HIPCC, "-x", "c++", *SAN_FLAGS, probe, "-o", os.path.join(SAN, "probe")], capture_output=True, text=True)
-    if p.returncode != 0 or subprocess.run([os.path.join(SAN, "probe")], capture_output=True).returncode != 0:
-        pytest.skip("the compiler cannot link or run a program with the AddressSanitizer / UndefinedBehaviorSanitizer runtime: " + p.stderr[-300:])
-    deps = [os.path.normpath(os.path.join(zbuild.CSRC, h)) for h in zbuild.HEADERS]
-    objs, jobs = [], []
-    for src in [os.path.join(zbuild.CSRC, name) for name in zbuild.HOST_SOURCES] + [DRIVER_SRC]:
-        obj = os.path.join(SAN, os.path.basename(src) + ".o")
-        objs.append(obj)
-        if zbuild._newer(src, obj, deps):
-            jobs.append(subprocess.Popen([zbuild.HIPCC, "-x", "c++", "-std=c++17", *SAN_FLAGS, "-Wall", "-Wno-unused-function", "-c", src, "-o", obj]))
-    for j in jobs:
-        assert j.wait() == 0, "a sanitizer build of a host source failed"
-    if zbuild._newer(objs[0], BIN, objs[1:]):
-        subprocess.check_call([_linker(), "-fsanitize=address,undefined", *objs, "-o", BIN])
-    return BIN
+    return build_driver()
 
 
 def test_batch_eval_verify(driver):

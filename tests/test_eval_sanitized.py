@@ -1,9 +1,10 @@
 """zkir_eval_verify under AddressSanitizer + UndefinedBehaviorSanitizer on honest and malformed evaluation proofs.  The host sources (zkir_amd.build.HOST_SOURCES) and a
-stand-alone driver (tests/cpp/eval_san_driver.cpp, its own main) are compiled with -fsanitize=address,undefined exactly as tests/test_host_sanitized.py builds its driver,
+stand-alone driver (tests/cpp/eval_san_driver.cpp, its own main; case kind 0 calls zkir_eval_verify) are compiled with -fsanitize=address,undefined exactly as tests/test_host_sanitized.py builds its driver,
 and the driver is run on test_eval_verify's reference proofs and mutants, each copied into a heap block of exactly its length: no sanitizer report, and every verdict the one
 tests/eval_ref.py gives.  CPU only; nothing is preloaded."""
 from __future__ import annotations
 
+import functools
 import os
 import subprocess
 
@@ -21,8 +22,9 @@ BIN = os.path.join(SAN, "eval_san_driver")
 EVAL = 0
 
 
-@pytest.fixture(scope="module")
-def driver():
+@functools.lru_cache(maxsize=None)
+def build_driver() -> str:
+    """the sanitizer build of the host sources and the driver (shared with tests/test_batch_eval_sanitized.py: one binary, built once)"""
     os.makedirs(SAN, exist_ok=True)
     probe = os.path.join(SAN, "probe.cpp")
     with open(probe, "w") as f:
@@ -42,6 +44,11 @@ def driver():
     if zbuild._newer(objs[0], BIN, objs[1:]):
         subprocess.check_call([_linker(), "-fsanitize=address,undefined", *objs, "-o", BIN])
     return BIN
+
+
+@pytest.fixture(scope="module")
+def driver():
+    return build_driver()
 
 
 def test_eval_verify(driver):

@@ -20,9 +20,11 @@ pytestmark = pytest.mark.gpu
 P = ld.P
 GUARD = 0xA5A5A5A5
 # (log_n, b, ((width, mask), ..), n_points, num_queries, pow_bits): the three CPU shapes; b = 1, two ragged matrices at one point; four matrices with every mask; the shape
-# a STARK would use (trace, auxiliary, quotient at the first point only); M = 2^16 (the lane-form leaf hash); b = 1 with a matrix opened at the second point only
+# a STARK would use (trace, auxiliary, quotient at the first point only); M = 2^16 (the lane-form leaf hash); b = 1 with a matrix opened at the second point only; ONE ragged
+# matrix at two points (a batch of one runs the single-matrix quotient kernel under the 'ZKBE' header)
 SHAPES = [(3, 1, ((1, 1),), 1, 3, 0), (3, 3, ((8, 3), (1, 1)), 2, 2, 4), (4, 2, ((9, 3), (7, 1), (8, 2)), 2, 4, 4), (6, 1, ((5, 1), (3, 1)), 1, 5, 6),
-          (7, 2, ((17, 3), (8, 1), (1, 2), (9, 3)), 2, 4, 4), (10, 2, ((152, 3), (40, 3), (4, 1)), 2, 8, 8), (13, 3, ((8, 3), (8, 1)), 2, 6, 8), (11, 1, ((9, 3), (9, 2)), 2, 8, 8)]
+          (7, 2, ((17, 3), (8, 1), (1, 2), (9, 3)), 2, 4, 4), (10, 2, ((152, 3), (40, 3), (4, 1)), 2, 8, 8), (13, 3, ((8, 3), (8, 1)), 2, 6, 8), (11, 1, ((9, 3), (9, 2)), 2, 8, 8),
+          (4, 2, ((9, 3),), 2, 4, 4)]
 BIG, SMALL = [P - 1, P - 2, P - 3, P - 4], [0, 1, 0, 0]
 
 
@@ -164,6 +166,7 @@ def test_quotient_kernel_against_the_reference(wm):
 
 
 def test_one_matrix_with_a_full_mask_is_eval_quotient():
+    """the two entries run one launch path (a batch of one takes eval_quotient_kernel): they agree with each other AND with the batch reference's quotient"""
     from zkir_amd import stark
     ctx = _ctx(KERNEL_LOG_N, KERNEL_B)
     rng = np.random.default_rng(5)
@@ -174,6 +177,7 @@ def test_one_matrix_with_a_full_mask_is_eval_quotient():
             want = _u32(stark.eval_quotient(ctx, mat, GAMMAS[0], pts, ys, width))
             got = _u32(stark.batch_eval_quotient(ctx, [mat], GAMMAS[0], pts, ys, [width], [(1 << len(pts)) - 1]))
             assert np.array_equal(got, want)
+            assert np.array_equal(got.T.astype(np.uint64), be.quotient([cols], [(1 << len(pts)) - 1], pts, ys.reshape(-1, 4), np.array(GAMMAS[0], np.uint32)))
 
 
 def test_a_24_column_matrix_equals_its_split_into_16_and_8():

@@ -1219,87 +1219,25 @@ int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_r
 }
 
 // ================================================================================================
-// zkir_eval_verify — the verifier of an EVALUATION PROOF OF A COMMITMENT (zkir_eval_prove, eval_open.inl; spec: tests/eval_ref.py).  Host only.
-//
-// The proof says: every column k of the matrix committed under the root is close to a polynomial p_k of degree < N over the coset 31 <w_M>, M = N << b, and
-// p_k(z_i) = y[i][k] at the n_points (1 or 2) points z_i of E4 it carries.  Batched FRI over F(x) = sum_i (a_i - A_i(x)) / (z_i - x), A_i(x) = sum_k gamma^(i width + k) col_k(x),
-// a_i = sum_k gamma^(i width + k) y[i][k]: F is a polynomial of degree < N - 1 exactly when every claim holds.
-//   [0..9)  'ZKEV', version 1, log_n, b, width, n_points, num_queries, pow_bits, n_layers | [9..13) the root | 4 n_points point words | 4 n_points width evaluation words
-//   (point-major) | from there on the low-degree proof's layout: n_layers x 4 layer roots | n_fin x 4 final layer | nonce | the queries
-// Transcript: header, root, points, evaluations, gamma; per layer root, beta; the final words; check_pow(nonce); q_t = sample_bits(log_n + b - 1).
-// Codes, first failing check in this order, lowest query first: 1 malformed (length not EXACTLY the header's, magic, version, a range, n_points, n_layers), 2 not the expected
-// root, 13 not the expected points or not the expected evaluations (NULL: any), 3 a word >= p, 12 a point in the base field (coordinates 1 .. 3 all zero) or two equal points,
-// 4 the final layer is not of degree < 4, 5 grinding, 6 a query's index word, 7 a matrix record does not hash to the root, 8 layer-0 values are not F at rows q / q + M/2,
-// recomputed from the opened records, the points and the evaluations (checked BEFORE layer 0's path), 9 a FRI leaf's path, 10 carried value != v[slot], 11 final value.
-// ================================================================================================
-uint64_t zkir_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t n_points, uint32_t num_queries) {
-  const uint64_t ld = zkir_lowdeg_proof_words(log_n, log_blowup, width, num_queries);
-  if (ld == 0 || n_points < 1 || n_points > 2) return 0;
-  return ld + 1 + 4 * (uint64_t)n_points * (1 + (uint64_t)width);           // one more header word, the points, the evaluations
-}
-
-int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals) {
-  // ---- 1: shape ----
-  if (!w || len < 9 || w[0] != 0x56454B5Au || w[1] != 1) return 1;
-  const uint32_t log_n = w[2], b = w[3], width = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
-  if (!lowdeg_params_ok(log_n, b, width, num_queries) || n_points < 1 || n_points > 2 || pow_bits > 24) return 1;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
-  if (w[8] != (uint32_t)ks.size() || len != zkir_eval_proof_words(log_n, b, width, n_points, num_queries)) return 1;
-  const uint32_t *root = w + 9, *pts = w + 13, *ys = pts + 4 * (size_t)n_points;
-  const size_t at_lroots = 13 + 4 * (size_t)n_points * (1 + (size_t)width);
-  // ---- 2, 13: what the caller expects ----
-  if (expect_root && memcmp(root, expect_root, 16)) return 2;
-  if (expect_points && memcmp(pts, expect_points, 16 * (size_t)n_points)) return 13;
-  if (expect_evals && memcmp(ys, expect_evals, 16 * (size_t)n_points * width)) return 13;
-  // ---- 3: canonical words ----
-  for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
-  // ---- 12: the points lie outside the base field (so z - x is invertible for every x of it) and differ ----
-  for (uint32_t i = 0; i < n_points; i++) if (!(pts[4 * i + 1] | pts[4 * i + 2] | pts[4 * i + 3])) return 12;
-  if (n_points == 2 && !memcmp(pts, pts + 4, 16)) return 12;
-  // ---- the transcript up to gamma ----
-  Challenger ch;
-  ch.observe_n(w, at_lroots);
-  const E4 gamma = bb::e_to_mont(ch.sample_ext());
-  auto get_m = [&](const uint32_t* at) { return bb::e_to_mont(E4{{at[0], at[1], at[2], at[3]}}); };
-  std::vector<E4> gp((size_t)n_points * width);
-  gp[0] = bb::e_one_m();
-  for (size_t k = 1; k < gp.size(); k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
-  E4 z[2], a[2];
-  for (uint32_t i = 0; i < n_points; i++) {
-    z[i] = get_m(pts + 4 * i);
-    a[i] = bb::e_zero();
-    for (size_t k = 0; k < width; k++) a[i] = bb::e_add(a[i], bb::e_mul_m(gp[(size_t)i * width + k], get_m(ys + 4 * ((size_t)i * width + k))));
-  }
-  const uint32_t wM = bb::root_of_unity((int)(log_n + b));
-  // ---- 4 .. 11; 8: layer-0 values are F at the two rows ----
-  return fri_part_verify(w, len, at_lroots, log_n, b, 1, &width, num_queries, pow_bits, ks, root, ch, [&](size_t pos, const uint32_t* const* rows) {
-    const uint32_t* row = rows[0];
-    const uint32_t x_m = bb::to_mont(bb::mul(bb::GEN, bb::pow(wM, pos)));
-    E4 F = bb::e_zero();
-    for (uint32_t i = 0; i < n_points; i++) {
-      E4 A = bb::e_zero();
-      for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[(size_t)i * width + k], row[k]));
-      E4 d = z[i]; d.c[0] = bb::sub(d.c[0], x_m);
-      F = bb::e_add(F, bb::e_mul_m(bb::e_sub(a[i], bb::e_to_mont(A)), bb::e_inv_m(d)));
-    }
-    return F;
-  });
-}
-
-// ================================================================================================
-// zkir_batch_eval_verify — the verifier of a BATCHED EVALUATION PROOF (zkir_batch_eval_prove, batch_eval.inl; spec: tests/batch_eval_ref.py).  Host only.
+// zkir_eval_verify and zkir_batch_eval_verify — the verifiers of an EVALUATION PROOF (zkir_eval_prove / zkir_batch_eval_prove, eval_open.inl).  Host only.
 //
 // The proof says: n_mats (1 .. 4) matrices committed over the same coset 31 <w_M>, M = N << b, each under its own root, have every column close to a polynomial of degree
-// < N, and matrix m's columns take the proof's values at the points z_i (of the n_points shared ones) its mask_m selects.  ONE batched FRI over
+// < N, and matrix m's columns take the proof's values at the points z_i (of the n_points (1 or 2) shared ones, in E4) its mask_m selects.  ONE batched FRI over
 // F(x) = sum_i (a_i - A_i(x)) / (z_i - x), A_i(x) = sum gamma^e col_{m,k}(x), a_i = sum gamma^e y[i][m][k]; the exponent e runs consecutively for i over the points, for m
-// over the matrices with bit i of mask_m set, in order, for k < width_m.
-//   [0..9)  'ZKBE', version 1, log_n, b, n_mats, n_points, num_queries, pow_bits, n_layers | (width_m, mask_m) per matrix | the n_mats roots | 4 n_points point words | the
-//   evaluations in the exponent order, 4 words each | from there on the low-degree proof's layout: n_layers x 4 layer roots | n_fin x 4 final layer | nonce | the queries;
-//   a query: q, then for each matrix in order record_m(q), record_m(q + M/2) (width_m + 4 log_M words each), then per layer the values and the path
+// over the matrices with bit i of mask_m set, in order, for k < width_m.  F is a polynomial of degree < N - 1 exactly when every claim holds.
+// Two headers state it, and everything after the header is one layout:
+//   'ZKBE' (spec: tests/batch_eval_ref.py)  [0..9) magic, version 1, log_n, b, n_mats, n_points, num_queries, pow_bits, n_layers | (width_m, mask_m) per matrix
+//   'ZKEV' (spec: tests/eval_ref.py)        [0..9) magic, version 1, log_n, b, width, n_points, num_queries, pow_bits, n_layers: ONE matrix opened at every point (a full mask)
+//   then: the n_mats roots | 4 n_points point words | the evaluations in the exponent order, 4 words each (one matrix: point-major) | the low-degree proof's layout:
+//   n_layers x 4 layer roots | n_fin x 4 final layer | nonce | the queries; a query: q, then for each matrix in order record_m(q), record_m(q + M/2) (width_m + 4 log_M
+//   words each), then per layer the values and the path
 // Transcript: every word up to and including the evaluations, gamma; per layer root, beta; the final words; check_pow(nonce); q_t = sample_bits(log_n + b - 1).
-// Codes: zkir_eval_verify's, in its order.  1 also covers n_mats, a width, the width total (at most 512: one product per column per point in a 96-bit sum), a mask (0, or a
-// bit at or above n_points) and a point no matrix is opened at; 2 compares all n_mats roots; 7 is a record of any matrix, lowest matrix first within a query; 8 recomputes
-// F from all the matrices' records.
+// Codes, first failing check in this order, lowest query first: 1 malformed (length not EXACTLY the header's, magic, version, a range, n_points, n_layers; 'ZKBE': n_mats, a
+// width, the width total (at most 512: one product per column per point in a 96-bit sum), a mask (0, or a bit at or above n_points), a point no matrix is opened at), 2 not
+// the expected roots (all n_mats), 13 not the expected points or not the expected evaluations (NULL: any), 3 a word >= p, 12 a point in the base field (coordinates 1 .. 3 all
+// zero) or two equal points, 4 the final layer is not of degree < 4, 5 grinding, 6 a query's index word, 7 a matrix record does not hash to its root (lowest matrix first
+// within a query), 8 layer-0 values are not F at rows q / q + M/2, recomputed from all the opened records, the points and the evaluations (checked BEFORE layer 0's path),
+// 9 a FRI leaf's path, 10 carried value != v[slot], 11 final value.
 // ================================================================================================
 namespace {
 
@@ -1321,37 +1259,19 @@ bool batch_shape_ok(uint32_t n_mats, uint32_t n_points, const uint32_t* widths, 
   return true;
 }
 
-}  // namespace
-
-uint64_t zkir_batch_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t n_mats, const uint32_t* widths, const uint32_t* masks, uint32_t n_points, uint32_t num_queries) {
-  BatchShape sh;
-  if (!widths || !masks || !batch_shape_ok(n_mats, n_points, widths, masks, &sh)) return 0;
-  const uint64_t ld = zkir_lowdeg_proof_words(log_n, log_blowup, 1, num_queries);      // one matrix of one column: 12 header and root words, 2 (1 + 4 log_M) record words a query
-  if (ld == 0) return 0;
-  const uint64_t log_M = (uint64_t)log_n + log_blowup;
-  return ld - 12 + 9 + 6 * (uint64_t)n_mats + 4 * (uint64_t)n_points + 4 * sh.n_evals + (uint64_t)num_queries * (2 * sh.sum_width - 2 + 8 * log_M * (n_mats - 1));
-}
-
-int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
-  // ---- 1: shape ----
-  if (!w || len < 9 || w[0] != 0x45424B5Au || w[1] != 1) return 1;
-  const uint32_t log_n = w[2], b = w[3], n_mats = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
-  if (n_mats < 1 || n_mats > 4 || n_points < 1 || n_points > 2 || len < 9 + 2 * (uint64_t)n_mats) return 1;
-  uint32_t widths[4], masks[4];
-  for (uint32_t m = 0; m < n_mats; m++) { widths[m] = w[9 + 2 * m]; masks[m] = w[10 + 2 * m]; }
-  BatchShape sh;
-  if (!batch_shape_ok(n_mats, n_points, widths, masks, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
-  if (w[8] != (uint32_t)ks.size() || len != zkir_batch_eval_proof_words(log_n, b, n_mats, widths, masks, n_points, num_queries)) return 1;
-  const uint32_t *roots = w + 9 + 2 * (size_t)n_mats, *pts = roots + 4 * (size_t)n_mats, *ys = pts + 4 * (size_t)n_points;
-  const size_t at_lroots = 9 + 6 * (size_t)n_mats + 4 * (size_t)n_points + 4 * (size_t)sh.n_evals;
+// Everything after check 1 of either header: the roots section starts at word at_roots, the shape and the length are checked, ks is the schedule of (log_n, b).
+int eval_core_verify(const BatchShape& sh, size_t at_roots, const uint32_t* w, uint64_t len, const std::vector<int>& ks, const uint32_t* expect_roots, const uint32_t* expect_points,
+                     const uint32_t* expect_evals) {
+  const uint32_t log_n = w[2], b = w[3], n_mats = sh.n_mats, n_points = sh.n_points, num_queries = w[6], pow_bits = w[7];
+  const uint32_t *roots = w + at_roots, *pts = roots + 4 * (size_t)n_mats, *ys = pts + 4 * (size_t)n_points;
+  const size_t at_lroots = at_roots + 4 * (size_t)n_mats + 4 * (size_t)n_points + 4 * (size_t)sh.n_evals;
   // ---- 2, 13: what the caller expects, read at the sizes the header states ----
   if (expect_roots && memcmp(roots, expect_roots, 16 * (size_t)n_mats)) return 2;
   if (expect_points && memcmp(pts, expect_points, 16 * (size_t)n_points)) return 13;
   if (expect_evals && memcmp(ys, expect_evals, 16 * (size_t)sh.n_evals)) return 13;
   // ---- 3: canonical words ----
   for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
-  // ---- 12: the points lie outside the base field and differ ----
+  // ---- 12: the points lie outside the base field (so z - x is invertible for every x of it) and differ ----
   for (uint32_t i = 0; i < n_points; i++) if (!(pts[4 * i + 1] | pts[4 * i + 2] | pts[4 * i + 3])) return 12;
   if (n_points == 2 && !memcmp(pts, pts + 4, 16)) return 12;
   // ---- the transcript up to gamma ----
@@ -1371,19 +1291,19 @@ int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
       z[i] = get_m(pts + 4 * i);
       a[i] = bb::e_zero();
       for (uint32_t m = 0; m < n_mats; m++) {
-        if (!((masks[m] >> i) & 1)) continue;
+        if (!((sh.masks[m] >> i) & 1)) continue;
         sel.push_back({i, m, e});
-        for (size_t k = 0; k < widths[m]; k++, e++) a[i] = bb::e_add(a[i], bb::e_mul_m(gp[e], get_m(ys + 4 * e)));
+        for (size_t k = 0; k < sh.widths[m]; k++, e++) a[i] = bb::e_add(a[i], bb::e_mul_m(gp[e], get_m(ys + 4 * e)));
       }
     }
   }
   const uint32_t wM = bb::root_of_unity((int)(log_n + b));
   // ---- 4 .. 11; 8: layer-0 values are F at the two rows, from all the matrices' records ----
-  return fri_part_verify(w, len, at_lroots, log_n, b, n_mats, widths, num_queries, pow_bits, ks, roots, ch, [&](size_t pos, const uint32_t* const* rows) {
+  return fri_part_verify(w, len, at_lroots, log_n, b, n_mats, sh.widths, num_queries, pow_bits, ks, roots, ch, [&](size_t pos, const uint32_t* const* rows) {
     const uint32_t x_m = bb::to_mont(bb::mul(bb::GEN, bb::pow(wM, pos)));
     E4 A[2] = {bb::e_zero(), bb::e_zero()};
     for (const Sel& s : sel)
-      for (size_t k = 0; k < widths[s.m]; k++) A[s.i] = bb::e_add(A[s.i], bb::e_mul_fm(gp[s.e + k], rows[s.m][k]));
+      for (size_t k = 0; k < sh.widths[s.m]; k++) A[s.i] = bb::e_add(A[s.i], bb::e_mul_fm(gp[s.e + k], rows[s.m][k]));
     E4 F = bb::e_zero();
     for (uint32_t i = 0; i < n_points; i++) {
       E4 d = z[i]; d.c[0] = bb::sub(d.c[0], x_m);
@@ -1391,6 +1311,52 @@ int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
     }
     return F;
   });
+}
+
+}  // namespace
+
+uint64_t zkir_batch_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t n_mats, const uint32_t* widths, const uint32_t* masks, uint32_t n_points, uint32_t num_queries) {
+  BatchShape sh;
+  if (!widths || !masks || !batch_shape_ok(n_mats, n_points, widths, masks, &sh)) return 0;
+  const uint64_t ld = zkir_lowdeg_proof_words(log_n, log_blowup, 1, num_queries);      // one matrix of one column: 12 header and root words, 2 (1 + 4 log_M) record words a query
+  if (ld == 0) return 0;
+  const uint64_t log_M = (uint64_t)log_n + log_blowup;
+  return ld - 12 + 9 + 6 * (uint64_t)n_mats + 4 * (uint64_t)n_points + 4 * sh.n_evals + (uint64_t)num_queries * (2 * sh.sum_width - 2 + 8 * log_M * (n_mats - 1));
+}
+
+// the batch of one matrix with a full mask, less its (width, mask) pair
+uint64_t zkir_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t n_points, uint32_t num_queries) {
+  if (n_points < 1 || n_points > 2) return 0;
+  const uint32_t mask = (1u << n_points) - 1;
+  const uint64_t words = zkir_batch_eval_proof_words(log_n, log_blowup, 1, &width, &mask, n_points, num_queries);
+  return words ? words - 2 : 0;
+}
+
+int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  // ---- 1: shape ----
+  if (!w || len < 9 || w[0] != 0x56454B5Au || w[1] != 1) return 1;
+  const uint32_t log_n = w[2], b = w[3], width = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
+  if (n_points < 1 || n_points > 2) return 1;
+  const uint32_t mask = (1u << n_points) - 1;                               // one matrix is opened at every point
+  BatchShape sh;
+  if (!batch_shape_ok(1, n_points, &width, &mask, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  if (w[8] != (uint32_t)ks.size() || len != zkir_eval_proof_words(log_n, b, width, n_points, num_queries)) return 1;
+  return eval_core_verify(sh, 9, w, len, ks, expect_root, expect_points, expect_evals);
+}
+
+int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  // ---- 1: shape ----
+  if (!w || len < 9 || w[0] != 0x45424B5Au || w[1] != 1) return 1;
+  const uint32_t log_n = w[2], b = w[3], n_mats = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
+  if (n_mats < 1 || n_mats > 4 || n_points < 1 || n_points > 2 || len < 9 + 2 * (uint64_t)n_mats) return 1;
+  uint32_t widths[4], masks[4];
+  for (uint32_t m = 0; m < n_mats; m++) { widths[m] = w[9 + 2 * m]; masks[m] = w[10 + 2 * m]; }
+  BatchShape sh;
+  if (!batch_shape_ok(n_mats, n_points, widths, masks, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
+  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  if (w[8] != (uint32_t)ks.size() || len != zkir_batch_eval_proof_words(log_n, b, n_mats, widths, masks, n_points, num_queries)) return 1;
+  return eval_core_verify(sh, 9 + 2 * (size_t)n_mats, w, len, ks, expect_roots, expect_points, expect_evals);
 }
 
 }  // extern "C"

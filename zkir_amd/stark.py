@@ -213,29 +213,47 @@ def merkle_verify(ctx: StarkContext, root: torch.Tensor, width: int, n_leaves: i
 lowdeg_proof_words = rt.lowdeg_proof_words
 
 
+def _matrix_width(name: str, ctx: StarkContext, lde_mat: torch.Tensor, width: Optional[int]) -> int:
+    """the real columns of a B8 matrix (default all); ValueError for a matrix that is not of the context's size or does not have them"""
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    if lde_mat.dim() != 3 or lde_mat.shape[1] != m or lde_mat.shape[2] != 8 or lde_mat.dtype != torch.int32 or not lde_mat.is_contiguous():
+        raise ValueError(f"{name}: the matrix must be contiguous int32[blocks][{m}][8], the context's extension size")
+    width = lde_mat.shape[0] * 8 if width is None else int(width)
+    if width > lde_mat.shape[0] * 8:
+        raise ValueError(f"{name}: width exceeds the matrix's columns")
+    return width
+
+
+def _check_tree(name: str, ctx: StarkContext, tree: torch.Tensor, the: str = "the") -> None:
+    """ValueError unless the tree is merkle_commit's over the context's leaves"""
+    m = 1 << (ctx.log_n + ctx.log_blowup)
+    if tree.dtype != torch.int32 or not tree.is_contiguous() or tree.numel() != 4 * (2 * m - 1):
+        raise ValueError(f"{name}: {the} tree must be contiguous int32[{4 * (2 * m - 1)}], merkle_commit's over {m} leaves")
+
+
+def _prove_call(entry: str, n_stages: int, args: tuple, cap: int, stream, want_stage_ms: bool):
+    """the tail of a prove call: a buffer of `cap` words, the entry or its _stages variant (n_stages device ms), the proof cut to the words written"""
+    out = np.zeros(max(cap, 1), np.uint32)
+    n_words = C.c_uint64()
+    args = (*args, out.ctypes.data, cap, C.byref(n_words))
+    if want_stage_ms:
+        ms = (C.c_float * n_stages)()
+        pl._check(getattr(rt.lib(), entry + "_stages")(*args, ms, _sp(stream)))
+        return out[:n_words.value], [float(x) for x in ms]
+    pl._check(getattr(rt.lib(), entry)(*args, _sp(stream)))
+    return out[:n_words.value]
+
+
 def lowdeg_prove(ctx: StarkContext, lde_mat: torch.Tensor, tree: torch.Tensor, width: Optional[int] = None, num_queries: int = 50, pow_bits: int = 12, stream=None,
                  want_stage_ms: bool = False):
     """zkir_lowdeg_prove: the low-degree proof (np.uint32 words) of the commitment `tree` (merkle_commit's) to the B8 matrix `lde_mat` (lde's output on `ctx`, `width` real
     columns, default all): every column is close to a polynomial of degree < 2^ctx.log_n — no constraint, no opening at a point.  Works at every rate a context serves.
     A matrix or tree that is not of the context's size raises ValueError; the library refuses bad parameters with ERR_ARGUMENT before any launch.
     want_stage_ms: also the device ms of (combine, FRI commit phase, grinding, query section)."""
-    m = 1 << (ctx.log_n + ctx.log_blowup)
-    if lde_mat.dim() != 3 or lde_mat.shape[1] != m or lde_mat.shape[2] != 8 or lde_mat.dtype != torch.int32 or not lde_mat.is_contiguous():
-        raise ValueError(f"lowdeg_prove: the matrix must be contiguous int32[blocks][{m}][8], the context's extension size")
-    if tree.dtype != torch.int32 or not tree.is_contiguous() or tree.numel() != 4 * (2 * m - 1):
-        raise ValueError(f"lowdeg_prove: the tree must be contiguous int32[{4 * (2 * m - 1)}], merkle_commit's over {m} leaves")
-    width = lde_mat.shape[0] * 8 if width is None else int(width)
-    if width > lde_mat.shape[0] * 8:
-        raise ValueError("lowdeg_prove: width exceeds the matrix's columns")
+    width = _matrix_width("lowdeg_prove", ctx, lde_mat, width)
+    _check_tree("lowdeg_prove", ctx, tree)
     cap = lowdeg_proof_words(ctx.log_n, ctx.log_blowup, width, num_queries)
-    out = np.zeros(max(cap, 1), np.uint32)
-    n_words = C.c_uint64()
-    if want_stage_ms:
-        ms = (C.c_float * 4)()
-        pl._check(rt.lib().zkir_lowdeg_prove_stages(ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words), ms, _sp(stream)))
-        return out[:n_words.value], [float(x) for x in ms]
-    pl._check(rt.lib().zkir_lowdeg_prove(ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words), _sp(stream)))
-    return out[:n_words.value]
+    return _prove_call("zkir_lowdeg_prove", 4, (ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), int(num_queries), int(pow_bits)), cap, stream, want_stage_ms)
 
 
 lowdeg_verify = rt.lowdeg_verify
@@ -261,12 +279,7 @@ eval_verify = rt.eval_verify
 
 def _eval_args(name: str, ctx: StarkContext, lde_mat: torch.Tensor, width: Optional[int], points):
     """(width, points uint32[n_points][4]) of an evaluation call; ValueError for a matrix that is not of the context's size or points that are not rows of four words"""
-    m = 1 << (ctx.log_n + ctx.log_blowup)
-    if lde_mat.dim() != 3 or lde_mat.shape[1] != m or lde_mat.shape[2] != 8 or lde_mat.dtype != torch.int32 or not lde_mat.is_contiguous():
-        raise ValueError(f"{name}: the matrix must be contiguous int32[blocks][{m}][8], the context's extension size")
-    width = lde_mat.shape[0] * 8 if width is None else int(width)
-    if width > lde_mat.shape[0] * 8:
-        raise ValueError(f"{name}: width exceeds the matrix's columns")
+    width = _matrix_width(name, ctx, lde_mat, width)
     pts = np.ascontiguousarray(points, dtype=np.uint32)
     if pts.ndim != 2 or pts.shape[1] != 4:
         raise ValueError(f"{name}: points must be [n_points][4] canonical words")
@@ -281,19 +294,9 @@ def eval_prove(ctx: StarkContext, lde_mat: torch.Tensor, tree: torch.Tensor, wid
     context's size raises ValueError; the library refuses bad parameters and points with ERR_ARGUMENT before any launch.
     want_stage_ms: also the device ms of (weights, evaluations, quotient, FRI commit phase, grinding, query section)."""
     width, pts = _eval_args("eval_prove", ctx, lde_mat, width, points)
-    m = 1 << (ctx.log_n + ctx.log_blowup)
-    if tree.dtype != torch.int32 or not tree.is_contiguous() or tree.numel() != 4 * (2 * m - 1):
-        raise ValueError(f"eval_prove: the tree must be contiguous int32[{4 * (2 * m - 1)}], merkle_commit's over {m} leaves")
+    _check_tree("eval_prove", ctx, tree)
     cap = eval_proof_words(ctx.log_n, ctx.log_blowup, width, len(pts), num_queries)
-    out = np.zeros(max(cap, 1), np.uint32)
-    n_words = C.c_uint64()
-    args = (ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), pts.ctypes.data, len(pts), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words))
-    if want_stage_ms:
-        ms = (C.c_float * 6)()
-        pl._check(rt.lib().zkir_eval_prove_stages(*args, ms, _sp(stream)))
-        return out[:n_words.value], [float(x) for x in ms]
-    pl._check(rt.lib().zkir_eval_prove(*args, _sp(stream)))
-    return out[:n_words.value]
+    return _prove_call("zkir_eval_prove", 6, (ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), pts.ctypes.data, len(pts), int(num_queries), int(pow_bits)), cap, stream, want_stage_ms)
 
 
 def eval_at(ctx: StarkContext, lde_mat: torch.Tensor, points, width: Optional[int] = None, stream=None) -> torch.Tensor:
@@ -361,23 +364,14 @@ def batch_eval_prove(ctx: StarkContext, mats, trees, widths, masks, points, num_
     want_stage_ms: also the device ms of (weights, evaluations, quotient, FRI commit phase, grinding, query section)."""
     ws, ks, pts, mat_ptrs = _batch_args("batch_eval_prove", ctx, mats, widths, masks, points)
     trees = list(trees)
-    m = 1 << (ctx.log_n + ctx.log_blowup)
     if len(trees) != len(ws):
         raise ValueError("batch_eval_prove: trees must have one entry per matrix")
     for tree in trees:
-        if tree.dtype != torch.int32 or not tree.is_contiguous() or tree.numel() != 4 * (2 * m - 1):
-            raise ValueError(f"batch_eval_prove: a tree must be contiguous int32[{4 * (2 * m - 1)}], merkle_commit's over {m} leaves")
+        _check_tree("batch_eval_prove", ctx, tree, "a")
     tree_ptrs = (C.c_void_p * max(len(trees), 1))(*[t.data_ptr() for t in trees])
     cap = batch_eval_proof_words(ctx.log_n, ctx.log_blowup, ws, ks, len(pts), num_queries)
-    out = np.zeros(max(cap, 1), np.uint32)
-    n_words = C.c_uint64()
-    args = (ctx.handle, len(ws), mat_ptrs, ws.ctypes.data, tree_ptrs, ks.ctypes.data, pts.ctypes.data, len(pts), int(num_queries), int(pow_bits), out.ctypes.data, cap, C.byref(n_words))
-    if want_stage_ms:
-        ms = (C.c_float * 6)()
-        pl._check(rt.lib().zkir_batch_eval_prove_stages(*args, ms, _sp(stream)))
-        return out[:n_words.value], [float(x) for x in ms]
-    pl._check(rt.lib().zkir_batch_eval_prove(*args, _sp(stream)))
-    return out[:n_words.value]
+    return _prove_call("zkir_batch_eval_prove", 6, (ctx.handle, len(ws), mat_ptrs, ws.ctypes.data, tree_ptrs, ks.ctypes.data, pts.ctypes.data, len(pts), int(num_queries), int(pow_bits)), cap,
+                       stream, want_stage_ms)
 
 
 def batch_eval_quotient(ctx: StarkContext, mats, gamma, points, evals, widths, masks, stream=None) -> torch.Tensor:
