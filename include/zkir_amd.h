@@ -464,6 +464,18 @@ int zkir_batch_eval_prove(zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* 
                           void* hip_stream);
 int zkir_batch_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals);
 
+/* VERIFYING ON THE DEVICE.  zkir_lowdeg_verify, zkir_eval_verify and zkir_batch_eval_verify with checks 7 - 11 of ALL the queries run on the current HIP device: one leaf-and-
+ * path job per matrix record and FRI layer (a row of 16 lanes each), the layer-0 values and the folds in a second kernel.  Everything else — the shape, the expectations, the
+ * word range, the whole transcript, the final layer's degree, grinding, the sampling of the rows, check 6 — is the host entries' own code in its order, and the device is
+ * used only after checks 1 and 3 have passed: every extent a kernel uses comes from the checked header, the row it opens is the transcript's sample.
+ * The verdict is the host entry's for every input: 0, or the same check's number, first failing check, lowest query first.  A NEGATIVE result is no verdict:
+ * -ZKIR_ERR_DEVICE (no usable device, a failed HIP call) or -ZKIR_ERR_OTHER (no host memory); zkir_last_error says which.  proof and the expectations are HOST memory.  No
+ * context: the entries use zkir_verify_device's per-device state (device block grown on demand, pinned staging), so calls on one device are serialised inside.  One staged
+ * upload, two launches, one download and one synchronisation on hip_stream; nothing is launched when the verdict is 1 - 5, 12 or 13. */
+int zkir_lowdeg_verify_device(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root, void* hip_stream);
+int zkir_eval_verify_device(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals, void* hip_stream);
+int zkir_batch_eval_verify_device(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, void* hip_stream);
+
 /* Public inputs of a proof: absorbed by the Fiat-Shamir transcript before the first commitment and carried in the proof header. */
 typedef struct zkir_public_inputs {
   uint64_t n_real;             /* executed rows = ExecutionResult.cycles */

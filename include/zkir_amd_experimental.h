@@ -58,6 +58,14 @@ uint64_t zkir_batch_eval_quotient_scratch_words(uint32_t log_m, uint32_t n_mats,
 int zkir_batch_eval_quotient_launch(const zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* const* lde_mats, const uint32_t* widths, const uint32_t* masks, const uint32_t gamma[4],
                                     const uint32_t* points, uint32_t n_points, const uint32_t* evals, uint32_t* scratch, uint32_t* cw, void* hip_stream);
 
+/* DIAGNOSTIC: what the calling thread's last zkir_lowdeg_verify_device / zkir_eval_verify_device / zkir_batch_eval_verify_device call launched: hash_jobs = num_queries x
+ * (2 n_mats + n_layers) leaf-and-path jobs, value_jobs = num_queries x (2 + n_layers) (two layer-0 values and one fold a layer); (0, 0) when the call returned before its
+ * query stage (verdicts 1 - 5, 12, 13).  Either pointer may be NULL. */
+int zkir_pcs_verify_last_jobs(uint64_t* hash_jobs, uint64_t* value_jobs);
+/* MEASUREMENT: with ZKIR_PCS_VERIFY_TIMES set in the environment the device query stage synchronises after its upload and after its kernels; this reports the host clocks
+ * (ms) of the calling thread's last such call: upload | kernels | download.  Zeros without the variable or before the stage. */
+int zkir_pcs_verify_last_stage_ms(double ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

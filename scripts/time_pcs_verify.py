@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""Host against device verification of the commitment layer's three proofs, in one process, on the proofs of time_lowdeg.py, time_eval.py and time_batch_eval.py: a matrix of
+2^log_n rows x 152 columns ('ZKLD'; 'ZKEV' at two points) and the three-matrix batch 152 / 40 / 8 ('ZKBE'), committed at blow-up 2, 4, 8 (num_queries 50 / 25 / 17, 12
+grinding bits).  The host entry and the device entry ALTERNATE, call by call, after a warm-up; every figure is a median (min .. max) of wall ms over --calls calls each.
+A second loop with ZKIR_PCS_VERIFY_TIMES set (the stage then synchronises after its upload and after its kernels) splits the device entry into host part | upload | kernels |
+download.  Writes what profiles/r16_pcs_verify_device.txt records.
+
+    python scripts/time_pcs_verify.py [--log-n 20] [--calls 200] [--out FILE]
+"""
+import argparse, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from scripts.time_lowdeg import POW_BITS, QUERIES, _mmm            # noqa: E402
+from scripts.time_eval import POINTS                                 # noqa: E402
+from scripts.time_batch_eval import WIDTHS, MASKS                    # noqa: E402
+
+W = 152
+
+
+def proofs_for(log_n, b):
+    """[(name, host call, device call, proof words, hash jobs)] on matrices committed on a context of its own"""
+    import numpy as np, torch
+    from zkir_amd import runtime as rt, stark
+    ctx = stark.StarkContext(log_n, b)
+    g = torch.Generator(device="cuda"); g.manual_seed(20 + b)
+    def committed(width):
+        mat = stark.lde(ctx, torch.randint(0, stark.P, ((width + 7) // 8, 1 << log_n, 8), dtype=torch.int32, device="cuda", generator=g), clobber=True)
+        return mat, stark.merkle_commit(ctx, mat, width)
+    pairs = [committed(w) for w in WIDTHS]
+    mats, trees = [p[0] for p in pairs], [p[1] for p in pairs]
+    roots = np.concatenate([t[-4:].cpu().numpy().view(np.uint32) for t in trees])
+    pts, nq = np.array(POINTS, np.uint32), QUERIES[b]
+    ld = stark.lowdeg_prove(ctx, mats[0], trees[0], W, nq, POW_BITS)
+    ev = stark.eval_prove(ctx, mats[0], trees[0], W, pts, nq, POW_BITS)
+    be = stark.batch_eval_prove(ctx, mats, trees, WIDTHS, MASKS, pts, nq, POW_BITS)
+    ctx.close(); del mats, trees, pairs
+    torch.cuda.empty_cache()
+    return [("lowdeg", lambda d: rt.lowdeg_verify(ld, roots[:4], device=d), len(ld)),
+            ("eval", lambda d: rt.eval_verify(ev, roots[:4], pts, device=d), len(ev)),
+            ("batch_eval", lambda d: rt.batch_eval_verify(be, roots, pts, device=d), len(be))]
+
+
+def measure(call, calls):
+    from zkir_amd import runtime as rt
+    for _ in range(10):
+        assert call(False) == 0 and call(True) == 0
+    jobs = rt.pcs_verify_last_jobs()
+    host, dev = [], []
+    for _ in range(calls):                                          # alternating: a drift of the machine meets both alike
+        t0 = time.perf_counter(); rc = call(False); host.append((time.perf_counter() - t0) * 1e3); assert rc == 0
+        t0 = time.perf_counter(); rc = call(True); dev.append((time.perf_counter() - t0) * 1e3); assert rc == 0
+    os.environ["ZKIR_PCS_VERIFY_TIMES"] = "1"
+    parts = []
+    for _ in range(calls):
+        t0 = time.perf_counter(); rc = call(True); dt = (time.perf_counter() - t0) * 1e3; assert rc == 0
+        up, kern, down = rt.pcs_verify_last_stage_ms()
+        parts.append((dt - up - kern - down, up, kern, down))
+    del os.environ["ZKIR_PCS_VERIFY_TIMES"]
+    return _mmm(host), _mmm(dev), [_mmm([p[i] for p in parts]) for i in range(4)], jobs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log-n", type=int, default=20)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    lines = []
+    def say(s):
+        print(s, flush=True); lines.append(s)
+    f3 = lambda t: f"{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})"
+    say(f"# {torch.cuda.get_device_name(0)}; 2^{args.log_n} rows; lowdeg / eval: {W} columns (eval at two points); batch_eval: {WIDTHS} columns, masks {MASKS}; pow_bits {POW_BITS}; "
+        f"host and device entries alternating, {args.calls} calls each after 10 warm-up pairs; wall ms, median (min .. max)")
+    say(f"{'proof':>10s} {'b':>2s} {'q':>3s} {'words':>7s} {'hash jobs':>9s} | {'host entry ms':>24s} | {'device entry ms':>24s} | device median < host min | "
+        f"device entry split (stage synchronising): {'host part':>22s} | {'upload':>22s} | {'kernels':>22s} | {'download':>22s}")
+    for b in (1, 2, 3):
+        for name, call, words in proofs_for(args.log_n, b):
+            host, dev, parts, jobs = measure(call, args.calls)
+            say(f"{name:>10s} {b:2d} {QUERIES[b]:3d} {words:7d} {jobs[0]:9d} | {f3(host):>24s} | {f3(dev):>24s} | {'yes' if dev[0] < host[1] else 'NO':>23s} | "
+                + " " * 43 + " | ".join(f"{f3(p):>22s}" for p in parts))
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

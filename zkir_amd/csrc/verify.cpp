@@ -1092,44 +1092,44 @@ bool lowdeg_params_ok(uint32_t log_n, uint32_t b, uint32_t width, uint32_t num_q
   return log_n >= 3 && log_n <= 26 && b >= 1 && b <= 3 && log_n + b <= 27 && width >= 1 && width <= 512 && num_queries >= 1 && num_queries <= 128;
 }
 
-// What zkir_lowdeg_verify, zkir_eval_verify and zkir_batch_eval_verify share: checks 4 .. 11 of a proof whose FRI part (layer roots | final layer | nonce | queries) starts at
-// word `at_lroots`.  A query opens n_mats (1 .. FRI_PART_MAX_MATS) matrices of widths[m] columns under roots[4 m ..]: record_m(q), record_m(q + M/2) matrix by matrix.
-// The caller has checked the shape and the words' range and hands over the transcript as it stands once gamma is drawn; layer0_want(pos, rows) is the value (Montgomery E4)
-// the codeword has at row `pos` of the domain, computed from that row's opened words (rows[m]: matrix m's widths[m] words) — the one thing the proofs disagree about.
-constexpr uint32_t FRI_PART_MAX_MATS = 4;
-template <class Layer0>
-int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_lroots, uint32_t log_n, uint32_t b, uint32_t n_mats, const uint32_t* widths, uint32_t num_queries, uint32_t pow_bits,
-                    const std::vector<int>& ks, const uint32_t* roots, Challenger& ch, Layer0&& layer0_want) {
-  const int n_layers = (int)ks.size();
-  const int log_M = (int)(log_n + b);
-  const size_t M = (size_t)1 << log_M, n_fin = (size_t)4 << b;
-  const uint32_t* lroots = w + at_lroots;
-  const size_t at_fin = at_lroots + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1;
-  auto get_m = [&](size_t at) { return bb::e_to_mont(E4{{w[at], w[at + 1], w[at + 2], w[at + 3]}}); };
-  std::vector<E4> fin(n_fin);
-  for (size_t i = 0; i < n_fin; i++) fin[i] = get_m(at_fin + 4 * i);
-  // ---- 4: the final layer has degree < 4: coefficients 4 .. n_fin - 1 of its interpolant vanish (a plain inverse DFT decides: the coset shift scales coefficient k by
-  //         shift^-k and cannot make a non-zero one vanish) ----
-  {
-    const uint32_t winv_m = bb::to_mont(bb::inv(bb::root_of_unity(2 + (int)b)));
-    for (size_t k = 4; k < n_fin; k++) {
-      E4 c = bb::e_zero();
-      uint32_t tw = bb::R1, step = bb::R1;
-      for (size_t t = 0; t < k; t++) step = bb::mont_mul(step, winv_m);     // w^-k
-      for (size_t i = 0; i < n_fin; i++) { c = bb::e_add(c, bb::e_mul_fm(fin[i], tw)); tw = bb::mont_mul(tw, step); }
-      if (c.c[0] | c.c[1] | c.c[2] | c.c[3]) return 4;
-    }
+constexpr uint32_t FRI_PART_MAX_MATS = zkir::PCS_MAX_MATS;
+
+// The layer-0 value (Montgomery E4) the codeword has at row `pos`, from that row's opened words (rows[m]: matrix m's widths[m] words), by the rule PcsQueries states as data
+E4 layer0_want(const zkir::PcsQueries& Q, size_t pos, const uint32_t* const* rows) {
+  auto gp = [&](size_t e) { return E4{{Q.gamma_m[4 * e], Q.gamma_m[4 * e + 1], Q.gamma_m[4 * e + 2], Q.gamma_m[4 * e + 3]}}; };
+  if (Q.n_points == 0) {
+    const uint32_t* row = rows[0];
+    E4 A = bb::e_zero();                                                    // canonical word x Montgomery gamma^k = canonical; lifted to Montgomery at the end
+    for (size_t k = 0; k < Q.widths[0]; k++) A = bb::e_add(A, bb::e_mul_fm(gp(k), row[k]));
+    return bb::e_to_mont(A);
   }
-  // ---- the transcript after gamma ----
-  std::vector<E4> betas(n_layers);
-  for (int j = 0; j < n_layers; j++) { ch.observe_n(lroots + 4 * j, 4); betas[j] = bb::e_to_mont(ch.sample_ext()); }
-  ch.observe_n(w + at_fin, 4 * n_fin);
-  // ---- 5: grinding ----
-  if (!ch.check_pow(w[at_nonce], (int)pow_bits)) return 5;
-  std::vector<uint32_t> qs(num_queries);
-  for (auto& q : qs) q = ch.sample_bits(log_M - 1);
-  // ---- 6 .. 11: queries ----
-  const size_t qsize = (len - at_queries) / num_queries;
+  const uint32_t x_m = bb::to_mont(bb::mul(bb::GEN, bb::pow(bb::root_of_unity((int)Q.log_M), pos)));
+  E4 A[2] = {bb::e_zero(), bb::e_zero()};
+  for (uint32_t si = 0; si < Q.n_sel; si++) {
+    const zkir::PcsQueries::Sel& s = Q.sel[si];
+    for (size_t k = 0; k < Q.widths[s.mat]; k++) A[s.point] = bb::e_add(A[s.point], bb::e_mul_fm(gp(s.e0 + k), rows[s.mat][k]));
+  }
+  E4 F = bb::e_zero();
+  for (uint32_t i = 0; i < Q.n_points; i++) {
+    E4 z, a; memcpy(z.c, Q.z_m[i], 16); memcpy(a.c, Q.a_m[i], 16);
+    E4 d = z; d.c[0] = bb::sub(d.c[0], x_m);
+    F = bb::e_add(F, bb::e_mul_m(bb::e_sub(a, bb::e_to_mont(A[i])), bb::e_inv_m(d)));
+  }
+  return F;
+}
+
+// The host form of the query stage (verify_stages.h): checks 6 .. 11, query after query
+int host_query_run(void*, const zkir::PcsQueries& Q) {
+  const uint32_t* w = Q.w;
+  const int n_layers = (int)Q.n_layers, log_M = (int)Q.log_M;
+  const size_t M = (size_t)1 << log_M, n_fin = (size_t)4 << Q.b, at_queries = (size_t)Q.at_queries, qsize = (size_t)Q.qsize;
+  const uint32_t n_mats = Q.n_mats;
+  const uint32_t *widths = Q.widths, *roots = w + Q.at_roots, *lroots = w + Q.at_lroots, *qs = Q.qs;
+  const uint32_t* ks = Q.ks;
+  auto get_m = [&](size_t at) { return bb::e_to_mont(E4{{w[at], w[at + 1], w[at + 2], w[at + 3]}}); };
+  std::vector<E4> fin(n_fin), betas(n_layers);
+  for (size_t i = 0; i < n_fin; i++) fin[i] = get_m((size_t)Q.at_fin + 4 * i);
+  for (int j = 0; j < n_layers; j++) memcpy(betas[j].c, Q.betas_m + 4 * j, 16);
   auto check_query = [&](int t) -> int {
     size_t p = at_queries + (size_t)t * qsize;
     const uint32_t q = qs[t];
@@ -1145,7 +1145,7 @@ int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_lroots, uint32_t 
         p += (size_t)widths[m] + 4 * (size_t)log_M;
       }
     E4 comb[2];
-    for (int s2 = 0; s2 < 2; s2++) comb[s2] = layer0_want((size_t)q + (s2 ? M / 2 : 0), rows[s2]);
+    for (int s2 = 0; s2 < 2; s2++) comb[s2] = layer0_want(Q, (size_t)q + (s2 ? M / 2 : 0), rows[s2]);
     E4 carried = bb::e_zero(); size_t carried_idx = q;
     uint32_t shift = bb::GEN; int log_m = log_M;
     for (int j = 0; j < n_layers; j++) {
@@ -1172,8 +1172,55 @@ int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_lroots, uint32_t 
     return 0;
   };
   // (the queries are independent; checked one after the other: a proof has at most 128 of them and its verdict is this loop's)
-  for (int t = 0; t < (int)num_queries; t++) { const int code = check_query(t); if (code) return code; }
+  for (int t = 0; t < (int)Q.num_queries; t++) { const int code = check_query(t); if (code) return code; }
   return 0;
+}
+
+// What zkir_lowdeg_verify, zkir_eval_verify and zkir_batch_eval_verify (and their *_device forms) share: checks 4 .. 11 of a proof whose FRI part (layer roots | final layer |
+// nonce | queries) starts at word `at_lroots`.  A query opens n_mats (1 .. FRI_PART_MAX_MATS) matrices of widths[m] columns under the roots at word at_roots: record_m(q),
+// record_m(q + M/2) matrix by matrix.  The caller has checked the shape and the words' range, hands over the transcript as it stands once gamma is drawn, and has filled Q's
+// layer-0 rule (n_points, the gamma table, the selected pairs, z, a) — the one thing the proofs disagree about.  Checks 4 and 5 and the sampling are here; checks 6 .. 11 are
+// the stage's (verify_stages.h).
+int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_roots, size_t at_lroots, uint32_t log_n, uint32_t b, uint32_t n_mats, const uint32_t* widths, uint32_t num_queries, uint32_t pow_bits,
+                    const std::vector<int>& ks, Challenger& ch, zkir::PcsQueries& Q, const zkir::QueryStage& stage) {
+  const int n_layers = (int)ks.size();
+  const int log_M = (int)(log_n + b);
+  const size_t n_fin = (size_t)4 << b;
+  const uint32_t* lroots = w + at_lroots;
+  const size_t at_fin = at_lroots + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1;
+  auto get_m = [&](size_t at) { return bb::e_to_mont(E4{{w[at], w[at + 1], w[at + 2], w[at + 3]}}); };
+  std::vector<E4> fin(n_fin);
+  for (size_t i = 0; i < n_fin; i++) fin[i] = get_m(at_fin + 4 * i);
+  // ---- 4: the final layer has degree < 4: coefficients 4 .. n_fin - 1 of its interpolant vanish (a plain inverse DFT decides: the coset shift scales coefficient k by
+  //         shift^-k and cannot make a non-zero one vanish) ----
+  {
+    const uint32_t winv_m = bb::to_mont(bb::inv(bb::root_of_unity(2 + (int)b)));
+    for (size_t k = 4; k < n_fin; k++) {
+      E4 c = bb::e_zero();
+      uint32_t tw = bb::R1, step = bb::R1;
+      for (size_t t = 0; t < k; t++) step = bb::mont_mul(step, winv_m);     // w^-k
+      for (size_t i = 0; i < n_fin; i++) { c = bb::e_add(c, bb::e_mul_fm(fin[i], tw)); tw = bb::mont_mul(tw, step); }
+      if (c.c[0] | c.c[1] | c.c[2] | c.c[3]) return 4;
+    }
+  }
+  // ---- the transcript after gamma ----
+  std::vector<E4> betas(n_layers);
+  for (int j = 0; j < n_layers; j++) { ch.observe_n(lroots + 4 * j, 4); betas[j] = bb::e_to_mont(ch.sample_ext()); }
+  ch.observe_n(w + at_fin, 4 * n_fin);
+  // ---- 5: grinding ----
+  if (!ch.check_pow(w[at_nonce], (int)pow_bits)) return 5;
+  std::vector<uint32_t> qs(num_queries);
+  for (auto& q : qs) q = ch.sample_bits(log_M - 1);
+  // ---- 6 .. 11: the query stage ----
+  if (n_layers > (int)zkir::PCS_MAX_LAYERS || n_mats > zkir::PCS_MAX_MATS) return 1;      // (no header that passed check 1 states either)
+  Q.w = w; Q.len = len;
+  Q.log_M = (uint32_t)log_M; Q.b = b; Q.n_mats = n_mats; Q.n_layers = (uint32_t)n_layers; Q.num_queries = num_queries;
+  for (uint32_t m = 0; m < n_mats; m++) Q.widths[m] = widths[m];
+  for (int j = 0; j < n_layers; j++) Q.ks[j] = (uint32_t)ks[j];
+  Q.at_roots = at_roots; Q.at_lroots = at_lroots; Q.at_fin = at_fin; Q.at_queries = at_queries; Q.qsize = (len - at_queries) / num_queries;
+  Q.qs = qs.data(); Q.betas_m = betas[0].c;
+  static_assert(sizeof(E4) == 16, "a vector of E4 is read as 4 words an element");
+  return stage.run(stage.self, Q);
 }
 
 }  // namespace
@@ -1189,7 +1236,8 @@ uint64_t zkir_lowdeg_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t w
   return 12 + 4 * (uint64_t)ks.size() + 4 * ((uint64_t)4 << log_blowup) + 1 + (uint64_t)num_queries * qsize;
 }
 
-int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root) {
+namespace {
+int lowdeg_verify_impl(const uint32_t* w, uint64_t len, const uint32_t* expect_root, const zkir::QueryStage& stage) {
   // ---- 1: shape ----
   if (!w || len < 12 || w[0] != 0x444C4B5Au || w[1] != 1) return 1;
   const uint32_t log_n = w[2], b = w[3], width = w[4], num_queries = w[5], pow_bits = w[6];
@@ -1210,13 +1258,13 @@ int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_r
   gp[0] = bb::e_one_m();
   for (size_t k = 1; k < width; k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
   // ---- 4 .. 11; 8: layer-0 values are sum gamma^k row ----
-  return fri_part_verify(w, len, 12, log_n, b, 1, &width, num_queries, pow_bits, ks, root, ch, [&](size_t, const uint32_t* const* rows) {
-    const uint32_t* row = rows[0];
-    E4 A = bb::e_zero();                                                    // canonical word x Montgomery gamma^k = canonical; lifted to Montgomery at the end
-    for (size_t k = 0; k < width; k++) A = bb::e_add(A, bb::e_mul_fm(gp[k], row[k]));
-    return bb::e_to_mont(A);
-  });
+  zkir::PcsQueries Q{};
+  Q.n_points = 0; Q.n_sel = 0; Q.n_gamma = width; Q.gamma_m = gp[0].c;
+  return fri_part_verify(w, len, 8, 12, log_n, b, 1, &width, num_queries, pow_bits, ks, ch, Q, stage);
 }
+}  // namespace
+
+int zkir_lowdeg_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root) { return lowdeg_verify_impl(w, len, expect_root, zkir::host_query_stage()); }
 
 // ================================================================================================
 // zkir_eval_verify and zkir_batch_eval_verify — the verifiers of an EVALUATION PROOF (zkir_eval_prove / zkir_batch_eval_prove, eval_open.inl).  Host only.
@@ -1261,7 +1309,7 @@ bool batch_shape_ok(uint32_t n_mats, uint32_t n_points, const uint32_t* widths, 
 
 // Everything after check 1 of either header: the roots section starts at word at_roots, the shape and the length are checked, ks is the schedule of (log_n, b).
 int eval_core_verify(const BatchShape& sh, size_t at_roots, const uint32_t* w, uint64_t len, const std::vector<int>& ks, const uint32_t* expect_roots, const uint32_t* expect_points,
-                     const uint32_t* expect_evals) {
+                     const uint32_t* expect_evals, const zkir::QueryStage& stage) {
   const uint32_t log_n = w[2], b = w[3], n_mats = sh.n_mats, n_points = sh.n_points, num_queries = w[6], pow_bits = w[7];
   const uint32_t *roots = w + at_roots, *pts = roots + 4 * (size_t)n_mats, *ys = pts + 4 * (size_t)n_points;
   const size_t at_lroots = at_roots + 4 * (size_t)n_mats + 4 * (size_t)n_points + 4 * (size_t)sh.n_evals;
@@ -1282,8 +1330,7 @@ int eval_core_verify(const BatchShape& sh, size_t at_roots, const uint32_t* w, u
   std::vector<E4> gp((size_t)sh.n_evals);
   gp[0] = bb::e_one_m();
   for (size_t k = 1; k < gp.size(); k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
-  struct Sel { uint32_t i, m; size_t e; };                                  // the selected (point, matrix) pairs in the exponent order
-  std::vector<Sel> sel;
+  zkir::PcsQueries Q{};                                                     // the selected (point, matrix) pairs in the exponent order
   E4 z[2], a[2];
   {
     size_t e = 0;
@@ -1292,25 +1339,15 @@ int eval_core_verify(const BatchShape& sh, size_t at_roots, const uint32_t* w, u
       a[i] = bb::e_zero();
       for (uint32_t m = 0; m < n_mats; m++) {
         if (!((sh.masks[m] >> i) & 1)) continue;
-        sel.push_back({i, m, e});
+        Q.sel[Q.n_sel++] = {i, m, (uint32_t)e};
         for (size_t k = 0; k < sh.widths[m]; k++, e++) a[i] = bb::e_add(a[i], bb::e_mul_m(gp[e], get_m(ys + 4 * e)));
       }
+      memcpy(Q.z_m[i], z[i].c, 16); memcpy(Q.a_m[i], a[i].c, 16);
     }
   }
-  const uint32_t wM = bb::root_of_unity((int)(log_n + b));
+  Q.n_points = n_points; Q.n_gamma = (uint32_t)gp.size(); Q.gamma_m = gp[0].c;
   // ---- 4 .. 11; 8: layer-0 values are F at the two rows, from all the matrices' records ----
-  return fri_part_verify(w, len, at_lroots, log_n, b, n_mats, sh.widths, num_queries, pow_bits, ks, roots, ch, [&](size_t pos, const uint32_t* const* rows) {
-    const uint32_t x_m = bb::to_mont(bb::mul(bb::GEN, bb::pow(wM, pos)));
-    E4 A[2] = {bb::e_zero(), bb::e_zero()};
-    for (const Sel& s : sel)
-      for (size_t k = 0; k < sh.widths[s.m]; k++) A[s.i] = bb::e_add(A[s.i], bb::e_mul_fm(gp[s.e + k], rows[s.m][k]));
-    E4 F = bb::e_zero();
-    for (uint32_t i = 0; i < n_points; i++) {
-      E4 d = z[i]; d.c[0] = bb::sub(d.c[0], x_m);
-      F = bb::e_add(F, bb::e_mul_m(bb::e_sub(a[i], bb::e_to_mont(A[i])), bb::e_inv_m(d)));
-    }
-    return F;
-  });
+  return fri_part_verify(w, len, at_roots, at_lroots, log_n, b, n_mats, sh.widths, num_queries, pow_bits, ks, ch, Q, stage);
 }
 
 }  // namespace
@@ -1332,7 +1369,8 @@ uint64_t zkir_eval_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t wid
   return words ? words - 2 : 0;
 }
 
-int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals) {
+namespace {
+int eval_verify_impl(const uint32_t* w, uint64_t len, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals, const zkir::QueryStage& stage) {
   // ---- 1: shape ----
   if (!w || len < 9 || w[0] != 0x56454B5Au || w[1] != 1) return 1;
   const uint32_t log_n = w[2], b = w[3], width = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
@@ -1342,10 +1380,10 @@ int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roo
   if (!batch_shape_ok(1, n_points, &width, &mask, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
   const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
   if (w[8] != (uint32_t)ks.size() || len != zkir_eval_proof_words(log_n, b, width, n_points, num_queries)) return 1;
-  return eval_core_verify(sh, 9, w, len, ks, expect_root, expect_points, expect_evals);
+  return eval_core_verify(sh, 9, w, len, ks, expect_root, expect_points, expect_evals, stage);
 }
 
-int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
+int batch_eval_verify_impl(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const zkir::QueryStage& stage) {
   // ---- 1: shape ----
   if (!w || len < 9 || w[0] != 0x45424B5Au || w[1] != 1) return 1;
   const uint32_t log_n = w[2], b = w[3], n_mats = w[4], n_points = w[5], num_queries = w[6], pow_bits = w[7];
@@ -1356,7 +1394,24 @@ int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
   if (!batch_shape_ok(n_mats, n_points, widths, masks, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
   const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
   if (w[8] != (uint32_t)ks.size() || len != zkir_batch_eval_proof_words(log_n, b, n_mats, widths, masks, n_points, num_queries)) return 1;
-  return eval_core_verify(sh, 9 + 2 * (size_t)n_mats, w, len, ks, expect_roots, expect_points, expect_evals);
+  return eval_core_verify(sh, 9 + 2 * (size_t)n_mats, w, len, ks, expect_roots, expect_points, expect_evals, stage);
+}
+}  // namespace
+
+int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  return eval_verify_impl(w, len, expect_root, expect_points, expect_evals, zkir::host_query_stage());
+}
+int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  return batch_eval_verify_impl(w, len, expect_roots, expect_points, expect_evals, zkir::host_query_stage());
 }
 
 }  // extern "C"
+
+namespace zkir {
+QueryStage host_query_stage() { return QueryStage{nullptr, host_query_run}; }
+int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage) {
+  if (kind == 0) return lowdeg_verify_impl(proof, n_words, expect_roots, stage);
+  if (kind == 1) return eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
+  return batch_eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
+}
+}  // namespace zkir

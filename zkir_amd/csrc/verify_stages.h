@@ -33,4 +33,28 @@ TapeStages host_tape_stages(HostTapes* h);
 int verify_with_stages(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, const TapeStages& stages);
 void verify_note_device_stages(uint32_t n);                      // (zkir_verify_device) how many stages of the calling thread's last verification ran on the device
 
+// ---- the QUERY STAGE of the commitment layer's verifiers (zkir_lowdeg_verify, zkir_eval_verify, zkir_batch_eval_verify and their *_device forms) ----
+// Checks 6 .. 11 of all the queries of a 'ZKLD' / 'ZKEV' / 'ZKBE' proof.  verify.cpp's fri_part_verify hands the stage what it has CHECKED (the shape: checks 1 and 3 passed,
+// so the length is exactly the header's and every word is below p) and what it has DRAWN from the transcript; verify.cpp fills the stage with its host loop (no HIP call),
+// pcs_verify.inl with two kernels.  The stage returns a verdict as above: 0, 6 .. 11 (first failing check, lowest query first), or a negative value.
+constexpr uint32_t PCS_MAX_MATS = 4, PCS_MAX_LAYERS = 9, PCS_MAX_SEL = 8;      // (log_M <= 27, the first layer folds once, the others LOG_ARITY = 3 times: at most 9 layers)
+struct PcsQueries {
+  const uint32_t* w; uint64_t len;                               // the proof
+  uint32_t log_M, b, n_mats, n_layers, num_queries;
+  uint32_t widths[PCS_MAX_MATS], ks[PCS_MAX_LAYERS];
+  uint64_t at_roots, at_lroots, at_fin, at_queries, qsize;      // word offsets: the n_mats matrix roots, the layer roots, the final layer (4 << b values), query 0; words a query
+  const uint32_t* qs;                                            // the transcript's samples, each below M / 2
+  const uint32_t* betas_m;                                       // n_layers Montgomery E4
+  // THE LAYER-0 RULE AS DATA.  n_points = 0: the value at a row is sum_k gamma^k row[k] over matrix 0 (the low-degree proof).  Else it is sum_i (a_i - A_i) / (z_i - x),
+  // x = 31 w_M^pos, A_i = the sum over the selected pairs of point i of sum_k gamma^(e0 + k) row_mat[k].  gamma_m: n_gamma Montgomery E4 powers; z_m, a_m: Montgomery E4.
+  uint32_t n_points, n_sel, n_gamma;
+  const uint32_t* gamma_m;
+  struct Sel { uint32_t point, mat, e0; } sel[PCS_MAX_SEL];
+  uint32_t z_m[2][4], a_m[2][4];
+};
+struct QueryStage { void* self; int (*run)(void* self, const PcsQueries& q); };
+QueryStage host_query_stage();                                   // the loop of verify.cpp
+// the three verifiers, by the proof's kind (0 'ZKLD', 1 'ZKEV', 2 'ZKBE'; 'ZKLD' has one root and no points): everything but the query stage is verify.cpp's host code
+int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage);
+
 }  // namespace zkir

@@ -406,6 +406,12 @@ def lib() -> C.CDLL:
         L.zkir_hash_tape_new_bytes_host.restype = C.c_int; L.zkir_hash_tape_new_bytes_host.argtypes = [V, U64, V]
         L.zkir_verify_device.restype = C.c_int; L.zkir_verify_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
         L.zkir_verify_last_stages.restype = C.c_int; L.zkir_verify_last_stages.argtypes = [V, C.POINTER(C.c_uint32)]
+    if hasattr(L, "zkir_lowdeg_verify_device"):               # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_lowdeg_verify_device.restype = C.c_int; L.zkir_lowdeg_verify_device.argtypes = [V, U64, V, V]
+        L.zkir_eval_verify_device.restype = C.c_int; L.zkir_eval_verify_device.argtypes = [V, U64, V, V, V, V]
+        L.zkir_batch_eval_verify_device.restype = C.c_int; L.zkir_batch_eval_verify_device.argtypes = [V, U64, V, V, V, V]
+        L.zkir_pcs_verify_last_jobs.restype = C.c_int; L.zkir_pcs_verify_last_jobs.argtypes = [C.POINTER(U64), C.POINTER(U64)]
+        L.zkir_pcs_verify_last_stage_ms.restype = C.c_int; L.zkir_pcs_verify_last_stage_ms.argtypes = [V]
     if hasattr(L, "zkir_merkle_open_launch"):                 # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
         L.zkir_merkle_opening_words.restype = U64; L.zkir_merkle_opening_words.argtypes = [U32, U64, U32]
         L.zkir_merkle_open_launch.restype = C.c_int; L.zkir_merkle_open_launch.argtypes = [V, V, U32, U64, V, V, U64, V, V]
@@ -679,12 +685,36 @@ def lowdeg_proof_words(log_n: int, log_blowup: int, width: int, num_queries: int
     return int(lib().zkir_lowdeg_proof_words(int(log_n), int(log_blowup), int(width), int(num_queries)))
 
 
-def lowdeg_verify(proof, root=None) -> int:
+def _pcs_verdict(rc: int) -> int:
+    """A *_verify_device result: a negative one is a device failure, not a verdict (raised)."""
+    if rc < 0:
+        _raise(-rc)
+    return int(rc)
+
+
+def pcs_verify_last_jobs():
+    """zkir_pcs_verify_last_jobs: (hash_jobs, value_jobs) this thread's last *_verify(device=True) call launched; (0, 0) when it returned before its query stage."""
+    h, v = C.c_uint64(0), C.c_uint64(0)
+    lib().zkir_pcs_verify_last_jobs(C.byref(h), C.byref(v))
+    return int(h.value), int(v.value)
+
+
+def pcs_verify_last_stage_ms():
+    """zkir_pcs_verify_last_stage_ms: (upload, kernels, download) host clocks in ms of this thread's last device query stage, measured only with ZKIR_PCS_VERIFY_TIMES set."""
+    ms = (C.c_double * 3)()
+    lib().zkir_pcs_verify_last_stage_ms(ms)
+    return float(ms[0]), float(ms[1]), float(ms[2])
+
+
+def lowdeg_verify(proof, root=None, device: bool = False, stream=None) -> int:
     """zkir_lowdeg_verify, on the host — no GPU: 0 = the proof convinces a holder of its root (or of `root`, four words, when given) that every committed column is close to a
-    polynomial of degree < 2^log_n; else the code of the first failing check (include/zkir_amd.h lists them)."""
+    polynomial of degree < 2^log_n; else the code of the first failing check (include/zkir_amd.h lists them).  device=True: zkir_lowdeg_verify_device — the same verdict,
+    checks 7 - 11 of all queries on the GPU."""
     w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
     r = None if root is None else np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
     assert r is None or len(r) == 4
+    if device:
+        return _pcs_verdict(lib().zkir_lowdeg_verify_device(w.ctypes.data if len(w) else None, len(w), r.ctypes.data if r is not None else None, stream))
     return int(lib().zkir_lowdeg_verify(w.ctypes.data if len(w) else None, len(w), r.ctypes.data if r is not None else None))
 
 
@@ -693,11 +723,11 @@ def eval_proof_words(log_n: int, log_blowup: int, width: int, n_points: int, num
     return int(lib().zkir_eval_proof_words(int(log_n), int(log_blowup), int(width), int(n_points), int(num_queries)))
 
 
-def eval_verify(proof, root=None, points=None, evals=None) -> int:
+def eval_verify(proof, root=None, points=None, evals=None, device: bool = False, stream=None) -> int:
     """zkir_eval_verify, on the host — no GPU: 0 = the proof convinces a holder of its root that every committed column is close to a polynomial of degree < 2^log_n that takes
     the proof's evaluations at the proof's points; `root` (four words), `points` ([n_points][4]) and `evals` ([n_points][width][4]), when given, must be the proof's.  Else the
     code of the first failing check (include/zkir_amd.h lists them).  The library reads as many expected words as the proof's header states: where the header is one a proof
-    can have, `points` / `evals` of another size raise ValueError."""
+    can have, `points` / `evals` of another size raise ValueError.  device=True: zkir_eval_verify_device — the same verdict, checks 7 - 11 of all queries on the GPU."""
     w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
     r = None if root is None else np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
     assert r is None or len(r) == 4
@@ -712,6 +742,8 @@ def eval_verify(proof, root=None, points=None, evals=None) -> int:
     else:
         p = e = None                                             # the proof is malformed (1) whatever is expected of it
     ptr = lambda a: a.ctypes.data if a is not None else None
+    if device:
+        return _pcs_verdict(lib().zkir_eval_verify_device(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e), stream))
     return int(lib().zkir_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
 
 
@@ -723,11 +755,12 @@ def batch_eval_proof_words(log_n: int, log_blowup: int, widths, masks, n_points:
     return int(lib().zkir_batch_eval_proof_words(int(log_n), int(log_blowup), len(ws), ws.ctypes.data, ks.ctypes.data, int(n_points), int(num_queries)))
 
 
-def batch_eval_verify(proof, roots=None, points=None, evals=None) -> int:
+def batch_eval_verify(proof, roots=None, points=None, evals=None, device: bool = False, stream=None) -> int:
     """zkir_batch_eval_verify, on the host — no GPU: 0 = the proof convinces a holder of its roots that every column of every committed matrix is close to a polynomial of
     degree < 2^log_n that takes the proof's evaluations at the points its matrix is opened at; `roots` ([n_mats][4]), `points` ([n_points][4]) and `evals` (the proof's
     evaluation words, in its exponent order), when given, must be the proof's.  Else the code of the first failing check (include/zkir_amd.h lists them).  The library reads
-    as many expected words as the proof's header states: where the header is one a proof can have, expectations of another size raise ValueError."""
+    as many expected words as the proof's header states: where the header is one a proof can have, expectations of another size raise ValueError.  device=True:
+    zkir_batch_eval_verify_device — the same verdict, checks 7 - 11 of all queries on the GPU."""
     w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
     r = None if roots is None else np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1)
     p = None if points is None else np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
@@ -745,6 +778,8 @@ def batch_eval_verify(proof, roots=None, points=None, evals=None) -> int:
     else:
         r = p = e = None                                         # the proof is malformed (1) whatever is expected of it
     ptr = lambda a: a.ctypes.data if a is not None else None
+    if device:
+        return _pcs_verdict(lib().zkir_batch_eval_verify_device(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e), stream))
     return int(lib().zkir_batch_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
 
 

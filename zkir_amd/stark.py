@@ -256,7 +256,17 @@ def lowdeg_prove(ctx: StarkContext, lde_mat: torch.Tensor, tree: torch.Tensor, w
     return _prove_call("zkir_lowdeg_prove", 4, (ctx.handle, lde_mat.data_ptr(), width, tree.data_ptr(), int(num_queries), int(pow_bits)), cap, stream, want_stage_ms)
 
 
-lowdeg_verify = rt.lowdeg_verify
+def _verify_stream(device: bool, stream):
+    """the stream a *_verify(device=True) call runs on (a torch stream, default the current one); None for the host form, which touches no GPU"""
+    return _sp(stream) if device else None
+
+
+def lowdeg_verify(proof, root=None, device: bool = False, stream=None) -> int:
+    """rt.lowdeg_verify; device=True checks the queries on the GPU, on the torch stream `stream` (default: the current one) — the same verdict."""
+    return rt.lowdeg_verify(proof, root, device=device, stream=_verify_stream(device, stream))
+
+
+pcs_verify_last_jobs = rt.pcs_verify_last_jobs
 
 
 def lowdeg_combine(ctx: StarkContext, lde_mat: torch.Tensor, gamma, width: Optional[int] = None, stream=None) -> torch.Tensor:
@@ -274,7 +284,11 @@ def lowdeg_combine(ctx: StarkContext, lde_mat: torch.Tensor, gamma, width: Optio
 
 
 eval_proof_words = rt.eval_proof_words
-eval_verify = rt.eval_verify
+
+
+def eval_verify(proof, root=None, points=None, evals=None, device: bool = False, stream=None) -> int:
+    """rt.eval_verify; device=True checks the queries on the GPU, on the torch stream `stream` (default: the current one) — the same verdict."""
+    return rt.eval_verify(proof, root, points, evals, device=device, stream=_verify_stream(device, stream))
 
 
 def _eval_args(name: str, ctx: StarkContext, lde_mat: torch.Tensor, width: Optional[int], points):
@@ -337,7 +351,11 @@ def eval_layout(proof) -> dict:
 
 
 batch_eval_proof_words = rt.batch_eval_proof_words
-batch_eval_verify = rt.batch_eval_verify
+
+
+def batch_eval_verify(proof, roots=None, points=None, evals=None, device: bool = False, stream=None) -> int:
+    """rt.batch_eval_verify; device=True checks the queries on the GPU, on the torch stream `stream` (default: the current one) — the same verdict."""
+    return rt.batch_eval_verify(proof, roots, points, evals, device=device, stream=_verify_stream(device, stream))
 
 
 def _batch_args(name: str, ctx: StarkContext, mats, widths, masks, points):
