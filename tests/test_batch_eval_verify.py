@@ -302,3 +302,11 @@ def test_proof_words():
         assert rt.batch_eval_proof_words(*args) == be.proof_words(*args) > 0
     # one matrix with a full mask: the evaluation proof's words, two more for the (width, mask) pair
     assert be.proof_words(10, 2, [152], [3], 2, 25) == ev.proof_words(10, 2, 152, 2, 25) + 2
+
+
+def test_proof_words_over_every_size_and_rate():
+    """One fixed batch shape at every (log_n, b) a proof can state: the count follows the one schedule and the one query-words function (fri_shape.h)."""
+    for log_n in range(3, 27):
+        for b in range(1, 4):
+            if log_n + b <= 27:
+                assert rt.batch_eval_proof_words(log_n, b, [8, 3], [3, 1], 2, 4) == be.proof_words(log_n, b, [8, 3], [3, 1], 2, 4) > 0, (log_n, b)

@@ -222,6 +222,20 @@ def test_proof_bytes_match_oracle_and_verify(name, n):
     ctx.close(); log.close()
 
 
+@pytest.mark.parametrize("n", [16, 64, 128])
+def test_proof_bytes_match_oracle_at_the_smallest_fri_schedules(n):
+    """zkir_prove runs the commitment layer's FRI at b = 1.  With test_proof_bytes_match_oracle_and_verify's fib at 8 and 32 rows, these sizes give every short schedule:
+    log_n = 3 .. 7 -> [1], [1, 1], [1, 2], [1, 3], [1, 3, 1] — a single layer, each fri_fold_k_kernel<K>, a short last layer.  Mode 0, word for word, accepted."""
+    from zkir_amd import stark
+    blob, log, tr, rows, opub, pub = _case("fib", n)
+    assert len(rows) == n
+    ctx = stark.StarkContext(stark.padded_log_n(n))
+    proof = stark.prove(ctx, tr, pub)
+    assert np.array_equal(proof, so.prove(rows, opub))
+    assert rt.verify(proof, pub) == 0
+    ctx.close(); log.close()
+
+
 def test_wrong_execution_is_rejected_on_the_gpu_path():
     """The GPU prover on a device trace whose values do not follow the program (patched in HBM): the proof it emits is rejected by
     both verifiers at the constraint check — a wrong ADD result, a wrong branch target."""

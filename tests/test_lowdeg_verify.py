@@ -138,6 +138,18 @@ def test_proof_words_of_bad_parameters_is_zero():
     assert rt.lowdeg_proof_words(24, 3, 1, 1) == ld.proof_words(24, 3, 1, 1) > 0
 
 
+def test_proof_words_over_every_size_and_rate():
+    """The one schedule and the one query-words function (fri_shape.h) against the reference's, at every (log_n, b) a proof can state: arithmetic only."""
+    n = 0
+    for log_n in range(3, 27):
+        for b in range(1, 4):
+            if log_n + b > 27:
+                continue
+            assert rt.lowdeg_proof_words(log_n, b, 8, 4) == ld.proof_words(log_n, b, 8, 4) > 0, (log_n, b)
+            n += 1
+    assert n == 24 + 23 + 22
+
+
 # ---- rejection: every code, the product's verdict = the reference's = the one named -------------------------------------------------------------------
 def _bump(pr, at, d=1):
     t = pr.copy()

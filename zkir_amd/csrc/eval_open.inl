@@ -1,5 +1,5 @@
 // eval_open.inl — zkir_batch_eval_prove and zkir_eval_prove (include/zkir_amd.h): AN EVALUATION PROOF OF ONE OR SEVERAL COMMITMENTS OF ONE HEIGHT, at any rate the context
-// serves (log_blowup 1, 2, 3).  Included by stark.hip at file scope after lowdeg.inl, whose sections 2 - 4 (FRI commit phase, grinding, queries: lowdeg_fri_and_queries) it
+// serves (log_blowup 1, 2, 3).  Included by stark.hip at file scope after lowdeg.inl, whose sections 2 - 4 (fri.inl's FRI commit phase and grinding, the queries: lowdeg_fri_and_queries) it
 // runs unchanged over its own codeword with a list of opened matrices.
 //
 // Statement: n_mats (1 .. 4) B8 matrices of the context's size (zkir_lde_launch's output: canonical words over 31 <w_M>, M = N << b), each under its own tree
@@ -380,7 +380,7 @@ int eval_prove_impl(const EvalEntry& en, zkir_stark_ctx* c, uint32_t n_mats, con
 
   std::lock_guard<std::mutex> ctx_lock(c->mu);                   // one proof at a time per context: the workspace is its arena, as in zkir_prove
   const uint64_t N = 1ull << log_n, M = 1ull << log_M;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const std::vector<int> ks = zkir::fri_schedule((int)log_n, (int)b);
   const uint32_t n_chunks = eval_chunks(N);
   OpenMat opens[BATCH_MAX_MATS];
   uint32_t np_of[BATCH_MAX_MATS];

@@ -1,11 +1,11 @@
 // lowdeg.inl — zkir_lowdeg_prove (include/zkir_amd.h): a LOW-DEGREE PROOF OF A COMMITMENT at any rate the context serves (log_blowup 1, 2, 3).  Included by stark.hip at file
-// scope after stark_prove.inl and merkle_open.inl, whose FRI, gather and opening kernels it launches unchanged.
+// scope after fri.inl (the FRI prover it shares with zkir_prove: commit phase, grinding, a query's layer jobs) and merkle_open.inl, whose opening kernel it launches unchanged.
 //
 // Statement: the B8 matrix under `tree` (zkir_lde_launch's output: canonical words over 31 <w_M>, M = N << b; zkir_merkle_commit_launch's tree) has every column close to a
 // polynomial of degree < N.  Proof: batched FRI over C(x) = sum_k gamma^k col_k(x), gamma in E4 drawn after the root — no DEEP point, no quotient, no constraint.  Format,
 // transcript and verifier: verify.cpp (zkir_lowdeg_verify) and DESIGN.md; spec of every word: tests/lowdeg_ref.py.
 //
-// The one HBM-bound pass is lowdeg_combine_kernel (4 * 8 * ceil(width / 8) B read and 16 B written per row); everything after it is zkir_prove's FRI with log_2n = log_n + b.
+// The one HBM-bound pass is lowdeg_combine_kernel (4 * 8 * ceil(width / 8) B read and 16 B written per row); everything after it is fri.inl's FRI with log_M = log_n + b.
 namespace {
 
 constexpr uint32_t LOWDEG_MAGIC = 0x444C4B5Au, LOWDEG_VERSION = 1;   // 'ZKLD'
@@ -13,18 +13,6 @@ constexpr uint32_t LOWDEG_MAGIC = 0x444C4B5Au, LOWDEG_VERSION = 1;   // 'ZKLD'
 // stays below width / 4.  bb::acc96_div_R asks for a top word below 2^9: 2^9 terms (deep_kernel's static_assert) are a quarter of what the bound admits.
 constexpr uint32_t LOWDEG_MAX_WIDTH = 512;
 static_assert(bb::P < (1u << 31) && LOWDEG_MAX_WIDTH / 4 <= (1u << 9), "lowdeg_combine_kernel: a 96-bit sum's top word stays below 2^9");
-
-// Folds per committed layer: zkir_prove's fri_schedule with the rate as a parameter — the codeword of 2^(log_n + b) values is folded once (its leaves are the pairs
-// (q, q + M/2) the matrix openings determine), later layers LOG_ARITY times, the last one as needed; the final layer has 4 << b values of a word of degree < 4.
-std::vector<int> lowdeg_schedule(int log_n, int b) {
-  std::vector<int> ks;
-  const int log_fin = 2 + b;
-  for (int log_m = log_n + b; log_m > log_fin;) {
-    const int k = ks.empty() ? 1 : (LOG_ARITY < log_m - log_fin ? LOG_ARITY : log_m - log_fin);
-    ks.push_back(k); log_m -= k;
-  }
-  return ks;
-}
 
 // ---- C(x_j) = sum_k gamma^k col_k(x_j), one lane per row ------------------------------------------------------------------------------------------------------------------
 // The loads are deep_kernel's: the two 16-byte halves of (block, row), M4[(blk M + j) 2 + {0, 1}] — 64-bit offsets throughout (block 18 of 2^27 rows starts past 2^32 words);
@@ -64,38 +52,6 @@ std::vector<E4> lowdeg_gamma_table(const E4& gamma, uint32_t width) {
   return t;
 }
 
-// ---- what a proof in the context's arena needs on the host side: pinned staging for uploads and downloads, stage events (zkir_lowdeg_prove and zkir_eval_prove) -------------
-struct ProofRun {
-  zkir_stark_ctx* c; hipStream_t s; const char* who; bool timed;
-  Arena ar; zkir::HostPin& pin; StageEvents se;
-  struct Staged { void* dst; const void* src; size_t n; };
-  std::vector<Staged> staged;
-  ProofRun(zkir_stark_ctx* ctx, hipStream_t stream, const char* name, bool want_times) : c(ctx), s(stream), who(name), timed(want_times), ar{ctx}, pin(ctx->pin) { pin.reset(); }
-  int fail(int code, const std::string& why) const { zkir::set_last_error({code, std::string(who) + ": " + why}); return code; }
-  hipError_t h2d(void* dst, const void* src, size_t bytes) {
-    void* p = pin.take(bytes);
-    if (!p) return hipErrorOutOfMemory;
-    memcpy(p, src, bytes);
-    return hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
-  }
-  hipError_t d2h(void* dst, const void* dsrc, size_t bytes) {
-    void* h = pin.take(bytes);
-    if (!h) return hipErrorOutOfMemory;
-    staged.push_back({dst, h, bytes});
-    return hipMemcpyAsync(h, dsrc, bytes, hipMemcpyDeviceToHost, s);
-  }
-  hipError_t sync_d2h() {
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess) for (const Staged& x : staged) memcpy(x.dst, x.src, x.n);
-    staged.clear();
-    return e;
-  }
-  void mark(int i) { if (timed) (void)hipEventRecord(se.ev[i], s); }
-  void times(float* stage_ms, int n) { (void)hipEventSynchronize(se.ev[n]); for (int i = 0; i < n; i++) (void)hipEventElapsedTime(&stage_ms[i], se.ev[i], se.ev[i + 1]); }
-};
-
-inline size_t arena_al(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 // A matrix a proof's queries open: the B8 matrix, its real columns, its tree (DEVICE pointers).  A proof opens one (zkir_lowdeg_prove, zkir_eval_prove) or several of the
 // same height (zkir_batch_eval_prove); a query carries record_m(q), record_m(q + M/2) matrix by matrix.
 struct OpenMat { const uint32_t* mat; uint32_t width; const uint32_t* tree; };
@@ -107,13 +63,8 @@ uint64_t open_rec_words(uint32_t log_M, const OpenMat* mats, uint32_t n_mats) {
   return rec;
 }
 
-// words of one query: q, two records per matrix (rec_words: open_rec_words), per layer its values and path
-uint64_t lowdeg_query_words(uint32_t log_M, uint64_t rec_words, const std::vector<int>& ks) {
-  uint64_t q = 1 + 2 * rec_words;
-  int lm = (int)log_M;
-  for (int k : ks) { q += 4 * ((uint64_t)1 << k) + 4 * (uint64_t)(lm - k); lm -= k; }
-  return q;
-}
+// words of one query: q, two records per matrix (rec_words: open_rec_words), its FRI layers
+uint64_t lowdeg_query_words(uint32_t log_M, uint64_t rec_words, const std::vector<int>& ks) { return 1 + 2 * rec_words + zkir::fri_query_words(log_M, ks); }
 
 // workspace of everything from the codeword on: the codeword (16 M bytes), the layers and their trees (at most 48 M bytes together at the schedules of log_n >= 5), the
 // query section and its inputs (one record buffer per opened matrix)
@@ -128,98 +79,26 @@ size_t lowdeg_fri_bytes(uint32_t log_M, uint64_t rec_words, uint32_t n_mats, con
          arena_al((size_t)num_queries * lowdeg_query_words(log_M, rec_words, ks) * 4);
 }
 
-// the context's arena holds at least `want` bytes, and is empty
-int arena_reserve(zkir_stark_ctx* c, size_t want) {
-  if (c->arena_size < want) {
-    if (c->arena) (void)hipFree(c->arena);
-    c->arena = nullptr; c->arena_size = 0;
-    HIP_OK(hipMalloc((void**)&c->arena, want));
-    c->arena_size = want;
-  }
-  c->arena_off = 0;
-  return ZKIR_OK;
-}
-
 // Sections 2 - 4 of a proof over a codeword of M = 2^log_M values (cw[t M + j], canonical) under the n_mats (1 .. OPEN_MAX_MATS) matrices `mats`: the FRI commit phase,
 // grinding, the queries (one merkle_open_kernel launch per matrix from the one index array; a query's gather jobs: the records matrix by matrix, then the layers).
 // `ch` is the transcript as it stands once the codeword's challenge is drawn, `head` the proof words so far (the layer roots, the final layer and the nonce are appended),
 // `total` the proof's length.  Stage marks first_mark .. first_mark + 2 are recorded after the three sections.  Writes the whole proof to proof_host.
 int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& head, const OpenMat* mats, uint32_t n_mats, uint32_t num_queries, uint32_t pow_bits,
                            const std::vector<int>& ks, uint32_t* codeword, uint64_t total, int first_mark, uint32_t* proof_host) {
-  zkir_stark_ctx* c = r.c;
+  const zkir_stark_ctx* c = r.c;
   hipStream_t s = r.s;
   Arena& ar = r.ar;
-  const uint32_t log_M = c->log_n + c->log_blowup, b = c->log_blowup;
+  const uint32_t log_M = c->log_n + c->log_blowup;
   const uint64_t M = 1ull << log_M;
-  const int n_layers = (int)ks.size();
-  const uint32_t n_fin = 4u << b;
   if (n_mats < 1 || n_mats > OPEN_MAX_MATS) return r.fail(ZKIR_ERR_OTHER, "number of opened matrices");
   const uint64_t qsize = lowdeg_query_words(log_M, open_rec_words(log_M, mats, n_mats), ks), head_words = total - qsize * num_queries;
-  uint32_t *dState, *dBest, *dChSt, *dFri;
-  std::vector<uint32_t*> fri_trees(n_layers), fri_layers(n_layers + 1);
-  HIP_OK(ar.take(&dState, 16)); HIP_OK(ar.take(&dBest, 4)); HIP_OK(ar.take(&dChSt, 16)); HIP_OK(ar.take(&dFri, 16 * (size_t)(n_layers + 1)));
-  fri_layers[0] = codeword;
 
-  // ---- 2. FRI commit phase, enqueued as a whole (zkir_prove's, with log_2n = log_n + b): nothing is pending in the transcript once the challenge is drawn -------------------
-  if (!ch.in.empty()) return r.fail(ZKIR_ERR_OTHER, "the transcript has pending input at the FRI commit phase");
-  HIP_OK(r.h2d(dChSt, ch.st, sizeof(ch.st)));
-  {
-    uint32_t shift = bb::GEN;
-    int log_m = (int)log_M;
-    for (int j = 0; j < n_layers; j++) {
-      const int k = ks[j];
-      const uint64_t m = 1ull << log_m, g = m >> k;
-      HIP_OK(ar.take(&fri_trees[j], 4 * (2 * g - 1)));
-      uint32_t* ltree = fri_trees[j];
-      if (g <= (1u << 11)) hipLaunchKernelGGL(fri_leaf_hash_row16_kernel, dim3(grid_for(16 * g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, ltree);
-      else if (g <= (1u << 14)) hipLaunchKernelGGL(fri_leaf_hash_quad_kernel, dim3(grid_for(4 * g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, ltree);
-      else hipLaunchKernelGGL(fri_leaf_hash_kernel, dim3(grid_for(g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, ltree);
-      launch_tree_levels(c->d_p2, ltree, g, c->sync, s);
-      hipLaunchKernelGGL(fri_transcript_kernel, dim3(1), dim3(16), 0, s, c->d_p2, dChSt, ltree + 4 * (2 * g - 2), dFri + 16 * j);
-      FoldParams fp{};
-      for (int f = 0; f < k; f++) {
-        fp.half_shift_inv_m[f] = bb::to_mont(bb::inv(bb::mul(2, shift)));
-        shift = bb::mul(shift, shift);
-      }
-      uint32_t* dst;
-      HIP_OK(ar.take(&dst, 4 * g));
-      const E4* dBeta = reinterpret_cast<const E4*>(dFri + 16 * j + 4);
-      if (k == 1) hipLaunchKernelGGL(fri_fold_k_kernel<1>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, dst);
-      else if (k == 2) hipLaunchKernelGGL(fri_fold_k_kernel<2>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, dst);
-      else hipLaunchKernelGGL(fri_fold_k_kernel<3>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, dst);
-      fri_layers[j + 1] = dst;
-      log_m -= k;
-    }
-  }
-  uint32_t fin_cols[4 * 32];                                                   // n_fin <= 32
-  std::vector<uint32_t> fri_out(16 * (size_t)n_layers);
-  HIP_OK(r.d2h(fri_out.data(), dFri, fri_out.size() * 4));
-  HIP_OK(r.d2h(fin_cols, fri_layers[n_layers], 4 * (size_t)n_fin * 4));
-  HIP_OK(r.sync_d2h());
-  if (check_launch(r.who) != ZKIR_OK) return ZKIR_ERR_DEVICE;
-  for (int j = 0; j < n_layers; j++) {                                         // the host's replay of the device's transcript steps
-    ch.observe_n(&fri_out[16 * (size_t)j], 4);
-    const E4 bm = bb::e_to_mont(ch.sample_ext());
-    if (memcmp(bm.c, &fri_out[16 * (size_t)j + 4], 16)) return r.fail(ZKIR_ERR_OTHER, "the device's FRI transcript diverged from the host's");
-    head.insert(head.end(), &fri_out[16 * (size_t)j], &fri_out[16 * (size_t)j] + 4);
-  }
-  for (uint32_t i = 0; i < n_fin; i++) for (int t = 0; t < 4; t++) { ch.observe(fin_cols[t * n_fin + i]); head.push_back(fin_cols[t * n_fin + i]); }
+  // ---- 2. FRI commit phase, 3. grinding (fri.inl) ----------------------------------------------------------------------------------------------------------------------------
+  std::vector<uint32_t*> fri_trees, fri_layers;
+  if (const int rc = fri_commit(r, ch, ks, log_M, zkir::fri_final_size((int)c->log_blowup), codeword, fri_layers, fri_trees, head)) return rc;
   r.mark(first_mark);
-
-  // ---- 3. grinding: the SMALLEST nonce that passes (batches in rising order, the smallest hit of a batch) -------------------------------------------------------------------
-  uint32_t pow_nonce = 0xFFFFFFFFu;
-  {
-    ch.flush();
-    HIP_OK(r.h2d(dState, ch.st, sizeof(ch.st)));
-    const uint32_t batch = 1u << 18;
-    for (uint64_t base = 0; base < bb::P && pow_nonce == 0xFFFFFFFFu; base += batch) {
-      HIP_OK(hipMemsetAsync(dBest, 0xFF, 4, s));
-      hipLaunchKernelGGL(pow_grind_kernel, dim3(batch / NT), dim3(NT), 0, s, c->d_p2, dState, (uint32_t)base, pow_bits, dBest);
-      HIP_OK(r.d2h(&pow_nonce, dBest, 4));
-      HIP_OK(r.sync_d2h());
-    }
-    if (pow_nonce == 0xFFFFFFFFu || !ch.check_pow(pow_nonce, (int)pow_bits)) return r.fail(ZKIR_ERR_OTHER, "proof-of-work search failed");
-  }
+  uint32_t pow_nonce;
+  if (const int rc = fri_grind(r, ch, pow_bits, &pow_nonce)) return rc;
   head.push_back(pow_nonce);
   r.mark(first_mark + 1);
   if (head.size() != head_words) return r.fail(ZKIR_ERR_OTHER, "header length");
@@ -244,12 +123,7 @@ int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& h
       const uint32_t rec = mats[m].width + 4 * log_M;
       jobs.push_back({dRec[m] + 2 * (size_t)t * rec, 1, 2 * rec, off, 0u, 0u}); off += 2 * rec;
     }
-    int log_m = (int)log_M;
-    for (int j = 0; j < n_layers; log_m -= ks[j], j++) {
-      const uint64_t m = 1ull << log_m, g = m >> ks[j], li = q & (g - 1);
-      for (uint64_t u = 0; u < (1ull << ks[j]); u++) { jobs.push_back({fri_layers[j] + li + u * g, m, 4, off, 0u, 0u}); off += 4; }
-      jobs.push_back({fri_trees[j], g, (uint32_t)li, off, 0u, 2u}); off += 4 * (uint32_t)(log_m - ks[j]);
-    }
+    fri_query_jobs(jobs, off, q, log_M, ks, fri_layers, fri_trees);
   }
   if ((uint64_t)off != qsize * num_queries) return r.fail(ZKIR_ERR_OTHER, "query section length");
   HIP_OK(ar.take(&dJobs, jobs.size())); HIP_OK(ar.take(&dOut, (size_t)off));
@@ -286,7 +160,7 @@ int lowdeg_prove_impl(zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, co
 
   std::lock_guard<std::mutex> ctx_lock(c->mu);                   // one proof at a time per context: the workspace is its arena, as in zkir_prove
   const uint64_t M = 1ull << log_M;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const std::vector<int> ks = zkir::fri_schedule((int)log_n, (int)b);
   const uint32_t n_blocks = (width + 7) / 8;
   if (const int rc = arena_reserve(c, lowdeg_fri_bytes(log_M, width + 4 * (uint64_t)log_M, 1, ks, num_queries) + arena_al(n_blocks * 8 * sizeof(E4)))) return rc;
   ProofRun r(c, s, "zkir_lowdeg_prove", stage_ms != nullptr);

@@ -28,6 +28,7 @@
 #include "../../include/zkir_amd_experimental.h"
 #include "air.h"
 #include "babybear.h"
+#include "fri_shape.h"
 #include "host.h"
 #include "hashcall.h"
 #include "poseidon2.h"
@@ -1103,6 +1104,7 @@ int zkir_merkle_cap_launch(const zkir_stark_ctx* c, uint32_t* tree, uint64_t n_d
 
 }  // extern "C"
 
+#include "fri.inl"
 #include "stark_prove.inl"
 #include "merkle_open.inl"
 #include "lowdeg.inl"

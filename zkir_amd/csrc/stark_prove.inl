@@ -1,5 +1,6 @@
-// stark_prove.inl — stage B of the self-defined prover (included by stark.hip): AIR quotient on the LDE coset, barycentric
-// openings, DEEP combination, FRI commit/fold, query gathering, proof serialisation; host-side Fiat-Shamir transcript.
+// stark_prove.inl — stage B of the self-defined prover (included by stark.hip behind fri.inl): AIR quotient on the LDE coset, barycentric
+// openings, DEEP combination, proof serialisation.  The FRI over the DEEP codeword (commit phase, grinding, a query's layer jobs), the host-side
+// Fiat-Shamir transcript and the proof's staging are fri.inl's, shared with the commitment layer's provers: zkir_prove is their case b = 1.
 // Spec: oracle/stark_oracle.cpp (so::prove / so::verify).  Parity unpinned vs the reference (it has no prover).
 //
 // Every kernel is one thread per evaluation point, column reads coalesced across lanes.  The quotient / DEEP kernels stream the
@@ -10,7 +11,7 @@ namespace {
 using bb::E4;
 
 // WMX / WTX: the largest committed width (deferred mode) — array sizes; a proof's own widths are air::committed_width(deferred) and that + WA
-constexpr int LOG_FINAL = air::LOG_FINAL, WMX = air::W_COMMITTED_MAX, WAX = air::W_AUX_MAX, WTX = WMX + WAX, LOG_ARITY = air::LOG_ARITY, NS = air::N_STATE, HEADER_WORDS = 21 + 2 * NS;   // (queries / grinding bits: air.h, per proof)
+constexpr int LOG_FINAL = air::LOG_FINAL, WMX = air::W_COMMITTED_MAX, WAX = air::W_AUX_MAX, WTX = WMX + WAX, NS = air::N_STATE, HEADER_WORDS = 21 + 2 * NS;   // (queries / grinding bits: air.h, per proof)
 constexpr int N_CONSTRAINTS = air::N_CONSTRAINTS;
 constexpr uint32_t PROOF_MAGIC = 0x46504B5Au;                  // (the version is the mode's: air::proof_version)
 
@@ -36,19 +37,6 @@ struct ProveParams {            // constants of one proof, Montgomery form; live
   uint32_t deferred;
   uint32_t lk[air::N_LK];       // lookup parameters (air.h LK_*): alpha, lambda powers, T / N — base-field coordinates, Montgomery
 };
-
-// Folds per committed FRI layer (so::fri_schedule): the DEEP codeword is folded once (its leaves are the pairs (q, q + N) the trace
-// openings determine), later layers 8-to-1 (three binary folds with beta, beta^2, beta^4), the last one as needed to reach 2^LOG_FINAL.
-// A commitment costs ~log2(leaves) SEQUENTIAL Poseidon2 levels (~10 us each once a level is small), so committing every third
-// fold cuts the latency-bound part of FRI from ~200 levels to ~80 at 2^20 rows.
-std::vector<int> fri_schedule(int log_n) {
-  std::vector<int> ks;
-  for (int log_m = log_n + 1; log_m > LOG_FINAL;) {
-    const int k = ks.empty() ? 1 : (LOG_ARITY < log_m - LOG_FINAL ? LOG_ARITY : log_m - LOG_FINAL);
-    ks.push_back(k); log_m -= k;
-  }
-  return ks;
-}
 
 __device__ __forceinline__ E4 e_from_base_m(uint32_t xm) { return E4{{xm, 0, 0, 0}}; }
 __device__ __forceinline__ E4 e_fma_base(const E4& acc, const E4& coef, uint32_t vm) {          // acc + coef * v   (all Montgomery)
@@ -811,185 +799,6 @@ __global__ __launch_bounds__(NT, DEEP_WAVES) void deep_kernel(const uint32_t* __
   for (int i = 0; i < 4; i++) cw[(uint64_t)i * N2 + j] = f.c[i];
 }
 
-// ---- FRI: leaf i of a layer of size m folded k times = (c[i + t g])_{t < 2^k}, g = m >> k: 4 * 2^k base elements absorbed
-// eight at a time (two extension values per permutation), as so::hash_elems does ------------------------------------------------
-__global__ __launch_bounds__(NT) void fri_leaf_hash_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ c, uint64_t m, uint32_t k, uint32_t* __restrict__ digests) {
-  const uint64_t g = m >> k, i = (uint64_t)blockIdx.x * NT + threadIdx.x;
-  if (i >= g) return;
-  uint32_t s[p2::T];
-#pragma unroll
-  for (int t = 0; t < p2::T; t++) s[t] = 0;
-  const uint32_t in_scale = cp->in_scale, carry = cp->carry, ko = cp->out_scale;
-  for (uint32_t u = 0; u < (1u << k); u += 2) {
-#pragma unroll
-    for (int t = 0; t < 4; t++) { s[t] = bb::mont_mul_lazy(c[(uint64_t)t * m + i + u * g], in_scale); s[4 + t] = bb::mont_mul_lazy(c[(uint64_t)t * m + i + (u + 1) * g], in_scale); }
-#pragma unroll
-    for (int t = p2::RATE; t < p2::T; t++) s[t] = bb::mont_mul_lazy(s[t], carry);
-    p2::permute_scaled(s, *cp);
-  }
-  reinterpret_cast<uint4*>(digests)[i] = make_uint4(bb::mont_mul(s[0], ko), bb::mont_mul(s[1], ko), bb::mont_mul(s[2], ko), bb::mont_mul(s[3], ko));
-}
-
-// the same leaf hash with one permutation per quad of lanes (p2::permute_quad): small layers are latency-bound
-__global__ __launch_bounds__(NT) void fri_leaf_hash_quad_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ c, uint64_t m, uint32_t k, uint32_t* __restrict__ digests) {
-  const uint64_t g = m >> k, t = (uint64_t)blockIdx.x * NT + threadIdx.x, i = t >> 2;
-  const int l = (int)(t & 3);
-  if (i >= g) return;                                                         // whole quads leave together
-  uint32_t s[3] = {0, 0, 0};
-  const uint32_t k_in = cp->in_scale, carry = cp->carry;
-  for (uint32_t u = 0; u < (1u << k); u += 2) {
-    s[0] = bb::mont_mul_lazy(c[(uint64_t)l * m + i + u * g], k_in); s[1] = bb::mont_mul_lazy(c[(uint64_t)l * m + i + (u + 1) * g], k_in);
-    s[2] = bb::mont_mul_lazy(s[2], carry);                                     // the capacity words stay: output factor -> input factor
-    p2::permute_quad_scaled(s, l, *cp);
-  }
-  digests[4 * i + l] = bb::mont_mul(s[0], cp->out_scale);
-}
-
-// .. and with one permutation per ROW of 16 lanes (p2::permute_row16_scaled: the shortest chain) for the smallest layers, whose few leaves wait for each other's 2^k / 2 permutations
-__global__ __launch_bounds__(NT) void fri_leaf_hash_row16_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ c, uint64_t m, uint32_t k, uint32_t* __restrict__ digests) {
-  const uint64_t g = m >> k, t = (uint64_t)blockIdx.x * NT + threadIdx.x, i = t >> 4;
-  const int l = (int)(t & 15);
-  if (i >= g) return;                                                         // whole rows leave together
-  uint32_t s = 0;
-  const uint32_t k_in = cp->in_scale, carry = cp->carry;
-  for (uint32_t u = 0; u < (1u << k); u += 2) {                               // words 0-3: the coordinates of value u, 4-7: of value u + 1, 8-11: the capacity (stays: output factor -> input factor)
-    if (l < 4) s = bb::mont_mul_lazy(c[(uint64_t)l * m + i + u * g], k_in);
-    else if (l < 8) s = bb::mont_mul_lazy(c[(uint64_t)(l - 4) * m + i + (u + 1) * g], k_in);
-    else s = bb::mont_mul_lazy(s, carry);
-    s = p2::permute_row16_scaled(s, l, *cp);
-  }
-  if (l < 4) digests[4 * i + l] = bb::mont_mul(s, cp->out_scale);
-}
-
-// one binary fold of a layer of m values: c'[i] = (c[i] + c[i+h])/2 + beta (c[i] - c[i+h]) / (2 x_i),  x_i = shift * w_m^i,  h = m / 2;
-// w_m^-i = w_2N^-(i << (log_2n - log_m)), and w^-k = -w^(N-k) for 0 < k < N (w^N = -1): the table holds w^k for k < N = 2^(log_2n - 1)
-// The K binary folds between two committed layers in ONE launch (round 4: three launches and two intermediate layers before): output i of the last fold depends on the 2^K
-// values c[i + u g], g = m >> K, and fold f pairs v[u] with v[u + 2^(K-f-1)] — exactly the pairs (j, j + h_f) of a binary fold of the size-(m >> f) layer, the same field operations in
-// the same order on every value, so the layer is the one the chain of binary folds leaves.
-// beta_m: the layer's challenge and its squares, beta^(2^f) (Montgomery), written by fri_transcript_kernel on the device (round 5: no host round trip between the layers)
-struct FoldParams { uint32_t half_shift_inv_m[3]; };
-template <int K>
-__global__ __launch_bounds__(NT) void fri_fold_k_kernel(const uint32_t* __restrict__ c, uint32_t log_m, uint32_t log_2n, const uint32_t* __restrict__ tw_fwd, FoldParams fp, const E4* __restrict__ beta_m, uint32_t* __restrict__ out) {
-  const uint64_t m = 1ull << log_m, g = m >> K, i = (uint64_t)blockIdx.x * NT + threadIdx.x;
-  if (i >= g) return;
-  E4 v[1 << K];
-#pragma unroll
-  for (int u = 0; u < (1 << K); u++)
-#pragma unroll
-    for (int t = 0; t < 4; t++) v[u].c[t] = c[(uint64_t)t * m + i + (uint64_t)u * g];
-  const uint32_t N = 1u << (log_2n - 1);
-  constexpr uint32_t HALF_M = (uint32_t)(((uint64_t)((bb::P + 1) / 2) * bb::R1) % bb::P);
-#pragma unroll
-  for (int f = 0; f < K; f++) {
-    const int cnt = 1 << (K - f - 1);
-#pragma unroll
-    for (int u = 0; u < cnt; u++) {
-      const uint64_t j = i + (uint64_t)u * g;                                  // position in the half of the size-(m >> f) domain
-      const uint32_t k = (uint32_t)(j << (log_2n - (log_m - f)));
-      const uint32_t winv = k == 0 ? bb::R1 : bb::neg(tw_fwd[N - k]);
-      const uint32_t inv2x = bb::mont_mul(winv, fp.half_shift_inv_m[f]);
-      const E4 a = v[u], b = v[u + cnt];
-      const E4 sum = bb::e_mul_fm(bb::e_add(a, b), HALF_M);
-      const E4 dif = bb::e_mul_fm(bb::e_sub(a, b), inv2x);
-      const E4 prod = bb::e_from_mont(bb::e_mul_m(bb::e_to_mont(dif), beta_m[f]));
-      v[u] = bb::e_add(sum, prod);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 4; t++) out[(uint64_t)t * g + i] = v[0].c[t];
-}
-
-// ---- the Fiat-Shamir step of one FRI layer ON THE DEVICE: observe the layer's root, sample beta -------------------------------------------
-// Challenger (below; so::Challenger) at this point of the transcript: nothing pending, so  observe(root[0..4)); sample_ext()  is ONE duplex — state words 0..3 overwritten
-// with the root, one permutation, beta = (st[7], st[6], st[5], st[4]) (sample() pops from the back of the eight rate words).  One row of lanes runs it
-// (p2::permute_row16_scaled: one row of 16 lanes, lane l holds word l) on the challenger state the host uploaded (Montgomery words, as Challenger::st), leaves the state for the next
-// layer, and writes  out[0..4) = the root, out[4..16) = beta, beta^2, beta^4 (Montgomery: what fri_fold_k_kernel multiplies by).  The host replays the same steps from
-// the roots once the whole commit phase is enqueued (the proof needs them anyway) and refuses to go on if its betas are not the device's.
-__global__ void fri_transcript_kernel(const p2::Consts* __restrict__ cp, uint32_t* __restrict__ st, const uint32_t* __restrict__ root, uint32_t* __restrict__ out) {
-  __shared__ uint32_t w[p2::T];
-  const int l = (int)(threadIdx.x & 15);                                      // one row of 16 lanes (p2::permute_row16_scaled): lane l < 12 holds state word l
-  const uint32_t k_in = bb::from_mont(cp->in_scale), ko_m = bb::to_mont(cp->out_scale);
-  const uint32_t r = l < 4 ? root[l] : 0u;
-  const uint32_t xm = l < 4 ? bb::to_mont(r) : l < p2::T ? st[l] : 0u;          // words 0-3 overwritten with the root, the rest of the state stays
-  uint32_t s = p2::permute_row16_scaled(bb::mont_mul_lazy(xm, k_in), l, *cp);
-  if (l < p2::T) { const uint32_t v = bb::mont_mul(s, ko_m); st[l] = v; w[l] = v; }
-  if (l < 4) out[l] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    E4 beta{{w[7], w[6], w[5], w[4]}};
-    E4* bo = reinterpret_cast<E4*>(out + 4);
-    for (int f = 0; f < 3; f++) { bo[f] = beta; beta = bb::e_mul_m(beta, beta); }
-  }
-}
-
-// ---- query gathering -------------------------------------------------------------------------------------------------------------
-// A job (one workgroup of 64 lanes) is one of three shapes (round 5: ~750 jobs a proof instead of ~15,000 one-line copies — building and uploading that list was 90 us of host time with the GPU idle):
-//   kind 0: `count` words src[k * stride] -> dst[k]                                    (a FRI leaf: the four coordinates of a value, one column apart)
-//   kind 1: `count` ROW PIECES of `width` words, src[b * stride + w] -> dst[b * width + w]  (a matrix row: 8 words out of each B8 block; the quotient's 4)
-//   kind 2: a MERKLE PATH — tree = src, `stride` = its number of leaves, `count` = the leaf index: the sibling digest (4 words) of every level, leaf level first
-// mont: the source words rest in Montgomery form (rows of the LDE matrices) and enter the proof canonical
-struct GatherJob { const uint32_t* src; uint64_t stride; uint32_t count; uint32_t dst; uint32_t mont; uint32_t kind_width; };   // kind_width = kind | width << 8
-__global__ void gather_kernel(const GatherJob* __restrict__ jobs, uint32_t n_jobs, uint32_t* __restrict__ dst) {
-  const uint32_t jb = blockIdx.x;
-  if (jb >= n_jobs) return;
-  const GatherJob g = jobs[jb];
-  const uint32_t kind = g.kind_width & 0xFF, width = g.kind_width >> 8;
-  if (kind == 0) {
-    for (uint32_t k = threadIdx.x; k < g.count; k += blockDim.x) { const uint32_t v = g.src[(uint64_t)k * g.stride]; dst[g.dst + k] = g.mont ? bb::from_mont(v) : v; }
-  } else if (kind == 1) {
-    for (uint32_t k = threadIdx.x; k < g.count * width; k += blockDim.x) { const uint32_t v = g.src[(uint64_t)(k / width) * g.stride + k % width]; dst[g.dst + k] = g.mont ? bb::from_mont(v) : v; }
-  } else {
-    uint32_t depth = 0;
-    for (uint64_t q = g.stride; q > 1; q >>= 1) depth++;
-    for (uint32_t k = threadIdx.x; k < 4 * depth; k += blockDim.x) {
-      const uint32_t lvl = k >> 2;                                             // level `lvl` starts 4 * (n + n/2 + .. ) = 4 * (2 n - (2 n >> lvl)) words into the tree
-      const uint64_t n = g.stride, at = 4 * (2 * n - ((2 * n) >> lvl)), sib = ((uint64_t)g.count >> lvl) ^ 1;
-      dst[g.dst + k] = g.src[at + 4 * sib + (k & 3)];
-    }
-  }
-}
-
-// ---- proof-of-work grinding: one candidate nonce per lane; the smallest hit wins (deterministic) ------------------------------
-__global__ __launch_bounds__(NT) void pow_grind_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ state_m, uint32_t base, uint32_t pow_bits, uint32_t* __restrict__ best) {
-  const uint32_t nonce = base + blockIdx.x * NT + threadIdx.x;
-  if (nonce >= bb::P) return;
-  uint32_t s[p2::T];
-  const uint32_t k_in = bb::from_mont(cp->in_scale);                          // Montgomery words R v -> input words F_IN v of the throughput formulation (a fifth fewer instructions)
-#pragma unroll
-  for (int i = 1; i < p2::T; i++) s[i] = bb::mont_mul_lazy(state_m[i], k_in);
-  s[0] = bb::mont_mul_lazy(nonce, cp->in_scale);                              // overwrite-absorb of the single pending element (canonical)
-  p2::permute_scaled(s, *cp);
-  if ((bb::mont_mul(s[p2::RATE - 1], cp->out_scale) & ((1u << pow_bits) - 1)) == 0) atomicMin(best, nonce);   // sample() takes the last rate element
-}
-
-// ---- host-side duplex challenger (Montgomery state; canonical in/out) -------------------------------------------------------
-struct Challenger {
-  const p2::Consts& c;
-  uint32_t st[p2::T];
-  std::vector<uint32_t> in, out;
-  explicit Challenger(const p2::Consts& cc) : c(cc) { for (auto& v : st) v = 0; }
-  // (round 5) the permutation in the hash kernels' formulation (p2::permute_scaled: a quarter fewer host instructions — a proof's transcript is ~330 permutations, all of
-  // them on the critical path with the GPU idle); the state stays what it was: Montgomery words R v, canonical range
-  void duplex() {
-    for (size_t i = 0; i < in.size(); i++) st[i] = bb::to_mont(in[i]);
-    in.clear();
-    const uint32_t k_in = bb::from_mont(c.in_scale), ko_m = bb::to_mont(c.out_scale);
-    uint32_t s[p2::T];
-    for (int i = 0; i < p2::T; i++) s[i] = bb::mont_mul_lazy(st[i], k_in);
-    p2::permute_scaled(s, c);
-    for (int i = 0; i < p2::T; i++) st[i] = bb::mont_mul(s[i], ko_m);
-    out.clear();
-    for (int i = 0; i < p2::RATE; i++) out.push_back(bb::from_mont(st[i]));
-  }
-  void observe(uint32_t x) { out.clear(); in.push_back(x); if ((int)in.size() == p2::RATE) duplex(); }
-  void observe_n(const uint32_t* x, size_t n) { for (size_t i = 0; i < n; i++) observe(x[i]); }
-  uint32_t sample() { if (!in.empty() || out.empty()) duplex(); const uint32_t v = out.back(); out.pop_back(); return v; }
-  E4 sample_ext() { E4 e; for (int i = 0; i < 4; i++) e.c[i] = sample(); return e; }
-  uint32_t sample_bits(int b) { return sample() & ((1u << b) - 1); }
-  void flush() { if (!in.empty()) duplex(); out.clear(); }                    // so::Challenger::flush
-  bool check_pow(uint32_t nonce, int pow_bits) { flush(); observe(nonce); return (sample() & ((1u << pow_bits) - 1)) == 0; }
-};
-
 // so::hash_elems on the host (the overwrite sponge of the section digests)
 void hash_elems_host(const p2::Consts& c, const uint32_t* in, size_t n, uint32_t out[4]) {
   uint32_t st[p2::T] = {0};
@@ -1004,26 +813,6 @@ void hash_elems_host(const p2::Consts& c, const uint32_t* in, size_t n, uint32_t
 
 E4 h_e_mul(const E4& a, const E4& b) { return bb::e_from_mont(bb::e_mul_m(bb::e_to_mont(a), bb::e_to_mont(b))); }   // canonical in/out
 E4 h_e_pow(E4 a, uint64_t e) { E4 r{{1, 0, 0, 0}}; while (e) { if (e & 1) r = h_e_mul(r, a); a = h_e_mul(a, a); e >>= 1; } return r; }
-
-#define HIP_OK(expr)                                                                                         \
-  do { hipError_t _e = (expr); if (_e != hipSuccess) { zkir::set_last_error({ZKIR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)}); return ZKIR_ERR_DEVICE; } } while (0)
-
-// Bump allocation out of the context's persistent workspace (reset at the start of every zkir_prove; the context's mutex is held).
-struct Arena {
-  const zkir_stark_ctx* c;
-  template <typename T> hipError_t take(T** out, size_t count) {
-    const size_t need = (count * sizeof(T) + 255) & ~(size_t)255;
-    if (c->arena_off + need > c->arena_size) return hipErrorOutOfMemory;
-    *out = (T*)(c->arena + c->arena_off);
-    c->arena_off += need;
-    return hipSuccess;
-  }
-};
-struct StageEvents {             // RAII: released on every return path
-  hipEvent_t ev[10]; bool on = false;
-  hipError_t create() { for (auto& e : ev) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } on = true; return hipSuccess; }
-  ~StageEvents() { if (on) for (auto& e : ev) (void)hipEventDestroy(e); }
-};
 
 #include "tape_table.inl"
 #include "tape_digest.inl"
@@ -1303,11 +1092,12 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   // live in the arena (no __constant__ / static state).
   std::lock_guard<std::mutex> ctx_lock(c->mu);
   *proof_out = nullptr; *proof_words = 0;
-  const std::vector<int> ks = fri_schedule((int)log_n);
+  const std::vector<int> ks = zkir::fri_schedule((int)log_n, 1);              // a STARK proof is the FRI's case b = 1: log_M = log_n + 1, a final layer of 2^LOG_FINAL values
   const int n_layers = (int)ks.size();
 
-  zkir::HostPin& pin = c->pin;                                 // every host block of unbounded size crosses through pinned staging (host.h)
-  pin.reset();
+  ProofRun run(c, s, "zkir_prove", stage_ms != nullptr);       // the proof's pinned staging (emptied here), arena view and stage events (fri.inl)
+  Arena& ar = run.ar;
+  zkir::HostPin& pin = run.pin;
   // (mode 4) a run with hash syscalls and no witness from the caller: the memory witness AND the hash tape are built on the device (memcheck.hip), the written digests coming
   // from the interpreter's records (pub->hash_outs).  It runs HERE, before the workspace is sized: how many cells the run touches and how long its tape is are known only
   // after its count pass (a call may touch 131 078 cells), so it makes its own device allocations; mem_old / mem_told are copied into the workspace below.
@@ -1331,38 +1121,9 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     static_assert(WMX % 8 == 0 && air::W_COMMITTED_DEFAULT % 8 == 0, "the main trace fills whole B8 blocks");
     const size_t want = (size_t)(12 * WM + 12 * WA + 16 + 544 + (IO ? 48 : 0) + (MEM ? 48 : 0) + (WIDE ? 8 : 0)) * N + (size_t)air::MAX_NUM_QUERIES * 64 * 1024 + (8u << 20) + (size_t)n_code * 24 + (1u << 16) + (WIDE ? (1u << 17) : 0) +
                         (IO ? (size_t)pub->n_inputs * 8 : 0) + (MEM ? (size_t)air::MEM_MULT * 24 + (size_t)CELL_CAP * 28 + SEC_WORDS * 4 + blob_len + (1u << 16) : 0);
-    if (c->arena_size < want) {
-      if (c->arena) (void)hipFree(c->arena);
-      c->arena = nullptr; c->arena_size = 0;
-      HIP_OK(hipMalloc((void**)&c->arena, want));
-      c->arena_size = want;
-    }
-    c->arena_off = 0;
+    if (const int arc = arena_reserve(c, want)) return arc;
   }
-  Arena ar{c};
-  auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-    void* p = pin.take(bytes);
-    if (!p) return hipErrorOutOfMemory;
-    memcpy(p, src, bytes);
-    return hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
-  };
-  // small results the host waits for (roots, boundary states, partial sums ..): copied into PINNED staging — a copy into a pageable block is served synchronously, one
-  // host round trip per copy (the kernel timeline showed 13-29 us between consecutive 16-byte copies) — and handed to their destinations after the ONE synchronisation that follows them
-  struct Staged { void* dst; const void* src; size_t n; };
-  std::vector<Staged> staged;
-  auto d2h = [&](void* dst, const void* dsrc, size_t bytes) -> hipError_t {
-    void* h = pin.take(bytes);
-    if (!h) return hipErrorOutOfMemory;
-    staged.push_back({dst, h, bytes});
-    return hipMemcpyAsync(h, dsrc, bytes, hipMemcpyDeviceToHost, s);
-  };
-  auto sync_d2h = [&]() -> hipError_t {
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess) for (const Staged& x : staged) memcpy(x.dst, x.src, x.n);
-    staged.clear();
-    return e;
-  };
-  uint32_t *dM, *dL, *dTree, *dQ, *dQTree, *dState, *dBest, *dBound, *dA, *dAL, *dATree, *dCode, *dMult;
+  uint32_t *dM, *dL, *dTree, *dQ, *dQTree, *dDeep, *dBound, *dA, *dAL, *dATree, *dCode, *dMult;
   unsigned long long* dBad;
   uint4 *dSide, *dSums;
   E4 *dW, *dDinv, *dPart, *dPartSum, *dInvRc, *dInvRom;
@@ -1371,7 +1132,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   uint64_t* dMemOld = nullptr; uint32_t* dMemTold = nullptr; uint4* dMemSide = nullptr; E4* dInvMem = nullptr; uint2* dWideSide = nullptr;
   uint64_t *dCellAddr = nullptr, *dCellBytes = nullptr; uint32_t* dCellTime = nullptr; uint8_t* dImage = nullptr; E4* dCellPart = nullptr; uint32_t* dSec = nullptr;
   E4* dTapePart = nullptr; unsigned long long* dTapeCheck = nullptr;
-  HIP_OK(ar.take(&dPP, 1)); HIP_OK(ar.take(&dState, 16)); HIP_OK(ar.take(&dBest, 4)); HIP_OK(ar.take(&dBound, 2 * NS + 4)); HIP_OK(ar.take(&dBad, 1));
+  HIP_OK(ar.take(&dPP, 1)); HIP_OK(ar.take(&dBound, 2 * NS + 4)); HIP_OK(ar.take(&dBad, 1));
   if (IO) { HIP_OK(ar.take(&dIo, N)); HIP_OK(ar.take(&dIoCount, 4)); HIP_OK(ar.take(&dInputs, (size_t)pub->n_inputs + 1)); HIP_OK(ar.take(&dIoScratch, 2 * N + 2 * (N / 1024 + 2))); }
   if (MEM) {
     HIP_OK(ar.take(&dMemOld, N)); HIP_OK(ar.take(&dMemTold, N)); HIP_OK(ar.take(&dMemSide, 2 * N)); HIP_OK(ar.take(&dInvMem, air::MEM_MULT));
@@ -1389,24 +1150,21 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   // chunks of the barycentric sums: enough workgroups to fill the chip (64 x 25 blocks), and few enough terms per 96-bit sum (bary_dot_kernel: BARY_MAX_TERMS)
   const uint32_t n_chunks = N2 > 64 * BARY_ROWS * BARY_MAX_TERMS ? (uint32_t)(N2 / (BARY_ROWS * BARY_MAX_TERMS)) : N2 >= 1024 * NT ? 256 : N2 >= 64 * NT ? 64 : (N2 >= 16 * NT ? 16 : 1);
   HIP_OK(ar.take(&dPart, (size_t)(WT + 4) * n_chunks * 2)); HIP_OK(ar.take(&dPartSum, (size_t)(WT + 4) * 2));
-  std::vector<uint32_t*> fri_trees(n_layers), fri_layers(n_layers + 1);
-
-  StageEvents se;
-  if (stage_ms) HIP_OK(se.create());
+  if (stage_ms) HIP_OK(run.se.create());
   double host_ms[10] = {0};                                     // (diagnostics) host wall time at every mark
-  auto mark = [&](int i) { if (stage_ms) (void)hipEventRecord(se.ev[i], s); if (dbg_t) host_ms[i] = since(t_entry); };
+  auto mark = [&](int i) { run.mark(i); if (dbg_t) host_ms[i] = since(t_entry); };
 
   // ---- 1. main trace, lookup indices + multiplicities, LDE, trace commitment ---------------------------------------------------
   const double t_pre = since(t_entry);
   mark(0);
   int rc;
   if (IO) {
-    if (pub->n_inputs) HIP_OK(h2d(dInputs, pub->inputs, (size_t)pub->n_inputs * 8));
+    if (pub->n_inputs) HIP_OK(run.h2d(dInputs, pub->inputs, (size_t)pub->n_inputs * 8));
     const zkir_io_args io{dInputs, pub->n_inputs, pub->writes_before, pub->reads_before};
     if (MEM) {
       if (MEM_HOST) {
-        HIP_OK(h2d(dMemOld, pub->mem_old, (size_t)pub->n_real * 8));
-        HIP_OK(h2d(dMemTold, pub->mem_told, (size_t)pub->n_real * 4));
+        HIP_OK(run.h2d(dMemOld, pub->mem_old, (size_t)pub->n_real * 8));
+        HIP_OK(run.h2d(dMemTold, pub->mem_told, (size_t)pub->n_real * 4));
         cell_addr_v.assign(pub->cell_addr, pub->cell_addr + pub->n_cells); cell_bytes_v.assign(pub->cell_bytes, pub->cell_bytes + pub->n_cells); cell_time_v.assign(pub->cell_time, pub->cell_time + pub->n_cells);
       } else if (HASH_DEV) {
         HIP_OK(hipMemcpyAsync(dMemOld, hw_rows.p, (size_t)pub->n_real * 8, hipMemcpyDeviceToDevice, s));
@@ -1424,7 +1182,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   if (rc) return rc;
   hipLaunchKernelGGL(boundary_states_kernel, dim3(1), dim3(256), 0, s, dM, N, pub->n_real - 1, MODE, dBound);   // before the LDE overwrites dM
   {
-    if (n_code) HIP_OK(h2d(dCode, blob + 32, (size_t)n_code * 4));           // the code words, little-endian as the blob holds them
+    if (n_code) HIP_OK(run.h2d(dCode, blob + 32, (size_t)n_code * 4));           // the code words, little-endian as the blob holds them
     HIP_OK(hipMemsetAsync(dMult, 0, n_mult * 4, s));
     HIP_OK(hipMemsetAsync(dBad, 0xFF, 8, s));
     unsigned g = grid_for(N); if (g > 2048) g = 2048;
@@ -1439,13 +1197,13 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   unsigned long long bad_row = ~0ull;
   uint32_t* mult = pin.take_n<uint32_t>(n_mult);               // (pinned: read back below, and part of the proof)
   if (!mult) HIP_OK(hipErrorOutOfMemory);
-  HIP_OK(d2h(troot, dTree + 4 * (2 * N2 - 2), 16));
-  HIP_OK(d2h(bound, dBound, sizeof bound));
+  HIP_OK(run.d2h(troot, dTree + 4 * (2 * N2 - 2), 16));
+  HIP_OK(run.d2h(bound, dBound, sizeof bound));
   uint32_t io_counts[4] = {0, 0, 0, 0};
-  if (IO) HIP_OK(d2h(io_counts, dIoCount, 16));
+  if (IO) HIP_OK(run.d2h(io_counts, dIoCount, 16));
   HIP_OK(hipMemcpyAsync(mult, dMult, n_mult * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(d2h(&bad_row, dBad, 8));
-  HIP_OK(sync_d2h());
+  HIP_OK(run.d2h(&bad_row, dBad, 8));
+  HIP_OK(run.sync_d2h());
   n_io = io_counts[0];
   if (bad_row != ~0ull) {
     char m[640];
@@ -1510,7 +1268,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     const size_t n_chunks_sec = (mem_sec.size() + SECTION_CHUNK - 1) / SECTION_CHUNK;
     if (mem_sec.size() + 4 * n_chunks_sec + 64 > SEC_WORDS) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: more touched cells than the workspace holds"}); return ZKIR_ERR_ARGUMENT; }
     uint32_t* dSecDg = dSec + ((mem_sec.size() + 63) & ~(size_t)63);
-    HIP_OK(h2d(dSec, mem_sec.data(), mem_sec.size() * 4));
+    HIP_OK(run.h2d(dSec, mem_sec.data(), mem_sec.size() * 4));
     hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks_sec + 63) / 64)), dim3(64), 0, s, c->d_p2, dSec, (uint64_t)mem_sec.size(), dSecDg);
     std::vector<uint32_t> sec_dg(4 * n_chunks_sec);
     HIP_OK(hipMemcpyAsync(sec_dg.data(), dSecDg, sec_dg.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1558,7 +1316,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       ch.observe_n(sec_dg.data(), sec_dg.size());
     } else if (hash_sec.size() + 4 * n_chunks_sec + 64 <= SEC_WORDS) {           // chunk digests on the device (the buffer of the memory section, free again)
       uint32_t* dSecDg = dSec + ((hash_sec.size() + 63) & ~(size_t)63);
-      HIP_OK(h2d(dSec, hash_sec.data(), hash_sec.size() * 4));
+      HIP_OK(run.h2d(dSec, hash_sec.data(), hash_sec.size() * 4));
       hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks_sec + 63) / 64)), dim3(64), 0, s, c->d_p2, dSec, (uint64_t)hash_sec.size(), dSecDg);
       std::vector<uint32_t> sec_dg(4 * n_chunks_sec);
       HIP_OK(hipMemcpyAsync(sec_dg.data(), dSecDg, sec_dg.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1587,7 +1345,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     const size_t n_chunks_sec = (wide_sec.size() + SECTION_CHUNK - 1) / SECTION_CHUNK;
     if (wide_sec.size() > 4 * SECTION_CHUNK && wide_sec.size() + 4 * n_chunks_sec + 64 <= SEC_WORDS) {     // a long tape: the chunk digests on the device
       uint32_t* dSecDg = dSec + ((wide_sec.size() + 63) & ~(size_t)63);
-      HIP_OK(h2d(dSec, wide_sec.data(), wide_sec.size() * 4));
+      HIP_OK(run.h2d(dSec, wide_sec.data(), wide_sec.size() * 4));
       hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks_sec + 63) / 64)), dim3(64), 0, s, c->d_p2, dSec, (uint64_t)wide_sec.size(), dSecDg);
       std::vector<uint32_t> sec_dg(4 * n_chunks_sec);
       HIP_OK(hipMemcpyAsync(sec_dg.data(), dSecDg, sec_dg.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1608,7 +1366,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     for (int k = 0; k < 4; k++) pp->lk[air::LK_TN + k] = 0;
     pp->lk[air::LK_NIN] = IO ? bb::to_mont((uint32_t)(pub->n_inputs % bb::P)) : 0u;
     { const uint64_t Bc = air::boundary_cell(4 * (uint64_t)n_code); pp->lk[air::LK_B0] = bb::to_mont((uint32_t)(Bc & 0xFFFFF)); pp->lk[air::LK_B1] = bb::to_mont((uint32_t)((Bc >> 20) & 0xFFFFF)); }   // (mode 4) the boundary cell
-    HIP_OK(h2d(dPP->lk, pp->lk, sizeof(pp->lk)));
+    HIP_OK(run.h2d(dPP->lk, pp->lk, sizeof(pp->lk)));
     hipLaunchKernelGGL(lookup_tables_kernel, dim3(grid_for((uint64_t)air::RC_TABLE + n_code)), dim3(NT), 0, s, dCode, n_code, dPP, dInvRc, dInvRom, MODE);
     if (MEM) hipLaunchKernelGGL(mem_tables_kernel, dim3(grid_for(air::MEM_MULT)), dim3(NT), 0, s, dPP, dInvMem);
     E4* inv = pin.take_n<E4>((size_t)air::RC_TABLE + n_code + (MEM ? air::MEM_MULT : 0));
@@ -1629,10 +1387,10 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
         if (n_cells_v > CELL_CAP) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: more touched cells than the workspace holds"}); return ZKIR_ERR_ARGUMENT; }
         uint32_t code_size, data_size; memcpy(&code_size, blob + 16, 4); memcpy(&data_size, blob + 20, 4);
         const uint64_t image_len = 32 + (uint64_t)code_size + data_size <= blob_len ? (uint64_t)code_size + data_size : 0;
-        if (image_len) HIP_OK(h2d(dImage, blob + 32, image_len));
-        HIP_OK(h2d(dCellAddr, cell_addr_v.data(), n_cells_v * 8));
-        HIP_OK(h2d(dCellBytes, cell_bytes_v.data(), n_cells_v * 8));
-        HIP_OK(h2d(dCellTime, cell_time_v.data(), n_cells_v * 4));
+        if (image_len) HIP_OK(run.h2d(dImage, blob + 32, image_len));
+        HIP_OK(run.h2d(dCellAddr, cell_addr_v.data(), n_cells_v * 8));
+        HIP_OK(run.h2d(dCellBytes, cell_bytes_v.data(), n_cells_v * 8));
+        HIP_OK(run.h2d(dCellTime, cell_time_v.data(), n_cells_v * 4));
         const unsigned nb = grid_for(n_cells_v);
         hipLaunchKernelGGL(mem_cells_sum_kernel, dim3(nb), dim3(NT), 0, s, dCellAddr, dCellBytes, dCellTime, (uint32_t)n_cells_v, dImage, image_len, dPP, dCellPart);
         std::vector<E4> part(nb);
@@ -1681,7 +1439,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       unsigned host_parts = 0;
       if (!HASH_DEV && !hcalls.empty()) {                      // (beside the wide tape's kernel)
         T = bb::e_add(T, hash_table_side_host(hcalls, nullptr, pp->lk, hash_aux, &host_parts));
-        HIP_OK(h2d(dHashAux, hash_aux.data(), hash_aux.size() * sizeof(HashAux)));
+        HIP_OK(run.h2d(dHashAux, hash_aux.data(), hash_aux.size() * sizeof(HashAux)));
       }
       HIP_OK(hipStreamSynchronize(s));
       hash_part.add_to(T); wide_part.add_to(T);
@@ -1694,7 +1452,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     }
     const E4 tn = bb::e_mul_fm(T, bb::to_mont(bb::inv((uint32_t)(N % bb::P))));
     for (int k = 0; k < 4; k++) pp->lk[air::LK_TN + k] = tn.c[k];
-    HIP_OK(h2d(dPP->lk + air::LK_TN, pp->lk + air::LK_TN, 16));
+    HIP_OK(run.h2d(dPP->lk + air::LK_TN, pp->lk + air::LK_TN, 16));
     hipLaunchKernelGGL(aux_rows_kernel, dim3(grid_for(N)), dim3(NT), 0, s, dSide, N, dInvRc, dInvRom, dPP, dA);
     if (IO) {                                                 // the tape helpers HO | HI: zero but on the WRITE / live READ rows
       HIP_OK(hipMemsetAsync(dA + (size_t)(air::A_HO / 8) * N * 8, 0, (size_t)N * 32, s));
@@ -1712,8 +1470,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     hipLaunchKernelGGL(scan_add_kernel, dim3(grid_for(N)), dim3(NT), 0, s, dA, N, dSums);
     rc = lde_launch(c, dA, WA, dAL, /*mont_out=*/false, s); if (rc) return rc;      // the aux rows are written in Montgomery form already; the extension is linear
     rc = merkle_commit(c, dAL, WA, N2, dATree, /*mont_in=*/true, s); if (rc) return rc;
-    HIP_OK(d2h(aroot, dATree + 4 * (2 * N2 - 2), 16));
-    HIP_OK(sync_d2h());
+    HIP_OK(run.d2h(aroot, dATree + 4 * (2 * N2 - 2), 16));
+    HIP_OK(run.sync_d2h());
     ch.observe_n(aroot, 4);
   }
   mark(4);
@@ -1733,7 +1491,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     for (int k = 0; k < 4; k++) pp->cnt_m[k] = bb::to_mont(bound[2 * NS + k]);
     air::boundary_constants(alpha_pow.data(), pp->first_m, pp->last_m, pp->cf, pp->cl, IO ? pp->cnt_m : nullptr);
     pp->deferred = pub->deferred ? 1 : 0;
-    HIP_OK(h2d(dPP, pp.get(), sizeof(ProveParams)));
+    HIP_OK(run.h2d(dPP, pp.get(), sizeof(ProveParams)));
   }
   const uint32_t wn = bb::root_of_unity((int)log_n);
   const uint32_t gN = bb::pow(bb::GEN, N), wn_inv_m = bb::to_mont(bb::inv(wn)), w_last_inv_m = bb::to_mont(bb::inv(bb::pow(wn, pub->n_real - 1)));
@@ -1745,8 +1503,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   else if (MODE == 2) hipLaunchKernelGGL(quotient_kernel<2>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
   else hipLaunchKernelGGL(quotient_kernel<0>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
   rc = merkle_commit(c, dQ, 4, N2, dQTree, /*mont_in=*/true, s); if (rc) return rc;
-  HIP_OK(d2h(qroot, dQTree + 4 * (2 * N2 - 2), 16));
-  HIP_OK(sync_d2h());
+  HIP_OK(run.d2h(qroot, dQTree + 4 * (2 * N2 - 2), 16));
+  HIP_OK(run.sync_d2h());
   mark(5);
   ch.observe_n(qroot, 4);
   const E4 zeta = ch.sample_ext();
@@ -1754,14 +1512,14 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
 
   // ---- 3. openings by barycentric evaluation over the LDE coset ------------------------------------------------------------
   pp->zeta = bb::e_to_mont(zeta); pp->zeta_w = bb::e_to_mont(zeta_w);
-  HIP_OK(h2d(&dPP->zeta, &pp->zeta, 2 * sizeof(E4)));
+  HIP_OK(run.h2d(&dPP->zeta, &pp->zeta, 2 * sizeof(E4)));
   hipLaunchKernelGGL(bary_weights_kernel, dim3(grid_for(N2)), dim3(NT), 0, s, log_n, c->d_tw_fwd, dPP, dW, dDinv);
   // columns in the order used everywhere below: main (WM), aux (WA) = WT "trace" columns, then the quotient's four
   hipLaunchKernelGGL(bary_dot_kernel, dim3(n_chunks, (WT + 8) / 8), dim3(NT), 0, s, dL, dAL, dQ, (uint32_t)WM / 8, (uint32_t)WA / 8, (uint64_t)N2, dW, dPart, n_chunks, (uint32_t)__builtin_ctzll(N2 / n_chunks));
   hipLaunchKernelGGL(bary_sum_kernel, dim3(((WT + 4) * 2 + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, s, dPart, (uint32_t)(WT + 4) * 2, n_chunks, dPartSum);
   std::vector<E4> part((size_t)(WT + 4) * 2);
-  HIP_OK(d2h(part.data(), dPartSum, part.size() * sizeof(E4)));
-  HIP_OK(sync_d2h());
+  HIP_OK(run.d2h(part.data(), dPartSum, part.size() * sizeof(E4)));
+  HIP_OK(run.sync_d2h());
   std::vector<E4> t_z(WT), t_zw(WT), q_z(4);
   {
     // the quotient's columns, over the whole coset g H_2N: scale = ((z/g)^2N - 1) / (2N);  for z = zeta*w the factor is the same because w^(2N) = 1
@@ -1798,78 +1556,19 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       g = bb::e_mul_m(g, gamma_m);
     }
     pp->a0 = bb::e_to_mont(a0); pp->b0 = bb::e_to_mont(b0);
-    HIP_OK(h2d(dPP->gamma_pow, pp->gamma_pow, sizeof(pp->gamma_pow)));
-    HIP_OK(h2d(&dPP->a0, &pp->a0, 2 * sizeof(E4)));
+    HIP_OK(run.h2d(dPP->gamma_pow, pp->gamma_pow, sizeof(pp->gamma_pow)));
+    HIP_OK(run.h2d(&dPP->a0, &pp->a0, 2 * sizeof(E4)));
   }
-  HIP_OK(ar.take(&fri_layers[0], 4 * N2));
-  hipLaunchKernelGGL(deep_kernel, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, dQ, log_n, dDinv, dPP, wn_inv_m, WM, WA, fri_layers[0]);
+  HIP_OK(ar.take(&dDeep, 4 * N2));
+  hipLaunchKernelGGL(deep_kernel, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, dQ, log_n, dDinv, dPP, wn_inv_m, WM, WA, dDeep);
   mark(7);
 
-  // ---- 5. FRI commit phase ----------------------------------------------------------------------------------------------------
-  // Enqueued as a whole (round 5): per layer  leaf hash -> tree -> fri_transcript_kernel (root -> beta on the device) -> fold;  ONE copy and ONE synchronisation at the
-  // end bring the roots, the betas and the final layer to the host, which replays the transcript (round 4: a root copy, a synchronisation and a parameter upload per layer).
-  std::vector<std::array<uint32_t, 4>> lroots(n_layers);
-  std::vector<E4> betas(n_layers);
-  uint32_t *dChSt, *dFri;
-  HIP_OK(ar.take(&dChSt, 16)); HIP_OK(ar.take(&dFri, 16 * (size_t)(n_layers + 1)));
-  if (!ch.in.empty()) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: the transcript has pending input at the FRI commit phase"}); return ZKIR_ERR_OTHER; }
-  HIP_OK(h2d(dChSt, ch.st, sizeof(ch.st)));
-  {
-    uint32_t shift = bb::GEN;
-    int log_m = (int)log_n + 1;
-    for (int j = 0; j < n_layers; j++) {
-      const int k = ks[j];
-      const uint64_t m = 1ull << log_m, g = m >> k;
-      HIP_OK(ar.take(&fri_trees[j], 4 * (2 * g - 1)));
-      uint32_t* tree = fri_trees[j];
-      if (g <= (1u << 11)) hipLaunchKernelGGL(fri_leaf_hash_row16_kernel, dim3(grid_for(16 * g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, tree);
-      else if (g <= (1u << 14)) hipLaunchKernelGGL(fri_leaf_hash_quad_kernel, dim3(grid_for(4 * g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, tree);
-      else hipLaunchKernelGGL(fri_leaf_hash_kernel, dim3(grid_for(g)), dim3(NT), 0, s, c->d_p2, fri_layers[j], m, (uint32_t)k, tree);
-      launch_tree_levels(c->d_p2, tree, g, c->sync, s);
-      hipLaunchKernelGGL(fri_transcript_kernel, dim3(1), dim3(16), 0, s, c->d_p2, dChSt, tree + 4 * (2 * g - 2), dFri + 16 * j);
-      FoldParams fp{};                                                         // k binary folds: beta^(2^f) (device), shift^(2^f) — one launch for all of them
-      for (int f = 0; f < k; f++) {
-        fp.half_shift_inv_m[f] = bb::to_mont(bb::inv(bb::mul(2, shift)));
-        shift = bb::mul(shift, shift);
-      }
-      uint32_t* dst;
-      HIP_OK(ar.take(&dst, 4 * g));
-      const E4* dBeta = reinterpret_cast<const E4*>(dFri + 16 * j + 4);
-      if (k == 1) hipLaunchKernelGGL(fri_fold_k_kernel<1>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_n + 1, c->d_tw_fwd, fp, dBeta, dst);
-      else if (k == 2) hipLaunchKernelGGL(fri_fold_k_kernel<2>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_n + 1, c->d_tw_fwd, fp, dBeta, dst);
-      else hipLaunchKernelGGL(fri_fold_k_kernel<3>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_n + 1, c->d_tw_fwd, fp, dBeta, dst);
-      fri_layers[j + 1] = dst;
-      log_m -= k;
-    }
-  }
-  const uint64_t fin_n = 1ull << LOG_FINAL;
-  uint32_t fin_cols[4 * 8];
-  std::vector<uint32_t> fri_out(16 * (size_t)n_layers);
-  if (n_layers) HIP_OK(d2h(fri_out.data(), dFri, fri_out.size() * 4));
-  HIP_OK(d2h(fin_cols, fri_layers[n_layers], 4 * fin_n * 4));
-  HIP_OK(sync_d2h());
-  for (int j = 0; j < n_layers; j++) {                                       // the host's replay of the device's transcript steps
-    memcpy(lroots[j].data(), &fri_out[16 * (size_t)j], 16);
-    ch.observe_n(lroots[j].data(), 4);
-    betas[j] = ch.sample_ext();
-    const E4 bm = bb::e_to_mont(betas[j]);
-    if (memcmp(bm.c, &fri_out[16 * (size_t)j + 4], 16)) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: the device's FRI transcript diverged from the host's"}); return ZKIR_ERR_OTHER; }
-  }
-  for (uint64_t i = 0; i < fin_n; i++) for (int t = 0; t < 4; t++) ch.observe(fin_cols[t * fin_n + i]);
-  // grinding: smallest nonce whose absorption makes the next squeezed element end in POW_BITS zero bits (so::Challenger::grind)
-  uint32_t pow_nonce = 0xFFFFFFFFu;
-  {
-    ch.flush();
-    HIP_OK(h2d(dState, ch.st, sizeof(ch.st)));
-    const uint32_t batch = 1u << 18;
-    for (uint64_t base = 0; base < bb::P && pow_nonce == 0xFFFFFFFFu; base += batch) {
-      HIP_OK(hipMemsetAsync(dBest, 0xFF, 4, s));
-      hipLaunchKernelGGL(pow_grind_kernel, dim3(batch / NT), dim3(NT), 0, s, c->d_p2, dState, (uint32_t)base, (uint32_t)POW_BITS, dBest);
-      HIP_OK(d2h(&pow_nonce, dBest, 4));
-      HIP_OK(sync_d2h());
-    }
-    if (pow_nonce == 0xFFFFFFFFu || !ch.check_pow(pow_nonce, POW_BITS)) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: proof-of-work search failed"}); return ZKIR_ERR_OTHER; }
-  }
+  // ---- 5. FRI commit phase and grinding (fri.inl: the commitment layer's, at b = 1) ---------------------------------------------
+  std::vector<uint32_t*> fri_trees, fri_layers;
+  std::vector<uint32_t> fri_words;                                            // the layer roots and the final layer, as the proof carries them
+  uint32_t pow_nonce;
+  if ((rc = fri_commit(run, ch, ks, log_n + 1, zkir::fri_final_size(1), dDeep, fri_layers, fri_trees, fri_words))) return rc;
+  if ((rc = fri_grind(run, ch, (uint32_t)POW_BITS, &pow_nonce))) return rc;
   mark(8);
   std::vector<uint32_t> queries(NUM_QUERIES);
   for (auto& q : queries) q = ch.sample_bits((int)log_n);
@@ -1887,8 +1586,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   for (int k = 0; k < WT; k++) head.insert(head.end(), t_zw[k].c, t_zw[k].c + 4);
   for (int i = 0; i < 4; i++) head.insert(head.end(), q_z[i].c, q_z[i].c + 4);
   head.push_back((uint32_t)n_layers);
-  for (auto& r : lroots) head.insert(head.end(), r.begin(), r.end());
-  for (uint64_t i = 0; i < fin_n; i++) for (int t = 0; t < 4; t++) head.push_back(fin_cols[t * fin_n + i]);
+  head.insert(head.end(), fri_words.begin(), fri_words.end());
   head.push_back(pow_nonce);
 
   std::vector<GatherJob> jobs;
@@ -1908,16 +1606,11 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       path_jobs(dATree, N2, pos);
     }
     for (uint64_t pos : {(uint64_t)q, (uint64_t)q + N}) { jobs.push_back({dQ + pos * 8, 1, 4, off, 1u, 0u}); off += 4; path_jobs(dQTree, N2, pos); }
-    int log_m = (int)log_n + 1;
-    for (int j = 0; j < n_layers; log_m -= ks[j], j++) {
-      const uint64_t m = 1ull << log_m, g = m >> ks[j], idx = q & (g - 1);
-      for (uint64_t t = 0; t < (1ull << ks[j]); t++) { jobs.push_back({fri_layers[j] + idx + t * g, m, 4, off, 0u, 0u}); off += 4; }
-      path_jobs(fri_trees[j], g, idx);
-    }
+    fri_query_jobs(jobs, off, q, log_n + 1, ks, fri_layers, fri_trees);
   }
   GatherJob* dJobs; uint32_t* dOut;
   HIP_OK(ar.take(&dJobs, jobs.size())); HIP_OK(ar.take(&dOut, (size_t)off));
-  HIP_OK(h2d(dJobs, jobs.data(), jobs.size() * sizeof(GatherJob)));
+  HIP_OK(run.h2d(dJobs, jobs.data(), jobs.size() * sizeof(GatherJob)));
   hipLaunchKernelGGL(gather_kernel, dim3((unsigned)jobs.size()), dim3(64), 0, s, dJobs, (uint32_t)jobs.size(), dOut);
   const uint64_t total = head.size() + off;
   uint32_t* out = (uint32_t*)malloc(total * 4);
@@ -1931,10 +1624,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   for (size_t t = 0; t < queries.size(); t++) out[head.size() + qpos[t]] = queries[t];
   mark(9);
   const double t_body = since(t_entry);
-  if (stage_ms) {
-    (void)hipEventSynchronize(se.ev[9]);
-    for (int i = 0; i < 9; i++) (void)hipEventElapsedTime(&stage_ms[i], se.ev[i], se.ev[i + 1]);
-  }
+  if (stage_ms) run.times(stage_ms, 9);
   if (dbg_t) {
     fprintf(stderr, "zkir_prove mode %d: %.2f ms before the first stage, %.2f ms to the last mark, %.2f ms at return; host ms per stage:", MODE, t_pre, t_body, since(t_entry));
     for (int i = 0; i < 9; i++) fprintf(stderr, " %.2f", host_ms[i + 1] - host_ms[i]);

@@ -17,6 +17,7 @@
 #include "../../include/zkir_amd.h"
 #include "air.h"
 #include "babybear.h"
+#include "fri_shape.h"
 #include "host.h"
 #include "hashcall.h"
 #include "poseidon2.h"
@@ -25,7 +26,7 @@
 namespace {
 
 using bb::E4;
-constexpr int LOG_FINAL = air::LOG_FINAL, LOG_ARITY = air::LOG_ARITY, NS = air::N_STATE, HEADER_WORDS = 21 + 2 * NS;   // (queries / grinding bits: the proof's own, air.h; the version: the mode's)
+constexpr int LOG_FINAL = air::LOG_FINAL, NS = air::N_STATE, HEADER_WORDS = 21 + 2 * NS;   // (queries / grinding bits: the proof's own, air.h; the version: the mode's)
 constexpr uint32_t PROOF_MAGIC = 0x46504B5Au;
 
 const p2::Consts& consts() { static const p2::Consts c = [] { p2::Consts k; p2::generate(k); return k; }(); return c; }
@@ -76,12 +77,6 @@ struct Challenger {                                                        // du
   bool check_pow(uint32_t nonce, int pow_bits) { if (!in.empty()) duplex(); out.clear(); observe(nonce); return (sample() & ((1u << pow_bits) - 1)) == 0; }
 };
 
-std::vector<int> fri_schedule(int log_n) {
-  std::vector<int> ks;
-  for (int log_m = log_n + 1; log_m > LOG_FINAL;) { const int k = ks.empty() ? 1 : (LOG_ARITY < log_m - LOG_FINAL ? LOG_ARITY : log_m - LOG_FINAL); ks.push_back(k); log_m -= k; }
-  return ks;
-}
-
 // E4 helpers on MONTGOMERY values
 inline E4 m_base(uint32_t xm) { return E4{{xm, 0, 0, 0}}; }
 inline E4 m_pow(E4 a, uint64_t e) { E4 r = bb::e_one_m(); while (e) { if (e & 1) r = bb::e_mul_m(r, a); a = bb::e_mul_m(a, a); e >>= 1; } return r; }
@@ -131,6 +126,61 @@ inline E4 fold_pair(const E4& a, const E4& b, uint32_t x_m, const E4& beta) {
   uint32_t inv = bb::R1, base = bb::mont_mul(two_m, x_m), e = bb::P - 2;
   while (e) { if (e & 1) inv = bb::mont_mul(inv, base); base = bb::mont_mul(base, base); e >>= 1; }
   return bb::e_add(bb::e_mul_fm(bb::e_add(a, b), half_m), bb::e_mul_m(beta, bb::e_mul_fm(bb::e_sub(a, b), inv)));
+}
+
+// ---- the FRI verifier core: what verify_impl (a STARK proof: b = 1) and fri_part_verify / host_query_run (the commitment layer's proofs: any b) share.  Each caller keeps
+//      its own order of checks and its own codes: the oracle and the Python specifications fix them. ----
+
+// The final layer (fri_final_size(b) Montgomery values) has degree < 4: coefficients 4 .. n_fin - 1 of its interpolant vanish.  A plain inverse DFT decides: the coset shift
+// scales coefficient k by shift^-k and cannot make a non-zero one vanish.
+bool fri_final_degree_ok(const std::vector<E4>& fin, int b) {
+  const size_t n_fin = fin.size();
+  const uint32_t winv_m = bb::to_mont(bb::inv(bb::root_of_unity(2 + b)));
+  for (size_t k = 4; k < n_fin; k++) {
+    E4 c = bb::e_zero();
+    uint32_t tw = bb::R1, step = bb::R1;
+    for (size_t t = 0; t < k; t++) step = bb::mont_mul(step, winv_m);       // w^-k
+    for (size_t i = 0; i < n_fin; i++) { c = bb::e_add(c, bb::e_mul_fm(fin[i], tw)); tw = bb::mont_mul(tw, step); }
+    if (c.c[0] | c.c[1] | c.c[2] | c.c[3]) return false;
+  }
+  return true;
+}
+
+// The transcript after gamma: per layer root -> beta (Montgomery), the final layer's words, the grinding check.  The caller samples its queries next.
+bool fri_transcript(Challenger& ch, const uint32_t* lroots, int n_layers, const uint32_t* fin_words, size_t n_fin, uint32_t nonce, int pow_bits, std::vector<E4>& betas) {
+  betas.resize(n_layers);
+  for (int j = 0; j < n_layers; j++) { ch.observe_n(lroots + 4 * j, 4); betas[j] = bb::e_to_mont(ch.sample_ext()); }
+  ch.observe_n(fin_words, 4 * n_fin);
+  return ch.check_pow(nonce, pow_bits);
+}
+
+// A query's walk down the layers: where it stands before a layer, and what one layer shows of it
+struct FriWalk {
+  uint32_t shift; int log_m; E4 carried; size_t carried_idx;
+  FriWalk(int log_M, size_t q) : shift(bb::GEN), log_m(log_M), carried(bb::e_zero()), carried_idx(q) {}
+};
+struct FriLayerSeen {
+  E4 v0, v1;          // the leaf's first two values (layer 0: the codeword at q and q + M/2)
+  bool leaf_ok;       // the leaf hashes up its path to the layer's root
+  bool carried_ok;    // v[slot] is the value carried from the layer before (meaningless at layer 0, which carries nothing)
+};
+// One layer: `words` are its 4 * 2^k value words and 4 * (log_m - k) path words, all present (the caller has checked the length).  Folds k times with beta, beta^2, ..
+// and the squared shift, and carries the result to the next layer.
+FriLayerSeen fri_walk_step(FriWalk& s, const uint32_t* words, int k, const uint32_t* root, E4 beta) {
+  const int depth = s.log_m - k;
+  const size_t nv = (size_t)1 << k, g = (size_t)1 << depth, idx = s.carried_idx & (g - 1), slot = s.carried_idx >> depth;
+  std::vector<E4> v(nv);
+  for (size_t t = 0; t < nv; t++) v[t] = bb::e_to_mont(E4{{words[4 * t], words[4 * t + 1], words[4 * t + 2], words[4 * t + 3]}});
+  uint32_t dg[4]; hash_elems(words, 4 * nv, dg);
+  const FriLayerSeen seen{v[0], v[1], check_path(dg, idx, words + 4 * nv, depth, root), e_eq(v[slot], s.carried)};
+  for (int f = 0; f < k; f++) {
+    const size_t half = nv >> (f + 1);
+    const uint32_t wm = bb::root_of_unity(s.log_m);
+    for (size_t t = 0; t < half; t++) v[t] = fold_pair(v[t], v[t + half], bb::to_mont(bb::mul(s.shift, bb::pow(wm, idx + t * g))), beta);
+    s.shift = bb::mul(s.shift, s.shift); s.log_m--; beta = bb::e_mul_m(beta, beta);
+  }
+  s.carried = v[0]; s.carried_idx = idx;
+  return seen;
 }
 
 // the VM's initial state at `entry` (VMState::new, state.rs:55-71) as a state vector: cycle 0, pc limbs, zero registers, Normalized
@@ -787,12 +837,12 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   p += (size_t)(2 * WT + 4) * 4;
   if (!need(1)) return 4;
   const int n_layers = (int)w[p++];
-  const std::vector<int> ks = fri_schedule(log_n);
+  const std::vector<int> ks = zkir::fri_schedule(log_n, 1);
   if (n_layers != (int)ks.size()) return 5;
-  if (!need((size_t)4 * n_layers + 4 * ((size_t)1 << LOG_FINAL) + 1)) return 4;
-  std::vector<const uint32_t*> lroots(n_layers);
-  for (int j = 0; j < n_layers; j++) { lroots[j] = w + p; p += 4; }
-  const size_t at_fin = p, n_fin = (size_t)1 << LOG_FINAL;
+  const size_t n_fin = zkir::fri_final_size(1);
+  if (!need((size_t)4 * n_layers + 4 * n_fin + 1)) return 4;
+  const uint32_t* lroots = w + p; p += 4 * (size_t)n_layers;
+  const size_t at_fin = p;
   std::vector<E4> fin(n_fin);
   for (size_t i = 0; i < n_fin; i++) { fin[i] = get_m(p); p += 4; }
   const uint32_t pow_nonce = w[p++];
@@ -921,10 +971,8 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   const E4 zeta = bb::e_to_mont(ch.sample_ext());
   ch.observe_n(w + at_tz, (size_t)(2 * WT + 4) * 4);
   const E4 gamma = bb::e_to_mont(ch.sample_ext());
-  std::vector<E4> betas(n_layers);
-  for (int j = 0; j < n_layers; j++) { ch.observe_n(lroots[j], 4); betas[j] = bb::e_to_mont(ch.sample_ext()); }
-  ch.observe_n(w + at_fin, 4 * n_fin);
-  if (!ch.check_pow(pow_nonce, POW_BITS)) return 12;
+  std::vector<E4> betas;
+  if (!fri_transcript(ch, lroots, n_layers, w + at_fin, n_fin, pow_nonce, POW_BITS, betas)) return 12;
   // ---- 1. constraints at zeta: sum_c alpha^c C_c(zeta) == Q(zeta) Z_H(zeta) ----
   const uint32_t wn = bb::root_of_unity(log_n), wn_m = bb::to_mont(wn);
   {
@@ -946,18 +994,8 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     for (int i = 0; i < 4; i++) { E4 basis = bb::e_zero(); basis.c[i] = bb::R1; qz = bb::e_add(qz, bb::e_mul_m(basis, q_z[i])); }
     if (!e_eq(o.acc, bb::e_mul_m(qz, zh))) return 10;
   }
-  // ---- 2. final codeword has degree < 4: the four upper coefficients of its interpolant over an order-8 coset vanish (the coset
-  //         shift scales coefficient k by shift^-k and cannot make a non-zero one vanish, so a plain size-8 inverse DFT decides) ----
-  {
-    const uint32_t w8inv_m = bb::to_mont(bb::inv(bb::root_of_unity(LOG_FINAL)));
-    for (size_t k = n_fin / 2; k < n_fin; k++) {
-      E4 c = bb::e_zero();
-      uint32_t tw = bb::R1, step = bb::R1;
-      for (size_t t = 0; t < k; t++) step = bb::mont_mul(step, w8inv_m);  // w^-k
-      for (size_t i = 0; i < n_fin; i++) { c = bb::e_add(c, bb::e_mul_fm(fin[i], tw)); tw = bb::mont_mul(tw, step); }
-      if (c.c[0] | c.c[1] | c.c[2] | c.c[3]) return 11;
-    }
-  }
+  // ---- 2. final codeword has degree < 4: the four upper coefficients of its interpolant over an order-8 coset vanish ----
+  if (!fri_final_degree_ok(fin, 1)) return 11;
   // ---- 3. queries ----
   std::vector<E4> gp(2 * WT + 4);
   gp[0] = bb::e_one_m();
@@ -973,8 +1011,7 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   // order: exactly what the sequential loop returned.
   std::vector<uint32_t> qs(NUM_QUERIES);
   for (auto& q : qs) q = ch.sample_bits(log_n);
-  size_t qsize = 1 + 2 * ((size_t)WM + 4 * depth0) + 2 * ((size_t)WA + 4 * depth0) + 2 * ((size_t)4 + 4 * depth0);
-  { int lm = log_n + 1; for (int j = 0; j < n_layers; j++) { qsize += 4 * ((size_t)1 << ks[j]) + 4 * (size_t)(lm - ks[j]); lm -= ks[j]; } }
+  const size_t qsize = 1 + 2 * ((size_t)WM + 4 * depth0) + 2 * ((size_t)WA + 4 * depth0) + 2 * ((size_t)4 + 4 * depth0) + (size_t)zkir::fri_query_words((uint32_t)depth0, ks);
   const size_t p_queries = p;
   auto check_query = [&](int t) -> int {
     size_t p = p_queries + (size_t)t * qsize;
@@ -1019,30 +1056,17 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
       dz = bb::e_sub(dz, zeta); dzw = bb::e_sub(dzw, zeta_w);
       deep[s2] = bb::e_add(bb::e_mul_m(bb::e_sub(A, a0), bb::e_inv_m(dz)), bb::e_mul_m(bb::e_sub(B, b0), bb::e_inv_m(dzw)));
     }
-    E4 carried = bb::e_zero(); size_t carried_idx = q;
-    uint32_t shift = bb::GEN; int log_m = log_n + 1;
+    FriWalk walk(log_n + 1, q);
     for (int j = 0; j < n_layers; j++) {
-      const int k = ks[j], depth = log_m - k;
-      const size_t nv = (size_t)1 << k, g = (size_t)1 << depth, idx = carried_idx & (g - 1), slot = carried_idx >> depth;
-      if (!need(4 * nv + 4 * (size_t)depth)) return 4;
-      std::vector<E4> v(nv);
-      for (size_t t2 = 0; t2 < nv; t2++) v[t2] = get_m(p + 4 * t2);
-      uint32_t dg[4]; hash_elems(w + p, 4 * nv, dg);
-      p += 4 * nv;
-      if (!check_path(dg, idx, w + p, depth, lroots[j])) return 23;
-      p += 4 * (size_t)depth;
-      if (j == 0) { if (!e_eq(v[0], deep[0]) || !e_eq(v[1], deep[1])) return 24; }
-      else if (!e_eq(v[slot], carried)) return 25;
-      E4 beta = betas[j];
-      for (int f = 0; f < k; f++) {
-        const size_t half = nv >> (f + 1);
-        const uint32_t wm = bb::root_of_unity(log_m);
-        for (size_t t2 = 0; t2 < half; t2++) v[t2] = fold_pair(v[t2], v[t2 + half], bb::to_mont(bb::mul(shift, bb::pow(wm, idx + t2 * g))), beta);
-        shift = bb::mul(shift, shift); log_m--; beta = bb::e_mul_m(beta, beta);
-      }
-      carried = v[0]; carried_idx = idx;
+      const size_t layer_words = 4 * ((size_t)1 << ks[j]) + 4 * (size_t)(walk.log_m - ks[j]);
+      if (!need(layer_words)) return 4;
+      const FriLayerSeen seen = fri_walk_step(walk, w + p, ks[j], lroots + 4 * j, betas[j]);
+      p += layer_words;
+      if (!seen.leaf_ok) return 23;
+      if (j == 0) { if (!e_eq(seen.v0, deep[0]) || !e_eq(seen.v1, deep[1])) return 24; }
+      else if (!seen.carried_ok) return 25;
     }
-    if (!e_eq(fin[carried_idx & (n_fin - 1)], carried)) return 26;
+    if (!e_eq(fin[walk.carried_idx & (n_fin - 1)], walk.carried)) return 26;
     return 0;
   };
   std::vector<int> codes(NUM_QUERIES, 0);
@@ -1082,12 +1106,6 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
 // ================================================================================================
 namespace {
 
-std::vector<int> lowdeg_schedule(int log_n, int b) {
-  std::vector<int> ks;
-  const int log_fin = 2 + b;
-  for (int log_m = log_n + b; log_m > log_fin;) { const int k = ks.empty() ? 1 : (LOG_ARITY < log_m - log_fin ? LOG_ARITY : log_m - log_fin); ks.push_back(k); log_m -= k; }
-  return ks;
-}
 bool lowdeg_params_ok(uint32_t log_n, uint32_t b, uint32_t width, uint32_t num_queries) {
   return log_n >= 3 && log_n <= 26 && b >= 1 && b <= 3 && log_n + b <= 27 && width >= 1 && width <= 512 && num_queries >= 1 && num_queries <= 128;
 }
@@ -1122,7 +1140,7 @@ E4 layer0_want(const zkir::PcsQueries& Q, size_t pos, const uint32_t* const* row
 int host_query_run(void*, const zkir::PcsQueries& Q) {
   const uint32_t* w = Q.w;
   const int n_layers = (int)Q.n_layers, log_M = (int)Q.log_M;
-  const size_t M = (size_t)1 << log_M, n_fin = (size_t)4 << Q.b, at_queries = (size_t)Q.at_queries, qsize = (size_t)Q.qsize;
+  const size_t M = (size_t)1 << log_M, n_fin = zkir::fri_final_size((int)Q.b), at_queries = (size_t)Q.at_queries, qsize = (size_t)Q.qsize;
   const uint32_t n_mats = Q.n_mats;
   const uint32_t *widths = Q.widths, *roots = w + Q.at_roots, *lroots = w + Q.at_lroots, *qs = Q.qs;
   const uint32_t* ks = Q.ks;
@@ -1146,29 +1164,17 @@ int host_query_run(void*, const zkir::PcsQueries& Q) {
       }
     E4 comb[2];
     for (int s2 = 0; s2 < 2; s2++) comb[s2] = layer0_want(Q, (size_t)q + (s2 ? M / 2 : 0), rows[s2]);
-    E4 carried = bb::e_zero(); size_t carried_idx = q;
-    uint32_t shift = bb::GEN; int log_m = log_M;
+    FriWalk walk(log_M, q);
     for (int j = 0; j < n_layers; j++) {
-      const int k = ks[j], depth = log_m - k;
-      const size_t nv = (size_t)1 << k, g = (size_t)1 << depth, idx = carried_idx & (g - 1), slot = carried_idx >> depth;
-      std::vector<E4> v(nv);
-      for (size_t t2 = 0; t2 < nv; t2++) v[t2] = get_m(p + 4 * t2);
-      if (j == 0 && (!e_eq(v[0], comb[0]) || !e_eq(v[1], comb[1]))) return 8;
-      uint32_t dg[4]; hash_elems(w + p, 4 * nv, dg);
-      p += 4 * nv;
-      if (!check_path(dg, idx, w + p, depth, lroots + 4 * j)) return 9;
-      p += 4 * (size_t)depth;
-      if (j > 0 && !e_eq(v[slot], carried)) return 10;
-      E4 beta = betas[j];
-      for (int f = 0; f < k; f++) {
-        const size_t half = nv >> (f + 1);
-        const uint32_t wm = bb::root_of_unity(log_m);
-        for (size_t t2 = 0; t2 < half; t2++) v[t2] = fold_pair(v[t2], v[t2 + half], bb::to_mont(bb::mul(shift, bb::pow(wm, idx + t2 * g))), beta);
-        shift = bb::mul(shift, shift); log_m--; beta = bb::e_mul_m(beta, beta);
-      }
-      carried = v[0]; carried_idx = idx;
+      const int k = (int)ks[j];
+      const size_t layer_words = 4 * ((size_t)1 << k) + 4 * (size_t)(walk.log_m - k);
+      const FriLayerSeen seen = fri_walk_step(walk, w + p, k, lroots + 4 * j, betas[j]);
+      p += layer_words;
+      if (j == 0 && (!e_eq(seen.v0, comb[0]) || !e_eq(seen.v1, comb[1]))) return 8;
+      if (!seen.leaf_ok) return 9;
+      if (j > 0 && !seen.carried_ok) return 10;
     }
-    if (!e_eq(fin[carried_idx & (n_fin - 1)], carried)) return 11;
+    if (!e_eq(fin[walk.carried_idx & (n_fin - 1)], walk.carried)) return 11;
     return 0;
   };
   // (the queries are independent; checked one after the other: a proof has at most 128 of them and its verdict is this loop's)
@@ -1185,30 +1191,17 @@ int fri_part_verify(const uint32_t* w, uint64_t len, size_t at_roots, size_t at_
                     const std::vector<int>& ks, Challenger& ch, zkir::PcsQueries& Q, const zkir::QueryStage& stage) {
   const int n_layers = (int)ks.size();
   const int log_M = (int)(log_n + b);
-  const size_t n_fin = (size_t)4 << b;
+  const size_t n_fin = zkir::fri_final_size((int)b);
   const uint32_t* lroots = w + at_lroots;
   const size_t at_fin = at_lroots + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1;
   auto get_m = [&](size_t at) { return bb::e_to_mont(E4{{w[at], w[at + 1], w[at + 2], w[at + 3]}}); };
   std::vector<E4> fin(n_fin);
   for (size_t i = 0; i < n_fin; i++) fin[i] = get_m(at_fin + 4 * i);
-  // ---- 4: the final layer has degree < 4: coefficients 4 .. n_fin - 1 of its interpolant vanish (a plain inverse DFT decides: the coset shift scales coefficient k by
-  //         shift^-k and cannot make a non-zero one vanish) ----
-  {
-    const uint32_t winv_m = bb::to_mont(bb::inv(bb::root_of_unity(2 + (int)b)));
-    for (size_t k = 4; k < n_fin; k++) {
-      E4 c = bb::e_zero();
-      uint32_t tw = bb::R1, step = bb::R1;
-      for (size_t t = 0; t < k; t++) step = bb::mont_mul(step, winv_m);     // w^-k
-      for (size_t i = 0; i < n_fin; i++) { c = bb::e_add(c, bb::e_mul_fm(fin[i], tw)); tw = bb::mont_mul(tw, step); }
-      if (c.c[0] | c.c[1] | c.c[2] | c.c[3]) return 4;
-    }
-  }
-  // ---- the transcript after gamma ----
-  std::vector<E4> betas(n_layers);
-  for (int j = 0; j < n_layers; j++) { ch.observe_n(lroots + 4 * j, 4); betas[j] = bb::e_to_mont(ch.sample_ext()); }
-  ch.observe_n(w + at_fin, 4 * n_fin);
-  // ---- 5: grinding ----
-  if (!ch.check_pow(w[at_nonce], (int)pow_bits)) return 5;
+  // ---- 4: the final layer has degree < 4 ----
+  if (!fri_final_degree_ok(fin, (int)b)) return 4;
+  // ---- the transcript after gamma; 5: grinding ----
+  std::vector<E4> betas;
+  if (!fri_transcript(ch, lroots, n_layers, w + at_fin, n_fin, w[at_nonce], (int)pow_bits, betas)) return 5;
   std::vector<uint32_t> qs(num_queries);
   for (auto& q : qs) q = ch.sample_bits(log_M - 1);
   // ---- 6 .. 11: the query stage ----
@@ -1229,11 +1222,9 @@ extern "C" {
 
 uint64_t zkir_lowdeg_proof_words(uint32_t log_n, uint32_t log_blowup, uint32_t width, uint32_t num_queries) {
   if (!lowdeg_params_ok(log_n, log_blowup, width, num_queries)) return 0;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)log_blowup);
-  uint64_t qsize = 1 + 2 * ((uint64_t)width + 4 * (uint64_t)(log_n + log_blowup));
-  int lm = (int)(log_n + log_blowup);
-  for (int k : ks) { qsize += 4 * ((uint64_t)1 << k) + 4 * (uint64_t)(lm - k); lm -= k; }
-  return 12 + 4 * (uint64_t)ks.size() + 4 * ((uint64_t)4 << log_blowup) + 1 + (uint64_t)num_queries * qsize;
+  const std::vector<int> ks = zkir::fri_schedule((int)log_n, (int)log_blowup);
+  const uint64_t qsize = 1 + 2 * ((uint64_t)width + 4 * (uint64_t)(log_n + log_blowup)) + zkir::fri_query_words(log_n + log_blowup, ks);
+  return 12 + 4 * (uint64_t)ks.size() + 4 * (uint64_t)zkir::fri_final_size((int)log_blowup) + 1 + (uint64_t)num_queries * qsize;
 }
 
 namespace {
@@ -1242,7 +1233,7 @@ int lowdeg_verify_impl(const uint32_t* w, uint64_t len, const uint32_t* expect_r
   if (!w || len < 12 || w[0] != 0x444C4B5Au || w[1] != 1) return 1;
   const uint32_t log_n = w[2], b = w[3], width = w[4], num_queries = w[5], pow_bits = w[6];
   if (!lowdeg_params_ok(log_n, b, width, num_queries) || pow_bits > 24) return 1;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const std::vector<int> ks = zkir::fri_schedule((int)log_n, (int)b);
   if (w[7] != (uint32_t)ks.size() || len != zkir_lowdeg_proof_words(log_n, b, width, num_queries)) return 1;
   // ---- 2: the root ----
   const uint32_t* root = w + 8;
@@ -1378,7 +1369,7 @@ int eval_verify_impl(const uint32_t* w, uint64_t len, const uint32_t* expect_roo
   const uint32_t mask = (1u << n_points) - 1;                               // one matrix is opened at every point
   BatchShape sh;
   if (!batch_shape_ok(1, n_points, &width, &mask, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const std::vector<int> ks = zkir::fri_schedule((int)log_n, (int)b);
   if (w[8] != (uint32_t)ks.size() || len != zkir_eval_proof_words(log_n, b, width, n_points, num_queries)) return 1;
   return eval_core_verify(sh, 9, w, len, ks, expect_root, expect_points, expect_evals, stage);
 }
@@ -1392,7 +1383,7 @@ int batch_eval_verify_impl(const uint32_t* w, uint64_t len, const uint32_t* expe
   for (uint32_t m = 0; m < n_mats; m++) { widths[m] = w[9 + 2 * m]; masks[m] = w[10 + 2 * m]; }
   BatchShape sh;
   if (!batch_shape_ok(n_mats, n_points, widths, masks, &sh) || !lowdeg_params_ok(log_n, b, 1, num_queries) || pow_bits > 24) return 1;
-  const std::vector<int> ks = lowdeg_schedule((int)log_n, (int)b);
+  const std::vector<int> ks = zkir::fri_schedule((int)log_n, (int)b);
   if (w[8] != (uint32_t)ks.size() || len != zkir_batch_eval_proof_words(log_n, b, n_mats, widths, masks, n_points, num_queries)) return 1;
   return eval_core_verify(sh, 9 + 2 * (size_t)n_mats, w, len, ks, expect_roots, expect_points, expect_evals, stage);
 }
