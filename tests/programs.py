@@ -2,6 +2,8 @@
  and a seeded random-program generator.  Each entry returns (blob, inputs, cfg_kwargs)."""
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from zkir_amd import spec
@@ -549,3 +551,148 @@ def hash_misaligned_sha_shape():
 
 HASH_EDGES = {f.__name__: f for f in (hash_edge_calls, hash_edge_top, hash_edge_boundary, hash_edge_max_len)}                      # these have a mode-4 proof
 HASH_EDGES_NO_PROOF = {f.__name__: f for f in (hash_edge_len_over, hash_edge_out_over_2p40, hash_edge_in_over_code, hash_edge_out_over_code)}
+
+
+# ---- programs larger than the prover's LDS window over the instruction ROM (4096 words) and pcs past 2^20 (tests/test_big_code.py, tests/test_gpu_big_code.py) -------------
+# Built at run time and cached: the largest blob is about 1 MiB.  Every word that is not placed is an EBREAK, so a run that strays halts; every run is capped with max_cycles a
+# little above its intended row count, so a builder mistake costs rows and not minutes.
+ROM_LDS = 4096                                   # the first ROM rows the prover counts in LDS; rows from here on are counted with global atomics
+W20 = (0x100000 - 0x1000) // 4                   # the code word whose pc is 2^20 (261120): JAL's 21-bit offset reaches it from the first words
+PC = lambda word: 0x1000 + 4 * word              # noqa: E731
+
+
+def _big(n_words, placed, data=b""):
+    """A blob of n_words code words: `placed` = {first word index: [words]}, EBREAK everywhere else."""
+    code = [EB] * n_words
+    for at, words in placed.items():
+        assert 0 <= at and at + len(words) <= n_words and all(w == EB for w in code[at:at + len(words)]), at
+        code[at:at + len(words)] = words
+    return _p(code, data)
+
+
+def _jal_to(rd, frm, to):
+    """JAL at word `frm` to word `to`."""
+    assert -(1 << 20) <= 4 * (to - frm) < (1 << 20)
+    return spec.jal(rd, 4 * (to - frm))
+
+
+@functools.lru_cache(maxsize=None)
+def _rom_straddle():
+    n, body = 4200, ROM_LDS - 2
+    return _big(n, {
+        0: [A(3, 0, 300), A(1, 0, 0), _jal_to(14, 2, 10), _jal_to(0, 3, body - 4)],
+        10: [A(2, 2, 7), A(1, 1, 1), E(O.JALR, 0, 14, imm=0)],                               # a block below the window's end, called before and after the loop
+        body - 4: [A(4, 0, 1), A(4, 4, 1), A(4, 4, 1), A(4, 4, 1),                          # words 4090 .. 4093: straight-line code that runs on through 4099
+                   spec.add(4, 4, 2), A(1, 1, 3), A(3, 3, -1), spec.bne(3, 0, -12),          # words 4094 .. 4097: the loop body, 300 times, two words on each side of the split
+                   A(4, 4, 1), A(4, 4, 1), _jal_to(14, body + 6, 10),                        # words 4098 .. 4100
+                   A(11, 1, 0), A(10, 0, 2), EC] + _exit0()})
+
+
+def rom_straddle():
+    """4200 code words; straight-line code through words 4093 .. 4099, a counted loop over words 4094 .. 4097 run 300 times (multiplicities above 255 on both sides of the
+    split), a block at words 10 .. 12 called before and after the loop.  1223 rows: more ROM rows than trace rows (N = 2048)."""
+    return _rom_straddle(), [], {"max_cycles": 1240}
+
+
+@functools.lru_cache(maxsize=None)
+def _rom_far_hot():
+    hot = 4300
+    return _big(4400, {0: [A(1, 0, 1), _jal_to(0, 1, hot)],
+                       hot: [spec.add(2, 2, 1), A(3, 2, 5), E(O.XOR, 4, 3, 2), spec.sub(5, 4, 1), E(O.SLTU, 6, 5, 4), A(1, 1, 1), _jal_to(0, hot + 6, hot)]})
+
+
+def rom_far_hot():
+    """About 4400 code words, the whole hot loop (7 words) above word 4096, run to exactly 2^12 rows: every lane of every block adds to the same few global counters."""
+    return _rom_far_hot(), [], {"max_cycles": 1 << 12}
+
+
+@functools.lru_cache(maxsize=None)
+def _rom_exact(n):
+    return _big(n, {0: [A(3, 0, 3), _jal_to(0, 1, n - 6)], n - 6: [A(1, 1, 1), A(3, 3, -1), spec.bne(3, 0, -8), A(10, 0, 0), A(11, 0, 0), EC]})
+
+
+def rom_exact_4096():
+    """Exactly 4096 code words (the LDS window is the whole ROM), the last one executed."""
+    return _rom_exact(ROM_LDS), [], {"max_cycles": 24}
+
+
+def rom_exact_4097():
+    """Exactly 4097 code words: the global path holds a single ROM row, executed once (the exit's ECALL)."""
+    return _rom_exact(ROM_LDS + 1), [], {"max_cycles": 24}
+
+
+PC_CARRY_WORDS = W20 + 64
+
+
+@functools.lru_cache(maxsize=None)
+def _pc_carry():
+    return _big(PC_CARRY_WORDS, {
+        0: [A(1, 0, 0), A(7, 0, 2), _jal_to(0, 2, W20 - 3)],                                  # the delta is 0xFEFEC: below 2^20
+        W20 - 6: [A(8, 6, 0), _jal_to(9, W20 - 5, W20 + 4)],                                  # 0xFFFE8: where the JALR lands; forward over the boundary again (link 0xFFFF0)
+        W20 - 3: [A(3, 3, 5), A(1, 1, 1),                                                     # 0xFFFF4, 0xFFFF8 (the BNE's target: the pass counter)
+                  spec.jal(5, 4),                                                             # 0xFFFFC: the link is 0x100000, and so is the next pc
+                  A(4, 5, 0), E(O.SRLI, 12, 5, imm=20),                                       # 0x100000, 0x100004: the link's second limb, read
+                  spec.bne(1, 7, -16),                                                        # 0x100008 -> 0xFFFF8: taken on the first pass, not on the second
+                  E(O.JALR, 6, 5, imm=-24),                                                   # 0x10000C -> 0xFFFE8 through the linked register; link 0x100010
+                  spec.add(11, 4, 12), A(10, 0, 2), EC] + _exit0()})                          # 0x100010: WRITE 0x100001, exit
+
+
+def pc_carry():
+    """W20 + 64 code words (1 MiB).  A JAL from word 2 to pc 0xFFFF4; a JAL at pc 0xFFFFC whose link and target are 0x100000; a BNE at 0x100008 back to 0xFFFF8 (a negative
+    imm17 borrowing out of pc limb 1), taken once and not taken once; a JALR through the linked register from 0x10000C back to 0xFFFE8; a JAL forward again; WRITE, exit.
+    23 rows; rows 5 and 10 sit at pc 0xFFFFC."""
+    return _pc_carry(), [], {"max_cycles": 32}
+
+
+PC_CARRY_MEM_WORDS = W20 + 65                                         # odd: the boundary cell 0x100100 holds the last code word and the first data word
+PC_CARRY_MEM_DATA = PC(PC_CARRY_MEM_WORDS)                            # 0x100104
+PC_CARRY_MEM_BC = PC_CARRY_MEM_DATA - 4
+
+
+@functools.lru_cache(maxsize=None)
+def _pc_carry_mem(wide):
+    base = PC_CARRY_MEM_DATA + 4                                      # 0x100108: the first whole data cell
+    head = li40(5, base) + [A(1, 0, 0x1234)]
+    body = [A(3, 3, 5), A(3, 3, 1), A(3, 3, 1),                       # 0xFFFF4 .. 0xFFFFC: the pc + 4 carry of a sequential row
+            spec.sw(5, 1, 40), spec.lw(2, 5, 40), E(O.LB, 4, 5, imm=1), spec.lw(6, 5, 0), E(O.SB, rs1=5, rs2=1, imm=33), E(O.LD, 7, 5, imm=32)]
+    if wide:
+        body += [spec.lw(8, 5, -4),                                   # the data half of the boundary cell
+                 A(11, 5, 0), A(12, 0, 32), A(13, 5, 32), A(10, 0, 3), EC, spec.lw(9, 13, 0)]       # SHA-256 of the data's first 32 bytes, the digest right behind them
+    body += [A(11, 2, 0), A(10, 0, 2), EC] + _exit0()
+    return _big(PC_CARRY_MEM_WORDS, {0: head + [_jal_to(0, len(head), W20 - 3)], W20 - 3: body}, data=bytes(range(0x41, 0x41 + 36)))
+
+
+def pc_carry_mem(wide=False):
+    """pc_carry's jump to 0xFFFF4 and straight-line code over pc 0x100000 (the sequential pc + 4 carry), an odd word count and 36 data bytes at 0x100104 — above 2^20, so
+    every address limb 1 and every touched cell's second limb is non-zero: SW / LW / LB / SB / LD there.  `wide` (mode 4) adds a load of the boundary cell's data half and
+    one SHA-256 call whose input is that data and whose output lies right behind it."""
+    return _pc_carry_mem(bool(wide)), [], {"max_cycles": 48}
+
+
+def _on_last_code_word(store):
+    last = PC(PC_CARRY_WORDS - 1)
+    return _big(PC_CARRY_WORDS, {0: li40(5, last) + [A(1, 0, 7), spec.sw(5, 1, 0) if store else spec.lw(2, 5, 0), A(3, 0, 1), EB]})
+
+
+@functools.lru_cache(maxsize=None)
+def _big_store_on_code():
+    return _on_last_code_word(True)
+
+
+@functools.lru_cache(maxsize=None)
+def _big_load_on_code():
+    return _on_last_code_word(False)
+
+
+def big_store_on_code():
+    """A store to the last code word of a 1 MiB code segment (0x1000FC): the VM runs it, a mode-3 proof is refused (the overlap rule, with a bound above 2^20)."""
+    return _big_store_on_code(), [], {"max_cycles": 16}
+
+
+def big_load_on_code():
+    """A load from the last code word of a 1 MiB code segment: likewise."""
+    return _big_load_on_code(), [], {"max_cycles": 16}
+
+
+BIG_CODE = {f.__name__: f for f in (rom_straddle, rom_far_hot, rom_exact_4096, rom_exact_4097, pc_carry, pc_carry_mem)}
+BIG_CODE_REFUSED = {f.__name__: f for f in (big_store_on_code, big_load_on_code)}

@@ -1117,10 +1117,15 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   // witness — the caller's when it brings one, the device's of a run with hash calls (a device witness of loads and stores only touches at most one cell per row)
   const uint64_t CELL_CAP = std::max<uint64_t>(N, MEM_HOST ? pub->n_cells + 1 : HASH_DEV ? cell_addr_v.size() + 1 : 0);
   const size_t SEC_WORDS = std::max<size_t>(8 * (size_t)CELL_CAP, !WIDE ? 0 : HASH_DEV ? (size_t)hw.n_words / 64 + 128 : (size_t)pub->hash_section_words + (size_t)pub->hash_section_words / 100) + 4096;   // (the memory section, then the hash section, each with its chunk digests behind it; the device-built tape stays in its own block: only its digests come here)
+  // (modes 3 / 4) the device memory witness of a run without hash calls works in the LDE output buffer, which nothing has written yet (WM * 2N words: 1600 B per row
+  // against the ~70 B per row the witness needs).  Its scratch also holds the program image: a long program run for a few rows (1 MiB of code, 32 rows) does not fit there
+  // and gets a block of its own.
+  const size_t mc_need = MEM && !MEM_HOST && !HASH_DEV ? zkir::memcheck_scratch_bytes(pub->n_real, blob_len) : 0;
+  const size_t mc_own = mc_need > (size_t)WM * N2 * 4 ? mc_need : 0;
   {                                               // workspace: 12 W (M + L) + 440 (trees, quotient, weights, FRI) bytes per row, allocated once per context
     static_assert(WMX % 8 == 0 && air::W_COMMITTED_DEFAULT % 8 == 0, "the main trace fills whole B8 blocks");
     const size_t want = (size_t)(12 * WM + 12 * WA + 16 + 544 + (IO ? 48 : 0) + (MEM ? 48 : 0) + (WIDE ? 8 : 0)) * N + (size_t)air::MAX_NUM_QUERIES * 64 * 1024 + (8u << 20) + (size_t)n_code * 24 + (1u << 16) + (WIDE ? (1u << 17) : 0) +
-                        (IO ? (size_t)pub->n_inputs * 8 : 0) + (MEM ? (size_t)air::MEM_MULT * 24 + (size_t)CELL_CAP * 28 + SEC_WORDS * 4 + blob_len + (1u << 16) : 0);
+                        (IO ? (size_t)pub->n_inputs * 8 : 0) + (MEM ? (size_t)air::MEM_MULT * 24 + (size_t)CELL_CAP * 28 + SEC_WORDS * 4 + blob_len + (1u << 16) : 0) + (mc_own ? mc_own + 256 : 0);
     if (const int arc = arena_reserve(c, want)) return arc;
   }
   uint32_t *dM, *dL, *dTree, *dQ, *dQTree, *dDeep, *dBound, *dA, *dAL, *dATree, *dCode, *dMult;
@@ -1131,7 +1136,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   IoEntry* dIo = nullptr; uint32_t* dIoCount = nullptr; uint64_t* dInputs = nullptr; uint32_t* dIoScratch = nullptr;
   uint64_t* dMemOld = nullptr; uint32_t* dMemTold = nullptr; uint4* dMemSide = nullptr; E4* dInvMem = nullptr; uint2* dWideSide = nullptr;
   uint64_t *dCellAddr = nullptr, *dCellBytes = nullptr; uint32_t* dCellTime = nullptr; uint8_t* dImage = nullptr; E4* dCellPart = nullptr; uint32_t* dSec = nullptr;
-  E4* dTapePart = nullptr; unsigned long long* dTapeCheck = nullptr;
+  E4* dTapePart = nullptr; unsigned long long* dTapeCheck = nullptr; unsigned char* dMcScratch = nullptr;
   HIP_OK(ar.take(&dPP, 1)); HIP_OK(ar.take(&dBound, 2 * NS + 4)); HIP_OK(ar.take(&dBad, 1));
   if (IO) { HIP_OK(ar.take(&dIo, N)); HIP_OK(ar.take(&dIoCount, 4)); HIP_OK(ar.take(&dInputs, (size_t)pub->n_inputs + 1)); HIP_OK(ar.take(&dIoScratch, 2 * N + 2 * (N / 1024 + 2))); }
   if (MEM) {
@@ -1139,6 +1144,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     HIP_OK(ar.take(&dCellAddr, CELL_CAP)); HIP_OK(ar.take(&dCellBytes, CELL_CAP)); HIP_OK(ar.take(&dCellTime, CELL_CAP)); HIP_OK(ar.take(&dImage, (size_t)blob_len + 1)); HIP_OK(ar.take(&dCellPart, CELL_CAP / NT + 1));
     HIP_OK(ar.take(&dSec, SEC_WORDS));                      // the memory section (seven words per touched cell) and its chunk digests
     if (WIDE) { HIP_OK(ar.take(&dWideSide, N)); HIP_OK(ar.take(&dTapePart, 2 * (size_t)TAPE_MAX_BLOCKS)); HIP_OK(ar.take(&dTapeCheck, 1)); }   // (the tapes' table side: two kernels' partial sums; the record checks' result)
+    if (mc_own) HIP_OK(ar.take(&dMcScratch, mc_own));
   }
   HIP_OK(ar.take(&dM, WM * N)); HIP_OK(ar.take(&dL, WM * N2)); HIP_OK(ar.take(&dTree, 4 * (2 * N2 - 1)));
   HIP_OK(ar.take(&dA, WA * N)); HIP_OK(ar.take(&dAL, WA * N2)); HIP_OK(ar.take(&dATree, 4 * (2 * N2 - 1)));
@@ -1170,10 +1176,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
         HIP_OK(hipMemcpyAsync(dMemOld, hw_rows.p, (size_t)pub->n_real * 8, hipMemcpyDeviceToDevice, s));
         HIP_OK(hipMemcpyAsync(dMemTold, (uint64_t*)hw_rows.p + pub->n_real, (size_t)pub->n_real * 4, hipMemcpyDeviceToDevice, s));
       } else {
-        // scratch = the LDE output buffer, which nothing has written yet (WM * 2N words: 1600 B per row against the ~70 B per row the witness needs)
-        const size_t need = zkir::memcheck_scratch_bytes(pub->n_real, blob_len);
-        if (need > (size_t)WM * N2 * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: memcheck scratch does not fit the LDE buffer"}); return ZKIR_ERR_OTHER; }
-        rc = zkir::memcheck_device(trace, pub->n_real, blob, blob_len, dL, (size_t)WM * N2 * 4, dMemOld, dMemTold, cell_addr_v, cell_bytes_v, cell_time_v, pin, s);
+        // scratch = the LDE output buffer, or the block taken above where the program image does not fit it
+        rc = zkir::memcheck_device(trace, pub->n_real, blob, blob_len, mc_own ? (void*)dMcScratch : (void*)dL, mc_own ? mc_own : (size_t)WM * N2 * 4, dMemOld, dMemTold, cell_addr_v, cell_bytes_v, cell_time_v, pin, s);
         if (rc) return rc;
       }
       rc = WIDE ? zkir_main_trace_wide_launch(trace, pub->n_real, &io, dMemOld, dMemTold, 4 * (uint64_t)n_code, dIoScratch, dM, s) : zkir_main_trace_mem_launch(trace, pub->n_real, &io, dMemOld, dMemTold, dIoScratch, dM, s);
