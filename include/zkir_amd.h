@@ -464,6 +464,38 @@ int zkir_batch_eval_prove(zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* 
                           void* hip_stream);
 int zkir_batch_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals);
 
+/* OPENING COMMITMENTS OF DIFFERENT HEIGHTS IN ONE EVALUATION PROOF ('ZKMH'; zkir_amd/csrc/mixed_eval.inl, verify.cpp; spec of every word: tests/mixed_eval_ref.py).
+ * Statement: n_groups (2 or 3) groups at ONE log_blowup b, of strictly decreasing heights log_n_0 > log_n_1 > .. (each >= 3, log_n_0 + b <= 27).  Group h is exactly what
+ * zkir_batch_eval_prove states at its own height: n_mats[h] (1 .. 4) B8 matrices of M_h = N_h << b rows on ctxs[h], each under its own tree, widths 1 .. 512 summing to at most
+ * 512 in the group, its own n_points[h] (1 or 2) points, a mask per matrix with zkir_batch_eval_prove's rules.  Points of different groups are unrelated.  One group is
+ * refused (that is zkir_batch_eval_prove), and so are equal heights (they belong in one group).
+ * One gamma is drawn after the header and all roots, points and evaluations; its exponent runs consecutively through the groups in order, and inside a group in
+ * zkir_batch_eval_prove's order.  F_h is that proof's quotient of group h over 31 <w_{M_h}> with those exponents.  ONE FRI: layer 0 is F_0; the schedule is the low-degree
+ * proof's with one more cap — a step never jumps over a lower M_h, so every M_h is a committed layer's size — and when a fold leaves the layer of size M_h, F_h is added to it
+ * by index before it is hashed.  The final layer (4 << b values of degree < 4), grinding and q_t = sample_bits(log M_0 - 1) are the low-degree proof's.
+ * Proof words (all canonical): [0..7) 'ZKMH' = 0x484D4B5A, version 1, log_blowup, n_groups, num_queries, pow_bits, n_layers | per group: log_n, n_mats, n_points, then
+ * (width, mask) per matrix | all roots (groups in order, matrices in order) | all points | all evaluations in the exponent order | layer roots | final layer | nonce | queries.
+ * A query: q; group 0's matrices in order, record_m(q) and record_m(q + M_0/2); each lower group's matrices in order, ONE record_m(q mod M_h) of width + 4 log M_h words; the
+ * layers as in the low-degree proof.  Transcript: every word up to and including the evaluations, gamma, then the low-degree proof's steps.
+ * The arrays are flat HOST arrays with the groups concatenated: ctxs, n_mats, n_points have n_groups entries; lde_mats, trees (DEVICE pointers), widths, masks one entry per
+ * matrix; points 4 words per point.  zkir_mixed_eval_proof_words: the proof's length; 0 for a shape no proof can state.
+ * zkir_mixed_eval_prove: the workspace arena and the one-proof-at-a-time lock are ctxs[0]'s; the other contexts are only read.  Synchronises the stream; nothing past *n_words
+ * is written.  ZKIR_ERR_ARGUMENT with *n_words = 0, nothing written and nothing launched for: a null pointer, n_groups outside 2 .. 3, a context whose log_blowup is not
+ * ctxs[0]'s, heights that do not strictly decrease, and, per group, zkir_batch_eval_prove's refusals.
+ * zkir_mixed_eval_verify: host only (there is no device form).  zkir_batch_eval_verify's codes in its order: 1 malformed (exact length, magic, version, ranges, group order, a
+ * group's shape, n_layers), 2 roots, 13 points / evaluations, 3 a word >= p, 12 a point in the base field or two equal points WITHIN a group, 4 final layer, 5 grinding,
+ * 6 index word, 7 a record (in the order they stand in the query), 8 layer-0 values (from group 0's records), 9 a FRI leaf's path, 10 carried value — before the step into
+ * the layer of size M_h the carried value gains F_h(q mod M_h), recomputed from group h's records — 11 final value.  (Which code a false evaluation gets depends on the prover: one that follows the honest
+ * procedure after it folds a quotient with a pole and meets check 4, in any group; 8 (group 0) and 10 (a lower group) appear where the committed layers are those of other
+ * evaluations than the stated ones.)  The expected
+ * arrays (all roots, all points, all evaluations, in the proof's order) are read at the sizes the PROOF's header states, and only once check 1 has passed. */
+uint64_t zkir_mixed_eval_proof_words(uint32_t log_blowup, uint32_t n_groups, const uint32_t* log_ns, const uint32_t* n_mats, const uint32_t* n_points, const uint32_t* widths,
+                                     const uint32_t* masks, uint32_t num_queries);
+int zkir_mixed_eval_prove(zkir_stark_ctx* const* ctxs, uint32_t n_groups, const uint32_t* n_mats, const uint32_t* const* lde_mats, const uint32_t* widths, const uint32_t* const* trees,
+                          const uint32_t* masks, const uint32_t* points, const uint32_t* n_points, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words,
+                          uint64_t* n_words, void* hip_stream);
+int zkir_mixed_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals);
+
 /* VERIFYING ON THE DEVICE.  zkir_lowdeg_verify, zkir_eval_verify and zkir_batch_eval_verify with checks 7 - 11 of ALL the queries run on the current HIP device: one leaf-and-
  * path job per matrix record and FRI layer (a row of 16 lanes each), the layer-0 values and the folds in a second kernel.  Everything else — the shape, the expectations, the
  * word range, the whole transcript, the final layer's degree, grinding, the sampling of the rows, check 6 — is the host entries' own code in its order, and the device is

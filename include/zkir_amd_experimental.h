@@ -58,6 +58,17 @@ uint64_t zkir_batch_eval_quotient_scratch_words(uint32_t log_m, uint32_t n_mats,
 int zkir_batch_eval_quotient_launch(const zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* const* lde_mats, const uint32_t* widths, const uint32_t* masks, const uint32_t gamma[4],
                                     const uint32_t* points, uint32_t n_points, const uint32_t* evals, uint32_t* scratch, uint32_t* cw, void* hip_stream);
 
+/* MEASUREMENT: zkir_mixed_eval_prove with the device time (ms, HIP events) of its six stages, each over all the groups: weights | evaluations | quotients | FRI commit phase |
+ * grinding | query section. */
+int zkir_mixed_eval_prove_stages(zkir_stark_ctx* const* ctxs, uint32_t n_groups, const uint32_t* n_mats, const uint32_t* const* lde_mats, const uint32_t* widths,
+                                 const uint32_t* const* trees, const uint32_t* masks, const uint32_t* points, const uint32_t* n_points, uint32_t num_queries, uint32_t pow_bits,
+                                 uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words, float stage_ms[6], void* hip_stream);
+/* TEST / MEASUREMENT: the FRI fold kernel alone.  layer: DEVICE, the 2^log_m values of a layer of the context's FRI, layer[t m + j] = coordinate t of value j, canonical
+ * (k <= log_m <= log_n + log_blowup; the layer's coset shift is 31^(2^(log_n + log_blowup - log_m))).  It is folded k (1 .. 3) times with beta (HOST, canonical E4), beta^2,
+ * beta^4 into out[t g + i], g = m >> k.  addend: NULL, or DEVICE 4 g words added by index (out = fold + addend: the add form zkir_mixed_eval_prove uses at a layer of a lower
+ * group's size).  Synchronises the stream. */
+int zkir_fri_fold_launch(const zkir_stark_ctx* ctx, const uint32_t* layer, uint32_t log_m, uint32_t k, const uint32_t beta[4], const uint32_t* addend, uint32_t* out, void* hip_stream);
+
 /* DIAGNOSTIC: what the calling thread's last zkir_lowdeg_verify_device / zkir_eval_verify_device / zkir_batch_eval_verify_device call launched: hash_jobs = num_queries x
  * (2 n_mats + n_layers) leaf-and-path jobs, value_jobs = num_queries x (2 + n_layers) (two layer-0 values and one fold a layer); (0, 0) when the call returned before its
  * query stage (verdicts 1 - 5, 12, 13).  Either pointer may be NULL. */

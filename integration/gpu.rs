@@ -131,7 +131,17 @@ extern "C" {
     pub fn zkir_batch_eval_prove(ctx: *mut ZkirStarkCtx, n_mats: u32, lde_mats: *const *const u32, widths: *const u32, trees: *const *const u32, masks: *const u32, points: *const u32,
                                  n_points: u32, num_queries: u32, pow_bits: u32, proof_host: *mut u32, cap_words: u64, n_words: *mut u64, stream: *mut c_void) -> c_int;
     pub fn zkir_batch_eval_verify(proof: *const u32, n_words: u64, expect_roots: *const u32, expect_points: *const u32, expect_evals: *const u32) -> c_int;
-    // the three verifiers above with checks 7 - 11 of all queries on the current HIP device (proof and expectations: host memory; no context): the host entry's verdict for
+    // an evaluation proof over SEVERAL HEIGHTS at one log_blowup ('ZKMH'): n_groups (2 or 3) groups of strictly decreasing log_n, each what zkir_batch_eval_prove takes at its
+    // own height with its own points.  Flat host arrays, groups concatenated: ctxs / n_mats / n_points / log_ns have n_groups entries, lde_mats / trees / widths / masks one per
+    // matrix, points 4 words per point.  The workspace and the lock are ctxs[0]'s.  The verifier is host only (no device form): zkir_batch_eval_verify's codes, expect_* read at
+    // the sizes the proof's header states (all roots, all points, all evaluations, in the proof's order)
+    pub fn zkir_mixed_eval_proof_words(log_blowup: u32, n_groups: u32, log_ns: *const u32, n_mats: *const u32, n_points: *const u32, widths: *const u32, masks: *const u32,
+                                       num_queries: u32) -> u64;
+    pub fn zkir_mixed_eval_prove(ctxs: *const *mut ZkirStarkCtx, n_groups: u32, n_mats: *const u32, lde_mats: *const *const u32, widths: *const u32, trees: *const *const u32,
+                                 masks: *const u32, points: *const u32, n_points: *const u32, num_queries: u32, pow_bits: u32, proof_host: *mut u32, cap_words: u64,
+                                 n_words: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn zkir_mixed_eval_verify(proof: *const u32, n_words: u64, expect_roots: *const u32, expect_points: *const u32, expect_evals: *const u32) -> c_int;
+    // the three verifiers of ONE height above with checks 7 - 11 of all queries on the current HIP device (proof and expectations: host memory; no context): the host entry's verdict for
     // every input; a negative result is a device failure (-ZKIR_ERR_DEVICE) or no host memory (-ZKIR_ERR_OTHER), not a verdict
     pub fn zkir_lowdeg_verify_device(proof: *const u32, n_words: u64, expect_root: *const u32, stream: *mut c_void) -> c_int;
     pub fn zkir_eval_verify_device(proof: *const u32, n_words: u64, expect_root: *const u32, expect_points: *const u32, expect_evals: *const u32, stream: *mut c_void) -> c_int;

@@ -277,11 +277,11 @@ const char* batch_plan(uint32_t n_mats, const uint32_t* widths, const uint32_t* 
   *out = p;
   return nullptr;
 }
-// R gamma^e at [(i total_blocks + first_block[m] + blk) 8 + u] for the selected (i, m), k = 8 blk + u < width_m; zero everywhere else
-std::vector<E4> batch_gamma_table(const E4& gamma, const BatchPlan& p) {
+// R gamma^e at [(i total_blocks + first_block[m] + blk) 8 + u] for the selected (i, m), k = 8 blk + u < width_m; zero everywhere else.  `g`: R gamma^(the first exponent) —
+// one for a proof of one height; a group of mixed_eval.inl goes on where the group before it stopped.
+std::vector<E4> batch_gamma_table(const E4& gamma, const BatchPlan& p, E4 g = bb::e_one_m()) {
   std::vector<E4> t((size_t)p.n_points * p.total_blocks * 8, bb::e_zero());
   const E4 gamma_m = bb::e_to_mont(gamma);
-  E4 g = bb::e_one_m();
   for (uint32_t i = 0; i < p.n_points; i++) for (uint32_t m = 0; m < p.n_mats; m++) if (p.sel(i, m))
     for (uint32_t k = 0; k < p.width[m]; k++) { t[((size_t)i * p.total_blocks + p.first_block[m]) * 8 + k] = g; g = bb::e_mul_m(g, gamma_m); }
   return t;

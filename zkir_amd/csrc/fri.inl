@@ -64,9 +64,12 @@ __global__ __launch_bounds__(NT) void fri_leaf_hash_row16_kernel(const p2::Const
 // values c[i + u g], g = m >> K, and fold f pairs v[u] with v[u + 2^(K-f-1)] — exactly the pairs (j, j + h_f) of a binary fold of the size-(m >> f) layer, the same field operations in
 // the same order on every value, so the layer is the one the chain of binary folds leaves.
 // beta_m: the layer's challenge and its squares, beta^(2^f) (Montgomery), written by fri_transcript_kernel on the device (round 5: no host round trip between the layers)
+// ADD (a proof over codewords of several heights, mixed_eval.inl): the layer the folds leave has the size of a lower codeword, which is added to it by index before the
+// layer is hashed — out[t g + i] = fold + addend[t g + i], one bb::add per coordinate.  Without ADD the addend is not read and the kernel is what it was.
 struct FoldParams { uint32_t half_shift_inv_m[3]; };
-template <int K>
-__global__ __launch_bounds__(NT) void fri_fold_k_kernel(const uint32_t* __restrict__ c, uint32_t log_m, uint32_t log_2n, const uint32_t* __restrict__ tw_fwd, FoldParams fp, const E4* __restrict__ beta_m, uint32_t* __restrict__ out) {
+template <int K, bool ADD = false>
+__global__ __launch_bounds__(NT) void fri_fold_k_kernel(const uint32_t* __restrict__ c, uint32_t log_m, uint32_t log_2n, const uint32_t* __restrict__ tw_fwd, FoldParams fp, const E4* __restrict__ beta_m, uint32_t* __restrict__ out,
+                                                        const uint32_t* __restrict__ addend) {
   const uint64_t m = 1ull << log_m, g = m >> K, i = (uint64_t)blockIdx.x * NT + threadIdx.x;
   if (i >= g) return;
   E4 v[1 << K];
@@ -93,7 +96,18 @@ __global__ __launch_bounds__(NT) void fri_fold_k_kernel(const uint32_t* __restri
     }
   }
 #pragma unroll
-  for (int t = 0; t < 4; t++) out[(uint64_t)t * g + i] = v[0].c[t];
+  for (int t = 0; t < 4; t++) out[(uint64_t)t * g + i] = ADD ? bb::add(v[0].c[t], addend[(uint64_t)t * g + i]) : v[0].c[t];
+}
+// the one launch of the K folds of a layer of 2^log_m values into `out` (addend: null, or the codeword of out's size that is added to it)
+void fri_launch_fold(int k, const uint32_t* layer, uint32_t log_m, uint32_t log_2n, const uint32_t* tw_fwd, const FoldParams& fp, const E4* beta_m, uint32_t* out, const uint32_t* addend, hipStream_t s) {
+  const dim3 grid(grid_for((1ull << log_m) >> k)), block(NT);
+  if (!addend) {
+    if (k == 1) hipLaunchKernelGGL(fri_fold_k_kernel<1>, grid, block, 0, s, layer, log_m, log_2n, tw_fwd, fp, beta_m, out, (const uint32_t*)nullptr);
+    else if (k == 2) hipLaunchKernelGGL(fri_fold_k_kernel<2>, grid, block, 0, s, layer, log_m, log_2n, tw_fwd, fp, beta_m, out, (const uint32_t*)nullptr);
+    else hipLaunchKernelGGL(fri_fold_k_kernel<3>, grid, block, 0, s, layer, log_m, log_2n, tw_fwd, fp, beta_m, out, (const uint32_t*)nullptr);
+  } else if (k == 1) hipLaunchKernelGGL((fri_fold_k_kernel<1, true>), grid, block, 0, s, layer, log_m, log_2n, tw_fwd, fp, beta_m, out, addend);
+  else if (k == 2) hipLaunchKernelGGL((fri_fold_k_kernel<2, true>), grid, block, 0, s, layer, log_m, log_2n, tw_fwd, fp, beta_m, out, addend);
+  else hipLaunchKernelGGL((fri_fold_k_kernel<3, true>), grid, block, 0, s, layer, log_m, log_2n, tw_fwd, fp, beta_m, out, addend);
 }
 
 // ---- the Fiat-Shamir step of one FRI layer ON THE DEVICE: observe the layer's root, sample beta -------------------------------------------
@@ -260,8 +274,9 @@ int arena_reserve(const zkir_stark_ctx* c, size_t want) {
 // roots, the betas and the final layer to the host, which replays the transcript and refuses to go on if its betas are not the device's.  `ch` is the transcript as it stands
 // once the codeword's challenge is drawn (nothing pending); it leaves with the layer roots and the final layer observed.  fri_layers (ks.size() + 1 entries) and fri_trees
 // (ks.size()) are filled for the queries; `words` gains what the proof carries: the layer roots, then the final layer value by value.
+// addends (may be null: none; else ks.size() entries): entry j is null or a codeword of (1 << log_m_j) >> ks[j] values that is added by index to the layer fold j leaves.
 int fri_commit(ProofRun& r, Challenger& ch, const std::vector<int>& ks, uint32_t log_M, uint32_t n_fin, uint32_t* codeword, std::vector<uint32_t*>& fri_layers,
-               std::vector<uint32_t*>& fri_trees, std::vector<uint32_t>& words) {
+               std::vector<uint32_t*>& fri_trees, std::vector<uint32_t>& words, const std::vector<const uint32_t*>* addends = nullptr) {
   const zkir_stark_ctx* c = r.c;
   hipStream_t s = r.s;
   const int n_layers = (int)ks.size();
@@ -291,9 +306,7 @@ int fri_commit(ProofRun& r, Challenger& ch, const std::vector<int>& ks, uint32_t
     }
     HIP_OK(r.ar.take(&fri_layers[j + 1], 4 * g));
     const E4* dBeta = reinterpret_cast<const E4*>(dFri + 16 * j + 4);
-    if (k == 1) hipLaunchKernelGGL(fri_fold_k_kernel<1>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, fri_layers[j + 1]);
-    else if (k == 2) hipLaunchKernelGGL(fri_fold_k_kernel<2>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, fri_layers[j + 1]);
-    else hipLaunchKernelGGL(fri_fold_k_kernel<3>, dim3(grid_for(g)), dim3(NT), 0, s, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, fri_layers[j + 1]);
+    fri_launch_fold(k, fri_layers[j], (uint32_t)log_m, log_M, c->d_tw_fwd, fp, dBeta, fri_layers[j + 1], addends ? (*addends)[j] : nullptr, s);
     log_m -= k;
   }
   std::vector<uint32_t> fri_out(16 * (size_t)n_layers);

@@ -31,6 +31,23 @@ inline std::vector<int> fri_schedule(int log_n, int b) {
   return ks;
 }
 
+// The schedule of a proof over codewords of several heights ('ZKMH', mixed_eval.inl): log_ns[0] > log_ns[1] > .. at one b.  fri_schedule's rule with one more cap: a step never
+// jumps over the size M_h = 2^(log_ns[h] + b) of a lower codeword, so every M_h (h >= 1) is the size of a committed layer — the layer F_h is added to before it is hashed.
+// ks[0] stays 1.  One height gives fri_schedule(log_ns[0], b).  Spec: tests/mixed_eval_ref.py.
+inline std::vector<int> fri_mixed_schedule(const uint32_t* log_ns, uint32_t n_groups, int b) {
+  std::vector<int> ks;
+  const int log_fin = 2 + b;
+  for (int log_m = (int)log_ns[0] + b; log_m > log_fin;) {
+    int k = ks.empty() ? 1 : (air::LOG_ARITY < log_m - log_fin ? air::LOG_ARITY : log_m - log_fin);
+    for (uint32_t h = 1; h < n_groups; h++) {
+      const int lower = (int)log_ns[h] + b;
+      if (lower < log_m && log_m - lower < k) k = log_m - lower;
+    }
+    ks.push_back(k); log_m -= k;
+  }
+  return ks;
+}
+
 // words of one query's FRI layers: per layer its 2^k values (4 words each) and the path of its leaf (4 words a level, depth = log2 of the layer's leaves)
 inline uint64_t fri_query_words(uint32_t log_M, const std::vector<int>& ks) {
   uint64_t words = 0;

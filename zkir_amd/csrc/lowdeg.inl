@@ -79,6 +79,64 @@ size_t lowdeg_fri_bytes(uint32_t log_M, uint64_t rec_words, uint32_t n_mats, con
          arena_al((size_t)num_queries * lowdeg_query_words(log_M, rec_words, ks) * 4);
 }
 
+// Matrices of ONE height 2^log_M that a proof's queries open, and at how many rows a query: per = 2 — rows q and q + 2^log_M / 2 (the codeword's own matrices) — or
+// per = 1 — the row q mod 2^log_M (a lower group of mixed_eval.inl: the index the walk stands at when it reaches the layer of that size).
+struct OpenGroup { uint32_t log_M; const OpenMat* mats; uint32_t n_mats; uint32_t per; };
+
+// The query section of every proof here, for the sampled `queries` (each below 2^(log_M - 1), log_M: the codeword's): the matrix records by merkle_open_kernel from one device
+// index array per group, copied next to the FRI leaves and paths by gather_kernel; one download.  A query: q, the groups' records in order (matrix by matrix, `per` records
+// each), the layers.  `head` is the whole proof before the queries, qsize the words of a query; stage mark `mark` is recorded; the whole proof is written to proof_host.
+int open_query_section(ProofRun& r, const std::vector<uint32_t>& queries, const OpenGroup* groups, uint32_t n_groups, uint32_t log_M, const std::vector<int>& ks,
+                       const std::vector<uint32_t*>& fri_layers, const std::vector<uint32_t*>& fri_trees, uint64_t qsize, const std::vector<uint32_t>& head, int mark, uint32_t* proof_host) {
+  hipStream_t s = r.s;
+  Arena& ar = r.ar;
+  const size_t nq = queries.size();
+  std::vector<std::vector<uint32_t*>> dRec(n_groups);
+  for (uint32_t h = 0; h < n_groups; h++) {
+    const OpenGroup& g = groups[h];
+    const uint64_t Mh = 1ull << g.log_M;
+    std::vector<uint64_t> idx;
+    for (uint32_t q : queries) {
+      if (g.per == 2) { idx.push_back(q); idx.push_back((uint64_t)q + Mh / 2); }
+      else idx.push_back(q & (Mh - 1));
+    }
+    uint64_t* dIdx;
+    HIP_OK(ar.take(&dIdx, idx.size()));
+    HIP_OK(r.h2d(dIdx, idx.data(), idx.size() * 8));
+    dRec[h].resize(g.n_mats);
+    for (uint32_t m = 0; m < g.n_mats; m++) {
+      HIP_OK(ar.take(&dRec[h][m], idx.size() * (g.mats[m].width + 4 * (size_t)g.log_M)));
+      hipLaunchKernelGGL(merkle_open_kernel, dim3(grid_for(idx.size() * OPEN_LANES)), dim3(NT), 0, s, g.mats[m].mat, g.mats[m].width, Mh, g.log_M, g.mats[m].tree, dIdx, (uint64_t)idx.size(), dRec[h][m]);
+    }
+  }
+  std::vector<GatherJob> jobs;
+  uint32_t off = 0;
+  for (size_t t = 0; t < nq; t++) {
+    off += 1;                                                                // the index word: written by the host below
+    for (uint32_t h = 0; h < n_groups; h++)
+      for (uint32_t m = 0; m < groups[h].n_mats; m++) {
+        const uint32_t rec = groups[h].mats[m].width + 4 * groups[h].log_M, per = groups[h].per;
+        jobs.push_back({dRec[h][m] + per * t * rec, 1, per * rec, off, 0u, 0u}); off += per * rec;
+      }
+    fri_query_jobs(jobs, off, queries[t], log_M, ks, fri_layers, fri_trees);
+  }
+  if ((uint64_t)off != qsize * nq) return r.fail(ZKIR_ERR_OTHER, "query section length");
+  GatherJob* dJobs; uint32_t* dOut;
+  HIP_OK(ar.take(&dJobs, jobs.size())); HIP_OK(ar.take(&dOut, (size_t)off));
+  HIP_OK(r.h2d(dJobs, jobs.data(), jobs.size() * sizeof(GatherJob)));
+  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)jobs.size()), dim3(64), 0, s, dJobs, (uint32_t)jobs.size(), dOut);
+  uint32_t* h_out = r.pin.take_n<uint32_t>((size_t)off);
+  if (!h_out) return r.fail(ZKIR_ERR_DEVICE, "no pinned host memory for the query section");
+  HIP_OK(hipMemcpyAsync(h_out, dOut, (size_t)off * 4, hipMemcpyDeviceToHost, s));
+  r.mark(mark);
+  HIP_OK(hipStreamSynchronize(s));
+  if (check_launch(r.who) != ZKIR_OK) return ZKIR_ERR_DEVICE;
+  for (size_t t = 0; t < nq; t++) h_out[t * qsize] = queries[t];
+  memcpy(proof_host, head.data(), head.size() * 4);
+  memcpy(proof_host + head.size(), h_out, (size_t)off * 4);
+  return ZKIR_OK;
+}
+
 // Sections 2 - 4 of a proof over a codeword of M = 2^log_M values (cw[t M + j], canonical) under the n_mats (1 .. OPEN_MAX_MATS) matrices `mats`: the FRI commit phase,
 // grinding, the queries (one merkle_open_kernel launch per matrix from the one index array; a query's gather jobs: the records matrix by matrix, then the layers).
 // `ch` is the transcript as it stands once the codeword's challenge is drawn, `head` the proof words so far (the layer roots, the final layer and the nonce are appended),
@@ -86,10 +144,7 @@ size_t lowdeg_fri_bytes(uint32_t log_M, uint64_t rec_words, uint32_t n_mats, con
 int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& head, const OpenMat* mats, uint32_t n_mats, uint32_t num_queries, uint32_t pow_bits,
                            const std::vector<int>& ks, uint32_t* codeword, uint64_t total, int first_mark, uint32_t* proof_host) {
   const zkir_stark_ctx* c = r.c;
-  hipStream_t s = r.s;
-  Arena& ar = r.ar;
   const uint32_t log_M = c->log_n + c->log_blowup;
-  const uint64_t M = 1ull << log_M;
   if (n_mats < 1 || n_mats > OPEN_MAX_MATS) return r.fail(ZKIR_ERR_OTHER, "number of opened matrices");
   const uint64_t qsize = lowdeg_query_words(log_M, open_rec_words(log_M, mats, n_mats), ks), head_words = total - qsize * num_queries;
 
@@ -103,42 +158,11 @@ int lowdeg_fri_and_queries(ProofRun& r, Challenger& ch, std::vector<uint32_t>& h
   r.mark(first_mark + 1);
   if (head.size() != head_words) return r.fail(ZKIR_ERR_OTHER, "header length");
 
-  // ---- 4. queries: the matrix records by merkle_open_kernel from a device index array, copied next to the FRI leaves and paths by gather_kernel; one download --------------
+  // ---- 4. queries ----------------------------------------------------------------------------------------------------------------------------------------------------------------
   std::vector<uint32_t> queries(num_queries);
-  std::vector<uint64_t> idx(2 * (size_t)num_queries);
-  for (uint32_t t = 0; t < num_queries; t++) { queries[t] = ch.sample_bits((int)log_M - 1); idx[2 * t] = queries[t]; idx[2 * t + 1] = (uint64_t)queries[t] + M / 2; }
-  uint64_t* dIdx; uint32_t *dRec[OPEN_MAX_MATS], *dOut; GatherJob* dJobs;
-  HIP_OK(ar.take(&dIdx, idx.size()));
-  HIP_OK(r.h2d(dIdx, idx.data(), idx.size() * 8));
-  for (uint32_t m = 0; m < n_mats; m++) {
-    HIP_OK(ar.take(&dRec[m], idx.size() * (mats[m].width + 4 * (size_t)log_M)));
-    hipLaunchKernelGGL(merkle_open_kernel, dim3(grid_for(idx.size() * OPEN_LANES)), dim3(NT), 0, s, mats[m].mat, mats[m].width, M, log_M, mats[m].tree, dIdx, (uint64_t)idx.size(), dRec[m]);
-  }
-  std::vector<GatherJob> jobs;
-  uint32_t off = 0;
-  for (uint32_t t = 0; t < num_queries; t++) {
-    const uint32_t q = queries[t];
-    off += 1;                                                                // the index word: written by the host below
-    for (uint32_t m = 0; m < n_mats; m++) {                                  // record_m(q), record_m(q + M/2)
-      const uint32_t rec = mats[m].width + 4 * log_M;
-      jobs.push_back({dRec[m] + 2 * (size_t)t * rec, 1, 2 * rec, off, 0u, 0u}); off += 2 * rec;
-    }
-    fri_query_jobs(jobs, off, q, log_M, ks, fri_layers, fri_trees);
-  }
-  if ((uint64_t)off != qsize * num_queries) return r.fail(ZKIR_ERR_OTHER, "query section length");
-  HIP_OK(ar.take(&dJobs, jobs.size())); HIP_OK(ar.take(&dOut, (size_t)off));
-  HIP_OK(r.h2d(dJobs, jobs.data(), jobs.size() * sizeof(GatherJob)));
-  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)jobs.size()), dim3(64), 0, s, dJobs, (uint32_t)jobs.size(), dOut);
-  uint32_t* h_out = r.pin.take_n<uint32_t>((size_t)off);
-  if (!h_out) return r.fail(ZKIR_ERR_DEVICE, "no pinned host memory for the query section");
-  HIP_OK(hipMemcpyAsync(h_out, dOut, (size_t)off * 4, hipMemcpyDeviceToHost, s));
-  r.mark(first_mark + 2);
-  HIP_OK(hipStreamSynchronize(s));
-  if (check_launch(r.who) != ZKIR_OK) return ZKIR_ERR_DEVICE;
-  for (uint32_t t = 0; t < num_queries; t++) h_out[(size_t)t * qsize] = queries[t];
-  memcpy(proof_host, head.data(), head_words * 4);
-  memcpy(proof_host + head_words, h_out, (size_t)off * 4);
-  return ZKIR_OK;
+  for (auto& q : queries) q = ch.sample_bits((int)log_M - 1);
+  const OpenGroup group{log_M, mats, n_mats, 2};
+  return open_query_section(r, queries, &group, 1, log_M, ks, fri_layers, fri_trees, qsize, head, first_mark + 2, proof_host);
 }
 
 int lowdeg_bad(const std::string& why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_lowdeg_prove: " + why}); return ZKIR_ERR_ARGUMENT; }

@@ -1109,4 +1109,5 @@ int zkir_merkle_cap_launch(const zkir_stark_ctx* c, uint32_t* tree, uint64_t n_d
 #include "merkle_open.inl"
 #include "lowdeg.inl"
 #include "eval_open.inl"
+#include "mixed_eval.inl"
 #include "pcs_verify.inl"

@@ -1398,6 +1398,182 @@ int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
 
 }  // extern "C"
 
+// ================================================================================================
+// zkir_mixed_eval_verify — the verifier of an EVALUATION PROOF OVER SEVERAL HEIGHTS (zkir_mixed_eval_prove, mixed_eval.inl; spec: tests/mixed_eval_ref.py).  Host only.
+//
+// The proof says: n_groups (2 or 3) groups at one rate b, of strictly decreasing heights; group h is what a 'ZKBE' proof states at height log_n_h (1 .. 4 matrices over
+// 31 <w_{M_h}>, M_h = N_h << b, each under its own root; its own 1 or 2 points; a mask per matrix).  ONE gamma, drawn after everything up to the evaluations; its exponent runs
+// consecutively through the groups in order and inside a group in 'ZKBE''s order.  F_h = 'ZKBE''s quotient of group h with those exponents.  ONE FRI (fri_mixed_schedule: every
+// M_h is a committed layer's size): layer 0 is F_0, and the layer of size M_h is the fold of the layer before it PLUS F_h, by index.
+//   [0..7) 'ZKMH', version 1, b, n_groups, num_queries, pow_bits, n_layers | per group: log_n, n_mats, n_points, (width, mask) per matrix | all roots (groups in order, matrices
+//   in order) | all points | all evaluations in the exponent order | n_layers x 4 layer roots | n_fin x 4 final layer | nonce | the queries; a query: q, then group 0's matrices
+//   record_m(q), record_m(q + M_0/2), then each lower group's matrices ONE record_m(q mod M_h) (width_m + 4 log M_h words), then per layer the values and the path
+// Transcript: every word up to and including the evaluations, gamma; per layer root, beta; the final words; check_pow(nonce); q_t = sample_bits(log M_0 - 1).
+// Codes, 'ZKBE''s in 'ZKBE''s order: 1 malformed (length not EXACTLY the header's, magic, version, a range, n_groups, heights not strictly decreasing, a group's shape,
+// n_layers), 2 roots, 13 points / evaluations, 3 a word >= p, 12 a point in the base field or two equal points within a group, 4 final layer, 5 grinding, 6 index word, 7 a
+// record (in the order they stand in the query), 8 layer-0 values from group 0's records, 9 a FRI leaf's path, 10 carried value — BEFORE the step into the layer of size M_h the
+// carried value becomes carried + F_h(q mod M_h), recomputed from group h's records by layer0_want's rule at log M_h — 11 final value.  (A false evaluation followed by the honest procedure
+// folds a quotient with a pole: check 4, in any group.  Layers committed for other evaluations than the stated ones: 8 in group 0, 10 in a lower group.)
+// ================================================================================================
+namespace {
+
+constexpr uint32_t MIXED_MAGIC = 0x484D4B5Au, MIXED_MAX_GROUPS = 3;
+struct MixedShape {
+  uint32_t b, n_groups, log_n[MIXED_MAX_GROUPS];
+  BatchShape g[MIXED_MAX_GROUPS];
+  uint64_t n_mats, n_points, n_evals;                                      // over all the groups
+};
+// the groups are ones a proof can state (flat arrays, groups concatenated)
+bool mixed_shape_ok(uint32_t b, uint32_t n_groups, const uint32_t* log_ns, const uint32_t* n_mats, const uint32_t* n_points, const uint32_t* widths, const uint32_t* masks, MixedShape* out) {
+  if (b < 1 || b > 3 || n_groups < 2 || n_groups > MIXED_MAX_GROUPS) return false;
+  MixedShape sh{};
+  sh.b = b; sh.n_groups = n_groups;
+  for (uint32_t h = 0; h < n_groups; h++) {
+    if (log_ns[h] < 3 || log_ns[h] > 26 || log_ns[h] + b > 27 || (h && log_ns[h] >= log_ns[h - 1])) return false;
+    if (n_mats[h] < 1 || n_mats[h] > 4 || !batch_shape_ok(n_mats[h], n_points[h], widths + sh.n_mats, masks + sh.n_mats, &sh.g[h])) return false;
+    sh.log_n[h] = log_ns[h];
+    sh.n_mats += n_mats[h]; sh.n_points += n_points[h]; sh.n_evals += sh.g[h].n_evals;
+  }
+  *out = sh;
+  return true;
+}
+uint64_t mixed_words(const MixedShape& sh, uint32_t num_queries, std::vector<int>* ks_out) {
+  const std::vector<int> ks = zkir::fri_mixed_schedule(sh.log_n, sh.n_groups, (int)sh.b);
+  uint64_t head = 7, qsize = 1 + zkir::fri_query_words(sh.log_n[0] + sh.b, ks);
+  for (uint32_t h = 0; h < sh.n_groups; h++) {
+    head += 3 + 2 * (uint64_t)sh.g[h].n_mats;
+    qsize += (h ? 1 : 2) * (sh.g[h].sum_width + 4 * (uint64_t)(sh.log_n[h] + sh.b) * sh.g[h].n_mats);
+  }
+  if (ks_out) *ks_out = ks;
+  return head + 4 * sh.n_mats + 4 * sh.n_points + 4 * sh.n_evals + 4 * (uint64_t)ks.size() + 4 * (uint64_t)zkir::fri_final_size((int)sh.b) + 1 + (uint64_t)num_queries * qsize;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t zkir_mixed_eval_proof_words(uint32_t log_blowup, uint32_t n_groups, const uint32_t* log_ns, const uint32_t* n_mats, const uint32_t* n_points, const uint32_t* widths,
+                                     const uint32_t* masks, uint32_t num_queries) {
+  MixedShape sh;
+  if (!log_ns || !n_mats || !n_points || !widths || !masks || num_queries < 1 || num_queries > 128) return 0;
+  if (n_groups < 2 || n_groups > MIXED_MAX_GROUPS) return 0;               // (before the arrays are read: they have n_groups entries)
+  for (uint32_t h = 0; h < n_groups; h++) if (n_mats[h] < 1 || n_mats[h] > 4) return 0;      // (widths and masks have sum n_mats entries)
+  if (!mixed_shape_ok(log_blowup, n_groups, log_ns, n_mats, n_points, widths, masks, &sh)) return 0;
+  return mixed_words(sh, num_queries, nullptr);
+}
+
+int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  // ---- 1: shape ----
+  if (!w || len < 7 || w[0] != MIXED_MAGIC || w[1] != 1) return 1;
+  const uint32_t b = w[2], n_groups = w[3], num_queries = w[4], pow_bits = w[5];
+  if (b < 1 || b > 3 || n_groups < 2 || n_groups > MIXED_MAX_GROUPS || num_queries < 1 || num_queries > 128 || pow_bits > 24) return 1;
+  uint32_t log_ns[MIXED_MAX_GROUPS], n_mats[MIXED_MAX_GROUPS], n_points[MIXED_MAX_GROUPS], widths[4 * MIXED_MAX_GROUPS], masks[4 * MIXED_MAX_GROUPS];
+  size_t at = 7, n_m = 0;
+  for (uint32_t h = 0; h < n_groups; h++) {
+    if (len < at + 3) return 1;
+    log_ns[h] = w[at]; n_mats[h] = w[at + 1]; n_points[h] = w[at + 2];
+    if (n_mats[h] < 1 || n_mats[h] > 4 || len < at + 3 + 2 * (uint64_t)n_mats[h]) return 1;
+    for (uint32_t m = 0; m < n_mats[h]; m++, n_m++) { widths[n_m] = w[at + 3 + 2 * m]; masks[n_m] = w[at + 4 + 2 * m]; }
+    at += 3 + 2 * (size_t)n_mats[h];
+  }
+  MixedShape sh;
+  if (!mixed_shape_ok(b, n_groups, log_ns, n_mats, n_points, widths, masks, &sh)) return 1;
+  std::vector<int> ks;
+  if (len != mixed_words(sh, num_queries, &ks) || w[6] != (uint32_t)ks.size()) return 1;
+  const size_t at_roots = at, at_points = at_roots + 4 * (size_t)sh.n_mats, at_evals = at_points + 4 * (size_t)sh.n_points, at_lroots = at_evals + 4 * (size_t)sh.n_evals;
+  const uint32_t *roots = w + at_roots, *pts = w + at_points, *ys = w + at_evals;
+  // ---- 2, 13: what the caller expects, read at the sizes the header states ----
+  if (expect_roots && memcmp(roots, expect_roots, 16 * (size_t)sh.n_mats)) return 2;
+  if (expect_points && memcmp(pts, expect_points, 16 * (size_t)sh.n_points)) return 13;
+  if (expect_evals && memcmp(ys, expect_evals, 16 * (size_t)sh.n_evals)) return 13;
+  // ---- 3: canonical words ----
+  for (uint64_t i = 0; i < len; i++) if (w[i] >= bb::P) return 3;
+  // ---- 12: every point lies outside the base field; the points of one group differ ----
+  {
+    const uint32_t* p = pts;
+    for (uint32_t h = 0; h < n_groups; p += 4 * (size_t)n_points[h], h++) {
+      for (uint32_t i = 0; i < n_points[h]; i++) if (!(p[4 * i + 1] | p[4 * i + 2] | p[4 * i + 3])) return 12;
+      if (n_points[h] == 2 && !memcmp(p, p + 4, 16)) return 12;
+    }
+  }
+  // ---- the transcript up to gamma; each group's layer-0 rule (layer0_want's data) with the group's exponents ----
+  Challenger ch;
+  ch.observe_n(w, at_lroots);
+  const E4 gamma = bb::e_to_mont(ch.sample_ext());
+  auto get_m = [&](const uint32_t* a) { return bb::e_to_mont(E4{{a[0], a[1], a[2], a[3]}}); };
+  std::vector<E4> gp((size_t)sh.n_evals);
+  gp[0] = bb::e_one_m();
+  for (size_t k = 1; k < gp.size(); k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
+  zkir::PcsQueries Q[MIXED_MAX_GROUPS] = {};
+  size_t first_mat[MIXED_MAX_GROUPS];
+  {
+    size_t e = 0, m0 = 0, p0 = 0;
+    for (uint32_t h = 0; h < n_groups; h++) {
+      zkir::PcsQueries& q = Q[h];
+      const BatchShape& g = sh.g[h];
+      q.log_M = log_ns[h] + b; q.b = b; q.n_mats = g.n_mats; q.n_points = g.n_points;
+      q.n_gamma = (uint32_t)gp.size(); q.gamma_m = gp[0].c;                 // (e0 below counts from the proof's first exponent)
+      for (uint32_t m = 0; m < g.n_mats; m++) q.widths[m] = g.widths[m];
+      for (uint32_t i = 0; i < g.n_points; i++) {
+        const E4 z = get_m(pts + 4 * (p0 + i));
+        E4 a = bb::e_zero();
+        for (uint32_t m = 0; m < g.n_mats; m++) {
+          if (!((g.masks[m] >> i) & 1)) continue;
+          q.sel[q.n_sel++] = {i, m, (uint32_t)e};
+          for (size_t k = 0; k < g.widths[m]; k++, e++) a = bb::e_add(a, bb::e_mul_m(gp[e], get_m(ys + 4 * e)));
+        }
+        memcpy(q.z_m[i], z.c, 16); memcpy(q.a_m[i], a.c, 16);
+      }
+      first_mat[h] = m0; m0 += g.n_mats; p0 += g.n_points;
+    }
+  }
+  // ---- 4: the final layer; the transcript after gamma; 5: grinding ----
+  const int n_layers = (int)ks.size(), log_M = (int)(log_ns[0] + b);
+  const size_t M = (size_t)1 << log_M, n_fin = zkir::fri_final_size((int)b);
+  const uint32_t* lroots = w + at_lroots;
+  const size_t at_fin = at_lroots + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1, qsize = (size_t)((len - at_queries) / num_queries);
+  std::vector<E4> fin(n_fin), betas;
+  for (size_t i = 0; i < n_fin; i++) fin[i] = get_m(w + at_fin + 4 * i);
+  if (!fri_final_degree_ok(fin, (int)b)) return 4;
+  if (!fri_transcript(ch, lroots, n_layers, w + at_fin, n_fin, w[at_nonce], (int)pow_bits, betas)) return 5;
+  // ---- 6 .. 11, query after query ----
+  for (uint32_t t = 0; t < num_queries; t++) {
+    const uint32_t q = ch.sample_bits(log_M - 1);
+    size_t p = at_queries + (size_t)t * qsize;
+    if (w[p++] != q) return 6;
+    const uint32_t* rows[MIXED_MAX_GROUPS][2][4];                           // group 0: rows q and q + M_0/2; a lower group: the row q mod M_h at [h][0]
+    for (uint32_t h = 0; h < n_groups; h++) {
+      const int log_Mh = (int)Q[h].log_M;
+      for (uint32_t m = 0; m < sh.g[h].n_mats; m++)
+        for (int s2 = 0; s2 < (h ? 1 : 2); s2++) {
+          const size_t pos = h ? (q & (((size_t)1 << log_Mh) - 1)) : (size_t)q + (s2 ? M / 2 : 0);
+          const uint32_t* row = w + p;
+          uint32_t dg[4]; hash_elems(row, sh.g[h].widths[m], dg);
+          if (!check_path(dg, pos, row + sh.g[h].widths[m], log_Mh, roots + 4 * (first_mat[h] + m))) return 7;
+          rows[h][s2][m] = row;
+          p += (size_t)sh.g[h].widths[m] + 4 * (size_t)log_Mh;
+        }
+    }
+    const E4 comb[2] = {layer0_want(Q[0], q, rows[0][0]), layer0_want(Q[0], (size_t)q + M / 2, rows[0][1])};
+    FriWalk walk(log_M, q);
+    for (int j = 0; j < n_layers; j++) {
+      const int k = ks[j];
+      for (uint32_t h = 1; h < n_groups; h++)                                // the layer of size M_h is the fold plus F_h: what is carried into it gains F_h(q mod M_h)
+        if ((int)Q[h].log_M == walk.log_m) walk.carried = bb::e_add(walk.carried, layer0_want(Q[h], walk.carried_idx, rows[h][0]));
+      const size_t layer_words = 4 * ((size_t)1 << k) + 4 * (size_t)(walk.log_m - k);
+      const FriLayerSeen seen = fri_walk_step(walk, w + p, k, lroots + 4 * j, betas[j]);
+      p += layer_words;
+      if (j == 0 && (!e_eq(seen.v0, comb[0]) || !e_eq(seen.v1, comb[1]))) return 8;
+      if (!seen.leaf_ok) return 9;
+      if (j > 0 && !seen.carried_ok) return 10;
+    }
+    if (!e_eq(fin[walk.carried_idx & (n_fin - 1)], walk.carried)) return 11;
+  }
+  return 0;
+}
+
+}  // extern "C"
+
 namespace zkir {
 QueryStage host_query_stage() { return QueryStage{nullptr, host_query_run}; }
 int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage) {

@@ -439,6 +439,12 @@ def lib() -> C.CDLL:
         L.zkir_batch_eval_prove_stages.restype = C.c_int; L.zkir_batch_eval_prove_stages.argtypes = [V, U32, V, V, V, V, V, U32, U32, U32, V, U64, C.POINTER(U64), V, V]
         L.zkir_batch_eval_quotient_scratch_words.restype = U64; L.zkir_batch_eval_quotient_scratch_words.argtypes = [U32, U32, V, U32]
         L.zkir_batch_eval_quotient_launch.restype = C.c_int; L.zkir_batch_eval_quotient_launch.argtypes = [V, U32, V, V, V, V, V, U32, V, V, V, V]
+    if hasattr(L, "zkir_mixed_eval_prove"):                   # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_mixed_eval_proof_words.restype = U64; L.zkir_mixed_eval_proof_words.argtypes = [U32, U32, V, V, V, V, V, U32]
+        L.zkir_mixed_eval_prove.restype = C.c_int; L.zkir_mixed_eval_prove.argtypes = [V, U32, V, V, V, V, V, V, V, U32, U32, V, U64, C.POINTER(U64), V]
+        L.zkir_mixed_eval_verify.restype = C.c_int; L.zkir_mixed_eval_verify.argtypes = [V, U64, V, V, V]
+        L.zkir_mixed_eval_prove_stages.restype = C.c_int; L.zkir_mixed_eval_prove_stages.argtypes = [V, U32, V, V, V, V, V, V, V, U32, U32, V, U64, C.POINTER(U64), V, V]
+        L.zkir_fri_fold_launch.restype = C.c_int; L.zkir_fri_fold_launch.argtypes = [V, V, U32, U32, V, V, V, V]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -781,6 +787,76 @@ def batch_eval_verify(proof, roots=None, points=None, evals=None, device: bool =
     if device:
         return _pcs_verdict(lib().zkir_batch_eval_verify_device(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e), stream))
     return int(lib().zkir_batch_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
+
+
+def _mixed_shape(log_ns, shapes):
+    """the flat arrays of the mixed-eval calls from shapes[h] = (widths, masks, n_points); None where the lists cannot be laid out (the library is then not called)"""
+    log_ns, shapes = [int(x) for x in log_ns], [([int(x) for x in w], [int(x) for x in k], int(n)) for w, k, n in shapes]
+    if len(shapes) != len(log_ns) or any(len(w) != len(k) for w, k, _ in shapes):
+        return None
+    if any(not 0 <= x < 2**32 for x in log_ns) or any(not 0 <= x < 2**32 for w, k, n in shapes for x in w + k + [n]):
+        return None
+    u = lambda xs: np.array(xs, np.uint32)
+    return u(log_ns), u([len(w) for w, _, _ in shapes]), u([n for _, _, n in shapes]), u([x for w, _, _ in shapes for x in w]), u([x for _, k, _ in shapes for x in k])
+
+
+def mixed_eval_proof_words(log_ns, log_blowup: int, shapes, num_queries: int) -> int:
+    """Words of an evaluation proof over several heights (zkir_mixed_eval_proof_words): log_ns strictly decreasing, shapes[h] = (widths, masks, n_points) of group h;
+    0 for a shape no proof can state."""
+    flat = _mixed_shape(log_ns, shapes)
+    if flat is None or not 0 <= int(log_blowup) < 2**32 or not 0 <= int(num_queries) < 2**32:
+        return 0
+    ln, nm, npt, ws, ks = flat
+    return int(lib().zkir_mixed_eval_proof_words(int(log_blowup), len(ln), ln.ctypes.data, nm.ctypes.data, npt.ctypes.data, ws.ctypes.data, ks.ctypes.data, int(num_queries)))
+
+
+def mixed_eval_groups(proof):
+    """The group words of a 'ZKMH' proof's header, the one Python parse of them (mixed_eval_verify's sizes, stark.mixed_eval_layout): [{log_n, widths, masks, n_points}] and
+    the word after them, or None where the header is one no proof can have (n_groups, a group's n_mats, n_points, a width, a mask; cut short)."""
+    w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
+    if len(w) < 7 or not 2 <= int(w[3]) <= 3:
+        return None
+    at, groups = 7, []
+    for _ in range(int(w[3])):
+        if len(w) < at + 3 or not 1 <= int(w[at + 1]) <= 4 or not 1 <= int(w[at + 2]) <= 2 or len(w) < at + 3 + 2 * int(w[at + 1]):
+            return None
+        nm, npt = int(w[at + 1]), int(w[at + 2])
+        widths, masks = [int(x) for x in w[at + 3:at + 3 + 2 * nm:2]], [int(x) for x in w[at + 4:at + 3 + 2 * nm:2]]
+        if not all(1 <= wd <= 512 and 1 <= k < (1 << npt) for wd, k in zip(widths, masks)):
+            return None
+        groups.append({"log_n": int(w[at]), "widths": widths, "masks": masks, "n_points": npt})
+        at += 3 + 2 * nm
+    return groups, at
+
+
+def mixed_eval_sizes(proof):
+    """(n_mats, n_points, n_evals) over all the groups as the header of a 'ZKMH' proof states them, or None where the header is one no proof can have"""
+    parsed = mixed_eval_groups(proof)
+    if parsed is None:
+        return None
+    groups = parsed[0]
+    return (sum(len(g["widths"]) for g in groups), sum(g["n_points"] for g in groups),
+            sum(wd * bin(k).count("1") for g in groups for wd, k in zip(g["widths"], g["masks"])))
+
+
+def mixed_eval_verify(proof, roots=None, points=None, evals=None) -> int:
+    """zkir_mixed_eval_verify, on the host — no GPU, and there is no device form: 0 = the proof convinces a holder of its roots that every column of every committed matrix of
+    every group is close to a polynomial of degree < 2^(its group's log_n) that takes the proof's evaluations at the points its matrix is opened at; `roots`, `points` and
+    `evals` (all groups' words, in the proof's order), when given, must be the proof's.  Else the code of the first failing check (include/zkir_amd.h lists them).  The library
+    reads as many expected words as the proof's header states: where the header is one a proof can have, expectations of another size raise ValueError."""
+    w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
+    r = None if roots is None else np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1)
+    p = None if points is None else np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
+    e = None if evals is None else np.ascontiguousarray(evals, dtype=np.uint32).reshape(-1)
+    sizes = mixed_eval_sizes(w)
+    if sizes is not None:
+        for name, a, want in (("roots", r, 4 * sizes[0]), ("points", p, 4 * sizes[1]), ("evals", e, 4 * sizes[2])):
+            if a is not None and len(a) != want:
+                raise ValueError(f"mixed_eval_verify: {name} must hold {want} words, what the proof's header states")
+    else:
+        r = p = e = None                                         # the proof is malformed (1) whatever is expected of it
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    return int(lib().zkir_mixed_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
 
 
 def verify_last_stages() -> dict:

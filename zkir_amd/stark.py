@@ -6,7 +6,7 @@ PyTorch is plumbing (device buffers, streams); all arithmetic happens in the HIP
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -434,6 +434,108 @@ def batch_eval_layout(proof) -> dict:
         at["records"].append((rel, rel + rec))
         rel += 2 * rec
     return at
+
+
+class EvalGroup(NamedTuple):
+    """One group of mixed_eval_prove: what batch_eval_prove takes at one height — the group's context, its 1 .. 4 B8 matrices and their trees, widths (None: all columns),
+    masks, and its own points ([1 or 2][4] canonical words)."""
+    ctx: StarkContext
+    mats: Sequence
+    trees: Sequence
+    widths: Optional[Sequence]
+    masks: Sequence
+    points: object
+
+
+mixed_eval_proof_words = rt.mixed_eval_proof_words
+mixed_eval_verify = rt.mixed_eval_verify
+
+
+def mixed_eval_prove(groups, num_queries: int = 50, pow_bits: int = 12, stream=None, want_stage_ms: bool = False):
+    """zkir_mixed_eval_prove: ONE evaluation proof (np.uint32 words) opening commitments of DIFFERENT heights: `groups` are 2 or 3 EvalGroups whose contexts share one
+    log_blowup and have strictly decreasing log_n; each group is opened as batch_eval_prove opens it, at its own points.  One gamma, one FRI commit phase (a lower group's
+    quotient is added to the layer of its size), one grind, one set of query rows (mixed_eval_layout finds the sections).  The workspace is the first group's context's.
+    Tensors of the wrong size — a matrix or tree that is not of ITS group's context's size — raise ValueError; the library refuses bad parameters (one group, four groups,
+    equal or rising heights, a context of another log_blowup, a group's shape, its points) with ERR_ARGUMENT before any launch.
+    want_stage_ms: also the device ms of (weights, evaluations, quotients, FRI commit phase, grinding, query section)."""
+    groups = [EvalGroup(*g) for g in groups]
+    if not groups:
+        raise ValueError("mixed_eval_prove: no group")
+    ws, ks, pts, mat_ptrs, tree_ptrs = [], [], [], [], []
+    for g in groups:
+        w, k, p, _ = _batch_args("mixed_eval_prove", g.ctx, g.mats, g.widths, g.masks, g.points)
+        trees = list(g.trees)
+        if len(trees) != len(w):
+            raise ValueError("mixed_eval_prove: trees must have one entry per matrix")
+        for tree in trees:
+            _check_tree("mixed_eval_prove", g.ctx, tree, "a")
+        ws.append(w); ks.append(k); pts.append(p.reshape(-1))
+        mat_ptrs += [m.data_ptr() for m in g.mats]; tree_ptrs += [t.data_ptr() for t in trees]
+    shapes = [(w, k, len(p) // 4) for w, k, p in zip(ws, ks, pts)]
+    cap = mixed_eval_proof_words([g.ctx.log_n for g in groups], groups[0].ctx.log_blowup, shapes, num_queries)
+    ctxs = (C.c_void_p * len(groups))(*[g.ctx.handle for g in groups])
+    n_mats, n_points = np.array([len(w) for w in ws], np.uint32), np.array([n for _, _, n in shapes], np.uint32)
+    w_all, k_all, p_all = np.concatenate(ws), np.concatenate(ks), np.concatenate(pts)
+    mp, tp = (C.c_void_p * len(mat_ptrs))(*mat_ptrs), (C.c_void_p * len(tree_ptrs))(*tree_ptrs)
+    return _prove_call("zkir_mixed_eval_prove", 6, (ctxs, len(groups), n_mats.ctypes.data, mp, w_all.ctypes.data, tp, k_all.ctypes.data, p_all.ctypes.data, n_points.ctypes.data,
+                                                    int(num_queries), int(pow_bits)), cap, stream, want_stage_ms)
+
+
+def mixed_eval_layout(proof) -> dict:
+    """Word offsets of a well-formed 'ZKMH' proof: log_blowup, n_groups, num_queries, n_layers; groups[h] = {log_n, widths, masks, n_points, roots, points, evals, n_evals,
+    evals_of[(i, m)], records[m] (relative to a query's start: (record(q), record(q + M_0/2)) for group 0, (record(q mod M_h),) below)}; roots, points, evals, layer_roots,
+    final, nonce, queries and the words of one query (qsize)."""
+    b, n_groups, nq, _, n_layers = (int(x) for x in proof[2:7])
+    parsed = rt.mixed_eval_groups(proof)
+    if parsed is None:
+        raise ValueError("mixed_eval_layout: the header is one no 'ZKMH' proof can have")
+    at = {"log_blowup": b, "n_groups": n_groups, "num_queries": nq, "n_layers": n_layers, "groups": parsed[0]}
+    at["roots"] = parsed[1]
+    at["points"] = at["roots"] + 4 * sum(len(g["widths"]) for g in at["groups"])
+    at["evals"] = at["points"] + 4 * sum(g["n_points"] for g in at["groups"])
+    r_at, p_at, e, rel = at["roots"], at["points"], 0, 1
+    for h, g in enumerate(at["groups"]):
+        g["roots"], g["points"], g["evals"], g["evals_of"], g["records"] = r_at, p_at, at["evals"] + 4 * e, {}, []
+        first = e
+        for i in range(g["n_points"]):
+            for m, (w, k) in enumerate(zip(g["widths"], g["masks"])):
+                if (k >> i) & 1:
+                    g["evals_of"][(i, m)] = at["evals"] + 4 * e
+                    e += w
+        g["n_evals"] = e - first
+        for w in g["widths"]:
+            rec = w + 4 * (g["log_n"] + b)
+            g["records"].append((rel, rel + rec) if h == 0 else (rel,))
+            rel += (2 if h == 0 else 1) * rec
+        r_at += 4 * len(g["widths"]); p_at += 4 * g["n_points"]
+    at["n_evals"] = e
+    at["layer_roots"] = at["evals"] + 4 * e
+    at["final"] = at["layer_roots"] + 4 * n_layers
+    at["nonce"] = at["final"] + 4 * (4 << b)
+    at["queries"] = at["nonce"] + 1
+    at["qsize"] = (len(proof) - at["queries"]) // nq if nq else 0
+    return at
+
+
+def fri_fold(ctx: StarkContext, layer: torch.Tensor, k: int, beta, addend: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """(tests, measurements) zkir_fri_fold_launch: the FRI fold kernel alone.  `layer` int32[4][m] (row t = coordinate t, canonical) is a layer of m = 2^log_m values of the
+    context's FRI (log_m <= log_n + log_blowup; its coset shift is 31^(2^(log_n + log_blowup - log_m))); it is folded k (1 .. 3) times with the canonical E4 `beta`,
+    beta^2, beta^4 into int32[4][m >> k].  addend (int32[4][m >> k] or None) is added by index: the add form mixed_eval_prove uses.  Wrong sizes raise ValueError."""
+    if layer.dim() != 2 or layer.shape[0] != 4 or layer.dtype != torch.int32 or not layer.is_contiguous():
+        raise ValueError("fri_fold: layer must be contiguous int32[4][m]")
+    m = layer.shape[1]
+    if m < 2 or m & (m - 1):
+        raise ValueError("fri_fold: the layer's size must be a power of two")
+    if not 1 <= int(k) <= 3 or m >> int(k) == 0:
+        raise ValueError("fri_fold: k must be 1 .. 3 and at most log2 of the layer's size")
+    g = m >> int(k)
+    if addend is not None and (tuple(addend.shape) != (4, g) or addend.dtype != torch.int32 or not addend.is_contiguous()):
+        raise ValueError(f"fri_fold: addend must be contiguous int32[4][{g}]")
+    bt = np.ascontiguousarray(beta, dtype=np.uint32).reshape(4)
+    out = torch.empty((4, g), dtype=torch.int32, device=layer.device)
+    pl._check(rt.lib().zkir_fri_fold_launch(ctx.handle, layer.data_ptr(), m.bit_length() - 1, int(k), bt.ctypes.data, addend.data_ptr() if addend is not None else None, out.data_ptr(),
+                                            _sp(stream)))
+    return out
 
 
 def commit_trace(ctx: StarkContext, trace: pl.DeviceTrace, stream=None, deferred: bool = False):
