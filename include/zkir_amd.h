@@ -482,7 +482,7 @@ int zkir_batch_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32
  * zkir_mixed_eval_prove: the workspace arena and the one-proof-at-a-time lock are ctxs[0]'s; the other contexts are only read.  Synchronises the stream; nothing past *n_words
  * is written.  ZKIR_ERR_ARGUMENT with *n_words = 0, nothing written and nothing launched for: a null pointer, n_groups outside 2 .. 3, a context whose log_blowup is not
  * ctxs[0]'s, heights that do not strictly decrease, and, per group, zkir_batch_eval_prove's refusals.
- * zkir_mixed_eval_verify: host only (there is no device form).  zkir_batch_eval_verify's codes in its order: 1 malformed (exact length, magic, version, ranges, group order, a
+ * zkir_mixed_eval_verify: host code, no HIP call (zkir_mixed_eval_verify_device below is its device form).  zkir_batch_eval_verify's codes in its order: 1 malformed (exact length, magic, version, ranges, group order, a
  * group's shape, n_layers), 2 roots, 13 points / evaluations, 3 a word >= p, 12 a point in the base field or two equal points WITHIN a group, 4 final layer, 5 grinding,
  * 6 index word, 7 a record (in the order they stand in the query), 8 layer-0 values (from group 0's records), 9 a FRI leaf's path, 10 carried value — before the step into
  * the layer of size M_h the carried value gains F_h(q mod M_h), recomputed from group h's records — 11 final value.  (Which code a false evaluation gets depends on the prover: one that follows the honest
@@ -496,17 +496,21 @@ int zkir_mixed_eval_prove(zkir_stark_ctx* const* ctxs, uint32_t n_groups, const 
                           uint64_t* n_words, void* hip_stream);
 int zkir_mixed_eval_verify(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals);
 
-/* VERIFYING ON THE DEVICE.  zkir_lowdeg_verify, zkir_eval_verify and zkir_batch_eval_verify with checks 7 - 11 of ALL the queries run on the current HIP device: one leaf-and-
+/* VERIFYING ON THE DEVICE.  zkir_lowdeg_verify, zkir_eval_verify, zkir_batch_eval_verify and zkir_mixed_eval_verify — all FOUR proofs — with checks 7 - 11 of ALL the queries run on the current HIP device: one leaf-and-
  * path job per matrix record and FRI layer (a row of 16 lanes each), the layer-0 values and the folds in a second kernel.  Everything else — the shape, the expectations, the
  * word range, the whole transcript, the final layer's degree, grinding, the sampling of the rows, check 6 — is the host entries' own code in its order, and the device is
  * used only after checks 1 and 3 have passed: every extent a kernel uses comes from the checked header, the row it opens is the transcript's sample.
  * The verdict is the host entry's for every input: 0, or the same check's number, first failing check, lowest query first.  A NEGATIVE result is no verdict:
  * -ZKIR_ERR_DEVICE (no usable device, a failed HIP call) or -ZKIR_ERR_OTHER (no host memory); zkir_last_error says which.  proof and the expectations are HOST memory.  No
  * context: the entries use zkir_verify_device's per-device state (device block grown on demand, pinned staging), so calls on one device are serialised inside.  One staged
- * upload, two launches, one download and one synchronisation on hip_stream; nothing is launched when the verdict is 1 - 5, 12 or 13. */
+ * upload, two launches, one download and one synchronisation on hip_stream; nothing is launched when the verdict is 1 - 5, 12 or 13.
+ * zkir_mixed_eval_verify_device makes THREE launches: the leaf-and-path jobs (a lower group's record is opened at the sample mod M_h), then the layer-0 values of group 0
+ * with one more wave per (query, lower group) that forms F_h(q mod M_h), then the folds, which add the stored F_h where the next layer has size M_h — a launch of their own
+ * so that the stream orders them behind the values.  Its limits are its own: at most 10 FRI layers and 26 leaf-and-path jobs a query. */
 int zkir_lowdeg_verify_device(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root, void* hip_stream);
 int zkir_eval_verify_device(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_root, const uint32_t* expect_points, const uint32_t* expect_evals, void* hip_stream);
 int zkir_batch_eval_verify_device(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, void* hip_stream);
+int zkir_mixed_eval_verify_device(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, void* hip_stream);
 
 /* Public inputs of a proof: absorbed by the Fiat-Shamir transcript before the first commitment and carried in the proof header. */
 typedef struct zkir_public_inputs {

@@ -71,7 +71,8 @@ int zkir_fri_fold_launch(const zkir_stark_ctx* ctx, const uint32_t* layer, uint3
 
 /* DIAGNOSTIC: what the calling thread's last zkir_lowdeg_verify_device / zkir_eval_verify_device / zkir_batch_eval_verify_device call launched: hash_jobs = num_queries x
  * (2 n_mats + n_layers) leaf-and-path jobs, value_jobs = num_queries x (2 + n_layers) (two layer-0 values and one fold a layer); (0, 0) when the call returned before its
- * query stage (verdicts 1 - 5, 12, 13).  Either pointer may be NULL. */
+ * query stage (verdicts 1 - 5, 12, 13).  After zkir_mixed_eval_verify_device: hash_jobs = num_queries x (2 n_mats_0 + the lower groups' n_mats + n_layers), value_jobs =
+ * num_queries x (2 + (n_groups - 1) + n_layers) (one more wave per lower group: its F_h).  Either pointer may be NULL. */
 int zkir_pcs_verify_last_jobs(uint64_t* hash_jobs, uint64_t* value_jobs);
 /* MEASUREMENT: with ZKIR_PCS_VERIFY_TIMES set in the environment the device query stage synchronises after its upload and after its kernels; this reports the host clocks
  * (ms) of the calling thread's last such call: upload | kernels | download.  Zeros without the variable or before the stage. */

@@ -141,11 +141,12 @@ extern "C" {
                                  masks: *const u32, points: *const u32, n_points: *const u32, num_queries: u32, pow_bits: u32, proof_host: *mut u32, cap_words: u64,
                                  n_words: *mut u64, stream: *mut c_void) -> c_int;
     pub fn zkir_mixed_eval_verify(proof: *const u32, n_words: u64, expect_roots: *const u32, expect_points: *const u32, expect_evals: *const u32) -> c_int;
-    // the three verifiers of ONE height above with checks 7 - 11 of all queries on the current HIP device (proof and expectations: host memory; no context): the host entry's verdict for
+    // the four verifiers above with checks 7 - 11 of all queries on the current HIP device (proof and expectations: host memory; no context): the host entry's verdict for
     // every input; a negative result is a device failure (-ZKIR_ERR_DEVICE) or no host memory (-ZKIR_ERR_OTHER), not a verdict
     pub fn zkir_lowdeg_verify_device(proof: *const u32, n_words: u64, expect_root: *const u32, stream: *mut c_void) -> c_int;
     pub fn zkir_eval_verify_device(proof: *const u32, n_words: u64, expect_root: *const u32, expect_points: *const u32, expect_evals: *const u32, stream: *mut c_void) -> c_int;
     pub fn zkir_batch_eval_verify_device(proof: *const u32, n_words: u64, expect_roots: *const u32, expect_points: *const u32, expect_evals: *const u32, stream: *mut c_void) -> c_int;
+    pub fn zkir_mixed_eval_verify_device(proof: *const u32, n_words: u64, expect_roots: *const u32, expect_points: *const u32, expect_evals: *const u32, stream: *mut c_void) -> c_int;
     // (mode 4) the tapes' share of the lookup table side and the hash tape's record checks as calls of their own (host arrays in, host arrays out)
     pub fn zkir_tape_table_side_launch(hash_words: *const u32, n_hash_words: u64, new_bytes: *const u64, wide_words: *const u32, n_wide_words: u64, alpha: *const u32, lambda: *const u32,
                                        sum: *mut u32, hh: *mut u32, ww: *mut u32, stream: *mut c_void) -> c_int;

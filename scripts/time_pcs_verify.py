@@ -6,6 +6,11 @@ A second loop with ZKIR_PCS_VERIFY_TIMES set (the stage then synchronises after 
 download.  Writes what profiles/r16_pcs_verify_device.txt records.
 
     python scripts/time_pcs_verify.py [--log-n 20] [--calls 200] [--out FILE]
+
+--mixed times the FOURTH proof the same way and nothing else: the mixed-height proof ('ZKMH') of time_mixed_eval.py — 2^20 x 152 and 2^16 x 40 at two points each, 2^12 x 8
+at one — with zkir_mixed_eval_verify against zkir_mixed_eval_verify_device.  Writes what profiles/r19_mixed_verify_device.txt records.
+
+    python scripts/time_pcs_verify.py --mixed [--log-ns 20,16,12] [--calls 200] [--out FILE]
 """
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,6 +45,28 @@ def proofs_for(log_n, b):
             ("batch_eval", lambda d: rt.batch_eval_verify(be, roots, pts, device=d), len(be))]
 
 
+def mixed_proof_for(log_ns, b):
+    """[(name, call, proof words)] of the mixed-height proof of time_mixed_eval.py's groups, each committed on a context of its own"""
+    import numpy as np, torch
+    from zkir_amd import runtime as rt, stark
+    from scripts.time_mixed_eval import WIDTHS as MW, MASKS as MM, N_POINTS as MP
+    g = torch.Generator(device="cuda"); g.manual_seed(20 + b)
+    rng = np.random.default_rng(30 + b)
+    groups = []
+    for log_n, width, mask, n_points in zip(log_ns, MW, MM, MP):
+        ctx = stark.StarkContext(log_n, b)
+        mat = stark.lde(ctx, torch.randint(0, stark.P, ((width + 7) // 8, 1 << log_n, 8), dtype=torch.int32, device="cuda", generator=g), clobber=True)
+        groups.append(stark.EvalGroup(ctx, [mat], [stark.merkle_commit(ctx, mat, width)], [width], [mask], rng.integers(1, stark.P, (n_points, 4), dtype=np.uint32)))
+    pr = stark.mixed_eval_prove(groups, QUERIES[b], POW_BITS)
+    lay = stark.mixed_eval_layout(pr)
+    roots, pts = pr[lay["roots"]:lay["points"]].copy(), np.concatenate([gr.points.reshape(-1) for gr in groups]).astype(np.uint32)
+    for gr in groups:
+        gr.ctx.close()
+    del groups
+    torch.cuda.empty_cache()
+    return [("mixed_eval", lambda d: rt.mixed_eval_verify(pr, roots, pts, device=d), len(pr))]
+
+
 def measure(call, calls):
     from zkir_amd import runtime as rt
     for _ in range(10):
@@ -64,18 +91,27 @@ def main():
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mixed", action="store_true", help="time the mixed-height proof ('ZKMH') and nothing else")
+    ap.add_argument("--log-ns", default="20,16,12", help="--mixed: the three heights")
     args = ap.parse_args()
+    log_ns = [int(x) for x in args.log_ns.split(",")]
     import torch
     lines = []
     def say(s):
         print(s, flush=True); lines.append(s)
     f3 = lambda t: f"{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})"
-    say(f"# {torch.cuda.get_device_name(0)}; 2^{args.log_n} rows; lowdeg / eval: {W} columns (eval at two points); batch_eval: {WIDTHS} columns, masks {MASKS}; pow_bits {POW_BITS}; "
-        f"host and device entries alternating, {args.calls} calls each after 10 warm-up pairs; wall ms, median (min .. max)")
+    if args.mixed:
+        from scripts.time_mixed_eval import WIDTHS as MW, MASKS as MM, N_POINTS as MP
+        say(f"# python scripts/time_pcs_verify.py --mixed --log-ns {args.log_ns} --calls {args.calls}")
+        say(f"# {torch.cuda.get_device_name(0)}; mixed_eval: groups of 2^{log_ns} rows x {MW} columns, masks {MM}, {MP} points; pow_bits {POW_BITS}; "
+            f"host and device entries alternating, {args.calls} calls each after 10 warm-up pairs; wall ms, median (min .. max)")
+    else:
+        say(f"# {torch.cuda.get_device_name(0)}; 2^{args.log_n} rows; lowdeg / eval: {W} columns (eval at two points); batch_eval: {WIDTHS} columns, masks {MASKS}; pow_bits {POW_BITS}; "
+            f"host and device entries alternating, {args.calls} calls each after 10 warm-up pairs; wall ms, median (min .. max)")
     say(f"{'proof':>10s} {'b':>2s} {'q':>3s} {'words':>7s} {'hash jobs':>9s} | {'host entry ms':>24s} | {'device entry ms':>24s} | device median < host min | "
         f"device entry split (stage synchronising): {'host part':>22s} | {'upload':>22s} | {'kernels':>22s} | {'download':>22s}")
     for b in (1, 2, 3):
-        for name, call, words in proofs_for(args.log_n, b):
+        for name, call, words in (mixed_proof_for(log_ns, b) if args.mixed else proofs_for(args.log_n, b)):
             host, dev, parts, jobs = measure(call, args.calls)
             say(f"{name:>10s} {b:2d} {QUERIES[b]:3d} {words:7d} {jobs[0]:9d} | {f3(host):>24s} | {f3(dev):>24s} | {'yes' if dev[0] < host[1] else 'NO':>23s} | "
                 + " " * 43 + " | ".join(f"{f3(p):>22s}" for p in parts))

@@ -17,16 +17,19 @@ constexpr uint32_t PCS_MAX_SLOTS = 2 * zkir::PCS_MAX_MATS + zkir::PCS_MAX_LAYERS
 
 // Job -> (query t, slot): a slot below 2 n_mats is matrix slot / 2's record at row q (even) or q + M/2 (odd); the others are the FRI layers in order.  Offsets are words from
 // the query's first word.  The leaf's Merkle index is (q + idx_add) mod 2^depth: the carried index of a FRI layer only ever drops high bits of q.
-struct PcsHashShape {
+// (SLOTS: the most slots a query of the proof's kind can have — PCS_MAX_SLOTS here, zkir::MIXED_MAX_SLOTS in mixed_verify.inl, whose slot order is its own.)
+template <uint32_t SLOTS> struct PcsHashShapeT {
   uint64_t at_queries, qsize;
   uint32_t n_slots, n_jobs;
-  uint32_t leaf_off[PCS_MAX_SLOTS], leaf_words[PCS_MAX_SLOTS], depth[PCS_MAX_SLOTS], root_at[PCS_MAX_SLOTS], idx_add[PCS_MAX_SLOTS];
+  uint32_t leaf_off[SLOTS], leaf_words[SLOTS], depth[SLOTS], root_at[SLOTS], idx_add[SLOTS];
 };
+using PcsHashShape = PcsHashShapeT<PCS_MAX_SLOTS>;
 
 // merkle_verify_row16_kernel's chain (a SECOND COPY: that kernel's code is left as it is) on a leaf read in place: lane l holds state word l; link t < n_sponge absorbs block
 // t of the leaf, link n_sponge + lvl compresses with the sibling of level lvl.  Scale factors and the ragged-last-block rule are leaf_hash_kernel's.  A leaf has at least one
 // word and every word is canonical (check 3), so there is no verdict but "hashes to the root" or not: flags[job] = 0 / 1, one plain store.
-__global__ __launch_bounds__(NT_MV) void pcs_hash_jobs_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ w, const uint32_t* __restrict__ qs, PcsHashShape sh, uint32_t* __restrict__ flags) {
+template <uint32_t SLOTS>
+__global__ __launch_bounds__(NT_MV) void pcs_hash_jobs_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ w, const uint32_t* __restrict__ qs, PcsHashShapeT<SLOTS> sh, uint32_t* __restrict__ flags) {
   const uint32_t job = (blockIdx.x * NT_MV + threadIdx.x) / 16;
   const uint32_t l = threadIdx.x & 15;
   if (job >= sh.n_jobs) return;                                  // (whole rows)
@@ -260,7 +263,7 @@ struct PcsDeviceStage {
     const uint32_t* d_betas = (const uint32_t*)(V.d + o_betas); const uint32_t* d_ltab = (const uint32_t*)(V.d + o_ltab);
     uint32_t* d_flags = (uint32_t*)(V.d + o_flags);
     uint32_t *d_f8 = d_flags + hash_jobs, *d_ff = d_f8 + 2 * (size_t)nq;
-    hipLaunchKernelGGL(pcs_hash_jobs_kernel, dim3(grid_for(hash_jobs * 16, NT_MV)), dim3(NT_MV), 0, s, V.d_p2, d_w, d_qs, hs, d_flags);
+    hipLaunchKernelGGL(pcs_hash_jobs_kernel<PCS_MAX_SLOTS>, dim3(grid_for(hash_jobs * 16, NT_MV)), dim3(NT_MV), 0, s, V.d_p2, d_w, d_qs, hs, d_flags);
     hipLaunchKernelGGL(pcs_value_kernel, dim3(2 * nq + grid_for((uint64_t)nq * Q.n_layers, 64)), dim3(64), 0, s, d_w, d_qs, d_gamma, d_betas, d_ltab, vs, d_f8, d_ff);
     pcs_last_jobs[0] = hash_jobs; pcs_last_jobs[1] = value_jobs;
     if (timed && hipStreamSynchronize(s) != hipSuccess) { (void)check_launch("zkir_*_verify_device: kernels"); return -ZKIR_ERR_DEVICE; }

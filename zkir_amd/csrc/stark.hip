@@ -1111,3 +1111,4 @@ int zkir_merkle_cap_launch(const zkir_stark_ctx* c, uint32_t* tree, uint64_t n_d
 #include "eval_open.inl"
 #include "mixed_eval.inl"
 #include "pcs_verify.inl"
+#include "mixed_verify.inl"

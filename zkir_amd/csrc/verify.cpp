@@ -1399,7 +1399,8 @@ int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
 }  // extern "C"
 
 // ================================================================================================
-// zkir_mixed_eval_verify — the verifier of an EVALUATION PROOF OVER SEVERAL HEIGHTS (zkir_mixed_eval_prove, mixed_eval.inl; spec: tests/mixed_eval_ref.py).  Host only.
+// zkir_mixed_eval_verify — the verifier of an EVALUATION PROOF OVER SEVERAL HEIGHTS (zkir_mixed_eval_prove, mixed_eval.inl; spec: tests/mixed_eval_ref.py).  Host code; zkir_mixed_eval_verify_device
+// (mixed_verify.inl) runs the same code with the query stage (verify_stages.h: MixedQueries, checks 6 .. 11) on the device.
 //
 // The proof says: n_groups (2 or 3) groups at one rate b, of strictly decreasing heights; group h is what a 'ZKBE' proof states at height log_n_h (1 .. 4 matrices over
 // 31 <w_{M_h}>, M_h = N_h << b, each under its own root; its own 1 or 2 points; a mask per matrix).  ONE gamma, drawn after everything up to the evaluations; its exponent runs
@@ -1462,7 +1463,58 @@ uint64_t zkir_mixed_eval_proof_words(uint32_t log_blowup, uint32_t n_groups, con
   return mixed_words(sh, num_queries, nullptr);
 }
 
-int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
+}  // extern "C"
+
+namespace {
+
+// The host form of the mixed query stage (verify_stages.h): checks 6 .. 11, query after query
+int host_mixed_query_run(void*, const zkir::MixedQueries& MQ) {
+  const uint32_t* w = MQ.w;
+  const zkir::PcsQueries* Q = MQ.g;
+  const uint32_t n_groups = MQ.n_groups;
+  const int n_layers = (int)MQ.n_layers, log_M = (int)Q[0].log_M;
+  const size_t M = (size_t)1 << log_M, n_fin = zkir::fri_final_size((int)MQ.b), at_queries = (size_t)MQ.at_queries, qsize = (size_t)MQ.qsize;
+  const uint32_t *roots = w + MQ.at_roots, *lroots = w + MQ.at_lroots;
+  const uint32_t* ks = MQ.ks;
+  std::vector<E4> fin(n_fin), betas(n_layers);
+  for (size_t i = 0; i < n_fin; i++) { const uint32_t* a = w + MQ.at_fin + 4 * i; fin[i] = bb::e_to_mont(E4{{a[0], a[1], a[2], a[3]}}); }
+  for (int j = 0; j < n_layers; j++) memcpy(betas[j].c, MQ.betas_m + 4 * j, 16);
+  for (uint32_t t = 0; t < MQ.num_queries; t++) {
+    const uint32_t q = MQ.qs[t];
+    size_t p = at_queries + (size_t)t * qsize;
+    if (w[p++] != q) return 6;
+    const uint32_t* rows[MIXED_MAX_GROUPS][2][4];                           // group 0: rows q and q + M_0/2; a lower group: the row q mod M_h at [h][0]
+    for (uint32_t h = 0; h < n_groups; h++) {
+      const int log_Mh = (int)Q[h].log_M;
+      for (uint32_t m = 0; m < Q[h].n_mats; m++)
+        for (int s2 = 0; s2 < (h ? 1 : 2); s2++) {
+          const size_t pos = h ? (q & (((size_t)1 << log_Mh) - 1)) : (size_t)q + (s2 ? M / 2 : 0);
+          const uint32_t* row = w + p;
+          uint32_t dg[4]; hash_elems(row, Q[h].widths[m], dg);
+          if (!check_path(dg, pos, row + Q[h].widths[m], log_Mh, roots + 4 * (MQ.first_mat[h] + m))) return 7;
+          rows[h][s2][m] = row;
+          p += (size_t)Q[h].widths[m] + 4 * (size_t)log_Mh;
+        }
+    }
+    const E4 comb[2] = {layer0_want(Q[0], q, rows[0][0]), layer0_want(Q[0], (size_t)q + M / 2, rows[0][1])};
+    FriWalk walk(log_M, q);
+    for (int j = 0; j < n_layers; j++) {
+      const int k = (int)ks[j];
+      for (uint32_t h = 1; h < n_groups; h++)                                // the layer of size M_h is the fold plus F_h: what is carried into it gains F_h(q mod M_h)
+        if ((int)Q[h].log_M == walk.log_m) walk.carried = bb::e_add(walk.carried, layer0_want(Q[h], walk.carried_idx, rows[h][0]));
+      const size_t layer_words = 4 * ((size_t)1 << k) + 4 * (size_t)(walk.log_m - k);
+      const FriLayerSeen seen = fri_walk_step(walk, w + p, k, lroots + 4 * j, betas[j]);
+      p += layer_words;
+      if (j == 0 && (!e_eq(seen.v0, comb[0]) || !e_eq(seen.v1, comb[1]))) return 8;
+      if (!seen.leaf_ok) return 9;
+      if (j > 0 && !seen.carried_ok) return 10;
+    }
+    if (!e_eq(fin[walk.carried_idx & (n_fin - 1)], walk.carried)) return 11;
+  }
+  return 0;
+}
+
+int mixed_eval_verify_impl(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const zkir::MixedQueryStage& stage) {
   // ---- 1: shape ----
   if (!w || len < 7 || w[0] != MIXED_MAGIC || w[1] != 1) return 1;
   const uint32_t b = w[2], n_groups = w[3], num_queries = w[4], pow_bits = w[5];
@@ -1504,8 +1556,9 @@ int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
   std::vector<E4> gp((size_t)sh.n_evals);
   gp[0] = bb::e_one_m();
   for (size_t k = 1; k < gp.size(); k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
-  zkir::PcsQueries Q[MIXED_MAX_GROUPS] = {};
-  size_t first_mat[MIXED_MAX_GROUPS];
+  zkir::MixedQueries MQ{};
+  zkir::PcsQueries* Q = MQ.g;
+  uint32_t* first_mat = MQ.first_mat;
   {
     size_t e = 0, m0 = 0, p0 = 0;
     for (uint32_t h = 0; h < n_groups; h++) {
@@ -1524,52 +1577,36 @@ int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
         }
         memcpy(q.z_m[i], z.c, 16); memcpy(q.a_m[i], a.c, 16);
       }
-      first_mat[h] = m0; m0 += g.n_mats; p0 += g.n_points;
+      first_mat[h] = (uint32_t)m0; m0 += g.n_mats; p0 += g.n_points;
     }
   }
   // ---- 4: the final layer; the transcript after gamma; 5: grinding ----
   const int n_layers = (int)ks.size(), log_M = (int)(log_ns[0] + b);
-  const size_t M = (size_t)1 << log_M, n_fin = zkir::fri_final_size((int)b);
+  const size_t n_fin = zkir::fri_final_size((int)b);
   const uint32_t* lroots = w + at_lroots;
   const size_t at_fin = at_lroots + 4 * (size_t)n_layers, at_nonce = at_fin + 4 * n_fin, at_queries = at_nonce + 1, qsize = (size_t)((len - at_queries) / num_queries);
   std::vector<E4> fin(n_fin), betas;
   for (size_t i = 0; i < n_fin; i++) fin[i] = get_m(w + at_fin + 4 * i);
   if (!fri_final_degree_ok(fin, (int)b)) return 4;
   if (!fri_transcript(ch, lroots, n_layers, w + at_fin, n_fin, w[at_nonce], (int)pow_bits, betas)) return 5;
-  // ---- 6 .. 11, query after query ----
-  for (uint32_t t = 0; t < num_queries; t++) {
-    const uint32_t q = ch.sample_bits(log_M - 1);
-    size_t p = at_queries + (size_t)t * qsize;
-    if (w[p++] != q) return 6;
-    const uint32_t* rows[MIXED_MAX_GROUPS][2][4];                           // group 0: rows q and q + M_0/2; a lower group: the row q mod M_h at [h][0]
-    for (uint32_t h = 0; h < n_groups; h++) {
-      const int log_Mh = (int)Q[h].log_M;
-      for (uint32_t m = 0; m < sh.g[h].n_mats; m++)
-        for (int s2 = 0; s2 < (h ? 1 : 2); s2++) {
-          const size_t pos = h ? (q & (((size_t)1 << log_Mh) - 1)) : (size_t)q + (s2 ? M / 2 : 0);
-          const uint32_t* row = w + p;
-          uint32_t dg[4]; hash_elems(row, sh.g[h].widths[m], dg);
-          if (!check_path(dg, pos, row + sh.g[h].widths[m], log_Mh, roots + 4 * (first_mat[h] + m))) return 7;
-          rows[h][s2][m] = row;
-          p += (size_t)sh.g[h].widths[m] + 4 * (size_t)log_Mh;
-        }
-    }
-    const E4 comb[2] = {layer0_want(Q[0], q, rows[0][0]), layer0_want(Q[0], (size_t)q + M / 2, rows[0][1])};
-    FriWalk walk(log_M, q);
-    for (int j = 0; j < n_layers; j++) {
-      const int k = ks[j];
-      for (uint32_t h = 1; h < n_groups; h++)                                // the layer of size M_h is the fold plus F_h: what is carried into it gains F_h(q mod M_h)
-        if ((int)Q[h].log_M == walk.log_m) walk.carried = bb::e_add(walk.carried, layer0_want(Q[h], walk.carried_idx, rows[h][0]));
-      const size_t layer_words = 4 * ((size_t)1 << k) + 4 * (size_t)(walk.log_m - k);
-      const FriLayerSeen seen = fri_walk_step(walk, w + p, k, lroots + 4 * j, betas[j]);
-      p += layer_words;
-      if (j == 0 && (!e_eq(seen.v0, comb[0]) || !e_eq(seen.v1, comb[1]))) return 8;
-      if (!seen.leaf_ok) return 9;
-      if (j > 0 && !seen.carried_ok) return 10;
-    }
-    if (!e_eq(fin[walk.carried_idx & (n_fin - 1)], walk.carried)) return 11;
-  }
-  return 0;
+  std::vector<uint32_t> qs(num_queries);
+  for (auto& q : qs) q = ch.sample_bits(log_M - 1);
+  // ---- 6 .. 11: the query stage ----
+  if (n_layers > (int)zkir::MIXED_MAX_LAYERS || sh.n_mats + sh.g[0].n_mats + (uint64_t)n_layers > zkir::MIXED_MAX_SLOTS) return 1;      // (no header that passed check 1 states either)
+  MQ.w = w; MQ.len = len;
+  MQ.n_groups = n_groups; MQ.b = b; MQ.n_layers = (uint32_t)n_layers; MQ.num_queries = num_queries;
+  for (int j = 0; j < n_layers; j++) MQ.ks[j] = (uint32_t)ks[j];
+  MQ.at_roots = at_roots; MQ.at_lroots = at_lroots; MQ.at_fin = at_fin; MQ.at_queries = at_queries; MQ.qsize = qsize;
+  MQ.qs = qs.data(); MQ.betas_m = betas[0].c;
+  return stage.run(stage.self, MQ);
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
+  return mixed_eval_verify_impl(w, len, expect_roots, expect_points, expect_evals, zkir::host_mixed_query_stage());
 }
 
 }  // extern "C"
@@ -1580,5 +1617,9 @@ int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, con
   if (kind == 0) return lowdeg_verify_impl(proof, n_words, expect_roots, stage);
   if (kind == 1) return eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
   return batch_eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
+}
+MixedQueryStage host_mixed_query_stage() { return MixedQueryStage{nullptr, host_mixed_query_run}; }
+int mixed_eval_verify_with_stage(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const MixedQueryStage& stage) {
+  return mixed_eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
 }
 }  // namespace zkir

@@ -57,4 +57,26 @@ QueryStage host_query_stage();                                   // the loop of 
 // the three verifiers, by the proof's kind (0 'ZKLD', 1 'ZKEV', 2 'ZKBE'; 'ZKLD' has one root and no points): everything but the query stage is verify.cpp's host code
 int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage);
 
+// ---- the QUERY STAGE of the mixed-height verifier (zkir_mixed_eval_verify and zkir_mixed_eval_verify_device: a 'ZKMH' proof) ----
+// Checks 6 .. 11 of all the queries, handed over as above: after checks 1 .. 5, 12 and 13 and the sampling.  The proof has ONE FRI and one layer-0 rule per GROUP: g[h] is a
+// PcsQueries of which only the rule counts (log_M = log M_h, n_mats, widths, n_points, n_sel, sel with e0 counted from the proof's first exponent, z_m, a_m, and the gamma
+// table all groups share); group h's first matrix is matrix first_mat[h] of the proof's roots at at_roots.  A query holds q, group 0's records at q and q + M_0/2, each lower
+// group's records at q mod M_h, then the layers; the layer of size M_h is the fold of the layer before it plus F_h (g[h]'s rule at row q mod M_h).
+// The mixed schedule (fri_mixed_schedule) is longer than the single-height one: over every pair and triple of heights and every b it has at most 10 layers
+// (log_ns = (26, 3), b = 1: 1,3,3,3,3,3,3,3,1,1), so this path has its own bounds; the hash jobs of one query are at most 2*4 (group 0) + 2*4 (two lower groups) + 10.
+constexpr uint32_t MIXED_MAX_GROUPS = 3, MIXED_MAX_LAYERS = 10, MIXED_MAX_SLOTS = 2 * PCS_MAX_MATS + (MIXED_MAX_GROUPS - 1) * PCS_MAX_MATS + MIXED_MAX_LAYERS;      // 26
+struct MixedQueries {
+  const uint32_t* w; uint64_t len;                               // the proof
+  uint32_t n_groups, b, n_layers, num_queries;
+  PcsQueries g[MIXED_MAX_GROUPS];
+  uint32_t first_mat[MIXED_MAX_GROUPS];
+  uint32_t ks[MIXED_MAX_LAYERS];
+  uint64_t at_roots, at_lroots, at_fin, at_queries, qsize;      // as in PcsQueries; at_roots: the first of all the groups' roots
+  const uint32_t* qs;                                            // the transcript's samples, each below M_0 / 2
+  const uint32_t* betas_m;                                       // n_layers Montgomery E4
+};
+struct MixedQueryStage { void* self; int (*run)(void* self, const MixedQueries& q); };
+MixedQueryStage host_mixed_query_stage();                        // the loop of verify.cpp
+int mixed_eval_verify_with_stage(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const MixedQueryStage& stage);
+
 }  // namespace zkir

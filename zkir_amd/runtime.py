@@ -410,6 +410,7 @@ def lib() -> C.CDLL:
         L.zkir_lowdeg_verify_device.restype = C.c_int; L.zkir_lowdeg_verify_device.argtypes = [V, U64, V, V]
         L.zkir_eval_verify_device.restype = C.c_int; L.zkir_eval_verify_device.argtypes = [V, U64, V, V, V, V]
         L.zkir_batch_eval_verify_device.restype = C.c_int; L.zkir_batch_eval_verify_device.argtypes = [V, U64, V, V, V, V]
+        L.zkir_mixed_eval_verify_device.restype = C.c_int; L.zkir_mixed_eval_verify_device.argtypes = [V, U64, V, V, V, V]
         L.zkir_pcs_verify_last_jobs.restype = C.c_int; L.zkir_pcs_verify_last_jobs.argtypes = [C.POINTER(U64), C.POINTER(U64)]
         L.zkir_pcs_verify_last_stage_ms.restype = C.c_int; L.zkir_pcs_verify_last_stage_ms.argtypes = [V]
     if hasattr(L, "zkir_merkle_open_launch"):                 # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
@@ -839,11 +840,12 @@ def mixed_eval_sizes(proof):
             sum(wd * bin(k).count("1") for g in groups for wd, k in zip(g["widths"], g["masks"])))
 
 
-def mixed_eval_verify(proof, roots=None, points=None, evals=None) -> int:
-    """zkir_mixed_eval_verify, on the host — no GPU, and there is no device form: 0 = the proof convinces a holder of its roots that every column of every committed matrix of
+def mixed_eval_verify(proof, roots=None, points=None, evals=None, device: bool = False, stream=None) -> int:
+    """zkir_mixed_eval_verify, on the host — no GPU: 0 = the proof convinces a holder of its roots that every column of every committed matrix of
     every group is close to a polynomial of degree < 2^(its group's log_n) that takes the proof's evaluations at the points its matrix is opened at; `roots`, `points` and
     `evals` (all groups' words, in the proof's order), when given, must be the proof's.  Else the code of the first failing check (include/zkir_amd.h lists them).  The library
-    reads as many expected words as the proof's header states: where the header is one a proof can have, expectations of another size raise ValueError."""
+    reads as many expected words as the proof's header states: where the header is one a proof can have, expectations of another size raise ValueError.  device=True:
+    zkir_mixed_eval_verify_device — the same verdict, checks 7 - 11 of all queries on the GPU (three launches on `stream`)."""
     w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
     r = None if roots is None else np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1)
     p = None if points is None else np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
@@ -856,6 +858,8 @@ def mixed_eval_verify(proof, roots=None, points=None, evals=None) -> int:
     else:
         r = p = e = None                                         # the proof is malformed (1) whatever is expected of it
     ptr = lambda a: a.ctypes.data if a is not None else None
+    if device:
+        return _pcs_verdict(lib().zkir_mixed_eval_verify_device(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e), stream))
     return int(lib().zkir_mixed_eval_verify(w.ctypes.data if len(w) else None, len(w), ptr(r), ptr(p), ptr(e)))
 
 

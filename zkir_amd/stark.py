@@ -448,7 +448,11 @@ class EvalGroup(NamedTuple):
 
 
 mixed_eval_proof_words = rt.mixed_eval_proof_words
-mixed_eval_verify = rt.mixed_eval_verify
+
+
+def mixed_eval_verify(proof, roots=None, points=None, evals=None, device: bool = False, stream=None) -> int:
+    """rt.mixed_eval_verify; device=True checks the queries on the GPU, on the torch stream `stream` (default: the current one) — the same verdict."""
+    return rt.mixed_eval_verify(proof, roots, points, evals, device=device, stream=_verify_stream(device, stream))
 
 
 def mixed_eval_prove(groups, num_queries: int = 50, pow_bits: int = 12, stream=None, want_stage_ms: bool = False):
