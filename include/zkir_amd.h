@@ -625,6 +625,29 @@ int zkir_hash_tape_new_bytes_host(const uint32_t* hash_words, uint64_t n_hash_wo
  * failed HIP call) or -ZKIR_ERR_OTHER (no host memory); zkir_last_error says which.  Calls on one device are serialised inside; the device block and the pinned staging of the
  * largest tape seen stay with the process, one set per HIP device the entry was called on. */
 int zkir_verify_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, void* hip_stream);
+/* THE QUERIES ON THE DEVICE: one proof, many, or a chain.  The three entries below are zkir_verify / zkir_verify_chain with the QUERY STAGE — checks 20 - 27 of all the
+ * queries: the Merkle paths of the three commitments' records and of the FRI layers, the layer-0 values, the folds, the final value — run on the current HIP device as ONE
+ * batch: a leaf-and-path job per record and layer (a row of 16 lanes each), the layer-0 values (a wave per query and half) and the folds (a lane per query and layer) in a
+ * second kernel.  Everything else — header, program, cells, the transcript, the constraints at zeta, the final layer's degree, grinding, the sampling, check 20's index
+ * words, check 30 — is zkir_verify's own host code in its order, a mode-4 proof's tape stages run as in zkir_verify_device.  Every extent a kernel uses comes from checked
+ * header words, the row it opens is the transcript's sample; only the words from the trace root to the end of the last query that lies wholly inside the proof are
+ * uploaded (never the program, the cells or the tapes), and a query the proof's end cuts is the host loop's.  One staged upload, two launches, one download and one
+ * synchronisation on hip_stream per call, however many proofs; nothing is launched where no proof reaches its queries.  The verdict is the host entry's for every input.
+ * A NEGATIVE result is no verdict: -ZKIR_ERR_DEVICE or -ZKIR_ERR_OTHER, zkir_last_error says which.  Calls on one device are serialised inside (zkir_verify_device's
+ * per-device block and pinned staging).
+ * zkir_verify_on_device: zkir_verify's verdict, any mode; a batch of one.
+ * zkir_verify_many_on_device: n independent proofs, 1 <= n <= 1024 (else ZKIR_ERR_ARGUMENT, as for a null proofs, proof_words or verdicts); expects may be NULL and so may
+ * each entry.  The host parts run proof after proof on the calling thread, then ONE stage run serves every proof that reached its queries.  Returns 0 with verdicts[i] =
+ * what zkir_verify(proofs[i], proof_words[i], expects[i]) returns for every i, or an error (ZKIR_ERR_ARGUMENT, a negative value) with NO verdict written.
+ * zkir_verify_chain_on_device: zkir_verify_chain's verdict; the segments' host parts run up to the first one that fails there, the collected segments' queries are one
+ * stage run, and the verdict is resolved in segment order.  A chain of one mode >= 3 proof is zkir_verify_on_device.
+ * zkir_verify_queries_last: what the calling thread's last verification (any entry) ran as its device query stage — leaf-and-path jobs, value jobs (two per query and one
+ * per query and layer), launches (0 or 2), words uploaded (proof words and the stage's own tables).  All zero after a host entry and after zkir_verify_device.  Any
+ * pointer may be NULL.  Whether the device pays for ONE small proof is a measurement (profiles/r20_verify_queries_device.txt); no threshold is built in. */
+int zkir_verify_on_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, void* hip_stream);
+int zkir_verify_many_on_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, void* hip_stream);
+int zkir_verify_chain_on_device(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, void* hip_stream);
+int zkir_verify_queries_last(uint64_t* hash_jobs, uint64_t* value_jobs, uint32_t* launches, uint64_t* uploaded_words);
 /* diagnostics of the calling thread's last zkir_verify* call: host wall time in ms of [0] parsing (the tapes' record checks among it), [1] the sections' chunk digests,
  * [2] the hash tape's share of the table side, [3] the wide tape's, [4] the rest; *device_stages = how many of these stages ran on the device (0 for every host entry).
  * Either pointer may be NULL.  ZKIR_ERR_ARGUMENT before the thread's first verification.  ZKIR_VERIFY_TIMES in the environment prints the clocks on stderr. */

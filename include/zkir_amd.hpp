@@ -463,6 +463,25 @@ inline int verify_chain(const std::vector<std::vector<uint32_t>>& proofs, const 
   for (const auto& p : proofs) { ptrs.push_back(p.data()); lens.push_back(p.size()); }
   return zkir_verify_chain(ptrs.data(), lens.data(), (uint32_t)proofs.size(), expect);
 }
+// The same verdicts with the QUERY STAGE on the current HIP device (zkir_verify_on_device, zkir_verify_many_on_device, zkir_verify_chain_on_device): one proof, many
+// independent proofs (verdicts[i] = verify(proofs[i], expects[i]); expects empty or one nullable entry per proof) or a chain's segments as ONE batch of two launches.
+// A negative return (many: any non-zero return) is no verdict: zkir_last_error says why.
+inline int verify_on_device(const std::vector<uint32_t>& proof, const zkir_public_inputs* expect = nullptr, void* hip_stream = nullptr) {
+  return zkir_verify_on_device(proof.data(), proof.size(), expect, hip_stream);
+}
+inline int verify_many_on_device(const std::vector<std::vector<uint32_t>>& proofs, std::vector<int32_t>& verdicts, const std::vector<const zkir_public_inputs*>& expects = {},
+                                 void* hip_stream = nullptr) {
+  std::vector<const uint32_t*> ptrs; std::vector<uint64_t> lens;
+  for (const auto& p : proofs) { ptrs.push_back(p.data()); lens.push_back(p.size()); }
+  verdicts.assign(proofs.size(), 0);
+  if (!expects.empty() && expects.size() != proofs.size()) return ZKIR_ERR_ARGUMENT;
+  return zkir_verify_many_on_device(ptrs.data(), lens.data(), expects.empty() ? nullptr : expects.data(), (uint32_t)proofs.size(), verdicts.data(), hip_stream);
+}
+inline int verify_chain_on_device(const std::vector<std::vector<uint32_t>>& proofs, const zkir_public_inputs* expect = nullptr, void* hip_stream = nullptr) {
+  std::vector<const uint32_t*> ptrs; std::vector<uint64_t> lens;
+  for (const auto& p : proofs) { ptrs.push_back(p.data()); lens.push_back(p.size()); }
+  return zkir_verify_chain_on_device(ptrs.data(), lens.data(), (uint32_t)proofs.size(), expect, hip_stream);
+}
 
 }  // namespace zkir_prover
 

@@ -77,6 +77,14 @@ int zkir_pcs_verify_last_jobs(uint64_t* hash_jobs, uint64_t* value_jobs);
 /* MEASUREMENT: with ZKIR_PCS_VERIFY_TIMES set in the environment the device query stage synchronises after its upload and after its kernels; this reports the host clocks
  * (ms) of the calling thread's last such call: upload | kernels | download.  Zeros without the variable or before the stage. */
 int zkir_pcs_verify_last_stage_ms(double ms[3]);
+/* MEASUREMENT: the same for the STARK verifier's device query stage (zkir_verify_on_device, zkir_verify_many_on_device, zkir_verify_chain_on_device), under
+ * ZKIR_VERIFY_QUERIES_TIMES: upload | kernels | download of the calling thread's last stage run. */
+int zkir_verify_queries_last_stage_ms(double ms[3]);
+/* TEST HOOK: the STARK verifier's query stage on PERTURBED DRAWS.  The roots are in the transcript, so a proof mutated by one word fails a hash check (21 / 22 / 23 / 27) or
+ * grinding before it can reach checks 24, 25 or 26; perturbing what the VERIFIER drew reaches them with an honest proof.  Runs zkir_verify's host part (no expectation; a
+ * failing one is returned as it is), perturbs, then runs the host form of the stage (device = 0: no HIP call) or the device form, then check 30.  what: 0 nothing, 1 a0 + 1,
+ * 2 b0 + 1, 3 zeta + 1, 4 betas[index] + 1, 5 qs[index] ^= 1.  Returns the verdict; negative: -ZKIR_ERR_ARGUMENT (no such what / layer / query) or a device failure. */
+int zkir_stark_query_stage_probe(const uint32_t* proof, uint64_t proof_words, uint32_t what, uint32_t index, int device, void* hip_stream);
 
 #ifdef __cplusplus
 }

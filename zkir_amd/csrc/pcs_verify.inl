@@ -1,6 +1,7 @@
 // pcs_verify.inl — zkir_lowdeg_verify_device, zkir_eval_verify_device, zkir_batch_eval_verify_device (include/zkir_amd.h): the verifiers of the commitment layer with their
 // QUERY STAGE (verify_stages.h: checks 6 .. 11 of all queries) on the device.  Included by stark.hip at file scope, after verify_device.inl (whose per-device state it uses)
-// and merkle_open.inl (whose row-of-16 chain the hash kernel repeats).
+// and merkle_open.inl (whose row-of-16 chain the hash kernel repeats).  The kernels'
+// __device__ pieces (pcs_row16_hashes_to, pcs_row_dot, pcs_wave_sum, pcs_point_sum, pcs_fold_step, pcs_fold_lane) are shared with stark_verify.inl.
 //
 // Everything before the stage — shape, expectations, word range, the whole transcript, the final-degree check, grinding, the sampling — is verify.cpp's host code, run
 // first and unchanged.  The stage uploads the proof as it stands with the transcript's samples and the gamma table, launches TWO kernels and downloads one flag per job:
@@ -25,22 +26,16 @@ template <uint32_t SLOTS> struct PcsHashShapeT {
 };
 using PcsHashShape = PcsHashShapeT<PCS_MAX_SLOTS>;
 
-// merkle_verify_row16_kernel's chain (a SECOND COPY: that kernel's code is left as it is) on a leaf read in place: lane l holds state word l; link t < n_sponge absorbs block
-// t of the leaf, link n_sponge + lvl compresses with the sibling of level lvl.  Scale factors and the ragged-last-block rule are leaf_hash_kernel's.  A leaf has at least one
-// word and every word is canonical (check 3), so there is no verdict but "hashes to the root" or not: flags[job] = 0 / 1, one plain store.
-template <uint32_t SLOTS>
-__global__ __launch_bounds__(NT_MV) void pcs_hash_jobs_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ w, const uint32_t* __restrict__ qs, PcsHashShapeT<SLOTS> sh, uint32_t* __restrict__ flags) {
-  const uint32_t job = (blockIdx.x * NT_MV + threadIdx.x) / 16;
-  const uint32_t l = threadIdx.x & 15;
-  if (job >= sh.n_jobs) return;                                  // (whole rows)
-  const uint32_t t = job / sh.n_slots, slot = job - t * sh.n_slots;
-  const uint32_t depth = sh.depth[slot], width = sh.leaf_words[slot];
-  const uint32_t j = (qs[t] + sh.idx_add[slot]) & ((1u << depth) - 1u);
-  const uint32_t* r = w + sh.at_queries + (uint64_t)t * sh.qsize + sh.leaf_off[slot];
+// merkle_verify_row16_kernel's chain (a SECOND COPY: that kernel's code is left as it is) on a leaf read in place: lane l of a row of 16 holds state word l; link
+// t < n_sponge absorbs block t of the leaf r (width words, its 4 depth sibling words behind it), link n_sponge + lvl compresses with the sibling of level lvl of Merkle
+// index j.  Scale factors and the ragged-last-block rule are leaf_hash_kernel's.  A leaf has at least one word and every word is canonical, so there is no verdict but
+// "hashes to the root" or not: non-zero on the row's lane 0 when it does.  Shared by pcs_hash_jobs_kernel and stark_hash_jobs_kernel (stark_verify.inl).
+__device__ __forceinline__ uint32_t pcs_row16_hashes_to(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ r, uint32_t width, uint32_t depth, uint32_t j, const uint32_t* __restrict__ root,
+                                                        uint32_t l) {
   const uint32_t* path = r + width;
   const uint32_t k_in = cp->in_scale, carry = cp->carry, out_scale = cp->out_scale;
   const uint32_t q = l & 3;
-  const uint32_t root_q = w[sh.root_at[slot] + q];
+  const uint32_t root_q = root[q];
   const uint32_t n_sponge = (width + p2::RATE - 1) / p2::RATE, n_links = n_sponge + depth;
   uint32_t s = 0;
   for (uint32_t lk = 0; lk < n_links; lk++) {
@@ -58,6 +53,20 @@ __global__ __launch_bounds__(NT_MV) void pcs_hash_jobs_kernel(const p2::Consts* 
   }
   uint32_t eq = bb::mont_mul(s, out_scale) == root_q;            // "my word of the digest is the root's" (lanes 0-3 count)
   eq &= (uint32_t)__shfl_xor((int)eq, 1, 16); eq &= (uint32_t)__shfl_xor((int)eq, 2, 16);
+  return eq;
+}
+
+// One leaf-and-path job a row of 16 lanes: flags[job] = 0 / 1, one plain store.
+template <uint32_t SLOTS>
+__global__ __launch_bounds__(NT_MV) void pcs_hash_jobs_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ w, const uint32_t* __restrict__ qs, PcsHashShapeT<SLOTS> sh, uint32_t* __restrict__ flags) {
+  const uint32_t job = (blockIdx.x * NT_MV + threadIdx.x) / 16;
+  const uint32_t l = threadIdx.x & 15;
+  if (job >= sh.n_jobs) return;                                  // (whole rows)
+  const uint32_t t = job / sh.n_slots, slot = job - t * sh.n_slots;
+  const uint32_t depth = sh.depth[slot], width = sh.leaf_words[slot];
+  const uint32_t j = (qs[t] + sh.idx_add[slot]) & ((1u << depth) - 1u);
+  const uint32_t* r = w + sh.at_queries + (uint64_t)t * sh.qsize + sh.leaf_off[slot];
+  const uint32_t eq = pcs_row16_hashes_to(cp, r, width, depth, j, w + sh.root_at[slot], l);
   if (l == 0) flags[job] = eq ? 0u : 1u;
 }
 
@@ -101,9 +110,55 @@ __device__ __forceinline__ void pcs_fold_step(E4 (&v)[8], E4& beta, const uint32
   beta = bb::e_mul_m(beta, beta);
 }
 
+// The pieces of a layer-0 wave and of a fold lane, shared by pcs_value_kernel and stark_value_kernel (stark_verify.inl).
+// sum_k gamma^(e0 + k) row[k] (g: the gamma table at e0, Montgomery; row: canonical words), lanes over the columns: this lane's share
+__device__ __forceinline__ E4 pcs_row_dot(const uint32_t* __restrict__ g, const uint32_t* __restrict__ row, uint32_t width, uint32_t lane) {
+  E4 acc = bb::e_zero();
+  for (uint32_t k = lane; k < width; k += 64) acc = bb::e_add(acc, bb::e_mul_fm(E4{{g[4 * k], g[4 * k + 1], g[4 * k + 2], g[4 * k + 3]}}, row[k]));
+  return acc;
+}
+// exact field sums over the wave (any order gives the same words): a butterfly, every lane ends with both totals
+__device__ __forceinline__ void pcs_wave_sum(E4& A0, E4& A1) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1)
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      A0.c[c] = bb::add(A0.c[c], (uint32_t)__shfl_xor((int)A0.c[c], d, 64));
+      A1.c[c] = bb::add(A1.c[c], (uint32_t)__shfl_xor((int)A1.c[c], d, 64));
+    }
+}
+// sum_i (a_i - A_i) / (z_i - x) over n_points <= 2 points, x = 31 w_M^pos (wM_m: Montgomery); A_i canonical-scaled sums as pcs_row_dot leaves them; z_m, a_m Montgomery
+__device__ __forceinline__ E4 pcs_point_sum(uint32_t n_points, const uint32_t (*z_m)[4], const uint32_t (*a_m)[4], const E4& A0, const E4& A1, uint32_t wM_m, uint32_t pos) {
+  const uint32_t x_m = bb::mont_mul(bb::to_mont(bb::GEN), pcs_pow_m(wM_m, pos));      // x = 31 w_M^pos
+  E4 want = bb::e_zero();
+#pragma unroll
+  for (uint32_t i = 0; i < 2; i++) {
+    if (i >= n_points) break;
+    E4 d{{z_m[i][0], z_m[i][1], z_m[i][2], z_m[i][3]}};
+    const E4 a{{a_m[i][0], a_m[i][1], a_m[i][2], a_m[i][3]}};
+    d.c[0] = bb::sub(d.c[0], x_m);
+    want = bb::e_add(want, bb::e_mul_m(bb::e_sub(a, bb::e_to_mont(i ? A1 : A0)), bb::e_inv_m(d)));
+  }
+  return want;
+}
+// A layer's own 2^k values (at vals, proof words) folded k times with beta (Montgomery words at beta_at), L: the layer's row of the layer table, idx: the carried index
+// below 2^depth.  Value t2 of the 2^k rests at position t2 << (3 - k) of eight: fold step f then pairs position p with p + (4 >> f), whatever k is (register indices only).
+__device__ __forceinline__ E4 pcs_fold_lane(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ L, const uint32_t* __restrict__ beta_at, uint32_t idx) {
+  const uint32_t k = L[PCS_L_K], depth = L[PCS_L_DEPTH], log_m = L[PCS_L_LOG_M];
+  const uint32_t sl = 3 - k;
+  E4 v[8];
+#pragma unroll
+  for (uint32_t p = 0; p < 8; p++) v[p] = (p & ((1u << sl) - 1u)) == 0 ? pcs_load_m(vals + 4 * (p >> sl)) : bb::e_zero();
+  E4 beta{{beta_at[0], beta_at[1], beta_at[2], beta_at[3]}};
+  if (k > 0) pcs_fold_step<0>(v, beta, L, log_m, idx, sl, depth);
+  if (k > 1) pcs_fold_step<1>(v, beta, L, log_m, idx, sl, depth);
+  if (k > 2) pcs_fold_step<2>(v, beta, L, log_m, idx, sl, depth);
+  return v[0];
+}
+
 // Workgroups [0, 2 num_queries): one WAVE per (query t, half s2) — the layer-0 value at row q + s2 M/2 from all the opened rows: lanes over the columns, gamma^e (Montgomery)
-// times the canonical word, exact field sums (any order gives the same words), a butterfly over the wave; then sum_i (a_i - A_i) / (z_i - x) on every lane alike and the
-// comparison with layer 0's value s2 (check 8): flags8[2 t + s2].
+// times the canonical word, exact field sums, a butterfly over the wave; then sum_i (a_i - A_i) / (z_i - x) on every lane alike and the comparison with layer 0's value s2
+// (check 8): flags8[2 t + s2].
 // The workgroups behind them: one LANE per (query t, layer j) — layer j's own 2^k values folded k times with beta_j and compared with the next layer's v[slot] (check 10 of
 // layer j + 1) or, for the last layer, with the final layer's value (check 11): flags_fold[t n_layers + j].  A fold starts from the proof's words, never from a carried value.
 __global__ __launch_bounds__(64) void pcs_value_kernel(const uint32_t* __restrict__ w, const uint32_t* __restrict__ qs, const uint32_t* __restrict__ gamma_m,
@@ -117,33 +172,11 @@ __global__ __launch_bounds__(64) void pcs_value_kernel(const uint32_t* __restric
     E4 A0 = bb::e_zero(), A1 = bb::e_zero();
     for (uint32_t si = 0; si < sh.n_sel; si++) {
       const uint32_t m = sh.sel_mat[si], width = sh.widths[m];
-      const uint32_t* row = qb + sh.rec_off[m] + s2 * (width + 4 * sh.log_M);
-      const uint32_t* g = gamma_m + 4 * (uint64_t)sh.sel_e0[si];
-      E4 acc = bb::e_zero();
-      for (uint32_t k = lane; k < width; k += 64) acc = bb::e_add(acc, bb::e_mul_fm(E4{{g[4 * k], g[4 * k + 1], g[4 * k + 2], g[4 * k + 3]}}, row[k]));
+      const E4 acc = pcs_row_dot(gamma_m + 4 * (uint64_t)sh.sel_e0[si], qb + sh.rec_off[m] + s2 * (width + 4 * sh.log_M), width, lane);
       if (sh.sel_point[si] == 0) A0 = bb::e_add(A0, acc); else A1 = bb::e_add(A1, acc);
     }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        A0.c[c] = bb::add(A0.c[c], (uint32_t)__shfl_xor((int)A0.c[c], d, 64));
-        A1.c[c] = bb::add(A1.c[c], (uint32_t)__shfl_xor((int)A1.c[c], d, 64));
-      }
-    E4 want;
-    if (sh.n_points == 0) want = bb::e_to_mont(A0);
-    else {
-      const uint32_t x_m = bb::mont_mul(bb::to_mont(bb::GEN), pcs_pow_m(sh.wM_m, pos));      // x = 31 w_M^pos
-      want = bb::e_zero();
-#pragma unroll
-      for (uint32_t i = 0; i < 2; i++) {
-        if (i >= sh.n_points) break;
-        E4 d{{sh.z_m[i][0], sh.z_m[i][1], sh.z_m[i][2], sh.z_m[i][3]}};
-        const E4 a{{sh.a_m[i][0], sh.a_m[i][1], sh.a_m[i][2], sh.a_m[i][3]}};
-        d.c[0] = bb::sub(d.c[0], x_m);
-        want = bb::e_add(want, bb::e_mul_m(bb::e_sub(a, bb::e_to_mont(i ? A1 : A0)), bb::e_inv_m(d)));
-      }
-    }
+    pcs_wave_sum(A0, A1);
+    const E4 want = sh.n_points == 0 ? bb::e_to_mont(A0) : pcs_point_sum(sh.n_points, sh.z_m, sh.a_m, A0, A1, sh.wM_m, pos);
     const E4 v = pcs_load_m(qb + sh.lay0_off + 4 * s2);
     if (lane == 0) flags8[blockIdx.x] = pcs_differ(v, want) ? 1u : 0u;
     return;
@@ -153,20 +186,10 @@ __global__ __launch_bounds__(64) void pcs_value_kernel(const uint32_t* __restric
   const uint32_t t = id / sh.n_layers, j = id - t * sh.n_layers;
   const uint32_t* qb = w + sh.at_queries + (uint64_t)t * sh.qsize;
   const uint32_t* L = ltab + PCS_LAYER_WORDS * j;
-  const uint32_t k = L[PCS_L_K], depth = L[PCS_L_DEPTH], log_m = L[PCS_L_LOG_M];
-  const uint32_t idx = qs[t] & ((1u << depth) - 1u);
-  // value t2 of the layer's 2^k rests at position t2 << (3 - k) of eight: fold step f then pairs position p with p + (4 >> f), whatever k is (register indices only)
-  const uint32_t sl = 3 - k;
-  const uint32_t* vals = qb + L[PCS_L_OFF];
-  E4 v[8];
-#pragma unroll
-  for (uint32_t p = 0; p < 8; p++) v[p] = (p & ((1u << sl) - 1u)) == 0 ? pcs_load_m(vals + 4 * (p >> sl)) : bb::e_zero();
-  E4 beta{{betas_m[4 * j], betas_m[4 * j + 1], betas_m[4 * j + 2], betas_m[4 * j + 3]}};
-  if (k > 0) pcs_fold_step<0>(v, beta, L, log_m, idx, sl, depth);
-  if (k > 1) pcs_fold_step<1>(v, beta, L, log_m, idx, sl, depth);
-  if (k > 2) pcs_fold_step<2>(v, beta, L, log_m, idx, sl, depth);
+  const uint32_t idx = qs[t] & ((1u << L[PCS_L_DEPTH]) - 1u);
+  const E4 got = pcs_fold_lane(qb + L[PCS_L_OFF], L, betas_m + 4 * j, idx);
   const uint32_t* nxt = j + 1 < sh.n_layers ? qb + L[PCS_LAYER_WORDS + PCS_L_OFF] + 4 * (idx >> L[PCS_LAYER_WORDS + PCS_L_DEPTH]) : w + sh.at_fin + 4 * (idx & sh.fin_mask);
-  flags_fold[id] = pcs_differ(pcs_load_m(nxt), v[0]) ? 1u : 0u;
+  flags_fold[id] = pcs_differ(pcs_load_m(nxt), got) ? 1u : 0u;
 }
 
 // The verdict of checks 7 .. 11 from the flags, with check 6 from the proof's own index words: for t rising — 6; 7 for matrix 0 row q, matrix 0 row q + M/2, matrix 1 ...;

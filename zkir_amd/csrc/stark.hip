@@ -1112,3 +1112,4 @@ int zkir_merkle_cap_launch(const zkir_stark_ctx* c, uint32_t* tree, uint64_t n_d
 #include "mixed_eval.inl"
 #include "pcs_verify.inl"
 #include "mixed_verify.inl"
+#include "stark_verify.inl"

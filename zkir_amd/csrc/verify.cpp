@@ -190,7 +190,9 @@ void initial_state(uint64_t entry, uint32_t st[NS]) {
 }
 
 int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out = nullptr,
-                const zkir::TapeStages* stages = nullptr);
+                const zkir::TapeStages* stages = nullptr, zkir::StarkQueries* defer = nullptr);
+int host_stark_run(void*, const zkir::StarkQueries* list, uint32_t n, int* codes);
+int host_stark_queries_of(const zkir::StarkQueries& Q, uint32_t first);
 inline int header_words_of(int mode) { return HEADER_WORDS + (mode >= 2 ? 4 : 0); }     // modes 2 / 3: + (oc, ic) of the first row, of the last row
 // (mode 3) the bytes of cell `addr` (a multiple of 8) in the VM's INITIAL memory: the code words at 0x1000, the data section right behind them (vm.rs:153-170), zero elsewhere
 uint64_t image_cell(const uint8_t* blob, size_t n, uint64_t addr) {
@@ -236,6 +238,8 @@ bool last_row_writes(const uint32_t* w, const uint32_t* last_state, int halt_kin
 // side, [3] the wide tape's, [4] the rest.  Kept per thread for zkir_verify_last_stages; printed on stderr when ZKIR_VERIFY_TIMES is set (nothing by default).
 struct LastStages { double ms[5] = {0, 0, 0, 0, 0}; uint32_t device_stages = 0; bool valid = false; };
 thread_local LastStages last_stages;
+struct LastQueries { uint64_t hash_jobs = 0, value_jobs = 0, uploaded_words = 0; uint32_t launches = 0; };      // zkir_verify_queries_last: the device query stage of the thread's last verification
+thread_local LastQueries last_queries;
 struct StageClock {
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   double ms[5] = {0, 0, 0, 0, 0};
@@ -244,6 +248,7 @@ struct StageClock {
     lap(4);
     for (int k = 0; k < 5; k++) last_stages.ms[k] = ms[k];
     last_stages.device_stages = 0; last_stages.valid = true;
+    last_queries = LastQueries{};                                            // (every host verification: the *_on_device entries note theirs once the stage has run)
     if (getenv("ZKIR_VERIFY_TIMES"))
       fprintf(stderr, "zkir_verify: parse %.3f ms | section digests %.3f | hash table side %.3f | wide table side %.3f | rest %.3f\n", ms[0], ms[1], ms[2], ms[3], ms[4]);
   }
@@ -363,6 +368,12 @@ int verify_with_stages(const uint32_t* proof, uint64_t proof_words, const zkir_p
   return verify_impl(proof, proof_words, expect, true, nullptr, nullptr, &stages);
 }
 void verify_note_device_stages(uint32_t n) { last_stages.device_stages = n; }
+void verify_note_queries(uint64_t hash_jobs, uint64_t value_jobs, uint32_t launches, uint64_t uploaded_words) { last_queries = LastQueries{hash_jobs, value_jobs, uploaded_words, launches}; }
+StarkQueryStage host_stark_query_stage() { return StarkQueryStage{nullptr, host_stark_run}; }
+int stark_host_queries_from(const StarkQueries& q, uint32_t first) { return first >= q.num_queries ? 0 : host_stark_queries_of(q, first); }
+int stark_verify_collect(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, bool whole_run, const TapeStages* stages, StarkQueries* out) {
+  return verify_impl(proof, proof_words, expect, whole_run, nullptr, nullptr, stages, out);
+}
 }  // namespace zkir
 
 extern "C" {
@@ -446,6 +457,13 @@ int zkir_merkle_verify_host(const uint32_t root[4], uint32_t width, uint64_t n_l
     if (v) { failed++; if (first == 0xFFFFFFFFu) first = (uint32_t)i; }
   }
   if (summary) { summary[0] = failed; summary[1] = first; }
+  return ZKIR_OK;
+}
+int zkir_verify_queries_last(uint64_t* hash_jobs, uint64_t* value_jobs, uint32_t* launches, uint64_t* uploaded_words) {
+  if (hash_jobs) *hash_jobs = last_queries.hash_jobs;
+  if (value_jobs) *value_jobs = last_queries.value_jobs;
+  if (launches) *launches = last_queries.launches;
+  if (uploaded_words) *uploaded_words = last_queries.uploaded_words;
   return ZKIR_OK;
 }
 int zkir_verify_last_stages(double ms[5], uint32_t* device_stages) {
@@ -566,17 +584,33 @@ int zkir_verify_segment(const uint32_t* w, uint64_t len, const zkir_public_input
 uint32_t zkir_proof_state_words(void) { return NS; }
 
 int zkir_verify_chain(const uint32_t* const* proofs, const uint64_t* lens, uint32_t n, const zkir_public_inputs* expect) {
+  if (proofs && lens && n == 1 && proofs[0] && lens[0] > 9 && proofs[0][9] >= 3) return verify_impl(proofs[0], lens[0], expect, true, nullptr, nullptr);   // a mode-3 proof is a whole run by itself (never a segment): a "chain" of one
+  return zkir::verify_chain_with_stage(proofs, lens, n, expect, zkir::host_stark_query_stage());
+}
+}  // extern "C"
+
+// The segments' host parts run first, segment after segment up to the first one that fails there; then ONE run of the stage over the collected segments' queries; then
+// the verdict in the order the sequential verifier returns it: per segment its host code, its query code, check 30, check 43 — then the linking checks.
+int zkir::verify_chain_with_stage(const uint32_t* const* proofs, const uint64_t* lens, uint32_t n, const zkir_public_inputs* expect, const zkir::StarkQueryStage& stage) {
   if (!proofs || !lens || n < 1) return 40;
-  if (n == 1 && proofs[0] && lens[0] > 9 && proofs[0][9] >= 3) return verify_impl(proofs[0], lens[0], expect, true, nullptr, nullptr);   // a mode-3 proof is a whole run by itself (never a segment): a "chain" of one
   std::vector<uint32_t> st((size_t)n * 2 * NS), cnt((size_t)n * 4, 0);
   uint64_t total = 1;
-  for (uint32_t i = 0; i < n; i++) {
-    const int rc = verify_impl(proofs[i], lens[i], nullptr, false, &st[(size_t)i * 2 * NS], &cnt[(size_t)i * 4]);
+  std::vector<zkir::StarkQueries> Q(n);
+  uint32_t n_ok = 0; int host_rc = 0;
+  for (; n_ok < n; n_ok++) {
+    host_rc = verify_impl(proofs[n_ok], lens[n_ok], nullptr, false, &st[(size_t)n_ok * 2 * NS], &cnt[(size_t)n_ok * 4], nullptr, &Q[n_ok]);
+    if (host_rc) break;
+  }
+  std::vector<int> codes(n_ok ? n_ok : 1, 0);
+  if (n_ok) { const int src = stage.run(stage.self, Q.data(), n_ok, codes.data()); if (src) return src; }
+  for (uint32_t i = 0; i < n_ok; i++) {
+    const int rc = codes[i] ? codes[i] : zkir::stark_length_check(Q[i]);
     if (rc) return 1000 * (int)(i + 1) + rc;
     const uint32_t* w = proofs[i];
     total += ((uint64_t)w[7] | ((uint64_t)w[8] << 30)) - 1;
     if (memcmp(w + 9, proofs[0] + 9, 12 * 4)) return 43;                   // mode, entry point, program digest, io digest
   }
+  if (n_ok < n) return 1000 * (int)(n_ok + 1) + host_rc;
   const uint32_t* w0 = proofs[0];
   const uint64_t entry = (uint64_t)w0[10] | ((uint64_t)w0[11] << 20) | ((uint64_t)w0[12] << 40);
   uint32_t init[NS];
@@ -612,6 +646,7 @@ int zkir_verify_chain(const uint32_t* const* proofs, const uint64_t* lens, uint3
   return 0;
 }
 
+extern "C" {
 // ---- what the run CLAIMS (round 4): its I/O tapes and how it ended -------------------------------------------------------------------
 // The io digest a proof carries is a hash of (inputs, outputs, halt kind, exit code, cycles) that the AIR does not look inside.  These two calls take
 // the claim in the clear and check, on top of zkir_verify / zkir_verify_chain:
@@ -698,7 +733,8 @@ int zkir_verify_chain_io(const uint32_t* const* proofs, const uint64_t* lens, ui
 
 namespace {
 
-int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out, const zkir::TapeStages* stages) {
+int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out, const zkir::TapeStages* stages,
+                zkir::StarkQueries* defer) {
   StageClock clk;                                                          // (diagnostics: the host wall time of the call's phases, kept for zkir_verify_last_stages)
   zkir::HostTapes host_tapes;
   const zkir::TapeStages host_stages = zkir::host_tape_stages(&host_tapes);
@@ -996,7 +1032,9 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   }
   // ---- 2. final codeword has degree < 4: the four upper coefficients of its interpolant over an order-8 coset vanish ----
   if (!fri_final_degree_ok(fin, 1)) return 11;
-  // ---- 3. queries ----
+  // ---- 3. queries: the stage behind zkir::StarkQueryStage (verify_stages.h) gets what has been CHECKED and what has been DRAWN ----
+  zkir::StarkQueries local_q;
+  zkir::StarkQueries& Q = defer ? *defer : local_q;
   std::vector<E4> gp(2 * WT + 4);
   gp[0] = bb::e_one_m();
   for (size_t k = 1; k < gp.size(); k++) gp[k] = bb::e_mul_m(gp[k - 1], gamma);
@@ -1004,15 +1042,45 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   for (int k = 0; k < WT; k++) { a0 = bb::e_add(a0, bb::e_mul_m(gp[k], t_z[k])); b0 = bb::e_add(b0, bb::e_mul_m(gp[WT + k], t_zw[k])); }
   for (int i = 0; i < 4; i++) a0 = bb::e_add(a0, bb::e_mul_m(gp[2 * WT + i], q_z[i]));
   const E4 zeta_w = bb::e_mul_fm(zeta, wn_m);
-  const uint32_t w2n = bb::root_of_unity(log_n + 1);
   const int depth0 = log_n + 1;
-  // The queries are independent of each other and all the same size: their indices are drawn first (the transcript is sequential), then they are checked on a few host
-  // threads (round 5: ~10,000 Poseidon2 permutations — the Merkle paths — were 11 of the verifier's 12 ms on one core).  The verdict is the first failing query's, in query
-  // order: exactly what the sequential loop returned.
-  std::vector<uint32_t> qs(NUM_QUERIES);
-  for (auto& q : qs) q = ch.sample_bits(log_n);
-  const size_t qsize = 1 + 2 * ((size_t)WM + 4 * depth0) + 2 * ((size_t)WA + 4 * depth0) + 2 * ((size_t)4 + 4 * depth0) + (size_t)zkir::fri_query_words((uint32_t)depth0, ks);
-  const size_t p_queries = p;
+  if (n_layers > (int)zkir::PCS_MAX_LAYERS) return 5;                       // (no log_n <= 26 has that many)
+  Q.w = w; Q.len = len;
+  Q.log_n = (uint32_t)log_n; Q.mode = (uint32_t)mode; Q.WM = (uint32_t)WM; Q.WA = (uint32_t)WA; Q.num_queries = (uint32_t)NUM_QUERIES; Q.n_layers = (uint32_t)n_layers;
+  for (int j = 0; j < n_layers; j++) Q.ks[j] = (uint32_t)ks[j];
+  Q.at_roots = (uint64_t)(troot - w); Q.at_lroots = (uint64_t)(lroots - w); Q.at_fin = at_fin; Q.at_queries = p;
+  Q.qsize = 1 + 2 * ((size_t)WM + 4 * depth0) + 2 * ((size_t)WA + 4 * depth0) + 2 * ((size_t)4 + 4 * depth0) + (size_t)zkir::fri_query_words((uint32_t)depth0, ks);
+  // the indices are drawn first (the transcript is sequential); the queries are independent of each other and all the same size
+  Q.qs.resize(NUM_QUERIES);
+  for (auto& q : Q.qs) q = ch.sample_bits(log_n);
+  static_assert(sizeof(E4) == 16, "a vector of E4 is copied as 4 words an element");
+  Q.betas_m.resize(4 * (size_t)n_layers); if (n_layers) memcpy(Q.betas_m.data(), betas[0].c, 16 * (size_t)n_layers);
+  Q.gamma_m.resize(4 * gp.size()); memcpy(Q.gamma_m.data(), gp[0].c, 16 * gp.size());
+  memcpy(Q.zeta_m, zeta.c, 16); memcpy(Q.zeta_w_m, zeta_w.c, 16); memcpy(Q.a0_m, a0.c, 16); memcpy(Q.b0_m, b0.c, 16);
+  if (defer) return 0;                                                     // (the caller runs the stage over all it has collected, then check 30)
+  int code = 0;
+  const zkir::StarkQueryStage stage = zkir::host_stark_query_stage();
+  const int src = stage.run(stage.self, &Q, 1, &code);
+  if (src) return src;
+  if (code) return code;
+  return zkir::stark_length_check(Q);
+}
+
+// The host form of the STARK query stage (verify_stages.h): proof after proof, each proof's queries on a few host threads (round 5: ~10,000 Poseidon2 permutations — the
+// Merkle paths — were 11 of the verifier's 12 ms on one core).  A proof's verdict is its first failing query's, in query order: exactly what a sequential loop returns.
+int host_stark_queries_of(const zkir::StarkQueries& Q, uint32_t first) {
+  const uint32_t* w = Q.w; const uint64_t len = Q.len;
+  const int log_n = (int)Q.log_n, WM = (int)Q.WM, WA = (int)Q.WA, WT = WM + WA, n_layers = (int)Q.n_layers, NUM_QUERIES = (int)Q.num_queries, depth0 = log_n + 1;
+  const size_t N = (size_t)1 << log_n, qsize = (size_t)Q.qsize, p_queries = (size_t)Q.at_queries, n_fin = zkir::fri_final_size(1);
+  const uint32_t *troot = w + Q.at_roots, *aroot = troot + 4, *qroot = troot + 8, *lroots = w + Q.at_lroots;
+  auto e4_at = [](const uint32_t* c) { E4 e; memcpy(e.c, c, 16); return e; };
+  std::vector<E4> gp(2 * (size_t)WT + 4), betas(n_layers), fin(n_fin);
+  for (size_t k = 0; k < gp.size(); k++) gp[k] = e4_at(Q.gamma_m.data() + 4 * k);
+  for (int j = 0; j < n_layers; j++) betas[j] = e4_at(Q.betas_m.data() + 4 * j);
+  for (size_t i = 0; i < n_fin; i++) fin[i] = bb::e_to_mont(e4_at(w + Q.at_fin + 4 * i));
+  const E4 zeta = e4_at(Q.zeta_m), zeta_w = e4_at(Q.zeta_w_m), a0 = e4_at(Q.a0_m), b0 = e4_at(Q.b0_m);
+  const uint32_t w2n = bb::root_of_unity(log_n + 1);
+  const uint32_t* ks = Q.ks;
+  const std::vector<uint32_t>& qs = Q.qs;
   auto check_query = [&](int t) -> int {
     size_t p = p_queries + (size_t)t * qsize;
     auto need = [&](size_t k) { return p + k <= len; };
@@ -1060,7 +1128,7 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     for (int j = 0; j < n_layers; j++) {
       const size_t layer_words = 4 * ((size_t)1 << ks[j]) + 4 * (size_t)(walk.log_m - ks[j]);
       if (!need(layer_words)) return 4;
-      const FriLayerSeen seen = fri_walk_step(walk, w + p, ks[j], lroots + 4 * j, betas[j]);
+      const FriLayerSeen seen = fri_walk_step(walk, w + p, (int)ks[j], lroots + 4 * j, betas[j]);
       p += layer_words;
       if (!seen.leaf_ok) return 23;
       if (j == 0) { if (!e_eq(seen.v0, deep[0]) || !e_eq(seen.v1, deep[1])) return 24; }
@@ -1074,9 +1142,9 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     unsigned n_thr = std::thread::hardware_concurrency() / 2;               // (half the logical cores, at most eight: SMT siblings and a busy host do not help a 10 ms job)
     n_thr = n_thr < 1 ? 1 : n_thr > 8 ? 8 : n_thr;
     if (const char* e = getenv("ZKIR_VERIFY_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 64) n_thr = (unsigned)v; }
-    std::atomic<int> next{0};
+    std::atomic<int> next{(int)first};
     auto work = [&]() { for (int t; (t = next.fetch_add(1)) < NUM_QUERIES;) codes[t] = check_query(t); };
-    if (log_n < 14 && !getenv("ZKIR_VERIFY_THREADS")) n_thr = 1;            // (a small proof is checked faster than threads start)
+    if ((log_n < 14 && !getenv("ZKIR_VERIFY_THREADS")) || (first && NUM_QUERIES - (int)first < 8)) n_thr = 1;            // (a small proof is checked faster than threads start)
     std::vector<std::thread> th;
     for (unsigned k = 1; k < n_thr; k++) {
       try { th.emplace_back(work); } catch (...) { break; }                 // (a host that refuses a thread — pids limit, sandbox — must not take the verdict down:
@@ -1084,9 +1152,11 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     work();
     for (auto& x : th) x.join();
   }
-  for (int t = 0; t < NUM_QUERIES; t++) if (codes[t]) return codes[t];
-  p = p_queries + (size_t)NUM_QUERIES * qsize;
-  if (p != len) return 30;
+  for (int t = (int)first; t < NUM_QUERIES; t++) if (codes[t]) return codes[t];
+  return 0;
+}
+int host_stark_run(void*, const zkir::StarkQueries* list, uint32_t n, int* codes) {
+  for (uint32_t i = 0; i < n; i++) codes[i] = host_stark_queries_of(list[i], 0);
   return 0;
 }
 

@@ -177,6 +177,28 @@ int dt_digests(void* p, int which, const uint32_t* sw, size_t sl, uint32_t* dg) 
 int dt_hash_side(void* p, const uint32_t* lk_m, uint32_t T[4]) { return guarded([&] { return static_cast<DeviceTapes*>(p)->hash_side(lk_m, T); }); }
 int dt_wide_side(void* p, const uint32_t* lk_m, uint32_t T[4]) { return guarded([&] { return static_cast<DeviceTapes*>(p)->wide_side(lk_m, T); }); }
 
+// zkir_verify_device's body.  queries == nullptr: the whole verification (zkir_verify's verdict).  Else the verification up to check 11 with *queries filled where it
+// returns 0 (zkir::stark_verify_collect): the query stage and check 30 are the caller's (stark_verify.inl).  *stages_run: the tape stages that ran on the device.
+int verify_device_part(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, void* stream, zkir::StarkQueries* queries, uint32_t* stages_run) {
+  *stages_run = 0;
+  // modes 0-3 have no tapes, and a proof too short to name its mode has no verdict that depends on them: zkir_verify itself, no HIP call
+  if (!proof || proof_words < 10 || proof[9] != 4) return guarded([&] { return zkir::stark_verify_collect(proof, proof_words, expect, true, nullptr, queries); });
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { zkir::set_last_error({ZKIR_ERR_DEVICE, "zkir_verify_device: no current HIP device"}); return -ZKIR_ERR_DEVICE; }
+  VerifyDevice* Vp = nullptr;
+  const int src = guarded([&] { Vp = &verify_device(dev); return 0; });
+  if (src) return src;
+  VerifyDevice& V = *Vp;
+  std::lock_guard<std::mutex> lock(V.mu);
+  V.pin.reset();
+  DeviceTapes dt(V, (hipStream_t)stream);
+  const zkir::TapeStages st{&dt, dt_hash_check, dt_wide_check, dt_digests, dt_hash_side, dt_wide_side};
+  const int rc = guarded([&] { return zkir::stark_verify_collect(proof, proof_words, expect, true, &st, queries); });
+  if (dt.stages_run) (void)hipStreamSynchronize((hipStream_t)stream);      // (a verdict reached before a stage's own synchronisation: nothing of this call stays in flight)
+  *stages_run = dt.stages_run;
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -245,21 +267,9 @@ int zkir_hash_tape_new_bytes_launch(const uint32_t* hash_words, uint64_t n_hash_
 }
 
 int zkir_verify_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, void* stream) {
-  // modes 0-3 have no tapes, and a proof too short to name its mode has no verdict that depends on them: zkir_verify itself, no HIP call
-  if (!proof || proof_words < 10 || proof[9] != 4) { const int rc = zkir_verify(proof, proof_words, expect); zkir::verify_note_device_stages(0); return rc; }
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { zkir::set_last_error({ZKIR_ERR_DEVICE, "zkir_verify_device: no current HIP device"}); return -ZKIR_ERR_DEVICE; }
-  VerifyDevice* Vp = nullptr;
-  const int src = guarded([&] { Vp = &verify_device(dev); return 0; });
-  if (src) return src;
-  VerifyDevice& V = *Vp;
-  std::lock_guard<std::mutex> lock(V.mu);
-  V.pin.reset();
-  DeviceTapes dt(V, (hipStream_t)stream);
-  const zkir::TapeStages st{&dt, dt_hash_check, dt_wide_check, dt_digests, dt_hash_side, dt_wide_side};
-  const int rc = guarded([&] { return zkir::verify_with_stages(proof, proof_words, expect, st); });
-  if (dt.stages_run) (void)hipStreamSynchronize((hipStream_t)stream);      // (a verdict reached before a stage's own synchronisation: nothing of this call stays in flight)
-  zkir::verify_note_device_stages(dt.stages_run);
+  uint32_t stages_run = 0;
+  const int rc = verify_device_part(proof, proof_words, expect, stream, nullptr, &stages_run);
+  zkir::verify_note_device_stages(stages_run);
   return rc;
 }
 

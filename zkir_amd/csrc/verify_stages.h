@@ -79,4 +79,33 @@ struct MixedQueryStage { void* self; int (*run)(void* self, const MixedQueries& 
 MixedQueryStage host_mixed_query_stage();                        // the loop of verify.cpp
 int mixed_eval_verify_with_stage(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const MixedQueryStage& stage);
 
+// ---- the QUERY STAGE of the STARK verifier (zkir_verify and its siblings; zkir_verify_on_device, zkir_verify_many_on_device, zkir_verify_chain_on_device) ----
+// Checks 20 .. 27 (and 4: a query cut by the proof's end) of all the queries of a ZKIR-STARK proof, handed over after check 11: the header, the word range (every word from
+// word 2 on is below p) and the whole transcript are verify.cpp's host code.  A STARK query is the commitment layer's at b = 1 — three matrices (main WM, aux WA, quotient 4)
+// under the three roots at at_roots, opened at q and q + N, then the FRI layers — and its layer-0 value (A - a0) / (x - zeta) + (B - b0) / (x - zeta w) is PcsQueries' rule
+// with z = (zeta, zeta w), a = (a0, b0) and the selections (0, main, 0), (0, aux, WM), (0, quot, 2 WT), (1, main, WT), (1, aux, WT + WM), WT = WM + WA.
+// The proof's LENGTH is not checked before the queries: query t lies at at_queries + t qsize and may run past len (codes 20 / 4).  Check 30 stays with the caller.
+// The stage takes a LIST (a chain's segments, a service's proofs): codes[i] = 0 or proof i's first failing check, lowest query first, in the order 20, 4, 21 (row q, then
+// q + N), 27, 22, per layer j 23 then 24 (j = 0) / 25 (j > 0), 26.  run returns 0, or a negative value (no verdict for any of them).
+// A StarkQueries OWNS what it points to except the proof: a caller collects several before it runs the stage.
+struct StarkQueries {
+  const uint32_t* w = nullptr; uint64_t len = 0;                 // the proof (borrowed)
+  uint32_t log_n = 0, mode = 0, WM = 0, WA = 0, num_queries = 0, n_layers = 0;
+  uint32_t ks[PCS_MAX_LAYERS] = {0};
+  uint64_t at_roots = 0, at_lroots = 0, at_fin = 0, at_queries = 0, qsize = 0;      // word offsets: the trace, aux and quotient roots (12 words), the layer roots, the final layer (8 values), query 0
+  std::vector<uint32_t> qs;                                      // the transcript's samples, each below N
+  std::vector<uint32_t> betas_m, gamma_m;                        // n_layers and 2 WT + 4 Montgomery E4
+  uint32_t zeta_m[4] = {0}, zeta_w_m[4] = {0}, a0_m[4] = {0}, b0_m[4] = {0};
+};
+struct StarkQueryStage { void* self; int (*run)(void* self, const StarkQueries* list, uint32_t n, int* codes); };
+StarkQueryStage host_stark_query_stage();                        // the loop of verify.cpp: host threads, ZKIR_VERIFY_THREADS
+// verify_impl up to check 11 (whole runs: check 7 included; a segment: whole_run = false, its boundary states and counters out): 0 = *out is filled and the queries are the
+// caller's (then check 30: stark_length_check), else the failed check.  stages: nullable (the host tape stages).
+int stark_verify_collect(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, bool whole_run, const TapeStages* stages, StarkQueries* out);
+int stark_host_queries_from(const StarkQueries& q, uint32_t first);      // the host loop over queries first .. num_queries - 1 (the device stage: the queries a short proof cuts)
+void verify_note_queries(uint64_t hash_jobs, uint64_t value_jobs, uint32_t launches, uint64_t uploaded_words);      // (the *_on_device entries) zkir_verify_queries_last's record
+inline int stark_length_check(const StarkQueries& q) { return q.at_queries + (uint64_t)q.num_queries * q.qsize != q.len ? 30 : 0; }
+// zkir_verify_chain with the segments' queries in ONE run of `stage` (a chain of one mode >= 3 proof is the caller's: it is a whole run)
+int verify_chain_with_stage(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, const StarkQueryStage& stage);
+
 }  // namespace zkir

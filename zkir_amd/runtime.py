@@ -406,6 +406,13 @@ def lib() -> C.CDLL:
         L.zkir_hash_tape_new_bytes_host.restype = C.c_int; L.zkir_hash_tape_new_bytes_host.argtypes = [V, U64, V]
         L.zkir_verify_device.restype = C.c_int; L.zkir_verify_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
         L.zkir_verify_last_stages.restype = C.c_int; L.zkir_verify_last_stages.argtypes = [V, C.POINTER(C.c_uint32)]
+    if hasattr(L, "zkir_verify_on_device"):                   # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_verify_on_device.restype = C.c_int; L.zkir_verify_on_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
+        L.zkir_verify_many_on_device.restype = C.c_int; L.zkir_verify_many_on_device.argtypes = [V, V, V, C.c_uint32, V, V]
+        L.zkir_verify_chain_on_device.restype = C.c_int; L.zkir_verify_chain_on_device.argtypes = [V, V, C.c_uint32, C.POINTER(PublicInputsC), V]
+        L.zkir_verify_queries_last.restype = C.c_int; L.zkir_verify_queries_last.argtypes = [C.POINTER(U64), C.POINTER(U64), C.POINTER(C.c_uint32), C.POINTER(U64)]
+        L.zkir_verify_queries_last_stage_ms.restype = C.c_int; L.zkir_verify_queries_last_stage_ms.argtypes = [V]
+        L.zkir_stark_query_stage_probe.restype = C.c_int; L.zkir_stark_query_stage_probe.argtypes = [V, U64, C.c_uint32, C.c_uint32, C.c_int, V]
     if hasattr(L, "zkir_lowdeg_verify_device"):               # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
         L.zkir_lowdeg_verify_device.restype = C.c_int; L.zkir_lowdeg_verify_device.argtypes = [V, U64, V, V]
         L.zkir_eval_verify_device.restype = C.c_int; L.zkir_eval_verify_device.argtypes = [V, U64, V, V, V, V]
@@ -612,12 +619,54 @@ def verify_segment(proof: np.ndarray, expect: Optional[PublicInputsC] = None):
     return rc, first, last
 
 
-def verify_chain(proofs, expect: Optional[PublicInputsC] = None) -> int:
-    """zkir_verify_chain: the segments of one run, in order; expect.n_real = the run's total executed rows."""
+def verify_chain(proofs, expect: Optional[PublicInputsC] = None, device: bool = False, stream=None) -> int:
+    """zkir_verify_chain: the segments of one run, in order; expect.n_real = the run's total executed rows.  device=True: zkir_verify_chain_on_device — the same verdict, all
+    the segments' queries as one batch on the GPU (two launches on `stream`); a negative result is a device failure, not a verdict (raised)."""
     ps = [np.ascontiguousarray(p, dtype=np.uint32) for p in proofs]
     ptrs = (C.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
     lens = (C.c_uint64 * len(ps))(*[len(p) for p in ps])
+    if device:
+        return _pcs_verdict(lib().zkir_verify_chain_on_device(ptrs, lens, len(ps), C.byref(expect) if expect is not None else None, stream))
     return lib().zkir_verify_chain(ptrs, lens, len(ps), C.byref(expect) if expect is not None else None)
+
+
+def verify_many(proofs, expects=None, stream=None):
+    """zkir_verify_many_on_device: n independent proofs (1 .. 1024) -> [zkir_verify(proofs[i], expects[i]) for i] with every proof's queries in ONE batch on the GPU.
+    `expects`: None, or one entry (a PublicInputsC or None) per proof.  An empty list, more than 1024 proofs or a device failure raise."""
+    ps = [np.ascontiguousarray(p, dtype=np.uint32) for p in proofs]
+    n = len(ps)
+    if expects is not None and len(expects) != n:
+        raise ValueError(f"{n} proofs, {len(expects)} expectations")
+    ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data if len(p) else None for p in ps])
+    lens = (C.c_uint64 * max(n, 1))(*[len(p) for p in ps])
+    exps = (C.c_void_p * max(n, 1))(*[C.addressof(e) if e is not None else None for e in expects]) if expects is not None else None
+    verdicts = (C.c_int32 * max(n, 1))()
+    rc = lib().zkir_verify_many_on_device(ptrs, lens, exps, n, verdicts, stream)
+    if rc != 0:
+        _raise(abs(rc))
+    return [int(verdicts[i]) for i in range(n)]
+
+
+def verify_queries_last() -> dict:
+    """zkir_verify_queries_last: the device query stage of this thread's last verification (all zero after a host entry and after verify(device=True) without queries)."""
+    h, v, l, u = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+    lib().zkir_verify_queries_last(C.byref(h), C.byref(v), C.byref(l), C.byref(u))
+    return {"hash_jobs": int(h.value), "value_jobs": int(v.value), "launches": int(l.value), "uploaded_words": int(u.value)}
+
+
+def verify_queries_last_stage_ms():
+    """zkir_verify_queries_last_stage_ms: (upload, kernels, download) host clocks in ms of this thread's last device query stage, measured only with
+    ZKIR_VERIFY_QUERIES_TIMES set."""
+    ms = (C.c_double * 3)()
+    lib().zkir_verify_queries_last_stage_ms(ms)
+    return float(ms[0]), float(ms[1]), float(ms[2])
+
+
+def stark_query_stage_probe(proof, what: int = 0, index: int = 0, device: bool = False, stream=None) -> int:
+    """zkir_stark_query_stage_probe (test hook): the verifier's host part, then its query stage on perturbed draws — what: 0 nothing, 1 a0 + 1, 2 b0 + 1, 3 zeta + 1,
+    4 betas[index] + 1, 5 qs[index] ^= 1 — on the host (device=False: no HIP call) or on the GPU.  Returns the verdict; a bad `what` / `index` or a device failure raise."""
+    proof = np.ascontiguousarray(proof, dtype=np.uint32)
+    return _pcs_verdict(lib().zkir_stark_query_stage_probe(proof.ctypes.data if len(proof) else None, len(proof), int(what), int(index), 1 if device else 0, stream))
 
 
 def _u64s(a):
@@ -648,13 +697,17 @@ def verify_chain_io(proofs, expect: Optional[PublicInputsC], inputs, outputs, ha
     return L.zkir_verify_chain_io(ptrs, lens, len(ps), C.byref(expect) if expect is not None else None, i.ctypes.data, len(i), o.ctypes.data, len(o), int(kind), int(code or 0))
 
 
-def verify(proof: np.ndarray, expect: Optional[PublicInputsC] = None, device: bool = False, stream=None) -> int:
+def verify(proof: np.ndarray, expect: Optional[PublicInputsC] = None, device: bool = False, stream=None, queries: bool = False) -> int:
     """zkir_verify (host only): 0 = accepted, otherwise the number of the failed check.  device=True: zkir_verify_device — the same verdict, a mode-4 proof's tape stages
-    (record checks, chunk digests, the table side with every hash call's digest) on the GPU; a negative result is a device failure, not a verdict (raised)."""
+    (record checks, chunk digests, the table side with every hash call's digest) on the GPU; device=True, queries=True: zkir_verify_on_device — the same verdict, any mode,
+    the query stage (Merkle paths, layer-0 values, folds) on the GPU as well; a negative result is a device failure, not a verdict (raised)."""
     proof = np.ascontiguousarray(proof, dtype=np.uint32)
     if not device:
+        if queries:
+            raise ValueError("queries=True needs device=True")
         return lib().zkir_verify(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None)
-    rc = lib().zkir_verify_device(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None, stream)
+    entry = lib().zkir_verify_on_device if queries else lib().zkir_verify_device
+    rc = entry(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None, stream)
     if rc < 0:
         _raise(-rc)
     return rc
