@@ -648,6 +648,33 @@ int zkir_verify_on_device(const uint32_t* proof, uint64_t proof_words, const zki
 int zkir_verify_many_on_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, void* hip_stream);
 int zkir_verify_chain_on_device(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, void* hip_stream);
 int zkir_verify_queries_last(uint64_t* hash_jobs, uint64_t* value_jobs, uint32_t* launches, uint64_t* uploaded_words);
+
+/* A ZKIR-STARK PROOF AT THE CONTEXT'S OWN RATE ('ZKSR', version 1; zkir_amd/csrc/stark_prove.inl, eval_open.inl, verify.cpp; DESIGN.md "Proofs at blow-up 4 and 8").
+ * zkir_prove is blow-up 2 and keeps refusing any other context.  zkir_prove_rate proves a WHOLE run in mode 0, 1 or 2 on a context of log_blowup 1, 2 or 3:
+ *   the STARK part: exactly the sections of a zkir_prove proof from the header through the quotient root — header, boundary states (mode 2: + counters), program, (mode 2)
+ *     I/O section, multiplicities, trace | aux | quotient root — under the header words 0 = 0x52534B5A ('ZKSR'), 1 = 1, 4 = num_queries, 5 = log_blowup, 6 = pow_bits (the
+ *     others as in zkir_prove).  The whole header from word 2 on is observed first, so the rate and the parameters are bound; the transcript is zkir_verify's up to zeta.
+ *   the embedded evaluation proof: a 'ZKBE' proof word for word as zkir_batch_eval_prove writes it for the three committed matrices (main: zkir_main_trace_width_for(mode)
+ *     columns, aux, the quotient's 4) with masks {3, 3, 1} at the points [zeta, w_N zeta] and the entry's num_queries and pow_bits.  It has its own transcript (roots,
+ *     points, evaluations ..), which zeta carries the outer one into; zkir_batch_eval_verify accepts these words on their own.
+ * num_queries 1 .. 128, pow_bits 0 .. 24 (zkir_batch_eval_prove's ranges); pub->fri_params is NOT consulted.  The usual choices are 50 / 25 / 17 queries at log_blowup
+ * 1 / 2 / 3 with 12 bits.  ZKIR_ERR_ARGUMENT with a message, before anything is launched, for: a null argument, mode 3 or 4, a segment (writes_before / reads_before),
+ * num_queries or pow_bits out of range, a context whose log_n is not zkir_padded_log_n(n_real), and zkir_prove's refusals of the public inputs.  stage_ms: NULL or ELEVEN
+ * floats — zkir_prove's [0..4] (main trace, LDE, trace Merkle, lookup argument, quotient + its Merkle tree), then the evaluation proof's six.  The proof is freed with
+ * zkir_proof_free.  The matrices of such a proof rest in canonical form (the commitment layer's), the quotient is evaluated by a kernel of its own over the N << log_blowup
+ * coset (quotient_rate_kernel).
+ * zkir_verify_rate: host only.  zkir_verify's checks and codes, in its order, through the program, the I/O section, the table side and the challenges (1 malformed header,
+ * magic, version; 2 a header range — also: a mode above 2, fewer queries than min_queries or fewer bits than min_pow_bits; 3 a word >= p; 4 truncated; 6 not `expect`'s
+ * run (fri_params not compared); 7 initial state; 8 program; 50 - 53 the I/O claim), then: 4 too short for the embedded header and evaluations; 5 the embedded proof is
+ * not a 'ZKBE' proof of the outer log_n, log_blowup, three widths, masks {3, 3, 1}, two points, num_queries and pow_bits; 10 sum_c alpha^c C_c(zeta) != Q(zeta) Z_H(zeta)
+ * on the embedded proof's evaluations; 100 + c where zkir_batch_eval_verify, told the outer roots and the points [zeta, w_N zeta], answers c (so 101 a wrong length,
+ * 102 other roots, 113 other points, 105 grinding, 107 a record's path, 108 layer-0 values ..).
+ * zkir_verify_rate_device: the same function with the embedded proof's query stage on the current HIP device (zkir_batch_eval_verify_device's); the same verdict for
+ * every input; a NEGATIVE result is a device failure, not a verdict. */
+int zkir_prove_rate(zkir_stark_ctx* ctx, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
+                    uint64_t* proof_words, float* stage_ms, void* hip_stream);
+int zkir_verify_rate(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits);
+int zkir_verify_rate_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, void* hip_stream);
 /* diagnostics of the calling thread's last zkir_verify* call: host wall time in ms of [0] parsing (the tapes' record checks among it), [1] the sections' chunk digests,
  * [2] the hash tape's share of the table side, [3] the wide tape's, [4] the rest; *device_stages = how many of these stages ran on the device (0 for every host entry).
  * Either pointer may be NULL.  ZKIR_ERR_ARGUMENT before the thread's first verification.  ZKIR_VERIFY_TIMES in the environment prints the clocks on stderr. */

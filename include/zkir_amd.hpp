@@ -366,6 +366,7 @@ class StarkContext {                                            // device tables
   StarkContext(const StarkContext&) = delete;
   StarkContext& operator=(const StarkContext&) = delete;
   const zkir_stark_ctx* handle() const { return h_; }
+  zkir_stark_ctx* handle() { return h_; }
   uint32_t log_n() const { return log_n_; }
   uint32_t log_blowup() const { return zkir_stark_ctx_log_blowup(h_); }
 
@@ -439,6 +440,26 @@ inline std::vector<uint32_t> prove(const StarkContext& ctx, const zkir_runtime::
   return out;
 }
 inline int verify(const std::vector<uint32_t>& proof, const zkir_public_inputs* expect = nullptr) { return zkir_verify(proof.data(), proof.size(), expect); }
+// The same at the CONTEXT's rate (log_blowup 1, 2, 3; modes 0 - 2, whole runs): a 'ZKSR' proof (zkir_prove_rate).  num_queries 0: 50 / 25 / 17 by log_blowup.
+inline std::vector<uint32_t> prove_rate(StarkContext& ctx, const zkir_runtime::ExecutionResult& result, const zkir_public_inputs& pub, uint32_t num_queries = 0, uint32_t pow_bits = 12,
+                                        void* hip_stream = nullptr) {
+  static const uint32_t by_rate[4] = {50, 50, 25, 17};
+  uint32_t* words = nullptr;
+  uint64_t n = 0;
+  const int rc = zkir_prove_rate(ctx.handle(), result.execution_trace.device_columns(), &pub, num_queries ? num_queries : by_rate[ctx.log_blowup() & 3], pow_bits, &words, &n, nullptr, hip_stream);
+  if (rc != ZKIR_OK) zkir_runtime::detail::raise(rc);
+  std::vector<uint32_t> out(words, words + n);
+  zkir_proof_free(words);
+  return out;
+}
+// 0 = accepted, with at least min_queries queries and min_pow_bits grinding bits; the codes: zkir_amd.h.  on_device: the embedded proof's query stage on the current HIP
+// device — the same verdict (a negative return is a device failure)
+inline int verify_rate(const std::vector<uint32_t>& proof, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits) {
+  return zkir_verify_rate(proof.data(), proof.size(), expect, min_queries, min_pow_bits);
+}
+inline int verify_rate_device(const std::vector<uint32_t>& proof, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, void* hip_stream = nullptr) {
+  return zkir_verify_rate_device(proof.data(), proof.size(), expect, min_queries, min_pow_bits, hip_stream);
+}
 // verify + the run's CLAIM in the clear (zkir_verify_io): the I/O tapes and the halt reason must hash to the proof's io digest and the halt row must be the
 // instruction the halt reason names (50 / 52 / 53, include/zkir_amd.h); what a caller who holds an ExecutionResult-shaped claim calls
 inline int verify_io(const std::vector<uint32_t>& proof, const std::vector<uint64_t>& inputs, const std::vector<uint64_t>& outputs, const zkir_runtime::HaltReason& halt,

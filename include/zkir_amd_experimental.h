@@ -47,6 +47,11 @@ uint64_t zkir_eval_quotient_scratch_words(uint32_t log_m, uint32_t width, uint32
 int zkir_eval_quotient_launch(const zkir_stark_ctx* ctx, const uint32_t* lde_mat, uint32_t width, const uint32_t gamma[4], const uint32_t* points, uint32_t n_points,
                               const uint32_t* evals, uint32_t* scratch, uint32_t* cw, void* hip_stream);
 
+/* TEST: the main, aux and quotient LDE matrices of the context's last zkir_prove_rate proof, copied to the HOST from where they still lie in its workspace: B8 layout
+ * ([blocks][M][8] words, M = N << log_blowup), canonical; the quotient's one block holds its 4 columns and 4 zero columns.  A NULL buffer is skipped; widths (may be NULL)
+ * gets the three widths, *rows (may be NULL) gets M.  ZKIR_ERR_ARGUMENT once any other proof has used the context's workspace (or before the first). */
+int zkir_prove_rate_last_matrices(const zkir_stark_ctx* ctx, uint32_t* main_host, uint32_t* aux_host, uint32_t* quotient_host, uint32_t widths[3], uint64_t* rows);
+
 /* MEASUREMENT: zkir_batch_eval_prove with the device time (ms, HIP events) of its six stages: weights | evaluations | quotient | FRI commit phase | grinding | query section. */
 int zkir_batch_eval_prove_stages(zkir_stark_ctx* ctx, uint32_t n_mats, const uint32_t* const* lde_mats, const uint32_t* widths, const uint32_t* const* trees, const uint32_t* masks,
                                  const uint32_t* points, uint32_t n_points, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words,

@@ -355,46 +355,62 @@ struct EvalEntry { const char* who; const char* words_call; bool zkev; };
 constexpr EvalEntry ENTRY_EVAL{"zkir_eval_prove", "zkir_eval_proof_words(log_n, log_blowup, width, n_points, num_queries)", true};
 constexpr EvalEntry ENTRY_BATCH{"zkir_batch_eval_prove", "zkir_batch_eval_proof_words(log_n, log_blowup, n_mats, widths, masks, n_points, num_queries)", false};
 
-// stage_ms (measurements; may be null): weights | evaluations | quotient | FRI commit phase | grinding | query section
-int eval_prove_impl(const EvalEntry& en, zkir_stark_ctx* c, uint32_t n_mats, const uint32_t* const* mats, const uint32_t* widths, const uint32_t* const* trees, const uint32_t* masks,
-                    const uint32_t* points, uint32_t n_points, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words, float* stage_ms,
-                    hipStream_t s) {
+constexpr EvalEntry ENTRY_RATE{"zkir_prove_rate", "the embedded evaluation proof's words", false};
+
+// What a proof needs beyond its matrices: the checked shape, the proof's length, the schedule and the arena bytes of its working set.  eval_plan makes every refusal
+// that does not look at a matrix or tree pointer, in the entries' order, before anything is launched.
+struct EvalPlan {
+  EvalPoints pts; BatchPlan p; uint64_t total; std::vector<int> ks; uint32_t n_chunks, np_of[BATCH_MAX_MATS]; size_t n_part[BATCH_MAX_MATS], n_gpow, arena_bytes;
+};
+int eval_plan(const EvalEntry& en, const zkir_stark_ctx* c, uint32_t n_mats, const uint32_t* widths, const uint32_t* masks, const uint32_t* points, uint32_t n_points,
+              uint32_t num_queries, uint32_t pow_bits, uint64_t cap_words, EvalPlan* out) {
   auto bad = [&](const std::string& why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(en.who) + ": " + why}); return (int)ZKIR_ERR_ARGUMENT; };
-  // every argument is checked before anything is launched
-  if (n_words) *n_words = 0;
-  if (!c || !mats || !widths || !trees || !masks || !points || !proof_host || !n_words) return bad("null context, matrices, widths, trees, masks, points, proof buffer or n_words");
-  if (n_mats < 1 || n_mats > BATCH_MAX_MATS) return bad("n_mats must be 1 .. 4");
-  for (uint32_t m = 0; m < n_mats; m++) if (!mats[m] || !trees[m]) return bad("null matrix or tree");
+  EvalPlan& e = *out;
   const uint32_t log_n = c->log_n, b = c->log_blowup, log_M = log_n + b;
   if (log_n < 3) return bad("the context's log_n must be at least 3: below that there is no layer to commit");
-  EvalPoints pts;
-  if (const char* why = eval_points_check(points, n_points, &pts)) return bad(why);
-  BatchPlan p;
-  if (const char* why = batch_plan(n_mats, widths, masks, n_points, &p)) return bad(why);
+  if (const char* why = eval_points_check(points, n_points, &e.pts)) return bad(why);
+  if (const char* why = batch_plan(n_mats, widths, masks, n_points, &e.p)) return bad(why);
   if (num_queries < 1 || num_queries > 128) return bad("num_queries must be 1 .. 128");
   if (pow_bits > 24) return bad("pow_bits must be 0 .. 24");
   const uint64_t batch_total = zkir_batch_eval_proof_words(log_n, b, n_mats, widths, masks, n_points, num_queries);
   if (batch_total == 0) return bad("the context's log_n / log_blowup are outside what a proof can state (log_n 3 .. 26, log_blowup 1 .. 3, their sum at most 27)");
-  const uint64_t total = batch_total - (en.zkev ? 2 : 0);                  // 'ZKEV' has no (width, mask) pair
-  if (cap_words < total) return bad(std::string("cap_words is below ") + en.words_call);
-
-  std::lock_guard<std::mutex> ctx_lock(c->mu);                   // one proof at a time per context: the workspace is its arena, as in zkir_prove
+  e.total = batch_total - (en.zkev ? 2 : 0);                               // 'ZKEV' has no (width, mask) pair
+  if (cap_words < e.total) return bad(std::string("cap_words is below ") + en.words_call);
   const uint64_t N = 1ull << log_n, M = 1ull << log_M;
-  const std::vector<int> ks = zkir::fri_schedule((int)log_n, (int)b);
-  const uint32_t n_chunks = eval_chunks(N);
+  e.ks = zkir::fri_schedule((int)log_n, (int)b);
+  e.n_chunks = eval_chunks(N);
   OpenMat opens[BATCH_MAX_MATS];
-  uint32_t np_of[BATCH_MAX_MATS];
-  size_t n_part[BATCH_MAX_MATS], want_part = 0;
+  size_t want_part = 0;
   for (uint32_t m = 0; m < n_mats; m++) {
-    opens[m] = OpenMat{mats[m], widths[m], trees[m]};
-    np_of[m] = (uint32_t)__builtin_popcount(masks[m]);
-    n_part[m] = (size_t)np_of[m] * p.n_blocks[m] * 8 * n_chunks;
-    want_part += arena_al(16 * n_part[m]) + arena_al(16 * (size_t)np_of[m] * widths[m]);
+    opens[m] = OpenMat{nullptr, widths[m], nullptr};                       // (the record sizes read the widths only)
+    e.np_of[m] = (uint32_t)__builtin_popcount(masks[m]);
+    e.n_part[m] = (size_t)e.np_of[m] * e.p.n_blocks[m] * 8 * e.n_chunks;
+    want_part += arena_al(16 * e.n_part[m]) + arena_al(16 * (size_t)e.np_of[m] * widths[m]);
   }
-  const size_t n_gpow = (size_t)n_points * p.total_blocks * 8;
+  e.n_gpow = (size_t)n_points * e.p.total_blocks * 8;
   // the arena: the FRI part with n_mats record buffers, ONE inverse table, ONE weights table, the gamma table, per matrix its partial sums and evaluations
-  if (const int rc = arena_reserve(c, lowdeg_fri_bytes(log_M, open_rec_words(log_M, opens, n_mats), n_mats, ks, num_queries) + arena_al(16 * n_gpow) + want_part +
-                                          arena_al(16 * n_points * N) + arena_al(16 * n_points * M))) return rc;
+  e.arena_bytes = lowdeg_fri_bytes(log_M, open_rec_words(log_M, opens, n_mats), n_mats, e.ks, num_queries) + arena_al(16 * e.n_gpow) + want_part + arena_al(16 * n_points * N) +
+                  arena_al(16 * n_points * M);
+  return ZKIR_OK;
+}
+
+// The proof itself, in the context's arena FROM ITS CURRENT OFFSET: the caller holds c->mu and has made room for e.arena_bytes above whatever it keeps there (the locked
+// entry below: the whole arena, emptied; zkir_prove_rate: above its matrices and trees).  The pinned staging is emptied: a caller keeps nothing there across the call.
+// stage_ms (measurements; may be null): weights | evaluations | quotient | FRI commit phase | grinding | query section
+int eval_prove_body(const EvalEntry& en, const EvalPlan& e, const zkir_stark_ctx* c, uint32_t n_mats, const uint32_t* const* mats, const uint32_t* widths, const uint32_t* const* trees,
+                    const uint32_t* masks, const uint32_t* points, uint32_t n_points, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t* n_words, float* stage_ms,
+                    hipStream_t s) {
+  const uint32_t log_n = c->log_n, b = c->log_blowup, log_M = log_n + b;
+  const uint64_t N = 1ull << log_n, M = 1ull << log_M, total = e.total;
+  const std::vector<int>& ks = e.ks;
+  const BatchPlan& p = e.p;
+  const EvalPoints& pts = e.pts;
+  const uint32_t* np_of = e.np_of;
+  const size_t* n_part = e.n_part;
+  const size_t n_gpow = e.n_gpow;
+  OpenMat opens[BATCH_MAX_MATS];
+  for (uint32_t m = 0; m < n_mats; m++) opens[m] = OpenMat{mats[m], widths[m], trees[m]};
+  if (c->arena_off + e.arena_bytes > c->arena_size) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string(en.who) + ": the workspace has no room for the evaluation proof"}); return ZKIR_ERR_OTHER; }
   ProofRun r(c, s, en.who, stage_ms != nullptr);
   if (stage_ms) HIP_OK(r.se.create());
   E4 *dGpow, *dWts, *dDinv, *dPart[BATCH_MAX_MATS], *dY[BATCH_MAX_MATS]; uint32_t* cw;
@@ -444,6 +460,37 @@ int eval_prove_impl(const EvalEntry& en, zkir_stark_ctx* c, uint32_t n_mats, con
   if (stage_ms) r.times(stage_ms, 6);
   *n_words = total;
   return ZKIR_OK;
+}
+
+// the locked entry: every argument is checked before anything is launched; one proof at a time per context, in its workspace arena, as in zkir_prove
+int eval_prove_impl(const EvalEntry& en, zkir_stark_ctx* c, uint32_t n_mats, const uint32_t* const* mats, const uint32_t* widths, const uint32_t* const* trees, const uint32_t* masks,
+                    const uint32_t* points, uint32_t n_points, uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t cap_words, uint64_t* n_words, float* stage_ms,
+                    hipStream_t s) {
+  auto bad = [&](const std::string& why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(en.who) + ": " + why}); return (int)ZKIR_ERR_ARGUMENT; };
+  if (n_words) *n_words = 0;
+  if (!c || !mats || !widths || !trees || !masks || !points || !proof_host || !n_words) return bad("null context, matrices, widths, trees, masks, points, proof buffer or n_words");
+  if (n_mats < 1 || n_mats > BATCH_MAX_MATS) return bad("n_mats must be 1 .. 4");
+  for (uint32_t m = 0; m < n_mats; m++) if (!mats[m] || !trees[m]) return bad("null matrix or tree");
+  EvalPlan e;
+  if (const int rc = eval_plan(en, c, n_mats, widths, masks, points, n_points, num_queries, pow_bits, cap_words, &e)) return rc;
+  std::lock_guard<std::mutex> ctx_lock(c->mu);
+  if (const int rc = arena_reserve(c, e.arena_bytes)) return rc;
+  return eval_prove_body(en, e, c, n_mats, mats, widths, trees, masks, points, n_points, num_queries, pow_bits, proof_host, n_words, stage_ms, s);
+}
+
+// zkir_prove_rate's two calls (stark_prove.inl declares them): the 'ZKBE' proof of the prover's three matrices at two points, inside the prover's lock and above its allocations
+int rate_eval_plan(const zkir_stark_ctx* c, const uint32_t* widths, const uint32_t* masks, const uint32_t* points, uint32_t num_queries, uint32_t pow_bits, size_t* arena_bytes,
+                   uint64_t* total_words) {
+  EvalPlan e;
+  if (const int rc = eval_plan(ENTRY_RATE, c, 3, widths, masks, points, 2, num_queries, pow_bits, ~0ull, &e)) return rc;
+  *arena_bytes = e.arena_bytes; *total_words = e.total;
+  return ZKIR_OK;
+}
+int rate_eval_prove(const zkir_stark_ctx* c, const uint32_t* const* mats, const uint32_t* widths, const uint32_t* const* trees, const uint32_t* masks, const uint32_t* points,
+                    uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t* n_words, float* stage_ms, hipStream_t s) {
+  EvalPlan e;
+  if (const int rc = eval_plan(ENTRY_RATE, c, 3, widths, masks, points, 2, num_queries, pow_bits, ~0ull, &e)) return rc;
+  return eval_prove_body(ENTRY_RATE, e, c, 3, mats, widths, trees, masks, points, 2, num_queries, pow_bits, proof_host, n_words, stage_ms, s);
 }
 
 // the one-matrix entries' mask: every point (a bad n_points is refused by the points check, before any mask is looked at)

@@ -266,6 +266,7 @@ int arena_reserve(const zkir_stark_ctx* c, size_t want) {
     c->arena_size = want;
   }
   c->arena_off = 0;
+  c->rate_mats[0] = c->rate_mats[1] = c->rate_mats[2] = nullptr;           // (what zkir_prove_rate left there is about to be overwritten)
   return ZKIR_OK;
 }
 

@@ -321,6 +321,14 @@ int zkir_batch_eval_verify_device(const uint32_t* proof, uint64_t n_words, const
   return pcs_verify_device(2, proof, n_words, expect_roots, expect_points, expect_evals, stream);
 }
 
+// zkir_verify_rate with the embedded evaluation proof's query stage on the device: the same function, the same verdict for every input
+int zkir_verify_rate_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, void* stream) {
+  pcs_last_jobs[0] = pcs_last_jobs[1] = 0;
+  pcs_last_ms[0] = pcs_last_ms[1] = pcs_last_ms[2] = 0;
+  PcsDeviceStage st{(hipStream_t)stream};
+  return guarded([&] { return zkir::rate_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::QueryStage{&st, pcs_device_run}); });
+}
+
 int zkir_pcs_verify_last_jobs(uint64_t* hash_jobs, uint64_t* value_jobs) {
   if (hash_jobs) *hash_jobs = pcs_last_jobs[0];
   if (value_jobs) *value_jobs = pcs_last_jobs[1];

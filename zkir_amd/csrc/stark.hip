@@ -497,10 +497,10 @@ __global__ __launch_bounds__(NT) void powers_kernel(uint32_t w, uint32_t scale_m
 }
 
 
-// 1 / (x_j - 1) over the LDE coset x_j = g w_2N^j (Montgomery), eight points per lane: one inversion per eight (Montgomery's trick).
-// Depends on log_n only: a table of the context.  x_j = 1 cannot happen (g generates the whole group, so g w^j is never in the 2-power subgroup).
-__global__ __launch_bounds__(NT) void selector_inverse_kernel(uint32_t log_n, const uint32_t* __restrict__ tw_fwd, uint32_t* __restrict__ inv_xm1) {
-  const uint32_t N2 = 2u << log_n, N = N2 >> 1;
+// 1 / (x_j - 1) over the LDE coset x_j = g w_M^j, M = 2^log_m rows (Montgomery), eight points per lane: one inversion per eight (Montgomery's trick).
+// Depends on log_n and the rate only: a table of the context.  x_j = 1 cannot happen (g generates the whole group, so g w^j is never in the 2-power subgroup).
+__global__ __launch_bounds__(NT) void selector_inverse_kernel(uint32_t log_m, const uint32_t* __restrict__ tw_fwd, uint32_t* __restrict__ inv_xm1) {
+  const uint32_t N2 = 1u << log_m, N = N2 >> 1;
   const uint32_t j0 = (blockIdx.x * NT + threadIdx.x) * 8;
   if (j0 >= N2) return;
   uint32_t d[8], pre[8];
@@ -741,7 +741,7 @@ struct zkir_stark_ctx {
   uint32_t* d_tw_fwd = nullptr;   // w_M^k, k < M/2, M = N << log_blowup   (blow-up 2: w_{2N}^k, k < N — the form the prover's kernels read)
   uint32_t* d_g_lo = nullptr;     // g^k / N, k < 1024
   uint32_t* d_g_lo_m = nullptr;   // R g^k / N: the same scale with the Montgomery factor folded in — the LDE then leaves its output in Montgomery form (zkir_prove)
-  uint32_t* d_inv_xm1 = nullptr;  // 1 / (x_j - 1), j < 2N, over the blow-up-2 LDE coset (Montgomery): the row selectors of the quotient (stark_prove.inl); filled at log_blowup 1 only
+  mutable uint32_t* d_inv_xm1 = nullptr;  // 1 / (x_j - 1), j < M, over the context's LDE coset (Montgomery): the row selectors of the quotient (stark_prove.inl); filled at creation at log_blowup 1, on the first zkir_prove_rate otherwise (4 M bytes a commit-only context never needs)
   uint32_t* d_g_hi = nullptr;     // g^(1024 k)
   uint32_t* d_small_inv = nullptr;  // w_{2^Bm}^-k, k < 2^(Bm-1)      (Bm = min(log_n, 10))
   uint32_t* d_small_fwd = nullptr;  // w_{2^(Bm+b)}^k, k < 2^(Bm+b-1), b = log_blowup   (blow-up 2: w_{2^(Bm+1)}^k, k < 2^Bm)
@@ -755,6 +755,9 @@ struct zkir_stark_ctx {
   mutable unsigned char* arena = nullptr;
   mutable size_t arena_size = 0, arena_off = 0;
   mutable zkir::HostPin pin;      // pinned host staging of the proof's large copies (host.h: why no large pageable block is handed to a copy)
+  // zkir_prove_rate's last proof: its main, aux and quotient LDE matrices where they still lie in the arena (zkir_prove_rate_last_matrices); forgotten when the arena is emptied
+  mutable const uint32_t* rate_mats[3] = {nullptr, nullptr, nullptr};
+  mutable uint32_t rate_widths[3] = {0, 0, 0};
 };
 
 namespace {
@@ -777,6 +780,16 @@ int merkle_commit(const zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, 
   hipLaunchKernelGGL(leaf_hash_kernel, dim3(grid_for(n_leaves)), dim3(NT), 0, s, c->d_p2, mat, width, n_leaves, mont_in ? bb::from_mont(c->consts.in_scale) : c->consts.in_scale, tree);
   launch_tree_levels(c->d_p2, tree, n_leaves, c->sync, s);
   return check_launch("merkle_commit");
+}
+// the selector table of a context that was created without one (log_blowup 2 / 3): allocated and filled once, on the caller's stream, under the context's mutex
+int selector_table_ensure(const zkir_stark_ctx* c, hipStream_t s) {
+  if (c->d_inv_xm1) return ZKIR_OK;
+  const uint64_t M = 1ull << (c->log_n + c->log_blowup);
+  uint32_t* t = nullptr;
+  if (hipMalloc(&t, (size_t)M * 4) != hipSuccess) { zkir::set_last_error({ZKIR_ERR_DEVICE, "zkir_prove_rate: no device memory for the selector table"}); return ZKIR_ERR_DEVICE; }
+  hipLaunchKernelGGL(selector_inverse_kernel, dim3(grid_for((M + 7) / 8)), dim3(NT), 0, s, c->log_n + c->log_blowup, c->d_tw_fwd, t);
+  c->d_inv_xm1 = t;
+  return check_launch("selector table");
 }
 }  // namespace
 
@@ -888,7 +901,7 @@ int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** 
   if (e == hipSuccess) e = hipMalloc(&c->d_g_lo, 1024 * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_g_hi, (size_t)n_hi * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_g_lo_m, 1024 * 4);
-  if (e == hipSuccess && log_blowup == 1) e = hipMalloc(&c->d_inv_xm1, (size_t)2 * N * 4);        // the prover's: it refuses any other rate
+  if (e == hipSuccess && log_blowup == 1) e = hipMalloc(&c->d_inv_xm1, (size_t)2 * N * 4);        // zkir_prove's; a context of another rate makes its own on its first zkir_prove_rate (selector_table_ensure)
   const int Bm = log_n < 10 ? (int)log_n : 10;
   const uint32_t n_si = Bm >= 1 ? (1u << (Bm - 1)) : 1, n_sf = 1u << (Bm + log_blowup - 1);
   if (e == hipSuccess) e = hipMalloc(&c->d_small_inv, (size_t)n_si * 4);
@@ -900,7 +913,7 @@ int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** 
   hipLaunchKernelGGL(powers_kernel, dim3(4), dim3(NT), 0, 0, bb::GEN, bb::to_mont(bb::inv(N % bb::P)), c->d_g_lo, 1024u);
   hipLaunchKernelGGL(powers_kernel, dim3(4), dim3(NT), 0, 0, bb::GEN, bb::to_mont(bb::to_mont(bb::inv(N % bb::P))), c->d_g_lo_m, 1024u);
   hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_hi)), dim3(NT), 0, 0, bb::pow(bb::GEN, 1024), bb::R1, c->d_g_hi, n_hi);
-  if (log_blowup == 1) hipLaunchKernelGGL(selector_inverse_kernel, dim3(grid_for((2ull * N + 7) / 8)), dim3(NT), 0, 0, log_n, c->d_tw_fwd, c->d_inv_xm1);
+  if (log_blowup == 1) hipLaunchKernelGGL(selector_inverse_kernel, dim3(grid_for((2ull * N + 7) / 8)), dim3(NT), 0, 0, log_n + 1, c->d_tw_fwd, c->d_inv_xm1);
   hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_si)), dim3(NT), 0, 0, bb::inv(bb::root_of_unity(Bm)), bb::R1, c->d_small_inv, n_si);
   hipLaunchKernelGGL(powers_kernel, dim3(grid_for(n_sf)), dim3(NT), 0, 0, bb::root_of_unity(Bm + log_blowup), bb::R1, c->d_small_fwd, n_sf);
   if (hipDeviceSynchronize() != hipSuccess || check_launch("stark ctx tables") != ZKIR_OK) { zkir_stark_ctx_free(c); return ZKIR_ERR_DEVICE; }

@@ -14,6 +14,12 @@ using bb::E4;
 constexpr int LOG_FINAL = air::LOG_FINAL, WMX = air::W_COMMITTED_MAX, WAX = air::W_AUX_MAX, WTX = WMX + WAX, NS = air::N_STATE, HEADER_WORDS = 21 + 2 * NS;   // (queries / grinding bits: air.h, per proof)
 constexpr int N_CONSTRAINTS = air::N_CONSTRAINTS;
 constexpr uint32_t PROOF_MAGIC = 0x46504B5Au;                  // (the version is the mode's: air::proof_version)
+constexpr uint32_t RATE_MAGIC = 0x52534B5Au, RATE_VERSION = 1;  // 'ZKSR': a proof at the context's own rate (zkir_prove_rate)
+// eval_open.inl's two calls for this entry (defined there, behind this file): the refusals, length and arena bytes of the embedded proof; the proof itself
+int rate_eval_plan(const zkir_stark_ctx* c, const uint32_t* widths, const uint32_t* masks, const uint32_t* points, uint32_t num_queries, uint32_t pow_bits, size_t* arena_bytes,
+                          uint64_t* total_words);
+int rate_eval_prove(const zkir_stark_ctx* c, const uint32_t* const* mats, const uint32_t* widths, const uint32_t* const* trees, const uint32_t* masks, const uint32_t* points,
+                           uint32_t num_queries, uint32_t pow_bits, uint32_t* proof_host, uint64_t* n_words, float* stage_ms, hipStream_t s);
 
 #ifndef DEEP_WAVES
 #define DEEP_WAVES 4
@@ -164,6 +170,61 @@ __global__ __launch_bounds__(NT, DEF >= 3 ? QUOT_WAVES_MEM : QUOT_WAVES) void qu
   uint4* q4 = reinterpret_cast<uint4*>(Q);                                     // one B8 block: four coordinate columns (Montgomery, like every matrix of a proof) + four zero columns
   q4[(uint64_t)j * 2] = make_uint4(q.c[0], q.c[1], q.c[2], q.c[3]);
   q4[(uint64_t)j * 2 + 1] = make_uint4(0, 0, 0, 0);
+}
+
+// ---- the quotient at the context's own rate (zkir_prove_rate): the coset has M = N 2^b rows, x_j = g w_M^j -------------------------------------------------------------
+// The same constraint list through the same QuotientOps; what differs from quotient_kernel:
+//   * the matrices rest in CANONICAL form (they are what the evaluation proof opens, and the commitment layer reads canonical words): RateRowSrc converts a word to
+//     Montgomery form as it is loaded — one multiplication per word read, the loads stay the merged 16-byte ones of DeviceRowSrc;
+//   * the next row of the trace domain is position j + 2^b;
+//   * Z_H(x_j) = g^N w_(2^b)^(j mod 2^b) - 1 takes 2^b values: their inverses come from the host (zh);
+//   * 1 / (x_j - w_N^last) is the selector table read at j - 2^b last, times w_N^-last;
+//   * the quotient is written canonical.
+struct RateRowSrc {
+  const uint4* __restrict__ L4; const uint4* __restrict__ A4; uint64_t N2, j, jn;
+  __device__ __forceinline__ uint32_t at(const uint4* __restrict__ m, int p, uint64_t row) const { return bb::to_mont(DeviceRowSrc::pick(m[((uint64_t)(p >> 3) * N2 + row) * 2 + ((p >> 2) & 1)], p & 3)); }
+  __device__ __forceinline__ uint32_t at_r(const uint4* __restrict__ m, int p, uint64_t row) const { return bb::to_mont(reinterpret_cast<const uint32_t*>(m)[((uint64_t)(p >> 3) * N2 + row) * 8 + (p & 7)]); }
+  __device__ __forceinline__ uint32_t loc_r(int p) const { return at_r(L4, p, j); }
+  __device__ __forceinline__ uint32_t nxt_r(int p) const { return at_r(L4, p, jn); }
+  __device__ __forceinline__ uint32_t loc(int p) const { return at(L4, p, j); }
+  __device__ __forceinline__ uint32_t nxt(int p) const { return at(L4, p, jn); }
+  __device__ __forceinline__ uint32_t aloc(int p) const { return at(A4, p, j); }
+  __device__ __forceinline__ uint32_t anxt(int p) const { return at(A4, p, jn); }
+};
+struct RateZh { uint32_t inv_m[8]; };                           // 1 / Z_H(x_j) by j mod 2^b (Montgomery); entries from 2^b on unused
+
+template <int DEF /* the mode: 0, 1, 2 */>
+__global__ __launch_bounds__(NT, QUOT_WAVES) void quotient_rate_kernel(const uint32_t* __restrict__ L, const uint32_t* __restrict__ AL, uint32_t log_m, uint32_t log_b, const uint32_t* __restrict__ tw_fwd,
+                                                                       const uint32_t* __restrict__ inv_xm1, const ProveParams* __restrict__ pp, uint32_t wn_inv_m, uint32_t w_last_inv_m,
+                                                                       uint32_t last_shift, RateZh zh, uint32_t* __restrict__ Q) {
+  const uint32_t M = 1u << log_m, H = M >> 1;
+  const uint32_t j = blockIdx.x * NT + threadIdx.x;
+  if (j >= M) return;
+  // x = g * w_M^j (Montgomery): w^j = tw[j] for j < M / 2, -tw[j - M / 2] otherwise
+  const uint32_t wj = j < H ? tw_fwd[j] : bb::neg(tw_fwd[j - H]);
+  const uint32_t x = bb::mont_mul(wj, bb::to_mont(bb::GEN));
+  const uint32_t r = j & ((1u << log_b) - 1);
+  uint32_t inv_zh = zh.inv_m[0];
+#pragma unroll
+  for (uint32_t k = 1; k < 8; k++) inv_zh = r == k ? zh.inv_m[k] : inv_zh;     // (selects on a kernel argument: no indexed read)
+  const uint32_t inv_first = inv_xm1[j], inv_last = bb::mont_mul(inv_xm1[(j + M - last_shift) & (M - 1)], w_last_inv_m);
+  const uint32_t is_trans = bb::sub(x, wn_inv_m);
+  using QO = QuotientOps<DEF, RateRowSrc>;
+  QO o{RateRowSrc{reinterpret_cast<const uint4*>(L), reinterpret_cast<const uint4*>(AL), M, j, (j + (1u << log_b)) & (M - 1)}, pp->alpha_seq, {}, pp->lk};
+  o.init();
+  air::eval(o, pp->first_m, pp->last_m, DEF, pp->cnt_m);
+  const E4 s0 = QO::sum_of(o.a0), st = o.st, sf = bb::e_sub(o.sf, pp->cf), sl = bb::e_sub(o.sl, pp->cl);
+  const E4 q = bb::e_add(bb::e_add(bb::e_mul_fm(bb::e_add(s0, bb::e_mul_fm(st, is_trans)), inv_zh), bb::e_mul_fm(sf, inv_first)), bb::e_mul_fm(sl, inv_last));
+  uint4* q4 = reinterpret_cast<uint4*>(Q);                                     // one B8 block: four coordinate columns, CANONICAL, + four zero columns
+  q4[(uint64_t)j * 2] = make_uint4(bb::from_mont(q.c[0]), bb::from_mont(q.c[1]), bb::from_mont(q.c[2]), bb::from_mont(q.c[3]));
+  q4[(uint64_t)j * 2 + 1] = make_uint4(0, 0, 0, 0);
+}
+// Montgomery words to canonical ones in place (16 bytes a lane): the aux trace's rows are written in Montgomery form, and zkir_prove_rate extends canonical rows
+__global__ __launch_bounds__(NT) void from_mont_kernel(uint4* __restrict__ a, uint64_t n4) {
+  const uint64_t i = (uint64_t)blockIdx.x * NT + threadIdx.x;
+  if (i >= n4) return;
+  const uint4 v = a[i];
+  a[i] = make_uint4(bb::from_mont(v.x), bb::from_mont(v.y), bb::from_mont(v.z), bb::from_mont(v.w));
 }
 
 // ---- lookup argument (AIR v2): per-row table indices + multiplicities, inverse tables, aux trace -------------------------------------
@@ -1037,41 +1098,56 @@ extern "C" {
 // Full proof of the run whose K1 output is `trace` (pub->n_real executed rows, padded to 2^ctx.log_n).  Phases are timed with HIP events
 // when stage_ms != NULL (NINE floats): [0] main trace (+ lookup indices), [1] LDE, [2] trace Merkle, [3] lookup argument (inverse tables, aux trace, its LDE and
 // Merkle tree), [4] quotient (+Merkle), [5] openings, [6] DEEP, [7] FRI (+grinding), [8] queries.
-int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t** proof_out, uint64_t* proof_words, float* stage_ms,
-               void* stream) {
-  if (!c || !trace || !pub || !proof_out || !proof_words) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: null argument"}); return ZKIR_ERR_ARGUMENT; }
-  if (!blowup2_only(c, "zkir_prove")) return ZKIR_ERR_ARGUMENT;
+//
+// zkir_prove_rate (rate != NULL) is the same function through stage 1b — the main trace, the lookup indices, the multiplicities, the aux trace and its scans work on N rows and
+// do not know the rate — with M = N << log_blowup rows from the LDE on: the matrices rest in CANONICAL form (the evaluation proof reads them), the quotient comes from
+// quotient_rate_kernel, and after zeta the body of zkir_batch_eval_prove (eval_open.inl) opens the three commitments: no second path through the openings, DEEP and the FRI.
+// Its stage_ms: ELEVEN floats, [0..4] as above, [5..10] the evaluation proof's six (weights | evaluations | quotient | FRI commit phase | grinding | query section).
+struct RateArgs { uint32_t num_queries, pow_bits; };
+static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t** proof_out, uint64_t* proof_words, float* stage_ms,
+                      void* stream, const RateArgs* rate) {
+  const char* const who = rate ? "zkir_prove_rate" : "zkir_prove";
+  if (!c || !trace || !pub || !proof_out || !proof_words) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": null argument"}); return ZKIR_ERR_ARGUMENT; }
+  if (!rate && !blowup2_only(c, "zkir_prove")) return ZKIR_ERR_ARGUMENT;
+  const uint32_t log_b = rate ? c->log_blowup : 1;
+  if (rate) {                                                   // every refusal of the rate entry before any launch
+    auto bad = [&](const char* why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string("zkir_prove_rate: ") + why}); return (int)ZKIR_ERR_ARGUMENT; };
+    if (pub->deferred > 2) return bad("pub->deferred (the proof's mode) must be 0, 1 or 2: the memory and wide-arithmetic arguments (modes 3 and 4) are proven at blow-up 2 only (zkir_prove)");
+    if (pub->writes_before || pub->reads_before) return bad("a segment of a run (writes_before / reads_before) is proven at blow-up 2 only (zkir_prove): this entry proves whole runs");
+    if (rate->num_queries < 1 || rate->num_queries > 128) return bad("num_queries must be 1 .. 128");
+    if (rate->pow_bits > 24) return bad("pow_bits must be 0 .. 24");
+  }
   const bool dbg_t = getenv("ZKIR_PROVE_TIMES") != nullptr;      // diagnostics: host wall time of the call's phases on stderr
   const auto t_entry = std::chrono::steady_clock::now();
   auto since = [&](const std::chrono::steady_clock::time_point& t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   const uint32_t log_n = c->log_n;
-  const uint64_t N = 1ull << log_n, N2 = 2 * N;
-  if (pub->deferred > 4) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: pub->deferred is the proof's mode: 0 default, 1 deferred model, 2 default + the I/O argument, 3 = 2 + the memory argument, 4 = 3 + MULH / DIVU / REMU / DIV / REM"}); return ZKIR_ERR_ARGUMENT; }
+  const uint64_t N = 1ull << log_n, N2 = N << log_b;            // N2: the rows of the LDE coset (2 N in zkir_prove; M = N 2^b at the context's rate)
+  if (pub->deferred > 4) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": pub->deferred is the proof's mode: 0 default, 1 deferred model, 2 default + the I/O argument, 3 = 2 + the memory argument, 4 = 3 + MULH / DIVU / REMU / DIV / REM"}); return ZKIR_ERR_ARGUMENT; }
   const int MODE = (int)pub->deferred;                         // 0 default, 1 deferred carry model, 2 default + the I/O argument, 3 = 2 + the memory argument (round 4), 4 = 3 + the wide-arithmetic class (round 6)
   const bool IO = MODE >= 2, MEM = MODE >= 3, WIDE = MODE == 4;
-  if (!air::fri_params_ok(pub->fri_params)) {
-    zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: pub->fri_params (num_queries | pow_bits << 16, 0 = 50 queries + 12 bits) must name 50..128 queries and 12..24 grinding bits (zkir_public_inputs_set_params)"});
+  if (!rate && !air::fri_params_ok(pub->fri_params)) {         // (zkir_prove_rate takes its parameters as arguments and does not consult fri_params)
+    zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": pub->fri_params (num_queries | pow_bits << 16, 0 = 50 queries + 12 bits) must name 50..128 queries and 12..24 grinding bits (zkir_public_inputs_set_params)"});
     return ZKIR_ERR_ARGUMENT;
   }
-  const int NUM_QUERIES = air::num_queries_of(pub->fri_params), POW_BITS = air::pow_bits_of(pub->fri_params);     // this proof's (header words 4 and 6)
+  const int NUM_QUERIES = rate ? (int)rate->num_queries : air::num_queries_of(pub->fri_params), POW_BITS = rate ? (int)rate->pow_bits : air::pow_bits_of(pub->fri_params);     // this proof's (header words 4 and 6)
   const int WM = air::committed_width(MODE), WA = air::aux_width(MODE), WT = WM + WA;     // this proof's committed main-trace / aux columns
   // (mode 3) the memory witness: computed HERE on the device (memcheck.hip) unless the caller brings one (pub->mem_old != NULL: zkir_memcheck_witness_of's host replay — the
   // independent implementation the tests compare with — or a forged one)
   const bool MEM_HOST = MEM && pub->mem_old != nullptr;
   if (MEM && (pub->writes_before || pub->reads_before || (MEM_HOST && (!pub->mem_told || (pub->n_cells && (!pub->cell_addr || !pub->cell_bytes || !pub->cell_time)) || pub->n_cells >= (1u << 28))))) {
-    zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: mode 3 proves a WHOLE run; a memory witness passed in the public inputs must be complete (zkir_memcheck_witness_of + zkir_public_inputs_set_memory)"});
+    zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": mode 3 proves a WHOLE run; a memory witness passed in the public inputs must be complete (zkir_memcheck_witness_of + zkir_public_inputs_set_memory)"});
     return ZKIR_ERR_ARGUMENT;
   }
   if (IO && ((!pub->inputs && pub->n_inputs) || (!pub->outputs && pub->n_outputs) || pub->n_inputs >= (1u << 28) || pub->n_outputs >= (1u << 28) || pub->halt_kind > 2)) {
-    zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: mode 2 needs the I/O tapes and the halt reason in the public inputs (zkir_public_inputs_of fills them)"});
+    zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": mode 2 needs the I/O tapes and the halt reason in the public inputs (zkir_public_inputs_of fills them)"});
     return ZKIR_ERR_ARGUMENT;
   }
   if (pub->n_real == 0 || zkir_padded_log_n(pub->n_real) != log_n || pub->entry_point >= (1ull << 40)) {
-    zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: the context's log_n must be zkir_padded_log_n(n_real) (n_real >= 1), and entry_point < 2^40"});
+    zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": the context's log_n must be zkir_padded_log_n(n_real) (n_real >= 1), and entry_point < 2^40"});
     return ZKIR_ERR_ARGUMENT;
   }
   for (int i = 0; i < 4; i++)
-    if (pub->program_digest[i] >= bb::P || pub->io_digest[i] >= bb::P) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: digests must be canonical field elements"}); return ZKIR_ERR_ARGUMENT; }
+    if (pub->program_digest[i] >= bb::P || pub->io_digest[i] >= bb::P) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": digests must be canonical field elements"}); return ZKIR_ERR_ARGUMENT; }
   // the program: its code words are the instruction ROM every row is looked up in (Program::to_bytes layout, program.rs:170-214)
   const uint8_t* blob = pub->program_blob;
   const uint64_t blob_len = pub->program_blob_len;
@@ -1082,12 +1158,19 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     if (ok) { const uint64_t code_size = le32(16); ok = code_size % 4 == 0 && 32 + code_size <= blob_len && le32(12) == pub->entry_point; n_code = (uint32_t)(code_size / 4); }
     if (ok) { uint32_t dg[4]; zkir_digest_bytes(blob, blob_len, dg); ok = !memcmp(dg, pub->program_digest, 16); }
     if (!ok) {
-      zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: pub->program_blob must be the program that ran (Program::to_bytes layout; its digest and entry point are the public inputs'): "
+      zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": pub->program_blob must be the program that ran (Program::to_bytes layout; its digest and entry point are the public inputs'): "
                                                "use zkir_public_inputs_of, and keep the blob alive while proving"});
       return ZKIR_ERR_ARGUMENT;
     }
   }
   hipStream_t s = (hipStream_t)stream;
+  // (rate) the embedded evaluation proof: main (WM) | aux (WA) | quotient (4) opened at [zeta, zeta w] with masks {3, 3, 1}; its working set lies above this proof's
+  const uint32_t rate_widths[3] = {(uint32_t)air::committed_width((int)pub->deferred), (uint32_t)air::aux_width((int)pub->deferred), 4u}, rate_masks[3] = {3u, 3u, 1u};
+  size_t rate_arena = 0; uint64_t rate_total = 0;
+  if (rate) {
+    const uint32_t any_points[8] = {0, 1, 0, 0, 0, 2, 0, 0};   // (the sizes do not depend on the points)
+    if (const int prc = rate_eval_plan(c, rate_widths, rate_masks, any_points, rate->num_queries, rate->pow_bits, &rate_arena, &rate_total)) return prc;
+  }
   // One proof at a time per context (its workspace arena); proofs on different contexts run concurrently: the per-proof constants
   // live in the arena (no __constant__ / static state).
   std::lock_guard<std::mutex> ctx_lock(c->mu);
@@ -1095,7 +1178,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   const std::vector<int> ks = zkir::fri_schedule((int)log_n, 1);              // a STARK proof is the FRI's case b = 1: log_M = log_n + 1, a final layer of 2^LOG_FINAL values
   const int n_layers = (int)ks.size();
 
-  ProofRun run(c, s, "zkir_prove", stage_ms != nullptr);       // the proof's pinned staging (emptied here), arena view and stage events (fri.inl)
+  ProofRun run(c, s, who, stage_ms != nullptr);       // the proof's pinned staging (emptied here), arena view and stage events (fri.inl)
   Arena& ar = run.ar;
   zkir::HostPin& pin = run.pin;
   // (mode 4) a run with hash syscalls and no witness from the caller: the memory witness AND the hash tape are built on the device (memcheck.hip), the written digests coming
@@ -1106,7 +1189,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   zkir::HashWitness hw;
   struct DevMem { void* p = nullptr; ~DevMem() { if (p) (void)hipFree(p); } } hw_rows;     // mem_old [n_real] | mem_told [n_real] of that witness
   if (HASH_DEV) {
-    if (pub->writes_before || pub->reads_before) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: mode 3 proves a WHOLE run; a memory witness passed in the public inputs must be complete (zkir_memcheck_witness_of + zkir_public_inputs_set_memory)"}); return ZKIR_ERR_ARGUMENT; }
+    if (pub->writes_before || pub->reads_before) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": mode 3 proves a WHOLE run; a memory witness passed in the public inputs must be complete (zkir_memcheck_witness_of + zkir_public_inputs_set_memory)"}); return ZKIR_ERR_ARGUMENT; }
     HIP_OK(hipMalloc(&hw_rows.p, (size_t)pub->n_real * 12 + 256));
     const int wrc = zkir::memcheck_device_hash(trace, pub->n_real, blob, blob_len, pub->hash_outs, pub->n_hash_outs, (uint64_t*)hw_rows.p, (uint32_t*)((uint64_t*)hw_rows.p + pub->n_real),
                                                cell_addr_v, cell_bytes_v, cell_time_v, hw, pin, s);
@@ -1124,7 +1207,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   const size_t mc_own = mc_need > (size_t)WM * N2 * 4 ? mc_need : 0;
   {                                               // workspace: 12 W (M + L) + 440 (trees, quotient, weights, FRI) bytes per row, allocated once per context
     static_assert(WMX % 8 == 0 && air::W_COMMITTED_DEFAULT % 8 == 0, "the main trace fills whole B8 blocks");
-    const size_t want = (size_t)(12 * WM + 12 * WA + 16 + 544 + (IO ? 48 : 0) + (MEM ? 48 : 0) + (WIDE ? 8 : 0)) * N + (size_t)air::MAX_NUM_QUERIES * 64 * 1024 + (8u << 20) + (size_t)n_code * 24 + (1u << 16) + (WIDE ? (1u << 17) : 0) +
+    // (at the context's rate: the N-row matrices, their M-row extensions, and the M-row part — trees, quotient — scaled from 2 N rows to M)
+    const size_t want = (rate ? rate_arena + (1u << 20) : 0) + (size_t)(4 * (WM + WA) * (1 + (1 << log_b)) + ((16 + 544) << (log_b - 1)) + (IO ? 48 : 0) + (MEM ? 48 : 0) + (WIDE ? 8 : 0)) * N + (rate ? 0 : (size_t)air::MAX_NUM_QUERIES * 64 * 1024) + (8u << 20) + (size_t)n_code * 24 + (1u << 16) + (WIDE ? (1u << 17) : 0) +
                         (IO ? (size_t)pub->n_inputs * 8 : 0) + (MEM ? (size_t)air::MEM_MULT * 24 + (size_t)CELL_CAP * 28 + SEC_WORDS * 4 + blob_len + (1u << 16) : 0) + (mc_own ? mc_own + 256 : 0);
     if (const int arc = arena_reserve(c, want)) return arc;
   }
@@ -1152,10 +1236,11 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   const size_t n_mult = (size_t)n_code + air::RC_TABLE + (MEM ? air::MEM_MULT : 0);
   HIP_OK(ar.take(&dCode, (size_t)n_code + 1)); HIP_OK(ar.take(&dMult, n_mult));                   // ROM multiplicities, then range multiplicities (mode 3: then LOW3 | BYTE | NIBBLE)
   HIP_OK(ar.take(&dInvRc, air::RC_TABLE)); HIP_OK(ar.take(&dInvRom, (size_t)n_code + 1));
-  HIP_OK(ar.take(&dQ, 8 * N2)); HIP_OK(ar.take(&dQTree, 4 * (2 * N2 - 1))); HIP_OK(ar.take(&dW, N2)); HIP_OK(ar.take(&dDinv, N2));
+  HIP_OK(ar.take(&dQ, 8 * N2)); HIP_OK(ar.take(&dQTree, 4 * (2 * N2 - 1)));
+  if (!rate) { HIP_OK(ar.take(&dW, N2)); HIP_OK(ar.take(&dDinv, N2)); }     // (the barycentric weights: the evaluation proof has its own)
   // chunks of the barycentric sums: enough workgroups to fill the chip (64 x 25 blocks), and few enough terms per 96-bit sum (bary_dot_kernel: BARY_MAX_TERMS)
   const uint32_t n_chunks = N2 > 64 * BARY_ROWS * BARY_MAX_TERMS ? (uint32_t)(N2 / (BARY_ROWS * BARY_MAX_TERMS)) : N2 >= 1024 * NT ? 256 : N2 >= 64 * NT ? 64 : (N2 >= 16 * NT ? 16 : 1);
-  HIP_OK(ar.take(&dPart, (size_t)(WT + 4) * n_chunks * 2)); HIP_OK(ar.take(&dPartSum, (size_t)(WT + 4) * 2));
+  if (!rate) { HIP_OK(ar.take(&dPart, (size_t)(WT + 4) * n_chunks * 2)); HIP_OK(ar.take(&dPartSum, (size_t)(WT + 4) * 2)); }
   if (stage_ms) HIP_OK(run.se.create());
   double host_ms[10] = {0};                                     // (diagnostics) host wall time at every mark
   auto mark = [&](int i) { run.mark(i); if (dbg_t) host_ms[i] = since(t_entry); };
@@ -1194,9 +1279,9 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     hipLaunchKernelGGL(lookup_index_kernel, dim3(g), dim3(NT), 0, s, dM, N, MODE, dCode, n_code, dSide, dMult + n_code, dMult, dBad, dIo, dIoCount, dMult + n_code + air::RC_TABLE, dMemSide, dWideSide, dSec);
   }
   mark(1);
-  rc = lde_launch(c, dM, WM, dL, /*mont_out=*/true, s); if (rc) return rc;        // canonical evaluations in, MONTGOMERY words out: the matrices of a proof rest in Montgomery form
+  rc = lde_launch(c, dM, WM, dL, /*mont_out=*/!rate, s); if (rc) return rc;        // canonical evaluations in, MONTGOMERY words out: the matrices of a proof rest in Montgomery form
   mark(2);
-  rc = merkle_commit(c, dL, WM, N2, dTree, /*mont_in=*/true, s); if (rc) return rc;
+  rc = merkle_commit(c, dL, WM, N2, dTree, /*mont_in=*/!rate, s); if (rc) return rc;
   uint32_t troot[4], aroot[4], qroot[4], bound[2 * NS + 4] = {}, n_io = 0;
   unsigned long long bad_row = ~0ull;
   uint32_t* mult = pin.take_n<uint32_t>(n_mult);               // (pinned: read back below, and part of the proof)
@@ -1211,9 +1296,9 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   n_io = io_counts[0];
   if (bad_row != ~0ull) {
     char m[640];
-    snprintf(m, sizeof m, "zkir_prove: row %llu of the trace has no proof in this AIR: its (pc, instruction word) is not in the program's code table (self-modified code, "
+    snprintf(m, sizeof m, "%s: row %llu of the trace has no proof in this AIR: its (pc, instruction word) is not in the program's code table (self-modified code, "
                           "a pc outside the code segment), a written limb is out of range, (mode 3) its memory witness is not the row's, or (mode 4) a wide-arithmetic chunk is out of range, or it stores into the low half "
-                          "of a cell B + 8 p j (j != 0; B the boundary cell, p the field's modulus), which the boundary-cell constraint cannot tell from B", bad_row);
+                          "of a cell B + 8 p j (j != 0; B the boundary cell, p the field's modulus), which the boundary-cell constraint cannot tell from B", who, bad_row);
     zkir::set_last_error({ZKIR_ERR_ARGUMENT, m});
     return ZKIR_ERR_ARGUMENT;
   }
@@ -1222,7 +1307,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   std::vector<WideRec> wrecs;
   if (WIDE && io_counts[2]) {
     const uint32_t nw = io_counts[2];
-    if ((size_t)nw * 8 > SEC_WORDS) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more wide-tape rows than the workspace holds"}); return ZKIR_ERR_OTHER; }
+    if ((size_t)nw * 8 > SEC_WORDS) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": more wide-tape rows than the workspace holds"}); return ZKIR_ERR_OTHER; }
     wrecs.resize(nw);
     HIP_OK(hipMemcpyAsync(wrecs.data(), dSec, (size_t)nw * 32, hipMemcpyDeviceToHost, s));
     // the records stay on the device for the table side (wide_table_side_kernel), in the order they were appended: moved into the quotient's buffer, which nothing
@@ -1234,6 +1319,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   mark(3);
   std::vector<uint32_t> head;
   header_words(log_n, *pub, bound, head);
+  if (rate) { head[0] = RATE_MAGIC; head[1] = RATE_VERSION; head[4] = rate->num_queries; head[5] = log_b; head[6] = rate->pow_bits; }   // ('ZKSR': the whole header is observed, so the rate is bound)
   Challenger ch(c->consts);
   ch.observe_n(head.data() + 2, head.size() - 2);
   ch.observe_n(troot, 4);
@@ -1255,7 +1341,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     mem_sec.push_back((uint32_t)n_cells_v);
     for (uint64_t k = 0; k < n_cells_v; k++) {
       const uint64_t a = cell_addr_v[k], b = cell_bytes_v[k];
-      if ((a & 7) || (a >> 40) || (k && a <= cell_addr_v[k - 1])) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: the touched cells must be multiples of 8 below 2^40 in strictly increasing order"}); return ZKIR_ERR_ARGUMENT; }
+      if ((a & 7) || (a >> 40) || (k && a <= cell_addr_v[k - 1])) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": the touched cells must be multiples of 8 below 2^40 in strictly increasing order"}); return ZKIR_ERR_ARGUMENT; }
       if (a + 8 > air::CODE_BASE && a < air::CODE_BASE + 4 * (uint64_t)n_code && !(WIDE && (n_code & 1) && a == air::boundary_cell(4 * (uint64_t)n_code))) {   // (mode 4 admits the boundary cell: I_BC)
         // (v11) instruction fetch is tied to the program's words: a store into the code would change what the VM executes next (vm.rs:175: strict protection is off) but not what
         // the AIR lets through — mode 3 proves runs whose loads and stores stay off the cells that overlap the code segment, and both verifiers check the list (55)
@@ -1270,7 +1356,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     }
     // the section enters the transcript through its chunk digests (so::observe_section), hashed in parallel on the device
     const size_t n_chunks_sec = (mem_sec.size() + SECTION_CHUNK - 1) / SECTION_CHUNK;
-    if (mem_sec.size() + 4 * n_chunks_sec + 64 > SEC_WORDS) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: more touched cells than the workspace holds"}); return ZKIR_ERR_ARGUMENT; }
+    if (mem_sec.size() + 4 * n_chunks_sec + 64 > SEC_WORDS) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": more touched cells than the workspace holds"}); return ZKIR_ERR_ARGUMENT; }
     uint32_t* dSecDg = dSec + ((mem_sec.size() + 63) & ~(size_t)63);
     HIP_OK(run.h2d(dSec, mem_sec.data(), mem_sec.size() * 4));
     hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks_sec + 63) / 64)), dim3(64), 0, s, c->d_p2, dSec, (uint64_t)mem_sec.size(), dSecDg);
@@ -1290,7 +1376,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       // hashcall::parse_section's checks, where the tape lies (hash_tape_check_kernel); its length is 1 + 8 calls + 5 cells by construction
       int hrc = 0;
       rc = hash_tape_check_run(hw.d_tape, hw.d_prefix, hw.n_calls, hw.n_calls, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, dTapeCheck, pin, s, &hrc); if (rc) return rc;
-      if (hrc == 55) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: a hash syscall of the run writes its output where it overlaps the code segment: such a run has no mode-4 proof"}); return ZKIR_ERR_ARGUMENT; }
+      if (hrc == 55) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": a hash syscall of the run writes its output where it overlaps the code segment: such a run has no mode-4 proof"}); return ZKIR_ERR_ARGUMENT; }
       if (hrc) {
         char m[200]; snprintf(m, sizeof m, "zkir_prove: the hash tape built from the trace is malformed (check %d): the trace is not a run of the VM", hrc);
         zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
@@ -1388,7 +1474,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       const size_t m0 = (size_t)n_code + air::RC_TABLE;
       for (int t = 0; t < air::MEM_MULT; t++) if (mult[m0 + t]) T = bb::e_add(T, bb::e_mul_fm(inv[air::RC_TABLE + n_code + t], bb::to_mont(mult[m0 + t] % bb::P)));
       if (n_cells_v) {
-        if (n_cells_v > CELL_CAP) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: more touched cells than the workspace holds"}); return ZKIR_ERR_ARGUMENT; }
+        if (n_cells_v > CELL_CAP) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": more touched cells than the workspace holds"}); return ZKIR_ERR_ARGUMENT; }
         uint32_t code_size, data_size; memcpy(&code_size, blob + 16, 4); memcpy(&data_size, blob + 20, 4);
         const uint64_t image_len = 32 + (uint64_t)code_size + data_size <= blob_len ? (uint64_t)code_size + data_size : 0;
         if (image_len) HIP_OK(run.h2d(dImage, blob + 32, image_len));
@@ -1418,7 +1504,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
       };
       const uint32_t* cn = bound + 2 * NS;                      // (oc, ic) of the first row, of the last row
       if (cn[2] > pub->n_outputs || cn[3] > pub->n_inputs || cn[0] > cn[2] || cn[1] > cn[3]) {
-        zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove: the trace writes more outputs / consumes more inputs than the public inputs' tapes hold (or writes_before / reads_before are wrong)"});
+        zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": the trace writes more outputs / consumes more inputs than the public inputs' tapes hold (or writes_before / reads_before are wrong)"});
         return ZKIR_ERR_ARGUMENT;
       }
       for (uint64_t k = cn[0]; k < cn[2]; k++) term(k, pub->outputs[k], 2);
@@ -1434,8 +1520,8 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     HashAux* dHashAux = reinterpret_cast<HashAux*>(dSec);
     HashAux* dWideAux = reinterpret_cast<HashAux*>(reinterpret_cast<char*>(dSec) + wide_aux_off);
     if (WIDE && (n_hash_calls || n_wide)) {
-      if (n_hash_calls * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more hash calls than the workspace holds"}); return ZKIR_ERR_OTHER; }
-      if (n_wide && wide_aux_off + (size_t)n_wide * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: more wide-tape rows than the workspace holds"}); return ZKIR_ERR_OTHER; }
+      if (n_hash_calls * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": more hash calls than the workspace holds"}); return ZKIR_ERR_OTHER; }
+      if (n_wide && wide_aux_off + (size_t)n_wide * sizeof(HashAux) > SEC_WORDS * 4) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": more wide-tape rows than the workspace holds"}); return ZKIR_ERR_OTHER; }
       const double t_side0 = since(t_entry);
       TapePartials hash_part, wide_part;
       if (HASH_DEV) { rc = hash_table_side_enqueue(hw.d_tape, hw.d_prefix, hw.d_side, hw.n_calls, hw.n_hcells, dPP->lk, dHashAux, dTapePart, pin, s, &hash_part); if (rc) return rc; }
@@ -1472,8 +1558,9 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     hipLaunchKernelGGL(scan_local_kernel, dim3(n_scan), dim3(NT), 0, s, dA, N, dSums);
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(NT), 0, s, dSums, n_scan);
     hipLaunchKernelGGL(scan_add_kernel, dim3(grid_for(N)), dim3(NT), 0, s, dA, N, dSums);
-    rc = lde_launch(c, dA, WA, dAL, /*mont_out=*/false, s); if (rc) return rc;      // the aux rows are written in Montgomery form already; the extension is linear
-    rc = merkle_commit(c, dAL, WA, N2, dATree, /*mont_in=*/true, s); if (rc) return rc;
+    if (rate) hipLaunchKernelGGL(from_mont_kernel, dim3(grid_for((uint64_t)WA * N / 4)), dim3(NT), 0, s, reinterpret_cast<uint4*>(dA), (uint64_t)WA * N / 4);   // (rate) canonical rows: one pass over the N-row matrix
+    rc = lde_launch(c, dA, WA, dAL, /*mont_out=*/false, s); if (rc) return rc;      // the aux rows are written in Montgomery form already (rate: canonical by now); the extension is linear
+    rc = merkle_commit(c, dAL, WA, N2, dATree, /*mont_in=*/!rate, s); if (rc) return rc;
     HIP_OK(run.d2h(aroot, dATree + 4 * (2 * N2 - 2), 16));
     HIP_OK(run.sync_d2h());
     ch.observe_n(aroot, 4);
@@ -1500,19 +1587,60 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   const uint32_t wn = bb::root_of_unity((int)log_n);
   const uint32_t gN = bb::pow(bb::GEN, N), wn_inv_m = bb::to_mont(bb::inv(wn)), w_last_inv_m = bb::to_mont(bb::inv(bb::pow(wn, pub->n_real - 1)));
   const uint32_t inv_zh_even_m = bb::to_mont(bb::inv(bb::sub(gN, 1))), inv_zh_odd_m = bb::to_mont(bb::inv(bb::sub(bb::neg(gN), 1)));
-  const uint32_t last_shift = (uint32_t)((2 * (pub->n_real - 1)) & (N2 - 1));   // x_j - w_N^last = w_N^last (x_(j - 2 last) - 1) on the 2N coset
-  if (MODE == 1) hipLaunchKernelGGL(quotient_kernel<1>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
+  const uint32_t last_shift = (uint32_t)(((pub->n_real - 1) << log_b) & (N2 - 1));   // x_j - w_N^last = w_N^last (x_(j - 2^b last) - 1) on the coset (2^b = 2 in zkir_prove)
+  if (rate) {
+    if (const int src = selector_table_ensure(c, s)) return src;      // (contexts of log_blowup 2 / 3 fill it on their first proof)
+    RateZh zh{};
+    const uint32_t w_b = bb::pow(bb::root_of_unity((int)(log_n + log_b)), N);      // w_M^N: x_j^N = g^N w_b^(j mod 2^b)
+    for (uint32_t k = 0; k < (1u << log_b); k++) zh.inv_m[k] = bb::to_mont(bb::inv(bb::sub(bb::mul(gN, bb::pow(w_b, k)), 1)));
+    const uint32_t log_m = log_n + log_b;
+    if (MODE == 1) hipLaunchKernelGGL(quotient_rate_kernel<1>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
+    else if (MODE == 2) hipLaunchKernelGGL(quotient_rate_kernel<2>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
+    else hipLaunchKernelGGL(quotient_rate_kernel<0>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
+  }
+  else if (MODE == 1) hipLaunchKernelGGL(quotient_kernel<1>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
   else if (MODE == 4) hipLaunchKernelGGL(quotient_kernel<4>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
   else if (MODE == 3) hipLaunchKernelGGL(quotient_kernel<3>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
   else if (MODE == 2) hipLaunchKernelGGL(quotient_kernel<2>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
   else hipLaunchKernelGGL(quotient_kernel<0>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_n, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, inv_zh_even_m, inv_zh_odd_m, dQ);
-  rc = merkle_commit(c, dQ, 4, N2, dQTree, /*mont_in=*/true, s); if (rc) return rc;
+  rc = merkle_commit(c, dQ, 4, N2, dQTree, /*mont_in=*/!rate, s); if (rc) return rc;
   HIP_OK(run.d2h(qroot, dQTree + 4 * (2 * N2 - 2), 16));
   HIP_OK(run.sync_d2h());
   mark(5);
   ch.observe_n(qroot, 4);
   const E4 zeta = ch.sample_ext();
   const E4 zeta_w = bb::E4{{bb::mul(zeta.c[0], wn), bb::mul(zeta.c[1], wn), bb::mul(zeta.c[2], wn), bb::mul(zeta.c[3], wn)}};
+  // the sections every proof carries between its header and its openings: the program, the tapes, the multiplicities, the three roots
+  auto push_sections = [&] {
+    head.reserve(head.size() + blob_len / 2 + io_sec.size() + mem_sec.size() + (WIDE ? hash_sec.size() + wide_sec.size() : 0) + n_mult + 8 * (size_t)WT + 4096);   // (one allocation: the tapes of mode 4 can be 100 MB)
+    head.push_back((uint32_t)blob_len);                                         // the program: byte length, then 16-bit halfwords
+    for (uint64_t i = 0; i < blob_len; i += 2) head.push_back((uint32_t)blob[i] | (i + 1 < blob_len ? (uint32_t)blob[i + 1] << 8 : 0u));
+    if (IO) head.insert(head.end(), io_sec.begin(), io_sec.end());              // the I/O section: the tapes and the halt reason the io digest is a digest of
+    if (MEM) head.insert(head.end(), mem_sec.begin(), mem_sec.end());           // (mode 3) the touched cells
+    if (WIDE) { head.insert(head.end(), hash_sec.data(), hash_sec.data() + hash_sec.size()); head.insert(head.end(), wide_sec.begin(), wide_sec.end()); }   // (mode 4) the hash calls, the wide tape
+    head.insert(head.end(), mult, mult + n_mult);                          // ROM multiplicities, range multiplicities (mode 3: LOW3 | BYTE | NIBBLE)
+    head.insert(head.end(), troot, troot + 4); head.insert(head.end(), aroot, aroot + 4); head.insert(head.end(), qroot, qroot + 4);
+  };
+  if (rate) {
+    // ---- 3 - 6 at the context's rate: the STARK part is complete; the evaluation proof of the three commitments at [zeta, zeta w] follows it word for word ----
+    push_sections();                                            // (before the evaluation proof empties the pinned staging the multiplicities lie in)
+    uint32_t points[8];
+    memcpy(points, zeta.c, 16); memcpy(points + 4, zeta_w.c, 16);
+    if (const int prc = rate_eval_plan(c, rate_widths, rate_masks, points, rate->num_queries, rate->pow_bits, &rate_arena, &rate_total)) return prc;   // (zeta in the base field: probability 2^-93)
+    const uint64_t total = head.size() + rate_total;
+    uint32_t* out = (uint32_t*)malloc(total * 4);
+    if (!out) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove_rate: out of host memory"}); return ZKIR_ERR_OTHER; }
+    memcpy(out, head.data(), head.size() * 4);
+    if (stage_ms) run.times(stage_ms, 5);
+    const uint32_t* mats[3] = {dL, dAL, dQ};
+    const uint32_t* trees[3] = {dTree, dATree, dQTree};
+    uint64_t n_eval = 0;
+    const int erc = rate_eval_prove(c, mats, rate_widths, trees, rate_masks, points, rate->num_queries, rate->pow_bits, out + head.size(), &n_eval, stage_ms ? stage_ms + 5 : nullptr, s);
+    if (erc || n_eval != rate_total) { free(out); if (!erc) zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove_rate: the evaluation proof has another length than planned"}); return erc ? erc : ZKIR_ERR_OTHER; }
+    for (int m = 0; m < 3; m++) { c->rate_mats[m] = mats[m]; c->rate_widths[m] = rate_widths[m]; }
+    *proof_out = out; *proof_words = total;
+    return ZKIR_OK;
+  }
 
   // ---- 3. openings by barycentric evaluation over the LDE coset ------------------------------------------------------------
   pp->zeta = bb::e_to_mont(zeta); pp->zeta_w = bb::e_to_mont(zeta_w);
@@ -1578,14 +1706,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   for (auto& q : queries) q = ch.sample_bits((int)log_n);
 
   // ---- 6. serialise: header + openings on the host, query section gathered on the device -----------------------------------
-  head.reserve(head.size() + blob_len / 2 + io_sec.size() + mem_sec.size() + (WIDE ? hash_sec.size() + wide_sec.size() : 0) + n_mult + 8 * (size_t)WT + 4096);   // (one allocation: the tapes of mode 4 can be 100 MB)
-  head.push_back((uint32_t)blob_len);                                         // the program: byte length, then 16-bit halfwords
-  for (uint64_t i = 0; i < blob_len; i += 2) head.push_back((uint32_t)blob[i] | (i + 1 < blob_len ? (uint32_t)blob[i + 1] << 8 : 0u));
-  if (IO) head.insert(head.end(), io_sec.begin(), io_sec.end());              // the I/O section: the tapes and the halt reason the io digest is a digest of
-  if (MEM) head.insert(head.end(), mem_sec.begin(), mem_sec.end());           // (mode 3) the touched cells
-  if (WIDE) { head.insert(head.end(), hash_sec.data(), hash_sec.data() + hash_sec.size()); head.insert(head.end(), wide_sec.begin(), wide_sec.end()); }   // (mode 4) the hash calls, the wide tape
-  head.insert(head.end(), mult, mult + n_mult);                          // ROM multiplicities, range multiplicities (mode 3: LOW3 | BYTE | NIBBLE)
-  head.insert(head.end(), troot, troot + 4); head.insert(head.end(), aroot, aroot + 4); head.insert(head.end(), qroot, qroot + 4);
+  push_sections();
   for (int k = 0; k < WT; k++) head.insert(head.end(), t_z[k].c, t_z[k].c + 4);
   for (int k = 0; k < WT; k++) head.insert(head.end(), t_zw[k].c, t_zw[k].c + 4);
   for (int i = 0; i < 4; i++) head.insert(head.end(), q_z[i].c, q_z[i].c + 4);
@@ -1618,7 +1739,7 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
   hipLaunchKernelGGL(gather_kernel, dim3((unsigned)jobs.size()), dim3(64), 0, s, dJobs, (uint32_t)jobs.size(), dOut);
   const uint64_t total = head.size() + off;
   uint32_t* out = (uint32_t*)malloc(total * 4);
-  if (!out) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove: out of host memory"}); return ZKIR_ERR_OTHER; }
+  if (!out) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": out of host memory"}); return ZKIR_ERR_OTHER; }
   memcpy(out, head.data(), head.size() * 4);
   uint32_t* h_out = pin.take_n<uint32_t>((size_t)off);          // (the proof block is the caller's to free: it is never the target of a copy itself)
   hipError_t e = h_out ? hipMemcpyAsync(h_out, dOut, (size_t)off * 4, hipMemcpyDeviceToHost, s) : hipErrorOutOfMemory;
@@ -1635,6 +1756,34 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
     fprintf(stderr, "\n");
   }
   *proof_out = out; *proof_words = total;
+  return ZKIR_OK;
+}
+
+int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t** proof_out, uint64_t* proof_words, float* stage_ms,
+               void* stream) {
+  return prove_impl(c, trace, pub, proof_out, proof_words, stage_ms, stream, nullptr);
+}
+
+// A proof at the context's own rate (log_blowup 1, 2 or 3), modes 0 - 2, whole runs: the 'ZKSR' format (zkir_amd.h).  stage_ms: NULL or ELEVEN floats.
+int zkir_prove_rate(zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
+                    uint64_t* proof_words, float* stage_ms, void* stream) {
+  const RateArgs rate{num_queries, pow_bits};
+  return prove_impl(c, trace, pub, proof_out, proof_words, stage_ms, stream, &rate);
+}
+
+// (zkir_amd_experimental.h) the main, aux and quotient LDE matrices of the context's last zkir_prove_rate proof, copied to the host (B8 layout, canonical words, M rows each);
+// a NULL buffer is skipped.  widths: the three widths (the quotient's block holds 8 columns, 4 of them zero); rows: M.  Refused once another proof has used the workspace.
+int zkir_prove_rate_last_matrices(const zkir_stark_ctx* c, uint32_t* main_host, uint32_t* aux_host, uint32_t* quotient_host, uint32_t widths[3], uint64_t* rows) {
+  if (!c) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove_rate_last_matrices: null context"}); return ZKIR_ERR_ARGUMENT; }
+  std::lock_guard<std::mutex> ctx_lock(c->mu);
+  if (!c->rate_mats[0]) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove_rate_last_matrices: the context's workspace holds no zkir_prove_rate proof (none yet, or another proof has used it since)"}); return ZKIR_ERR_ARGUMENT; }
+  const uint64_t M = 1ull << (c->log_n + c->log_blowup);
+  uint32_t* dst[3] = {main_host, aux_host, quotient_host};
+  for (int m = 0; m < 3; m++) {
+    if (widths) widths[m] = c->rate_widths[m];
+    if (dst[m]) HIP_OK(hipMemcpy(dst[m], c->rate_mats[m], (size_t)((c->rate_widths[m] + 7) / 8) * 8 * M * 4, hipMemcpyDeviceToHost));
+  }
+  if (rows) *rows = M;
   return ZKIR_OK;
 }
 

@@ -189,8 +189,13 @@ void initial_state(uint64_t entry, uint32_t st[NS]) {
   st[1] = (uint32_t)(entry & 0xFFFFF); st[2] = (uint32_t)((entry >> 20) & 0xFFFFF); st[3] = (uint32_t)(entry >> 40);
 }
 
+// A proof at the context's own rate ('ZKSR', zkir_prove_rate): the sections of a zkir_prove proof through the quotient root under its own header, then ONE embedded 'ZKBE'
+// evaluation proof in place of the openings, the FRI part and the queries.  verify_impl's front (header, program, I/O section, table side, challenges up to zeta) is the
+// same code for both formats; `rate` != NULL selects the header's checks and, after zeta, the tail (rate_tail below).
+constexpr uint32_t RATE_MAGIC = 0x52534B5Au, RATE_VERSION = 1, BATCH_EVAL_MAGIC = 0x45424B5Au;      // 'ZKSR'; 'ZKBE'
+struct RateCheck { uint32_t min_queries, min_pow_bits; const zkir::QueryStage* stage; };
 int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out = nullptr,
-                const zkir::TapeStages* stages = nullptr, zkir::StarkQueries* defer = nullptr);
+                const zkir::TapeStages* stages = nullptr, zkir::StarkQueries* defer = nullptr, const RateCheck* rate = nullptr);
 int host_stark_run(void*, const zkir::StarkQueries* list, uint32_t n, int* codes);
 int host_stark_queries_of(const zkir::StarkQueries& Q, uint32_t first);
 inline int header_words_of(int mode) { return HEADER_WORDS + (mode >= 2 ? 4 : 0); }     // modes 2 / 3: + (oc, ic) of the first row, of the last row
@@ -734,7 +739,7 @@ int zkir_verify_chain_io(const uint32_t* const* proofs, const uint64_t* lens, ui
 namespace {
 
 int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out, const zkir::TapeStages* stages,
-                zkir::StarkQueries* defer) {
+                zkir::StarkQueries* defer, const RateCheck* rate) {
   StageClock clk;                                                          // (diagnostics: the host wall time of the call's phases, kept for zkir_verify_last_stages)
   zkir::HostTapes host_tapes;
   const zkir::TapeStages host_stages = zkir::host_tape_stages(&host_tapes);
@@ -742,20 +747,23 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   if (!w) return 1;
   size_t p = 0;
   auto need = [&](size_t k) { return p + k <= len; };
-  if (!need(HEADER_WORDS) || w[0] != PROOF_MAGIC || w[9] > 4 || w[1] != air::proof_version((int)w[9])) return 1;
+  if (!need(HEADER_WORDS) || w[0] != (rate ? RATE_MAGIC : PROOF_MAGIC) || w[9] > 4 || w[1] != (rate ? RATE_VERSION : air::proof_version((int)w[9]))) return 1;
   const int log_n = (int)w[2];
   if (w[9] > 4) return 2;
   const int mode = (int)w[9];                                              // 0 default, 1 deferred, 2 default + the I/O argument, 3 = 2 + the memory argument
   if (mode >= 3 && !whole_run) return 2;                                   // the memory check spans the whole run: a mode-3 proof is never a segment
+  if (rate && mode > 2) return 2;                                          // ('ZKSR' v1: modes 0, 1 and 2)
   const int HW = header_words_of(mode), WA = air::aux_width(mode);
   if (!need(HW)) return 1;
   const int WM = (int)w[3], WT = WM + WA;                                  // committed main-trace columns (checked against the mode below); main + aux
   // the prover's parameters (header words 4 and 6): exactly what `expect` names (0 = the defaults) when there is one; otherwise anything from the defaults up
+  // ('ZKSR': the evaluation proof's ranges, 1 .. 128 queries and 0 .. 24 bits, at least what the caller asks for; word 5 is log_blowup; `expect->fri_params` is not consulted)
   if (w[4] > (uint32_t)air::MAX_NUM_QUERIES || w[6] > (uint32_t)air::MAX_POW_BITS) return 2;
   const int NUM_QUERIES = (int)w[4], POW_BITS = (int)w[6];
-  if (expect ? (!air::fri_params_ok(expect->fri_params) || NUM_QUERIES != air::num_queries_of(expect->fri_params) || POW_BITS != air::pow_bits_of(expect->fri_params))
+  if (rate) { if (w[4] < 1 || w[5] < 1 || w[5] > 3 || w[2] + w[5] > 27 || w[4] < rate->min_queries || w[6] < rate->min_pow_bits) return 2; }
+  else if (expect ? (!air::fri_params_ok(expect->fri_params) || NUM_QUERIES != air::num_queries_of(expect->fri_params) || POW_BITS != air::pow_bits_of(expect->fri_params))
              : (NUM_QUERIES < air::DEFAULT_NUM_QUERIES || POW_BITS < air::DEFAULT_POW_BITS)) return 2;
-  if (w[3] != (uint32_t)air::committed_width(mode) || w[5] != (uint32_t)LOG_FINAL || w[2] < (uint32_t)LOG_FINAL || w[2] > 26) return 2;
+  if (w[3] != (uint32_t)air::committed_width(mode) || (!rate && w[5] != (uint32_t)LOG_FINAL) || w[2] < (uint32_t)LOG_FINAL || w[2] > 26) return 2;
   if (w[7] >= (1u << 30) || w[10] >= (1u << 20) || w[11] >= (1u << 20) || w[12] >= (1u << 24)) return 2;
   zkir_public_inputs pub;
   memset(&pub, 0, sizeof pub);
@@ -865,23 +873,32 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   if (!need(12)) return 4;
   const uint32_t* troot = w + p; p += 4; const uint32_t* aroot = w + p; p += 4; const uint32_t* qroot = w + p; p += 4;
   auto get_m = [&](size_t at) { E4 e; memcpy(e.c, w + at, 16); return bb::e_to_mont(e); };      // proof word -> Montgomery E4
-  if (!need((size_t)(2 * WT + 4) * 4)) return 4;
-  const size_t at_tz = p, at_tzw = p + 4 * (size_t)WT, at_qz = p + 8 * (size_t)WT;
-  std::vector<E4> t_z(WT), t_zw(WT), q_z(4);                                // main columns, then aux columns
-  for (int k = 0; k < WT; k++) { t_z[k] = get_m(at_tz + 4 * k); t_zw[k] = get_m(at_tzw + 4 * k); }
-  for (int i = 0; i < 4; i++) q_z[i] = get_m(at_qz + 4 * i);
-  p += (size_t)(2 * WT + 4) * 4;
-  if (!need(1)) return 4;
-  const int n_layers = (int)w[p++];
-  const std::vector<int> ks = zkir::fri_schedule(log_n, 1);
-  if (n_layers != (int)ks.size()) return 5;
-  const size_t n_fin = zkir::fri_final_size(1);
-  if (!need((size_t)4 * n_layers + 4 * n_fin + 1)) return 4;
-  const uint32_t* lroots = w + p; p += 4 * (size_t)n_layers;
-  const size_t at_fin = p;
-  std::vector<E4> fin(n_fin);
-  for (size_t i = 0; i < n_fin; i++) { fin[i] = get_m(p); p += 4; }
-  const uint32_t pow_nonce = w[p++];
+  // (zkir_prove's format) the openings at zeta and zeta w, the FRI part's roots, final layer and nonce; a 'ZKSR' proof carries its embedded evaluation proof here (rate_tail)
+  size_t at_tz = 0, at_tzw = 0, at_qz = 0, at_fin = 0, n_fin = 0;
+  std::vector<E4> t_z, t_zw, q_z, fin;
+  int n_layers = 0;
+  std::vector<int> ks;
+  const uint32_t* lroots = nullptr;
+  uint32_t pow_nonce = 0;
+  if (!rate) {
+    if (!need((size_t)(2 * WT + 4) * 4)) return 4;
+    at_tz = p; at_tzw = p + 4 * (size_t)WT; at_qz = p + 8 * (size_t)WT;
+    t_z.resize(WT); t_zw.resize(WT); q_z.resize(4);                         // main columns, then aux columns
+    for (int k = 0; k < WT; k++) { t_z[k] = get_m(at_tz + 4 * k); t_zw[k] = get_m(at_tzw + 4 * k); }
+    for (int i = 0; i < 4; i++) q_z[i] = get_m(at_qz + 4 * i);
+    p += (size_t)(2 * WT + 4) * 4;
+    if (!need(1)) return 4;
+    n_layers = (int)w[p++];
+    ks = zkir::fri_schedule(log_n, 1);
+    if (n_layers != (int)ks.size()) return 5;
+    n_fin = zkir::fri_final_size(1);
+    if (!need((size_t)4 * n_layers + 4 * n_fin + 1)) return 4;
+    lroots = w + p; p += 4 * (size_t)n_layers;
+    at_fin = p;
+    fin.resize(n_fin);
+    for (size_t i = 0; i < n_fin; i++) { fin[i] = get_m(p); p += 4; }
+    pow_nonce = w[p++];
+  }
   clk.lap(0);
   // ---- transcript ----
   Challenger ch;
@@ -1005,13 +1022,9 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   const E4 alpha = bb::e_to_mont(ch.sample_ext());
   ch.observe_n(qroot, 4);
   const E4 zeta = bb::e_to_mont(ch.sample_ext());
-  ch.observe_n(w + at_tz, (size_t)(2 * WT + 4) * 4);
-  const E4 gamma = bb::e_to_mont(ch.sample_ext());
-  std::vector<E4> betas;
-  if (!fri_transcript(ch, lroots, n_layers, w + at_fin, n_fin, pow_nonce, POW_BITS, betas)) return 12;
-  // ---- 1. constraints at zeta: sum_c alpha^c C_c(zeta) == Q(zeta) Z_H(zeta) ----
+  // ---- 1. constraints at zeta: sum_c alpha^c C_c(zeta) == Q(zeta) Z_H(zeta), on the openings the proof states (main | aux at zeta, the same at zeta w, the quotient's four) ----
   const uint32_t wn = bb::root_of_unity(log_n), wn_m = bb::to_mont(wn);
-  {
+  auto constraints_hold = [&](const E4* tz, const E4* tzw, const E4* qzs) {
     std::vector<E4> ap(air::N_CONSTRAINTS);                                // (modes 0 / 1 use the first N_CONSTRAINTS_BASE)
     ap[0] = bb::e_one_m();
     for (int c = 1; c < air::N_CONSTRAINTS; c++) ap[c] = bb::e_mul_m(ap[c - 1], alpha);
@@ -1024,12 +1037,36 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     for (int i = 0; i < NS; i++) { first_m[i] = bb::to_mont(first[i]); last_m[i] = bb::to_mont(last[i]); }
     uint32_t cnt_m[4];
     for (int k = 0; k < 4; k++) cnt_m[k] = bb::to_mont(cnt[k]);
-    VerifierOps o{t_z.data(), t_zw.data(), t_z.data() + WM, t_zw.data() + WM, lk_m, ap.data(), bb::e_zero(), mode, is_first, is_last, is_trans};
+    VerifierOps o{tz, tzw, tz + WM, tzw + WM, lk_m, ap.data(), bb::e_zero(), mode, is_first, is_last, is_trans};
     air::eval(o, first_m, last_m, mode, cnt_m);
     E4 qz = bb::e_zero();                                                  // Q(zeta) = sum_i X^i q_i(zeta): basis element X^i times the E4 opening
-    for (int i = 0; i < 4; i++) { E4 basis = bb::e_zero(); basis.c[i] = bb::R1; qz = bb::e_add(qz, bb::e_mul_m(basis, q_z[i])); }
-    if (!e_eq(o.acc, bb::e_mul_m(qz, zh))) return 10;
+    for (int i = 0; i < 4; i++) { E4 basis = bb::e_zero(); basis.c[i] = bb::R1; qz = bb::e_add(qz, bb::e_mul_m(basis, qzs[i])); }
+    return e_eq(o.acc, bb::e_mul_m(qz, zh));
+  };
+  if (rate) {
+    // ---- the 'ZKSR' tail: the embedded 'ZKBE' proof opens main (WM) | aux (WA) | quotient (4) with masks {3, 3, 1} at [zeta, zeta w], under the header's rate and parameters
+    // (5: it states another shape; 4: too short to hold its evaluations); its evaluations satisfy the constraints (10); the evaluation proof's own verifier, told the outer
+    // roots and points, accepts it (100 + its code)
+    const uint32_t* e = w + p;
+    const uint64_t elen = len - p;
+    const size_t at_ev = 15 + 12 + 8, n_ev = (size_t)(2 * WT + 4);
+    if (elen < at_ev + 4 * n_ev) return 4;
+    const uint32_t shape[15] = {BATCH_EVAL_MAGIC, 1, (uint32_t)log_n, w[5], 3, 2, w[4], w[6], e[8], (uint32_t)WM, 3, (uint32_t)WA, 3, 4, 1};
+    if (memcmp(e, shape, sizeof shape)) return 5;
+    std::vector<E4> ev(n_ev);                                               // exponent order: main | aux | quotient at zeta, main | aux at zeta w
+    for (size_t k = 0; k < n_ev; k++) { E4 x; memcpy(x.c, e + at_ev + 4 * k, 16); ev[k] = bb::e_to_mont(x); }
+    if (!constraints_hold(ev.data(), ev.data() + WT + 4, ev.data() + WT)) return 10;
+    uint32_t pts[8];
+    const E4 z = bb::e_from_mont(zeta), zw = bb::e_from_mont(bb::e_mul_fm(zeta, wn_m));
+    memcpy(pts, z.c, 16); memcpy(pts + 4, zw.c, 16);
+    const int c = zkir::pcs_verify_with_stage(2, e, elen, troot, pts, nullptr, *rate->stage);       // (troot | aroot | qroot are consecutive proof words)
+    return c ? 100 + c : 0;
   }
+  ch.observe_n(w + at_tz, (size_t)(2 * WT + 4) * 4);
+  const E4 gamma = bb::e_to_mont(ch.sample_ext());
+  std::vector<E4> betas;
+  if (!fri_transcript(ch, lroots, n_layers, w + at_fin, n_fin, pow_nonce, POW_BITS, betas)) return 12;
+  if (!constraints_hold(t_z.data(), t_zw.data(), q_z.data())) return 10;
   // ---- 2. final codeword has degree < 4: the four upper coefficients of its interpolant over an order-8 coset vanish ----
   if (!fri_final_degree_ok(fin, 1)) return 11;
   // ---- 3. queries: the stage behind zkir::StarkQueryStage (verify_stages.h) gets what has been CHECKED and what has been DRAWN ----
@@ -1465,6 +1502,9 @@ int zkir_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roo
 int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals) {
   return batch_eval_verify_impl(w, len, expect_roots, expect_points, expect_evals, zkir::host_query_stage());
 }
+int zkir_verify_rate(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits) {
+  return zkir::rate_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::host_query_stage());
+}
 
 }  // extern "C"
 
@@ -1683,6 +1723,10 @@ int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
 
 namespace zkir {
 QueryStage host_query_stage() { return QueryStage{nullptr, host_query_run}; }
+int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage) {
+  const RateCheck rate{min_queries, min_pow_bits, &stage};
+  return verify_impl(proof, n_words, expect, true, nullptr, nullptr, nullptr, nullptr, &rate);
+}
 int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage) {
   if (kind == 0) return lowdeg_verify_impl(proof, n_words, expect_roots, stage);
   if (kind == 1) return eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);

@@ -453,6 +453,12 @@ def lib() -> C.CDLL:
         L.zkir_mixed_eval_verify.restype = C.c_int; L.zkir_mixed_eval_verify.argtypes = [V, U64, V, V, V]
         L.zkir_mixed_eval_prove_stages.restype = C.c_int; L.zkir_mixed_eval_prove_stages.argtypes = [V, U32, V, V, V, V, V, V, V, U32, U32, V, U64, C.POINTER(U64), V, V]
         L.zkir_fri_fold_launch.restype = C.c_int; L.zkir_fri_fold_launch.argtypes = [V, V, U32, U32, V, V, V, V]
+    if hasattr(L, "zkir_prove_rate"):                         # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_prove_rate.restype = C.c_int
+        L.zkir_prove_rate.argtypes = [V, C.POINTER(TraceColumnsC), C.POINTER(PublicInputsC), U32, U32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(U64), C.POINTER(C.c_float), V]
+        L.zkir_verify_rate.restype = C.c_int; L.zkir_verify_rate.argtypes = [V, U64, C.POINTER(PublicInputsC), U32, U32]
+        L.zkir_verify_rate_device.restype = C.c_int; L.zkir_verify_rate_device.argtypes = [V, U64, C.POINTER(PublicInputsC), U32, U32, V]
+        L.zkir_prove_rate_last_matrices.restype = C.c_int; L.zkir_prove_rate_last_matrices.argtypes = [V, V, V, V, V, C.POINTER(U64)]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -813,6 +819,24 @@ def batch_eval_proof_words(log_n: int, log_blowup: int, widths, masks, n_points:
     if len(ws) != len(ks) or not 1 <= len(ws) <= 4:
         return 0
     return int(lib().zkir_batch_eval_proof_words(int(log_n), int(log_blowup), len(ws), ws.ctypes.data, ks.ctypes.data, int(n_points), int(num_queries)))
+
+
+RATE_DEFAULT_QUERIES = {1: 50, 2: 25, 3: 17}                  # by log_blowup: about 100 bits from the queries at rate 2^-b, plus the grinding bits
+
+
+def verify_rate(proof, expect: Optional[PublicInputsC] = None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None) -> int:
+    """zkir_verify_rate, on the host — no GPU: 0 = the 'ZKSR' proof (stark.prove_rate: a ZKIR-STARK run at the rate its header states) is accepted and states at least
+    `min_queries` queries and `min_pow_bits` grinding bits; otherwise the number of the failed check (include/zkir_amd.h: zkir_verify's codes for the front, 2 also for too
+    few queries or bits, 5 an embedded proof of another shape, 10 the constraints at zeta, 100 + c for the embedded evaluation proof's code c).  `expect.fri_params` is not
+    consulted.  device=True: zkir_verify_rate_device — the same verdict, the embedded proof's query stage on the GPU; a negative result is a device failure (raised)."""
+    w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
+    e = C.byref(expect) if expect is not None else None
+    if not device:
+        return lib().zkir_verify_rate(w.ctypes.data, len(w), e, int(min_queries), int(min_pow_bits))
+    rc = lib().zkir_verify_rate_device(w.ctypes.data, len(w), e, int(min_queries), int(min_pow_bits), stream)
+    if rc < 0:
+        _raise(-rc)
+    return rc
 
 
 def batch_eval_verify(proof, roots=None, points=None, evals=None, device: bool = False, stream=None) -> int:

@@ -68,7 +68,7 @@ def trace_root(proof) -> list:
 class StarkContext:
     """zkir_stark_ctx: device tables for traces of 2^log_n rows, extended to 2^(log_n + log_blowup) (log_blowup 1, 2, 3: blow-up 2, 4, 8; log_n + log_blowup <= 27).
     Contexts of log_blowup 2 / 3 serve the commitment (lde, merkle_commit, commit_trace); and lowdeg_prove (a low-degree proof of such a
-    commitment, at the context's rate); zkir_prove's proofs are blow-up 2: prove() raises on them."""
+    commitment, at the context's rate); zkir_prove's proofs are blow-up 2: prove() raises on them, prove_rate() proves a run at the context's own rate."""
 
     def __init__(self, log_n: int, log_blowup: int = 1):
         pl._require_gpu()
@@ -566,3 +566,44 @@ def prove(ctx: StarkContext, trace, pub: rt.PublicInputsC, stream=None, want_sta
 
 
 verify = rt.verify
+
+
+def prove_rate(ctx: StarkContext, trace, pub: rt.PublicInputsC, num_queries: Optional[int] = None, pow_bits: int = 12, stream=None, want_stage_ms: bool = False):
+    """zkir_prove_rate: a ZKIR-STARK proof of a whole run in mode 0, 1 or 2 at the CONTEXT's rate (log_blowup 1, 2 or 3), in the 'ZKSR' format: the sections of a prove()
+    proof through the quotient root, then one batch evaluation proof ('ZKBE') of the main, aux and quotient commitments at [zeta, zeta w] (rate_proof_layout finds both).
+    num_queries None: 50 / 25 / 17 by log_blowup; `pub.fri_params` is not consulted.  Returns np.uint32 proof words (and the device ms of its eleven stages: prove()'s first
+    five, then batch_eval_prove's six)."""
+    cols = trace.c if hasattr(trace, "c") else trace
+    nq = rt.RATE_DEFAULT_QUERIES.get(ctx.log_blowup, 50) if num_queries is None else int(num_queries)
+    out = C.POINTER(C.c_uint32)()
+    n_words = C.c_uint64()
+    ms = (C.c_float * 11)()
+    pl._check(rt.lib().zkir_prove_rate(ctx.handle, C.byref(cols), C.byref(pub), nq, int(pow_bits), C.byref(out), C.byref(n_words), ms if want_stage_ms else None, _sp(stream)))
+    proof = np.ctypeslib.as_array(out, shape=(n_words.value,)).copy()
+    rt.lib().zkir_proof_free(out)
+    return (proof, list(ms)) if want_stage_ms else proof
+
+
+def rate_proof_layout(proof) -> dict:
+    """Word offsets inside a 'ZKSR' proof: proof_layout's sections of the STARK part (header .. quotient_root), the header's log_blowup, num_queries and pow_bits, and
+    `eval_proof`: where the embedded 'ZKBE' proof starts (it runs to the end; batch_eval_layout reads it)."""
+    at = proof_layout(proof)
+    at["log_n"], at["log_blowup"] = int(proof[2]), int(proof[5])
+    at["eval_proof"] = at.pop("openings")
+    return at
+
+
+def rate_last_matrices(ctx: StarkContext):
+    """(tests, measurements) zkir_prove_rate_last_matrices: the main, aux and quotient LDE matrices (np.uint32 [blocks][M][8], canonical words) of the context's last
+    prove_rate proof, copied out of its workspace; raises once another proof has used the context."""
+    widths = (C.c_uint32 * 3)()
+    rows = C.c_uint64()
+    pl._check(rt.lib().zkir_prove_rate_last_matrices(ctx.handle, None, None, None, widths, C.byref(rows)))
+    mats = [np.empty(((int(w) + 7) // 8, rows.value, 8), dtype=np.uint32) for w in widths]
+    pl._check(rt.lib().zkir_prove_rate_last_matrices(ctx.handle, mats[0].ctypes.data, mats[1].ctypes.data, mats[2].ctypes.data, widths, C.byref(rows)))
+    return mats
+
+
+def verify_rate(proof, expect=None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None) -> int:
+    """rt.verify_rate; device=True checks the embedded proof's queries on the GPU, on the torch stream `stream` (default: the current one) — the same verdict."""
+    return rt.verify_rate(proof, expect, min_queries, min_pow_bits, device=device, stream=_verify_stream(device, stream))
