@@ -664,13 +664,25 @@ int zkir_verify_queries_last(uint64_t* hash_jobs, uint64_t* value_jobs, uint32_t
  * zkir_proof_free.  The matrices of such a proof rest in canonical form (the commitment layer's), the quotient is evaluated by a kernel of its own over the N << log_blowup
  * coset (quotient_rate_kernel).
  * zkir_verify_rate: host only.  zkir_verify's checks and codes, in its order, through the program, the I/O section, the table side and the challenges (1 malformed header,
- * magic, version; 2 a header range — also: a mode above 2, fewer queries than min_queries or fewer bits than min_pow_bits; 3 a word >= p; 4 truncated; 6 not `expect`'s
+ * magic, version; 2 a header range — also: fewer queries than min_queries or fewer bits than min_pow_bits; 3 a word >= p; 4 truncated; 6 not `expect`'s
  * run (fri_params not compared); 7 initial state; 8 program; 50 - 53 the I/O claim), then: 4 too short for the embedded header and evaluations; 5 the embedded proof is
  * not a 'ZKBE' proof of the outer log_n, log_blowup, three widths, masks {3, 3, 1}, two points, num_queries and pow_bits; 10 sum_c alpha^c C_c(zeta) != Q(zeta) Z_H(zeta)
  * on the embedded proof's evaluations; 100 + c where zkir_batch_eval_verify, told the outer roots and the points [zeta, w_N zeta], answers c (so 101 a wrong length,
  * 102 other roots, 113 other points, 105 grinding, 107 a record's path, 108 layer-0 values ..).
  * zkir_verify_rate_device: the same function with the embedded proof's query stage on the current HIP device (zkir_batch_eval_verify_device's); the same verdict for
- * every input; a NEGATIVE result is a device failure, not a verdict. */
+ * every input; a NEGATIVE result is a device failure, not a verdict.
+ *
+ * zkir_prove_rate_modes: zkir_prove_rate with modes 0 - 4 admitted (zkir_prove_rate keeps its scope and its refusal).  Modes 0 - 2: zkir_prove_rate's words exactly.  Modes
+ * 3 / 4: the public inputs are what zkir_prove takes in those modes — the memory witness made on the device when pub->mem_old == NULL, or the host witness of
+ * zkir_memcheck_witness_of(_mode) + zkir_public_inputs_set_memory; in mode 4 the hash tape and the wide tape — and every refusal zkir_prove makes on them stays, under this
+ * entry's name (an incomplete witness, a cell that overlaps the code segment, an address at or above 2^40, a store into a boundary-cell alias, a hash call outside what a
+ * proof states); a segment stays refused.  The format is 'ZKSR' version 1 with the mode in header word 9: the STARK part is zkir_prove's sections for the mode through the
+ * quotient root (header with the four counter words, program, I/O section, touched cells, (mode 4) hash section and wide tape, ROM | range | memory multiplicities, three
+ * roots), the embedded proof opens widths {264 | 288, 96 | 128, 4}.  The version number is kept on purpose: a verifier built before these modes refuses such a proof with
+ * code 2.  zkir_verify_rate accepts modes 3 / 4 with zkir_verify's codes for the front (54 - 57 the cells and the tapes, 10, 5, 100 + c as above);
+ * zkir_verify_rate_device runs a mode-4 proof's three tape stages on the device as zkir_verify_device does (zkir_verify_last_stages reports them) beside the query stage. */
+int zkir_prove_rate_modes(zkir_stark_ctx* ctx, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
+                          uint64_t* proof_words, float* stage_ms, void* hip_stream);
 int zkir_prove_rate(zkir_stark_ctx* ctx, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
                     uint64_t* proof_words, float* stage_ms, void* hip_stream);
 int zkir_verify_rate(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits);
@@ -715,6 +727,9 @@ void zkir_proof_free(uint32_t* proof);
 /* SURVEY 8(b)'s shape of the call: the WHOLE-RUN handle of zkir_exec in (enable_execution_trace), the proof out as bytes (the little-endian u32 words of zkir_prove; free with
  * zkir_proof_bytes_free).  params may be NULL (mode 0, 50 queries, 12 bits).  Makes and frees a context for the run's size: a caller proving many runs keeps one and uses zkir_prove. */
 int zkir_prove_result(const zkir_result* result, const zkir_prover_params* params, uint8_t** proof, size_t* proof_len);
+/* The same at log_blowup 1, 2 or 3: a context of that rate and zkir_prove_rate_modes — a 'ZKSR' proof (any mode; verify with zkir_verify_rate).  params->num_queries 0 means
+ * 50 / 25 / 17 by rate, params->pow_bits 0 means 12; otherwise the rate entry's ranges (1 .. 128 queries, 0 .. 24 bits).  params may be NULL (mode 0). */
+int zkir_prove_result_rate(const zkir_result* result, const zkir_prover_params* params, uint32_t log_blowup, uint8_t** proof, size_t* proof_len);
 void zkir_proof_bytes_free(uint8_t* proof);
 uint32_t zkir_proof_num_queries(void);            /* the default (50) */
 uint32_t zkir_proof_version(void);                /* of modes 0 / 1 (10) */

@@ -452,6 +452,18 @@ inline std::vector<uint32_t> prove_rate(StarkContext& ctx, const zkir_runtime::E
   zkir_proof_free(words);
   return out;
 }
+// The same with modes 0 - 4 admitted (zkir_prove_rate_modes): `pub` carries what prove() takes in modes 3 / 4 (the memory witness or none, the tapes)
+inline std::vector<uint32_t> prove_rate_modes(StarkContext& ctx, const zkir_runtime::ExecutionResult& result, const zkir_public_inputs& pub, uint32_t num_queries = 0, uint32_t pow_bits = 12,
+                                              void* hip_stream = nullptr) {
+  static const uint32_t by_rate[4] = {50, 50, 25, 17};
+  uint32_t* words = nullptr;
+  uint64_t n = 0;
+  const int rc = zkir_prove_rate_modes(ctx.handle(), result.execution_trace.device_columns(), &pub, num_queries ? num_queries : by_rate[ctx.log_blowup() & 3], pow_bits, &words, &n, nullptr, hip_stream);
+  if (rc != ZKIR_OK) zkir_runtime::detail::raise(rc);
+  std::vector<uint32_t> out(words, words + n);
+  zkir_proof_free(words);
+  return out;
+}
 // 0 = accepted, with at least min_queries queries and min_pow_bits grinding bits; the codes: zkir_amd.h.  on_device: the embedded proof's query stage on the current HIP
 // device — the same verdict (a negative return is a device failure)
 inline int verify_rate(const std::vector<uint32_t>& proof, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits) {

@@ -104,6 +104,12 @@ extern "C" {
     // prove(result, params) -> proof bytes (the handle of zkir_exec keeps the program and the input tape)
     fn zkir_prove_result(result: *const ZkirResult, params: *const ZkirProverParams, proof: *mut *mut u8, len: *mut usize) -> c_int;
     fn zkir_proof_bytes_free(proof: *mut u8);
+    // proofs at the context's own rate ('ZKSR': log_blowup 1, 2, 3), every mode; the drop-in call makes its own context of that rate
+    pub fn zkir_prove_rate_modes(ctx: *mut ZkirStarkCtx, trace: *const ZkirTraceColumns, public: *const ZkirPublicInputs, num_queries: u32, pow_bits: u32, proof: *mut *mut u32,
+                                 words: *mut u64, stage_ms: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn zkir_prove_result_rate(result: *const ZkirResult, params: *const ZkirProverParams, log_blowup: u32, proof: *mut *mut u8, len: *mut usize) -> c_int;
+    pub fn zkir_verify_rate(proof: *const u32, words: u64, expect: *const ZkirPublicInputs, min_queries: u32, min_pow_bits: u32) -> c_int;
+    pub fn zkir_verify_rate_device(proof: *const u32, words: u64, expect: *const ZkirPublicInputs, min_queries: u32, min_pow_bits: u32, stream: *mut c_void) -> c_int;
     fn zkir_abi_version() -> u32;
     // openings of a commitment (rows of a committed B8 matrix + their Merkle paths) and their check: device pointers throughout, _host takes host pointers and needs no device
     pub fn zkir_merkle_opening_words(width: u32, n_leaves: u64, flags: u32) -> u64;

@@ -709,6 +709,34 @@ int zkir_prove_result(const zkir_result* res, const zkir_prover_params* params, 
   *proof_len = (size_t)n_words * 4;
   return ZKIR_OK;
 }
+// zkir_prove_result at another rate: a context of `log_blowup` (1, 2, 3) and zkir_prove_rate_modes — a 'ZKSR' proof of the run in any mode.  params->num_queries 0: 50 / 25 / 17 by
+// rate; params->pow_bits 0: 12; otherwise the rate entry's ranges (1 .. 128, 0 .. 24), which zkir_prove_rate_modes checks — zkir_public_inputs_set_params is not used: its
+// ranges are blow-up 2's, and a 'ZKSR' proof does not consult fri_params.
+int zkir_prove_result_rate(const zkir_result* res, const zkir_prover_params* params, uint32_t log_blowup, uint8_t** proof, size_t* proof_len) {
+  if (!res || !proof || !proof_len) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove_result_rate: null argument"}); return ZKIR_ERR_ARGUMENT; }
+  *proof = nullptr; *proof_len = 0;
+  if (!res->whole_run || !res->log || res->program.empty() || !res->cols.cycle) {
+    zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove_result_rate: the handle must be a whole traced run made by zkir_exec (enable_execution_trace; a window / shard is a segment: zkir_prove)"});
+    return ZKIR_ERR_ARGUMENT;
+  }
+  if (log_blowup < 1 || log_blowup > 3) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_prove_result_rate: log_blowup must be 1, 2 or 3"}); return ZKIR_ERR_ARGUMENT; }
+  const zkir_prover_params dflt{0, 0, 0};
+  const zkir_prover_params* pr = params ? params : &dflt;
+  static const uint32_t by_rate[4] = {50, 50, 25, 17};
+  zkir_public_inputs pub;
+  int rc = zkir_public_inputs_of(res->log, res->program.data(), res->program.size(), res->inputs.data(), res->inputs.size(), pr->mode, &pub);
+  if (rc != ZKIR_OK) return rc;
+  zkir_stark_ctx* ctx = nullptr;
+  rc = zkir_stark_ctx_create(zkir_padded_log_n(pub.n_real), log_blowup, &ctx);
+  if (rc != ZKIR_OK) return rc;
+  uint32_t* words = nullptr; uint64_t n_words = 0;
+  rc = zkir_prove_rate_modes(ctx, &res->cols, &pub, pr->num_queries ? pr->num_queries : by_rate[log_blowup], pr->pow_bits ? pr->pow_bits : 12, &words, &n_words, nullptr, nullptr);
+  zkir_stark_ctx_free(ctx);
+  if (rc != ZKIR_OK) return rc;
+  *proof = reinterpret_cast<uint8_t*>(words);
+  *proof_len = (size_t)n_words * 4;
+  return ZKIR_OK;
+}
 void zkir_proof_bytes_free(uint8_t* proof) { zkir_proof_free(reinterpret_cast<uint32_t*>(proof)); }
 
 }  // extern "C"

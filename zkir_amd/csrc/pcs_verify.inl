@@ -219,12 +219,14 @@ thread_local double pcs_last_ms[3] = {0, 0, 0};                  // upload, kern
 // synchronisation on the caller's stream.
 struct PcsDeviceStage {
   hipStream_t s;
+  bool held = false;                                             // the caller holds the device state's mutex already (zkir_verify_rate_device on a mode-4 proof: the tape stages ran under it)
   int run(const zkir::PcsQueries& Q) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { zkir::set_last_error({ZKIR_ERR_DEVICE, "zkir_*_verify_device: no current HIP device"}); return -ZKIR_ERR_DEVICE; }
     VerifyDevice& V = verify_device(dev);
-    std::lock_guard<std::mutex> lock(V.mu);
-    V.pin.reset();
+    std::unique_lock<std::mutex> lock(V.mu, std::defer_lock);
+    if (!held) lock.lock();
+    V.pin.reset();                                               // (the tape stages are over by the time the queries run: they keep nothing in the staging or the block)
     const uint32_t nq = Q.num_queries, n_slots = 2 * Q.n_mats + Q.n_layers;
     const uint64_t hash_jobs = (uint64_t)nq * n_slots, value_jobs = (uint64_t)nq * (2 + Q.n_layers);
     const size_t n_flags = (size_t)hash_jobs + (size_t)value_jobs;
@@ -326,7 +328,23 @@ int zkir_verify_rate_device(const uint32_t* proof, uint64_t proof_words, const z
   pcs_last_jobs[0] = pcs_last_jobs[1] = 0;
   pcs_last_ms[0] = pcs_last_ms[1] = pcs_last_ms[2] = 0;
   PcsDeviceStage st{(hipStream_t)stream};
-  return guarded([&] { return zkir::rate_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::QueryStage{&st, pcs_device_run}); });
+  // modes 0 - 3 have no tapes (and a proof too short to name its mode has no verdict that depends on them): the host front, the query stage on the device
+  if (!proof || proof_words < 10 || proof[9] != 4) return guarded([&] { return zkir::rate_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::QueryStage{&st, pcs_device_run}); });
+  // mode 4: the three tape stages on the device as in zkir_verify_device (verify_device.inl), under the device state's mutex for the whole call
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { zkir::set_last_error({ZKIR_ERR_DEVICE, "zkir_verify_rate_device: no current HIP device"}); return -ZKIR_ERR_DEVICE; }
+  VerifyDevice* Vp = nullptr;
+  const int src = guarded([&] { Vp = &verify_device(dev); return 0; });
+  if (src) return src;
+  std::lock_guard<std::mutex> lock(Vp->mu);
+  Vp->pin.reset();
+  DeviceTapes dt(*Vp, (hipStream_t)stream);
+  const zkir::TapeStages tapes{&dt, dt_hash_check, dt_wide_check, dt_digests, dt_hash_side, dt_wide_side};
+  st.held = true;
+  const int rc = guarded([&] { return zkir::rate_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::QueryStage{&st, pcs_device_run}, &tapes); });
+  if (dt.stages_run) (void)hipStreamSynchronize((hipStream_t)stream);      // (a verdict reached before a stage's own synchronisation: nothing of this call stays in flight)
+  zkir::verify_note_device_stages(dt.stages_run);
+  return rc;
 }
 
 int zkir_pcs_verify_last_jobs(uint64_t* hash_jobs, uint64_t* value_jobs) {

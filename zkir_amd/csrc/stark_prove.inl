@@ -193,8 +193,8 @@ struct RateRowSrc {
 };
 struct RateZh { uint32_t inv_m[8]; };                           // 1 / Z_H(x_j) by j mod 2^b (Montgomery); entries from 2^b on unused
 
-template <int DEF /* the mode: 0, 1, 2 */>
-__global__ __launch_bounds__(NT, QUOT_WAVES) void quotient_rate_kernel(const uint32_t* __restrict__ L, const uint32_t* __restrict__ AL, uint32_t log_m, uint32_t log_b, const uint32_t* __restrict__ tw_fwd,
+template <int DEF /* the mode: 0 .. 4 */>
+__global__ __launch_bounds__(NT, DEF >= 3 ? QUOT_WAVES_MEM : QUOT_WAVES) void quotient_rate_kernel(const uint32_t* __restrict__ L, const uint32_t* __restrict__ AL, uint32_t log_m, uint32_t log_b, const uint32_t* __restrict__ tw_fwd,
                                                                        const uint32_t* __restrict__ inv_xm1, const ProveParams* __restrict__ pp, uint32_t wn_inv_m, uint32_t w_last_inv_m,
                                                                        uint32_t last_shift, RateZh zh, uint32_t* __restrict__ Q) {
   const uint32_t M = 1u << log_m, H = M >> 1;
@@ -1103,16 +1103,16 @@ extern "C" {
 // do not know the rate — with M = N << log_blowup rows from the LDE on: the matrices rest in CANONICAL form (the evaluation proof reads them), the quotient comes from
 // quotient_rate_kernel, and after zeta the body of zkir_batch_eval_prove (eval_open.inl) opens the three commitments: no second path through the openings, DEEP and the FRI.
 // Its stage_ms: ELEVEN floats, [0..4] as above, [5..10] the evaluation proof's six (weights | evaluations | quotient | FRI commit phase | grinding | query section).
-struct RateArgs { uint32_t num_queries, pow_bits; };
+struct RateArgs { uint32_t num_queries, pow_bits; bool modes; };      // modes: zkir_prove_rate_modes (modes 0 - 4 admitted; the refusals name that entry)
 static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t** proof_out, uint64_t* proof_words, float* stage_ms,
                       void* stream, const RateArgs* rate) {
-  const char* const who = rate ? "zkir_prove_rate" : "zkir_prove";
+  const char* const who = !rate ? "zkir_prove" : rate->modes ? "zkir_prove_rate_modes" : "zkir_prove_rate";
   if (!c || !trace || !pub || !proof_out || !proof_words) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": null argument"}); return ZKIR_ERR_ARGUMENT; }
   if (!rate && !blowup2_only(c, "zkir_prove")) return ZKIR_ERR_ARGUMENT;
   const uint32_t log_b = rate ? c->log_blowup : 1;
   if (rate) {                                                   // every refusal of the rate entry before any launch
-    auto bad = [&](const char* why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string("zkir_prove_rate: ") + why}); return (int)ZKIR_ERR_ARGUMENT; };
-    if (pub->deferred > 2) return bad("pub->deferred (the proof's mode) must be 0, 1 or 2: the memory and wide-arithmetic arguments (modes 3 and 4) are proven at blow-up 2 only (zkir_prove)");
+    auto bad = [&](const char* why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": " + why}); return (int)ZKIR_ERR_ARGUMENT; };
+    if (!rate->modes && pub->deferred > 2) return bad("pub->deferred (the proof's mode) must be 0, 1 or 2: the memory and wide-arithmetic arguments (modes 3 and 4) are proven at blow-up 2 only (zkir_prove)");
     if (pub->writes_before || pub->reads_before) return bad("a segment of a run (writes_before / reads_before) is proven at blow-up 2 only (zkir_prove): this entry proves whole runs");
     if (rate->num_queries < 1 || rate->num_queries > 128) return bad("num_queries must be 1 .. 128");
     if (rate->pow_bits > 24) return bad("pow_bits must be 0 .. 24");
@@ -1164,6 +1164,11 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
     }
   }
   hipStream_t s = (hipStream_t)stream;
+  // the device witness (memcheck.hip) words its refusals for zkir_prove: under the rate entry of every mode the message names that entry in front of them
+  auto witness_refusal = [&](int wrc) {
+    if (rate && rate->modes && wrc == ZKIR_ERR_ARGUMENT) zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": " + zkir_last_error()});
+    return wrc;
+  };
   // (rate) the embedded evaluation proof: main (WM) | aux (WA) | quotient (4) opened at [zeta, zeta w] with masks {3, 3, 1}; its working set lies above this proof's
   const uint32_t rate_widths[3] = {(uint32_t)air::committed_width((int)pub->deferred), (uint32_t)air::aux_width((int)pub->deferred), 4u}, rate_masks[3] = {3u, 3u, 1u};
   size_t rate_arena = 0; uint64_t rate_total = 0;
@@ -1193,7 +1198,7 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
     HIP_OK(hipMalloc(&hw_rows.p, (size_t)pub->n_real * 12 + 256));
     const int wrc = zkir::memcheck_device_hash(trace, pub->n_real, blob, blob_len, pub->hash_outs, pub->n_hash_outs, (uint64_t*)hw_rows.p, (uint32_t*)((uint64_t*)hw_rows.p + pub->n_real),
                                                cell_addr_v, cell_bytes_v, cell_time_v, hw, pin, s);
-    if (wrc) return wrc;
+    if (wrc) return witness_refusal(wrc);
     if (dbg_t) fprintf(stderr, "zkir_prove mode 4: device witness with %llu hash calls (%llu cells, %llu tape words) at %.2f ms\n", (unsigned long long)hw.n_calls, (unsigned long long)hw.n_hcells, (unsigned long long)hw.n_words, since(t_entry));
   }
   // (mode 4) a run with hash calls can touch more cells than it has rows (a 5000-byte BLAKE3 input is 626 cells): the cell arrays and the section buffer are sized by the
@@ -1263,7 +1268,7 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
       } else {
         // scratch = the LDE output buffer, or the block taken above where the program image does not fit it
         rc = zkir::memcheck_device(trace, pub->n_real, blob, blob_len, mc_own ? (void*)dMcScratch : (void*)dL, mc_own ? mc_own : (size_t)WM * N2 * 4, dMemOld, dMemTold, cell_addr_v, cell_bytes_v, cell_time_v, pin, s);
-        if (rc) return rc;
+        if (rc) return witness_refusal(rc);
       }
       rc = WIDE ? zkir_main_trace_wide_launch(trace, pub->n_real, &io, dMemOld, dMemTold, 4 * (uint64_t)n_code, dIoScratch, dM, s) : zkir_main_trace_mem_launch(trace, pub->n_real, &io, dMemOld, dMemTold, dIoScratch, dM, s);
     } else rc = zkir_main_trace_io_launch(trace, pub->n_real, &io, dIoScratch, dM, s);
@@ -1346,7 +1351,7 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
         // (v11) instruction fetch is tied to the program's words: a store into the code would change what the VM executes next (vm.rs:175: strict protection is off) but not what
         // the AIR lets through — mode 3 proves runs whose loads and stores stay off the cells that overlap the code segment, and both verifiers check the list (55)
         char m[200];
-        snprintf(m, sizeof m, "zkir_prove: the run accesses memory cell 0x%llx, which overlaps the code segment [0x1000, 0x%llx): such a run has no mode-3 proof", (unsigned long long)a,
+        snprintf(m, sizeof m, "%s: the run accesses memory cell 0x%llx, which overlaps the code segment [0x1000, 0x%llx): such a run has no mode-3 proof", who, (unsigned long long)a,
                  (unsigned long long)(air::CODE_BASE + 4 * (uint64_t)n_code));
         zkir::set_last_error({ZKIR_ERR_ARGUMENT, m});
         return ZKIR_ERR_ARGUMENT;
@@ -1378,7 +1383,7 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
       rc = hash_tape_check_run(hw.d_tape, hw.d_prefix, hw.n_calls, hw.n_calls, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, dTapeCheck, pin, s, &hrc); if (rc) return rc;
       if (hrc == 55) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": a hash syscall of the run writes its output where it overlaps the code segment: such a run has no mode-4 proof"}); return ZKIR_ERR_ARGUMENT; }
       if (hrc) {
-        char m[200]; snprintf(m, sizeof m, "zkir_prove: the hash tape built from the trace is malformed (check %d): the trace is not a run of the VM", hrc);
+        char m[200]; snprintf(m, sizeof m, "%s: the hash tape built from the trace is malformed (check %d): the trace is not a run of the VM", who, hrc);
         zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
       }
       hash_sec.p = hw.h_tape; hash_sec.n = (size_t)hw.n_words; n_hash_calls = hw.n_calls;
@@ -1386,15 +1391,15 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
       size_t used = 0;
       const int hrc = hashcall::parse_section(pub->hash_section, (size_t)pub->hash_section_words, pub->n_real, air::CODE_BASE + 4 * (uint64_t)n_code, hcalls, &used);
       if (hrc || used != pub->hash_section_words) {
-        char m[160]; snprintf(m, sizeof m, "zkir_prove: the hash section of the public inputs is malformed (check %d): build it with zkir_memcheck_witness_of_mode(.., 4, ..)", hrc ? hrc : 4);
+        char m[192]; snprintf(m, sizeof m, "%s: the hash section of the public inputs is malformed (check %d): build it with zkir_memcheck_witness_of_mode(.., 4, ..)", who, hrc ? hrc : 4);
         zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
       }
       hash_sec.p = pub->hash_section; hash_sec.n = used; n_hash_calls = hcalls.size();
     }
     if (n_hash_calls != io_counts[1]) {
       char m[256];
-      snprintf(m, sizeof m, "zkir_prove: the run makes %u hash syscalls and the public inputs' hash section records %llu: a run with hash syscalls is proven (mode 4) from the host "
-                            "witness (zkir_memcheck_witness_of_mode(.., 4, ..) + zkir_public_inputs_set_memory)", io_counts[1], (unsigned long long)n_hash_calls);
+      snprintf(m, sizeof m, "%s: the run makes %u hash syscalls and the public inputs' hash section records %llu: a run with hash syscalls is proven (mode 4) from the host "
+                            "witness (zkir_memcheck_witness_of_mode(.., 4, ..) + zkir_public_inputs_set_memory)", who, io_counts[1], (unsigned long long)n_hash_calls);
       zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
     }
     const size_t n_chunks_sec = (hash_sec.size() + SECTION_CHUNK - 1) / SECTION_CHUNK;
@@ -1427,7 +1432,7 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
       const uint32_t* r = wrecs[k].w;
       const uint64_t b = (uint64_t)r[4] | ((uint64_t)r[5] << 20) | ((uint64_t)r[6] << 40);
       if (r[0] >= pub->n_real || (k && r[0] <= wrecs[k - 1].w[0]) || r[7] < 3 || r[7] > 7 || (r[7] >= 4 && b == 0)) {
-        char m[160]; snprintf(m, sizeof m, "zkir_prove: the wide-tape record of row %u is not one of an executed MULH / DIVU / REMU / DIV / REM (the trace is not a run of the VM)", r[0]);
+        char m[192]; snprintf(m, sizeof m, "%s: the wide-tape record of row %u is not one of an executed MULH / DIVU / REMU / DIV / REM (the trace is not a run of the VM)", who, r[0]);
         zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT;
       }
       wide_sec.insert(wide_sec.end(), r, r + 8);
@@ -1595,6 +1600,8 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
     for (uint32_t k = 0; k < (1u << log_b); k++) zh.inv_m[k] = bb::to_mont(bb::inv(bb::sub(bb::mul(gN, bb::pow(w_b, k)), 1)));
     const uint32_t log_m = log_n + log_b;
     if (MODE == 1) hipLaunchKernelGGL(quotient_rate_kernel<1>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
+    else if (MODE == 4) hipLaunchKernelGGL(quotient_rate_kernel<4>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
+    else if (MODE == 3) hipLaunchKernelGGL(quotient_rate_kernel<3>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
     else if (MODE == 2) hipLaunchKernelGGL(quotient_rate_kernel<2>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
     else hipLaunchKernelGGL(quotient_rate_kernel<0>, dim3(grid_for(N2)), dim3(NT), 0, s, dL, dAL, log_m, log_b, c->d_tw_fwd, c->d_inv_xm1, dPP, wn_inv_m, w_last_inv_m, last_shift, zh, dQ);
   }
@@ -1629,14 +1636,14 @@ static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, 
     if (const int prc = rate_eval_plan(c, rate_widths, rate_masks, points, rate->num_queries, rate->pow_bits, &rate_arena, &rate_total)) return prc;   // (zeta in the base field: probability 2^-93)
     const uint64_t total = head.size() + rate_total;
     uint32_t* out = (uint32_t*)malloc(total * 4);
-    if (!out) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove_rate: out of host memory"}); return ZKIR_ERR_OTHER; }
+    if (!out) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": out of host memory"}); return ZKIR_ERR_OTHER; }
     memcpy(out, head.data(), head.size() * 4);
     if (stage_ms) run.times(stage_ms, 5);
     const uint32_t* mats[3] = {dL, dAL, dQ};
     const uint32_t* trees[3] = {dTree, dATree, dQTree};
     uint64_t n_eval = 0;
     const int erc = rate_eval_prove(c, mats, rate_widths, trees, rate_masks, points, rate->num_queries, rate->pow_bits, out + head.size(), &n_eval, stage_ms ? stage_ms + 5 : nullptr, s);
-    if (erc || n_eval != rate_total) { free(out); if (!erc) zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_prove_rate: the evaluation proof has another length than planned"}); return erc ? erc : ZKIR_ERR_OTHER; }
+    if (erc || n_eval != rate_total) { free(out); if (!erc) zkir::set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": the evaluation proof has another length than planned"}); return erc ? erc : ZKIR_ERR_OTHER; }
     for (int m = 0; m < 3; m++) { c->rate_mats[m] = mats[m]; c->rate_widths[m] = rate_widths[m]; }
     *proof_out = out; *proof_words = total;
     return ZKIR_OK;
@@ -1767,7 +1774,15 @@ int zkir_prove(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const z
 // A proof at the context's own rate (log_blowup 1, 2 or 3), modes 0 - 2, whole runs: the 'ZKSR' format (zkir_amd.h).  stage_ms: NULL or ELEVEN floats.
 int zkir_prove_rate(zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
                     uint64_t* proof_words, float* stage_ms, void* stream) {
-  const RateArgs rate{num_queries, pow_bits};
+  const RateArgs rate{num_queries, pow_bits, false};
+  return prove_impl(c, trace, pub, proof_out, proof_words, stage_ms, stream, &rate);
+}
+
+// zkir_prove_rate with modes 0 - 4 admitted: modes 0 - 2 give zkir_prove_rate's words; modes 3 / 4 take zkir_prove's public inputs of those modes (the memory witness, the
+// hash tape, the wide tape) and keep its refusals.  Everything such a proof adds lies before zeta; past it the embedded evaluation proof opens 264 | 288, 96 | 128 and 4 columns.
+int zkir_prove_rate_modes(zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
+                          uint64_t* proof_words, float* stage_ms, void* stream) {
+  const RateArgs rate{num_queries, pow_bits, true};
   return prove_impl(c, trace, pub, proof_out, proof_words, stage_ms, stream, &rate);
 }
 

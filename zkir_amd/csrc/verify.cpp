@@ -191,7 +191,8 @@ void initial_state(uint64_t entry, uint32_t st[NS]) {
 
 // A proof at the context's own rate ('ZKSR', zkir_prove_rate): the sections of a zkir_prove proof through the quotient root under its own header, then ONE embedded 'ZKBE'
 // evaluation proof in place of the openings, the FRI part and the queries.  verify_impl's front (header, program, I/O section, table side, challenges up to zeta) is the
-// same code for both formats; `rate` != NULL selects the header's checks and, after zeta, the tail (rate_tail below).
+// same code for both formats — modes 3 and 4 included: the touched cells, the tapes, their digests and the table side all lie before zeta; `rate` != NULL selects the
+// header's checks and, after zeta, the tail (rate_tail below).
 constexpr uint32_t RATE_MAGIC = 0x52534B5Au, RATE_VERSION = 1, BATCH_EVAL_MAGIC = 0x45424B5Au;      // 'ZKSR'; 'ZKBE'
 struct RateCheck { uint32_t min_queries, min_pow_bits; const zkir::QueryStage* stage; };
 int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out = nullptr,
@@ -752,7 +753,6 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   if (w[9] > 4) return 2;
   const int mode = (int)w[9];                                              // 0 default, 1 deferred, 2 default + the I/O argument, 3 = 2 + the memory argument
   if (mode >= 3 && !whole_run) return 2;                                   // the memory check spans the whole run: a mode-3 proof is never a segment
-  if (rate && mode > 2) return 2;                                          // ('ZKSR' v1: modes 0, 1 and 2)
   const int HW = header_words_of(mode), WA = air::aux_width(mode);
   if (!need(HW)) return 1;
   const int WM = (int)w[3], WT = WM + WA;                                  // committed main-trace columns (checked against the mode below); main + aux
@@ -1723,9 +1723,9 @@ int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
 
 namespace zkir {
 QueryStage host_query_stage() { return QueryStage{nullptr, host_query_run}; }
-int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage) {
+int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage, const TapeStages* tapes) {
   const RateCheck rate{min_queries, min_pow_bits, &stage};
-  return verify_impl(proof, n_words, expect, true, nullptr, nullptr, nullptr, nullptr, &rate);
+  return verify_impl(proof, n_words, expect, true, nullptr, nullptr, tapes, nullptr, &rate);
 }
 int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage) {
   if (kind == 0) return lowdeg_verify_impl(proof, n_words, expect_roots, stage);

@@ -56,8 +56,10 @@ struct QueryStage { void* self; int (*run)(void* self, const PcsQueries& q); };
 QueryStage host_query_stage();                                   // the loop of verify.cpp
 // the three verifiers, by the proof's kind (0 'ZKLD', 1 'ZKEV', 2 'ZKBE'; 'ZKLD' has one root and no points): everything but the query stage is verify.cpp's host code
 int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage);
-// a 'ZKSR' proof (zkir_verify_rate): verify.cpp's STARK front and constraint check on the host, the embedded evaluation proof's query stage behind `stage`
-int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage);
+// a 'ZKSR' proof (zkir_verify_rate): verify.cpp's STARK front and constraint check on the host, the embedded evaluation proof's query stage behind `stage`; a mode-4
+// proof's three tape stages behind `tapes` (NULL: the host forms)
+int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage,
+                           const TapeStages* tapes = nullptr);
 
 // ---- the QUERY STAGE of the mixed-height verifier (zkir_mixed_eval_verify and zkir_mixed_eval_verify_device: a 'ZKMH' proof) ----
 // Checks 6 .. 11 of all the queries, handed over as above: after checks 1 .. 5, 12 and 13 and the sampling.  The proof has ONE FRI and one layer-0 rule per GROUP: g[h] is a

@@ -459,6 +459,10 @@ def lib() -> C.CDLL:
         L.zkir_verify_rate.restype = C.c_int; L.zkir_verify_rate.argtypes = [V, U64, C.POINTER(PublicInputsC), U32, U32]
         L.zkir_verify_rate_device.restype = C.c_int; L.zkir_verify_rate_device.argtypes = [V, U64, C.POINTER(PublicInputsC), U32, U32, V]
         L.zkir_prove_rate_last_matrices.restype = C.c_int; L.zkir_prove_rate_last_matrices.argtypes = [V, V, V, V, V, C.POINTER(U64)]
+    if hasattr(L, "zkir_prove_rate_modes"):
+        L.zkir_prove_rate_modes.restype = C.c_int; L.zkir_prove_rate_modes.argtypes = L.zkir_prove_rate.argtypes
+        L.zkir_prove_result_rate.restype = C.c_int
+        L.zkir_prove_result_rate.argtypes = [V, C.POINTER(ProverParamsC), U32, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -826,7 +830,7 @@ RATE_DEFAULT_QUERIES = {1: 50, 2: 25, 3: 17}                  # by log_blowup: a
 
 def verify_rate(proof, expect: Optional[PublicInputsC] = None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None) -> int:
     """zkir_verify_rate, on the host — no GPU: 0 = the 'ZKSR' proof (stark.prove_rate: a ZKIR-STARK run at the rate its header states) is accepted and states at least
-    `min_queries` queries and `min_pow_bits` grinding bits; otherwise the number of the failed check (include/zkir_amd.h: zkir_verify's codes for the front, 2 also for too
+    `min_queries` queries and `min_pow_bits` grinding bits; otherwise the number of the failed check (include/zkir_amd.h: zkir_verify's codes for the front — 54 - 57 in modes 3 / 4 —, 2 also for too
     few queries or bits, 5 an embedded proof of another shape, 10 the constraints at zeta, 100 + c for the embedded evaluation proof's code c).  `expect.fri_params` is not
     consulted.  device=True: zkir_verify_rate_device — the same verdict, the embedded proof's query stage on the GPU; a negative result is a device failure (raised)."""
     w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
@@ -1163,6 +1167,22 @@ class ExecutionResult:
         p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
         L = lib()
         rc = L.zkir_prove_result(self._r, C.byref(pr), C.byref(p), C.byref(n))
+        if rc != ZKIR_OK:
+            _raise(rc)
+        try:
+            return np.frombuffer(C.string_at(p, n.value), dtype="<u4").copy()
+        finally:
+            L.zkir_proof_bytes_free(p)
+
+    def prove_rate(self, mode: int, log_blowup: int, num_queries: int = 0, pow_bits: int = 0) -> np.ndarray:
+        """zkir_prove_result_rate: prove() at log_blowup 1, 2 or 3 — a 'ZKSR' proof of this whole traced run in any mode (verify_rate checks it).  num_queries 0: 50 / 25 / 17
+        by rate; pow_bits 0: 12; otherwise 1 .. 128 queries and 0 .. 24 bits."""
+        if not self._r:
+            raise ValueError("prove_rate() needs the device handle of a traced run (VMConfig.enable_execution_trace)")
+        pr = ProverParamsC(int(mode), int(num_queries), int(pow_bits))
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+        L = lib()
+        rc = L.zkir_prove_result_rate(self._r, C.byref(pr), int(log_blowup), C.byref(p), C.byref(n))
         if rc != ZKIR_OK:
             _raise(rc)
         try:

@@ -68,7 +68,7 @@ def trace_root(proof) -> list:
 class StarkContext:
     """zkir_stark_ctx: device tables for traces of 2^log_n rows, extended to 2^(log_n + log_blowup) (log_blowup 1, 2, 3: blow-up 2, 4, 8; log_n + log_blowup <= 27).
     Contexts of log_blowup 2 / 3 serve the commitment (lde, merkle_commit, commit_trace); and lowdeg_prove (a low-degree proof of such a
-    commitment, at the context's rate); zkir_prove's proofs are blow-up 2: prove() raises on them, prove_rate() proves a run at the context's own rate."""
+    commitment, at the context's rate); zkir_prove's proofs are blow-up 2: prove() raises on them, prove_rate() (modes 0 - 2) and prove_rate_modes() (every mode) prove a run at the context's own rate."""
 
     def __init__(self, log_n: int, log_blowup: int = 1):
         pl._require_gpu()
@@ -584,8 +584,23 @@ def prove_rate(ctx: StarkContext, trace, pub: rt.PublicInputsC, num_queries: Opt
     return (proof, list(ms)) if want_stage_ms else proof
 
 
+def prove_rate_modes(ctx: StarkContext, trace, pub: rt.PublicInputsC, num_queries: Optional[int] = None, pow_bits: int = 12, stream=None, want_stage_ms: bool = False):
+    """zkir_prove_rate_modes: prove_rate with modes 0 - 4 admitted.  Modes 0 - 2 give prove_rate's words; in modes 3 / 4 `pub` is what prove() takes there (no witness: the
+    memory witness, and a hash run's tape, are made on the device; or the host witness of rt.memcheck_witness; mode 4: the tapes), with prove()'s refusals.  The proof is a
+    'ZKSR' proof with the mode in word 9; rt.verify_rate checks it, rate_proof_layout and rate_last_matrices read it."""
+    cols = trace.c if hasattr(trace, "c") else trace
+    nq = rt.RATE_DEFAULT_QUERIES.get(ctx.log_blowup, 50) if num_queries is None else int(num_queries)
+    out = C.POINTER(C.c_uint32)()
+    n_words = C.c_uint64()
+    ms = (C.c_float * 11)()
+    pl._check(rt.lib().zkir_prove_rate_modes(ctx.handle, C.byref(cols), C.byref(pub), nq, int(pow_bits), C.byref(out), C.byref(n_words), ms if want_stage_ms else None, _sp(stream)))
+    proof = np.ctypeslib.as_array(out, shape=(n_words.value,)).copy()
+    rt.lib().zkir_proof_free(out)
+    return (proof, list(ms)) if want_stage_ms else proof
+
+
 def rate_proof_layout(proof) -> dict:
-    """Word offsets inside a 'ZKSR' proof: proof_layout's sections of the STARK part (header .. quotient_root), the header's log_blowup, num_queries and pow_bits, and
+    """Word offsets inside a 'ZKSR' proof of any mode: proof_layout's sections of the STARK part (header .. quotient_root; modes 3 / 4: the touched cells, the tapes), the header's log_blowup, num_queries and pow_bits, and
     `eval_proof`: where the embedded 'ZKBE' proof starts (it runs to the end; batch_eval_layout reads it)."""
     at = proof_layout(proof)
     at["log_n"], at["log_blowup"] = int(proof[2]), int(proof[5])
