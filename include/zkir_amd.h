@@ -687,6 +687,57 @@ int zkir_prove_rate(zkir_stark_ctx* ctx, const zkir_trace_columns* trace, const 
                     uint64_t* proof_words, float* stage_ms, void* hip_stream);
 int zkir_verify_rate(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits);
 int zkir_verify_rate_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, void* hip_stream);
+/* A RUN PROVEN IN SEGMENTS AT THE CONTEXT'S OWN RATE (DESIGN.md "Run segments at blow-up 4 and 8"; INTEGRATION.md has the recipe).
+ * zkir_prove_rate_segment: zkir_prove_rate's signature, stage_ms and format ('ZKSR' version 1, unchanged) for the K1 output of a ROW SHARD of a run, or of a whole run, in
+ * mode 0, 1 or 2 on a context of log_blowup 1, 2 or 3.  The header's boundary states are the trace's first and last rows; in mode 2 the four counter words follow from
+ * pub->writes_before / reads_before as zkir_prove forms them for a segment, and pub carries the WHOLE run's tapes, halt reason and io digest.  pub->n_real is the shard's
+ * row count.  On a whole run (writes_before = reads_before = 0, first row the initial state) the words are zkir_prove_rate's exactly.  ZKIR_ERR_ARGUMENT with a message
+ * that names this entry, before anything is launched, for modes 3 and 4 (the memory argument spans the run: zkir_prove refuses such segments too); zkir_prove_rate's other
+ * refusals stay (num_queries 1 .. 128, pow_bits 0 .. 24, log_n against n_real, the public inputs).  zkir_prove_rate and zkir_prove_rate_modes keep refusing
+ * writes_before / reads_before.  Not covered: segments in modes 3 / 4; zkir_prove_result_rate on a shard handle (zkir_prove_result refuses one too).
+ * zkir_verify_rate_segment: host only.  zkir_verify_rate without check 7 — the same codes in the same order; a mode >= 3 proof is never a segment: 2.  On acceptance the
+ * header's boundary states are written to first_state / last_state (68 words each; either may be NULL).
+ * zkir_verify_rate_chain: host only.  zkir_verify_chain's meaning and codes for 'ZKSR' segments, through the same linking code: 40 an empty chain (or null arguments);
+ * 1000 (i + 1) + c: segment i fails zkir_verify_rate_segment(.., NULL, min_queries, min_pow_bits) with code c (c <= 113); 41 the first state is not the VM's initial state;
+ * 42 a segment does not start in the state its predecessor ends in; 43 a segment's mode, entry point or digests (header words 9 .. 20) or its num_queries, log_blowup or
+ * pow_bits (words 4, 5, 6) are not segment 0's, or the chain is not `expect`'s run; 44 expect->n_real != sum (n_i - 1) + 1 (neighbours share a row); mode 2: 45, 46, 51,
+ * 50, 52 / 53 over the I/O sections and the counters, as in zkir_verify_chain.  min_queries / min_pow_bits hold for every segment; expect->fri_params is not consulted.  A
+ * chain of one mode >= 3 proof is zkir_verify_rate.  The segments' host fronts run segment after segment up to the first one that fails there, then ONE run of the query
+ * stage over the collected segments' embedded proofs, then the verdict is resolved in segment order (per segment its code, then 43), the linking checks last.
+ *
+ * THE COMMITMENT LAYER'S QUERY STAGE FOR MANY PROOFS (zkir_amd/csrc/pcs_verify_many.inl).  The four *_device entries below run checks 7 - 11 of ALL their proofs' queries on
+ * the current HIP device as one batch: the proofs may differ in log_n, log_blowup (so the final layer and the fold schedule), the number of matrices (1 .. 4) and their
+ * widths, the points (0 .. 2), the masks and the number of queries — a per-proof shape record lies in device memory and a job finds its proof in a prefix table.  One
+ * staged upload, two launches, one download of the flags and one synchronisation on hip_stream per call, however many proofs; nothing is launched where no proof reaches its
+ * queries.  Only 'ZKBE' / 'ZKEV' / 'ZKLD' words and the stage's tables are uploaded: of a 'ZKSR' proof the embedded evaluation proof, never its program, cells or tapes.
+ * Every extent a kernel reads is a function of header words the host has checked (a proof's length is checked EXACTLY before its queries), the row a job opens is the
+ * transcript's sample.  The verdict is the host entry's for every input.  A NEGATIVE result is a device failure, not a verdict (zkir_last_error says which).  Calls on one
+ * device are serialised inside.  zkir_verify_queries_last reports the calling thread's last stage run: hash jobs = sum_i nq_i (2 n_mats_i + n_layers_i), value jobs =
+ * sum_i nq_i (2 + n_layers_i), launches 0 or 2, uploaded words.
+ * zkir_verify_rate_segment_device: zkir_verify_rate_segment's verdict; a batch of one.
+ * zkir_verify_rate_chain_device: zkir_verify_rate_chain's verdict for every input, all segments' queries as one stage run.  A chain of one mode >= 3 proof is
+ * zkir_verify_rate_device.
+ * zkir_verify_rate_many_device: n independent WHOLE-RUN 'ZKSR' proofs of any mode and rate, 1 <= n <= 1024 (else ZKIR_ERR_ARGUMENT, as for a null proofs, proof_words or
+ * verdicts); expects, min_queries and min_pow_bits may be NULL (no expectation; 1; 0), and so may entries of expects.  Returns 0 with verdicts[i] = what
+ * zkir_verify_rate(proofs[i], proof_words[i], expects[i], min_queries[i], min_pow_bits[i]) returns for every i, or an error (ZKIR_ERR_ARGUMENT, a negative value) with NO
+ * verdict written.  A mode-4 proof's tape stages run on the device as in zkir_verify_rate_device, proof after proof, before the shared query stage.
+ * zkir_pcs_verify_many_device: n stand-alone proofs of the commitment layer, 1 <= n <= 1024; kinds[i] = 0 'ZKLD', 1 'ZKEV', 2 'ZKBE' (anything else: ZKIR_ERR_ARGUMENT);
+ * expect_roots / expect_points / expect_evals may be NULL and so may their entries (sized as the proof's header states, as in the single entries).  Returns 0 with
+ * verdicts[i] = what zkir_lowdeg_verify / zkir_eval_verify / zkir_batch_eval_verify answers, or an error with NO verdict written. */
+int zkir_prove_rate_segment(zkir_stark_ctx* ctx, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
+                            uint64_t* proof_words, float* stage_ms, void* hip_stream);
+int zkir_verify_rate_segment(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, uint32_t first_state[68],
+                             uint32_t last_state[68]);
+int zkir_verify_rate_chain(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, uint32_t min_queries,
+                           uint32_t min_pow_bits);
+int zkir_verify_rate_segment_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits,
+                                    uint32_t first_state[68], uint32_t last_state[68], void* hip_stream);
+int zkir_verify_rate_chain_device(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, uint32_t min_queries,
+                                  uint32_t min_pow_bits, void* hip_stream);
+int zkir_verify_rate_many_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                 const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts, void* hip_stream);
+int zkir_pcs_verify_many_device(const uint32_t* kinds, const uint32_t* const* proofs, const uint64_t* proof_words, const uint32_t* const* expect_roots,
+                                const uint32_t* const* expect_points, const uint32_t* const* expect_evals, uint32_t n, int32_t* verdicts, void* hip_stream);
 /* diagnostics of the calling thread's last zkir_verify* call: host wall time in ms of [0] parsing (the tapes' record checks among it), [1] the sections' chunk digests,
  * [2] the hash tape's share of the table side, [3] the wide tape's, [4] the rest; *device_stages = how many of these stages ran on the device (0 for every host entry).
  * Either pointer may be NULL.  ZKIR_ERR_ARGUMENT before the thread's first verification.  ZKIR_VERIFY_TIMES in the environment prints the clocks on stderr. */

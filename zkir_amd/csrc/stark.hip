@@ -1126,3 +1126,4 @@ int zkir_merkle_cap_launch(const zkir_stark_ctx* c, uint32_t* tree, uint64_t n_d
 #include "pcs_verify.inl"
 #include "mixed_verify.inl"
 #include "stark_verify.inl"
+#include "pcs_verify_many.inl"

@@ -1103,17 +1103,18 @@ extern "C" {
 // do not know the rate — with M = N << log_blowup rows from the LDE on: the matrices rest in CANONICAL form (the evaluation proof reads them), the quotient comes from
 // quotient_rate_kernel, and after zeta the body of zkir_batch_eval_prove (eval_open.inl) opens the three commitments: no second path through the openings, DEEP and the FRI.
 // Its stage_ms: ELEVEN floats, [0..4] as above, [5..10] the evaluation proof's six (weights | evaluations | quotient | FRI commit phase | grinding | query section).
-struct RateArgs { uint32_t num_queries, pow_bits; bool modes; };      // modes: zkir_prove_rate_modes (modes 0 - 4 admitted; the refusals name that entry)
+struct RateArgs { uint32_t num_queries, pow_bits; bool modes; bool segment = false; };      // modes: zkir_prove_rate_modes (modes 0 - 4 admitted; the refusals name that entry); segment: zkir_prove_rate_segment (modes 0 - 2, writes_before / reads_before admitted)
 static int prove_impl(const zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t** proof_out, uint64_t* proof_words, float* stage_ms,
                       void* stream, const RateArgs* rate) {
-  const char* const who = !rate ? "zkir_prove" : rate->modes ? "zkir_prove_rate_modes" : "zkir_prove_rate";
+  const char* const who = !rate ? "zkir_prove" : rate->segment ? "zkir_prove_rate_segment" : rate->modes ? "zkir_prove_rate_modes" : "zkir_prove_rate";
   if (!c || !trace || !pub || !proof_out || !proof_words) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": null argument"}); return ZKIR_ERR_ARGUMENT; }
   if (!rate && !blowup2_only(c, "zkir_prove")) return ZKIR_ERR_ARGUMENT;
   const uint32_t log_b = rate ? c->log_blowup : 1;
   if (rate) {                                                   // every refusal of the rate entry before any launch
     auto bad = [&](const char* why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": " + why}); return (int)ZKIR_ERR_ARGUMENT; };
+    if (rate->segment && pub->deferred > 2) return bad("pub->deferred (the proof's mode) must be 0, 1 or 2: the memory argument of modes 3 and 4 spans the whole run, so such a run is never proven in segments (zkir_prove_rate_modes proves it whole)");
     if (!rate->modes && pub->deferred > 2) return bad("pub->deferred (the proof's mode) must be 0, 1 or 2: the memory and wide-arithmetic arguments (modes 3 and 4) are proven at blow-up 2 only (zkir_prove)");
-    if (pub->writes_before || pub->reads_before) return bad("a segment of a run (writes_before / reads_before) is proven at blow-up 2 only (zkir_prove): this entry proves whole runs");
+    if (!rate->segment && (pub->writes_before || pub->reads_before)) return bad("a segment of a run (writes_before / reads_before) is proven at blow-up 2 only (zkir_prove): this entry proves whole runs");
     if (rate->num_queries < 1 || rate->num_queries > 128) return bad("num_queries must be 1 .. 128");
     if (rate->pow_bits > 24) return bad("pow_bits must be 0 .. 24");
   }
@@ -1783,6 +1784,15 @@ int zkir_prove_rate(zkir_stark_ctx* c, const zkir_trace_columns* trace, const zk
 int zkir_prove_rate_modes(zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
                           uint64_t* proof_words, float* stage_ms, void* stream) {
   const RateArgs rate{num_queries, pow_bits, true};
+  return prove_impl(c, trace, pub, proof_out, proof_words, stage_ms, stream, &rate);
+}
+
+// A SEGMENT of a run (the K1 output of a row shard) or a whole run at the context's own rate, modes 0 - 2: the 'ZKSR' format unchanged — the header's boundary states are
+// the trace's first and last rows, a mode-2 proof's counter words follow from pub->writes_before / reads_before as zkir_prove forms them.  On a whole run the words are
+// zkir_prove_rate's.  zkir_verify_rate_segment / zkir_verify_rate_chain check such proofs.
+int zkir_prove_rate_segment(zkir_stark_ctx* c, const zkir_trace_columns* trace, const zkir_public_inputs* pub, uint32_t num_queries, uint32_t pow_bits, uint32_t** proof_out,
+                            uint64_t* proof_words, float* stage_ms, void* stream) {
+  const RateArgs rate{num_queries, pow_bits, false, true};
   return prove_impl(c, trace, pub, proof_out, proof_words, stage_ms, stream, &rate);
 }
 

@@ -597,26 +597,12 @@ int zkir_verify_chain(const uint32_t* const* proofs, const uint64_t* lens, uint3
 
 // The segments' host parts run first, segment after segment up to the first one that fails there; then ONE run of the stage over the collected segments' queries; then
 // the verdict in the order the sequential verifier returns it: per segment its host code, its query code, check 30, check 43 — then the linking checks.
-int zkir::verify_chain_with_stage(const uint32_t* const* proofs, const uint64_t* lens, uint32_t n, const zkir_public_inputs* expect, const zkir::StarkQueryStage& stage) {
-  if (!proofs || !lens || n < 1) return 40;
-  std::vector<uint32_t> st((size_t)n * 2 * NS), cnt((size_t)n * 4, 0);
-  uint64_t total = 1;
-  std::vector<zkir::StarkQueries> Q(n);
-  uint32_t n_ok = 0; int host_rc = 0;
-  for (; n_ok < n; n_ok++) {
-    host_rc = verify_impl(proofs[n_ok], lens[n_ok], nullptr, false, &st[(size_t)n_ok * 2 * NS], &cnt[(size_t)n_ok * 4], nullptr, &Q[n_ok]);
-    if (host_rc) break;
-  }
-  std::vector<int> codes(n_ok ? n_ok : 1, 0);
-  if (n_ok) { const int src = stage.run(stage.self, Q.data(), n_ok, codes.data()); if (src) return src; }
-  for (uint32_t i = 0; i < n_ok; i++) {
-    const int rc = codes[i] ? codes[i] : zkir::stark_length_check(Q[i]);
-    if (rc) return 1000 * (int)(i + 1) + rc;
-    const uint32_t* w = proofs[i];
-    total += ((uint64_t)w[7] | ((uint64_t)w[8] << 30)) - 1;
-    if (memcmp(w + 9, proofs[0] + 9, 12 * 4)) return 43;                   // mode, entry point, program digest, io digest
-  }
-  if (n_ok < n) return 1000 * (int)(n_ok + 1) + host_rc;
+namespace {
+// What zkir_verify_chain and zkir_verify_rate_chain share once every segment is accepted on its own: checks 41, 42, `expect` (43 / 44) and the mode-2 argument across the
+// segments.  st: per segment first | last state; cnt: per segment the four counter words; total: sum (n_i - 1) + 1.  rate: 'ZKSR' segments — expect->fri_params is not
+// consulted (the segments' own parameters are compared with segment 0's by the caller).
+int chain_link_checks(const uint32_t* const* proofs, const uint64_t* lens, uint32_t n, const zkir_public_inputs* expect, const std::vector<uint32_t>& st, const std::vector<uint32_t>& cnt,
+                      uint64_t total, bool rate) {
   const uint32_t* w0 = proofs[0];
   const uint64_t entry = (uint64_t)w0[10] | ((uint64_t)w0[11] << 20) | ((uint64_t)w0[12] << 40);
   uint32_t init[NS];
@@ -626,8 +612,9 @@ int zkir::verify_chain_with_stage(const uint32_t* const* proofs, const uint64_t*
     if (memcmp(&st[(size_t)i * 2 * NS], &st[(size_t)(i - 1) * 2 * NS + NS], NS * 4)) return 42;
   if (expect) {
     if (expect->deferred != w0[9] || expect->entry_point != entry || memcmp(expect->program_digest, w0 + 13, 16) || memcmp(expect->io_digest, w0 + 17, 16)) return 43;
-    for (uint32_t i = 0; i < n; i++)                                        // every segment made with the parameters the caller expects
-      if (!air::fri_params_ok(expect->fri_params) || proofs[i][4] != (uint32_t)air::num_queries_of(expect->fri_params) || proofs[i][6] != (uint32_t)air::pow_bits_of(expect->fri_params)) return 43;
+    if (!rate)
+      for (uint32_t i = 0; i < n; i++)                                      // every segment made with the parameters the caller expects
+        if (!air::fri_params_ok(expect->fri_params) || proofs[i][4] != (uint32_t)air::num_queries_of(expect->fri_params) || proofs[i][6] != (uint32_t)air::pow_bits_of(expect->fri_params)) return 43;
     if (expect->n_real != total) return 44;
   }
   if (w0[9] == 2) {
@@ -650,6 +637,56 @@ int zkir::verify_chain_with_stage(const uint32_t* const* proofs, const uint64_t*
     if (hb) return hb;
   }
   return 0;
+}
+}  // namespace
+
+int zkir::verify_chain_with_stage(const uint32_t* const* proofs, const uint64_t* lens, uint32_t n, const zkir_public_inputs* expect, const zkir::StarkQueryStage& stage) {
+  if (!proofs || !lens || n < 1) return 40;
+  std::vector<uint32_t> st((size_t)n * 2 * NS), cnt((size_t)n * 4, 0);
+  uint64_t total = 1;
+  std::vector<zkir::StarkQueries> Q(n);
+  uint32_t n_ok = 0; int host_rc = 0;
+  for (; n_ok < n; n_ok++) {
+    host_rc = verify_impl(proofs[n_ok], lens[n_ok], nullptr, false, &st[(size_t)n_ok * 2 * NS], &cnt[(size_t)n_ok * 4], nullptr, &Q[n_ok]);
+    if (host_rc) break;
+  }
+  std::vector<int> codes(n_ok ? n_ok : 1, 0);
+  if (n_ok) { const int src = stage.run(stage.self, Q.data(), n_ok, codes.data()); if (src) return src; }
+  for (uint32_t i = 0; i < n_ok; i++) {
+    const int rc = codes[i] ? codes[i] : zkir::stark_length_check(Q[i]);
+    if (rc) return 1000 * (int)(i + 1) + rc;
+    const uint32_t* w = proofs[i];
+    total += ((uint64_t)w[7] | ((uint64_t)w[8] << 30)) - 1;
+    if (memcmp(w + 9, proofs[0] + 9, 12 * 4)) return 43;                   // mode, entry point, program digest, io digest
+  }
+  if (n_ok < n) return 1000 * (int)(n_ok + 1) + host_rc;
+  return chain_link_checks(proofs, lens, n, expect, st, cnt, total, false);
+}
+
+// The same for 'ZKSR' segments (zkir_verify_rate_chain): the fronts run with a collecting stage (verify_stages.h) up to the first segment that fails there, ONE run of the
+// list stage serves the collected embedded proofs, and the verdict is the sequential verifier's: per segment its code (100 + c for the embedded proof's query code c), then
+// check 43 — here also the rate and the parameters (header words 4, 5, 6) against segment 0's — then the linking checks.
+int zkir::rate_chain_with_stage(const uint32_t* const* proofs, const uint64_t* lens, uint32_t n, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits,
+                                const zkir::PcsManyStage& stage) {
+  if (!proofs || !lens || n < 1) return 40;
+  std::vector<uint32_t> st((size_t)n * 2 * NS), cnt((size_t)n * 4, 0);
+  uint64_t total = 1;
+  std::vector<zkir::PcsCollected> Q(n);
+  uint32_t n_ok = 0; int host_rc = 0;
+  for (; n_ok < n; n_ok++) {
+    host_rc = zkir::rate_segment_verify_with_stage(proofs[n_ok], lens[n_ok], nullptr, min_queries, min_pow_bits, zkir::pcs_collect_stage(&Q[n_ok]), &st[(size_t)n_ok * 2 * NS], &cnt[(size_t)n_ok * 4]);
+    if (host_rc) break;
+  }
+  std::vector<int> codes(n_ok ? n_ok : 1, 0);
+  if (n_ok) { const int src = stage.run(stage.self, Q.data(), n_ok, codes.data()); if (src) return src; }
+  for (uint32_t i = 0; i < n_ok; i++) {
+    if (codes[i]) return 1000 * (int)(i + 1) + 100 + codes[i];
+    const uint32_t* w = proofs[i];
+    total += ((uint64_t)w[7] | ((uint64_t)w[8] << 30)) - 1;
+    if (memcmp(w + 9, proofs[0] + 9, 12 * 4) || memcmp(w + 4, proofs[0] + 4, 3 * 4)) return 43;      // mode, entry point, digests; num_queries, log_blowup, pow_bits
+  }
+  if (n_ok < n) return 1000 * (int)(n_ok + 1) + host_rc;
+  return chain_link_checks(proofs, lens, n, expect, st, cnt, total, true);
 }
 
 extern "C" {
@@ -1505,6 +1542,18 @@ int zkir_batch_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
 int zkir_verify_rate(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits) {
   return zkir::rate_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::host_query_stage());
 }
+// a 'ZKSR' proof of a SEGMENT of a run (zkir_prove_rate_segment): zkir_verify_rate without check 7; the boundary states out on acceptance
+int zkir_verify_rate_segment(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, uint32_t first_state[68],
+                             uint32_t last_state[68]) {
+  uint32_t st[2 * NS];
+  const int rc = zkir::rate_segment_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::host_query_stage(), st, nullptr);
+  if (rc == 0) { if (first_state) memcpy(first_state, st, NS * 4); if (last_state) memcpy(last_state, st + NS, NS * 4); }
+  return rc;
+}
+int zkir_verify_rate_chain(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits) {
+  if (proofs && proof_words && n_segments == 1 && proofs[0] && proof_words[0] > 9 && proofs[0][9] >= 3) return zkir_verify_rate(proofs[0], proof_words[0], expect, min_queries, min_pow_bits);      // a whole run by itself
+  return zkir::rate_chain_with_stage(proofs, proof_words, n_segments, expect, min_queries, min_pow_bits, zkir::host_pcs_many_stage());
+}
 
 }  // extern "C"
 
@@ -1732,6 +1781,29 @@ int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, con
   if (kind == 1) return eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
   return batch_eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
 }
+int rate_segment_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage,
+                                   uint32_t* states_out, uint32_t* counters_out) {
+  const RateCheck rate{min_queries, min_pow_bits, &stage};
+  return verify_impl(proof, n_words, expect, false, states_out, counters_out, nullptr, nullptr, &rate);
+}
+namespace {
+int pcs_collect_run(void* self, const PcsQueries& Q) {
+  PcsCollected& c = *static_cast<PcsCollected*>(self);
+  c.q = Q;
+  c.qs.assign(Q.qs, Q.qs + Q.num_queries);
+  c.betas_m.assign(Q.betas_m, Q.betas_m + 4 * (size_t)Q.n_layers);
+  c.gamma_m.assign(Q.gamma_m, Q.gamma_m + 4 * (size_t)Q.n_gamma);
+  c.q.qs = c.qs.data(); c.q.betas_m = c.betas_m.data(); c.q.gamma_m = c.gamma_m.data();
+  c.filled = true;
+  return 0;
+}
+int host_pcs_many_run(void*, const PcsCollected* list, uint32_t n, int* codes) {
+  for (uint32_t i = 0; i < n; i++) { codes[i] = host_query_run(nullptr, list[i].q); if (codes[i] < 0) return codes[i]; }
+  return 0;
+}
+}  // namespace
+QueryStage pcs_collect_stage(PcsCollected* out) { return QueryStage{out, pcs_collect_run}; }
+PcsManyStage host_pcs_many_stage() { return PcsManyStage{nullptr, host_pcs_many_run}; }
 MixedQueryStage host_mixed_query_stage() { return MixedQueryStage{nullptr, host_mixed_query_run}; }
 int mixed_eval_verify_with_stage(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const MixedQueryStage& stage) {
   return mixed_eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);

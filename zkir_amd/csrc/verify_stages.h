@@ -61,6 +61,27 @@ int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, con
 int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage,
                            const TapeStages* tapes = nullptr);
 
+// ---- the query stage over a LIST of proofs (zkir_verify_rate_chain, zkir_verify_rate_many_device, zkir_pcs_verify_many_device and their siblings) ----
+// A PcsCollected OWNS what a PcsQueries points at except the proof (samples, gamma table, betas): pcs_collect_stage is a QueryStage that copies the description it is handed
+// into `out` and answers 0, so a caller runs the host fronts of several proofs first — proof after proof, each up to the point where its queries would start — and then ONE
+// run of a PcsManyStage over all it has collected: codes[i] = 0 or 6 .. 11, proof i's first failing check, lowest query first.  run returns 0, or a negative value (no verdict
+// for any of them).  verify.cpp fills the stage with its host loop (no HIP call), pcs_verify_many.inl with two kernels that serve proofs whose shapes differ.
+struct PcsCollected {
+  PcsQueries q{};
+  std::vector<uint32_t> qs, betas_m, gamma_m;
+  bool filled = false;                                           // the front reached its queries (a front that fails earlier never calls the stage)
+};
+QueryStage pcs_collect_stage(PcsCollected* out);
+struct PcsManyStage { void* self; int (*run)(void* self, const PcsCollected* list, uint32_t n, int* codes); };
+PcsManyStage host_pcs_many_stage();
+// zkir_verify_rate_segment: rate_verify_with_stage without check 7 (a mode >= 3 proof is never a segment: 2); states_out: NULL or 2 x 68 words (first | last), counters_out:
+// NULL or the four counter words — both written as soon as the header is read, whatever the verdict
+int rate_segment_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage,
+                                   uint32_t* states_out, uint32_t* counters_out);
+// zkir_verify_rate_chain with the segments' queries in ONE run of `stage` (a chain of one mode >= 3 proof is the caller's: it is a whole run)
+int rate_chain_with_stage(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, uint32_t min_queries,
+                          uint32_t min_pow_bits, const PcsManyStage& stage);
+
 // ---- the QUERY STAGE of the mixed-height verifier (zkir_mixed_eval_verify and zkir_mixed_eval_verify_device: a 'ZKMH' proof) ----
 // Checks 6 .. 11 of all the queries, handed over as above: after checks 1 .. 5, 12 and 13 and the sampling.  The proof has ONE FRI and one layer-0 rule per GROUP: g[h] is a
 // PcsQueries of which only the rule counts (log_M = log M_h, n_mats, widths, n_points, n_sel, sel with e0 counted from the proof's first exponent, z_m, a_m, and the gamma

@@ -463,6 +463,14 @@ def lib() -> C.CDLL:
         L.zkir_prove_rate_modes.restype = C.c_int; L.zkir_prove_rate_modes.argtypes = L.zkir_prove_rate.argtypes
         L.zkir_prove_result_rate.restype = C.c_int
         L.zkir_prove_result_rate.argtypes = [V, C.POINTER(ProverParamsC), U32, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+    if hasattr(L, "zkir_prove_rate_segment"):                 # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_prove_rate_segment.restype = C.c_int; L.zkir_prove_rate_segment.argtypes = L.zkir_prove_rate.argtypes
+        L.zkir_verify_rate_segment.restype = C.c_int; L.zkir_verify_rate_segment.argtypes = [V, U64, C.POINTER(PublicInputsC), U32, U32, V, V]
+        L.zkir_verify_rate_chain.restype = C.c_int; L.zkir_verify_rate_chain.argtypes = [V, V, U32, C.POINTER(PublicInputsC), U32, U32]
+        L.zkir_verify_rate_segment_device.restype = C.c_int; L.zkir_verify_rate_segment_device.argtypes = [V, U64, C.POINTER(PublicInputsC), U32, U32, V, V, V]
+        L.zkir_verify_rate_chain_device.restype = C.c_int; L.zkir_verify_rate_chain_device.argtypes = [V, V, U32, C.POINTER(PublicInputsC), U32, U32, V]
+        L.zkir_verify_rate_many_device.restype = C.c_int; L.zkir_verify_rate_many_device.argtypes = [V, V, V, V, V, U32, V, V]
+        L.zkir_pcs_verify_many_device.restype = C.c_int; L.zkir_pcs_verify_many_device.argtypes = [V, V, V, V, V, V, U32, V, V]
     L.zkir_prove_result.restype = C.c_int
     L.zkir_prove_result.argtypes = [V, C.POINTER(ProverParamsC), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.zkir_proof_bytes_free.restype = None
@@ -841,6 +849,92 @@ def verify_rate(proof, expect: Optional[PublicInputsC] = None, min_queries: int 
     if rc < 0:
         _raise(-rc)
     return rc
+
+
+def verify_rate_segment(proof, expect: Optional[PublicInputsC] = None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None):
+    """zkir_verify_rate_segment: a 'ZKSR' proof of a SEGMENT of a run (stark.prove_rate_segment) -> (code, first_state u32[68], last_state u32[68]): verify_rate's codes
+    without check 7; the states are the header's on acceptance (zero otherwise).  device=True: zkir_verify_rate_segment_device — the same verdict, the embedded proof's
+    queries on the GPU; a negative result is a device failure (raised)."""
+    w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
+    e = C.byref(expect) if expect is not None else None
+    first, last = np.zeros(68, np.uint32), np.zeros(68, np.uint32)
+    ptr = w.ctypes.data if len(w) else None
+    if device:
+        rc = _pcs_verdict(lib().zkir_verify_rate_segment_device(ptr, len(w), e, int(min_queries), int(min_pow_bits), first.ctypes.data, last.ctypes.data, stream))
+    else:
+        rc = lib().zkir_verify_rate_segment(ptr, len(w), e, int(min_queries), int(min_pow_bits), first.ctypes.data, last.ctypes.data)
+    return rc, first, last
+
+
+def verify_rate_chain(proofs, expect: Optional[PublicInputsC] = None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None) -> int:
+    """zkir_verify_rate_chain: the 'ZKSR' segments of one run, in order (verify_chain's codes: 40 empty, 1000 (i + 1) + c segment i's code c, 41 - 46, 50 - 53; 43 also for
+    a segment of another rate, query count or grinding than segment 0); expect.n_real = the run's total executed rows, `min_queries` / `min_pow_bits` hold for every
+    segment.  device=True: zkir_verify_rate_chain_device — the same verdict, all the segments' queries as one batch on the GPU (two launches on `stream`); a negative
+    result is a device failure, not a verdict (raised)."""
+    ps = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1) for p in proofs]
+    n = len(ps)
+    ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data if len(p) else None for p in ps])
+    lens = (C.c_uint64 * max(n, 1))(*[len(p) for p in ps])
+    e = C.byref(expect) if expect is not None else None
+    if device:
+        return _pcs_verdict(lib().zkir_verify_rate_chain_device(ptrs, lens, n, e, int(min_queries), int(min_pow_bits), stream))
+    return lib().zkir_verify_rate_chain(ptrs, lens, n, e, int(min_queries), int(min_pow_bits))
+
+
+def _many_args(proofs):
+    ps = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1) for p in proofs]
+    n = len(ps)
+    ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data if len(p) else None for p in ps])
+    lens = (C.c_uint64 * max(n, 1))(*[len(p) for p in ps])
+    return ps, n, ptrs, lens
+
+
+def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, stream=None):
+    """zkir_verify_rate_many_device: n independent whole-run 'ZKSR' proofs (1 .. 1024) of any mode and rate -> [verify_rate(proofs[i], expects[i], min_queries[i],
+    min_pow_bits[i]) for i] with every proof's queries in ONE batch on the GPU.  `expects`: None, or one entry (a PublicInputsC or None) per proof; `min_queries` /
+    `min_pow_bits`: None (1 / 0) or one value per proof.  An empty list, more than 1024 proofs or a device failure raise, and no verdict is formed."""
+    ps, n, ptrs, lens = _many_args(proofs)
+    for name, a in (("expectations", expects), ("min_queries", min_queries), ("min_pow_bits", min_pow_bits)):
+        if a is not None and len(a) != n:
+            raise ValueError(f"{n} proofs, {len(a)} {name}")
+    exps = (C.c_void_p * max(n, 1))(*[C.addressof(e) if e is not None else None for e in expects]) if expects is not None else None
+    mq = (C.c_uint32 * max(n, 1))(*[int(x) for x in min_queries]) if min_queries is not None else None
+    mb = (C.c_uint32 * max(n, 1))(*[int(x) for x in min_pow_bits]) if min_pow_bits is not None else None
+    verdicts = (C.c_int32 * max(n, 1))()
+    rc = lib().zkir_verify_rate_many_device(ptrs, lens, exps, mq, mb, n, verdicts, stream)
+    if rc != 0:
+        _raise(abs(rc))
+    return [int(verdicts[i]) for i in range(n)]
+
+
+PCS_KINDS = {"lowdeg": 0, "eval": 1, "batch_eval": 2}         # zkir_pcs_verify_many_device's kinds: 'ZKLD', 'ZKEV', 'ZKBE'
+
+
+def pcs_verify_many(kinds, proofs, roots=None, points=None, evals=None, stream=None):
+    """zkir_pcs_verify_many_device: n stand-alone proofs of the commitment layer (1 .. 1024) in ONE stage run on the GPU -> [lowdeg_verify / eval_verify / batch_eval_verify
+    of proof i].  kinds[i]: 0 / "lowdeg" ('ZKLD'), 1 / "eval" ('ZKEV'), 2 / "batch_eval" ('ZKBE').  `roots`, `points`, `evals`: None, or one entry (an array sized as the
+    proof's header states, or None) per proof.  A bad kind, an empty list, more than 1024 proofs or a device failure raise, and no verdict is formed."""
+    ps, n, ptrs, lens = _many_args(proofs)
+    ks = [PCS_KINDS.get(k, k) if isinstance(k, str) else int(k) for k in kinds]
+    if len(ks) != n:
+        raise ValueError(f"{n} proofs, {len(ks)} kinds")
+    keep = []
+
+    def table(a, name):
+        if a is None:
+            return None
+        if len(a) != n:
+            raise ValueError(f"{n} proofs, {len(a)} {name}")
+        arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in a]
+        keep.append(arrs)
+        return (C.c_void_p * max(n, 1))(*[x.ctypes.data if x is not None else None for x in arrs])
+    r, p, e = table(roots, "roots"), table(points, "points"), table(evals, "evals")
+    kinds_c = (C.c_uint32 * max(n, 1))(*[k & 0xFFFFFFFF for k in ks])
+    verdicts = (C.c_int32 * max(n, 1))()
+    rc = lib().zkir_pcs_verify_many_device(kinds_c, ptrs, lens, r, p, e, n, verdicts, stream)
+    if rc != 0:
+        _raise(abs(rc))
+    return [int(verdicts[i]) for i in range(n)]
 
 
 def batch_eval_verify(proof, roots=None, points=None, evals=None, device: bool = False, stream=None) -> int:

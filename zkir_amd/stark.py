@@ -599,6 +599,21 @@ def prove_rate_modes(ctx: StarkContext, trace, pub: rt.PublicInputsC, num_querie
     return (proof, list(ms)) if want_stage_ms else proof
 
 
+def prove_rate_segment(ctx: StarkContext, trace, pub: rt.PublicInputsC, num_queries: Optional[int] = None, pow_bits: int = 12, stream=None, want_stage_ms: bool = False):
+    """zkir_prove_rate_segment: prove_rate for a SEGMENT of a run — `trace` is the device trace of a row shard (rt.exec_shard on log.shard(a, e)), `pub` the shard's public
+    inputs (n_real = its rows; mode 2: the whole run's tapes with writes_before / reads_before) — or for a whole run, whose words are prove_rate's.  Modes 0, 1, 2; the
+    'ZKSR' format; rt.verify_rate_segment / rt.verify_rate_chain check such proofs."""
+    cols = trace.c if hasattr(trace, "c") else trace
+    nq = rt.RATE_DEFAULT_QUERIES.get(ctx.log_blowup, 50) if num_queries is None else int(num_queries)
+    out = C.POINTER(C.c_uint32)()
+    n_words = C.c_uint64()
+    ms = (C.c_float * 11)()
+    pl._check(rt.lib().zkir_prove_rate_segment(ctx.handle, C.byref(cols), C.byref(pub), nq, int(pow_bits), C.byref(out), C.byref(n_words), ms if want_stage_ms else None, _sp(stream)))
+    proof = np.ctypeslib.as_array(out, shape=(n_words.value,)).copy()
+    rt.lib().zkir_proof_free(out)
+    return (proof, list(ms)) if want_stage_ms else proof
+
+
 def rate_proof_layout(proof) -> dict:
     """Word offsets inside a 'ZKSR' proof of any mode: proof_layout's sections of the STARK part (header .. quotient_root; modes 3 / 4: the touched cells, the tapes), the header's log_blowup, num_queries and pow_bits, and
     `eval_proof`: where the embedded 'ZKBE' proof starts (it runs to the end; batch_eval_layout reads it)."""
@@ -622,3 +637,23 @@ def rate_last_matrices(ctx: StarkContext):
 def verify_rate(proof, expect=None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None) -> int:
     """rt.verify_rate; device=True checks the embedded proof's queries on the GPU, on the torch stream `stream` (default: the current one) — the same verdict."""
     return rt.verify_rate(proof, expect, min_queries, min_pow_bits, device=device, stream=_verify_stream(device, stream))
+
+
+def verify_rate_segment(proof, expect=None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None):
+    """rt.verify_rate_segment; device=True checks the embedded proof's queries on the GPU, on the torch stream `stream` (default: the current one) — the same verdict."""
+    return rt.verify_rate_segment(proof, expect, min_queries, min_pow_bits, device=device, stream=_verify_stream(device, stream))
+
+
+def verify_rate_chain(proofs, expect=None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None) -> int:
+    """rt.verify_rate_chain; device=True checks all the segments' queries as one batch on the GPU, on the torch stream `stream` (default: the current one)."""
+    return rt.verify_rate_chain(proofs, expect, min_queries, min_pow_bits, device=device, stream=_verify_stream(device, stream))
+
+
+def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, stream=None):
+    """rt.verify_rate_many on the torch stream `stream` (default: the current one)."""
+    return rt.verify_rate_many(proofs, expects, min_queries, min_pow_bits, stream=_verify_stream(True, stream))
+
+
+def pcs_verify_many(kinds, proofs, roots=None, points=None, evals=None, stream=None):
+    """rt.pcs_verify_many on the torch stream `stream` (default: the current one)."""
+    return rt.pcs_verify_many(kinds, proofs, roots, points, evals, stream=_verify_stream(True, stream))
