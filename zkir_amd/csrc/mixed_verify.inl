@@ -1,23 +1,43 @@
 // mixed_verify.inl — zkir_mixed_eval_verify_device (include/zkir_amd.h): the verifier of a mixed-height evaluation proof ('ZKMH') with its QUERY STAGE (verify_stages.h:
-// MixedQueries, checks 6 .. 11 of all queries) on the device.  Included by stark.hip at file scope, after pcs_verify.inl, whose hash kernel, fold step, per-thread job
-// counts and stage clocks it uses, and whose contract it keeps: verify_device(dev)'s block, pinned staging and mutex; one staged upload, one download, one synchronisation
-// on the caller's stream; nothing launched when the verdict is 1 .. 5, 12 or 13 (verify.cpp's host code runs first and unchanged); a negative return is "no verdict".
+// MixedQueries, checks 6 .. 11 of all queries) on the device.  Included by stark.hip at file scope, after query_stage.inl, whose __device__ pieces and layout builder it
+// uses and whose untrusted-input contract it keeps (the stage runs after checks 1 and 3, so the proof's length is EXACTLY its header's and every word is below p), and
+// after pcs_verify.inl, whose per-thread job counts and stage clocks it shares.  Its kernels and its block are its own — a query's rule differs by group and a fold may
+// add another launch's value — under the same contract: verify_device(dev)'s block, pinned staging and mutex; one staged upload, one download, one synchronisation on the
+// caller's stream; nothing launched when the verdict is 1 .. 5, 12 or 13 (verify.cpp's host code runs first and unchanged); a negative return is "no verdict".
 //
 // THREE launches on the one stream:
-//   pcs_hash_jobs_kernel<MIXED_MAX_SLOTS>   num_queries (2 n_mats_0 + sum_{h>=1} n_mats_h + n_layers) jobs, a row of 16 lanes each.  A query's slots in the order its
-//                                           records stand: group 0's matrices at q and q + M_0/2 (depth log M_0), each lower group's matrices once at depth log M_h with
-//                                           idx_add = 0 (the kernel's mask gives q mod M_h), the FRI layers
-//   mixed_value_kernel                      a wave per (query, half) — group 0's rule at q / q + M_0/2 against layer 0's values (check 8) — and a wave per (query, lower
-//                                           group h): F_h(q mod M_h) by group h's rule at x = 31 w_{M_h}^(q mod M_h), four Montgomery words to the F buffer, no comparison
-//   mixed_fold_kernel                       a lane per (query, layer j): layer j's own values folded and compared with the next layer's v[slot] — PLUS the stored F_h when
-//                                           the next layer has size M_h — or, for the last layer, with the final layer (no M_h is the final layer's size)
+//   mixed_hash_jobs_kernel   num_queries (2 n_mats_0 + sum_{h>=1} n_mats_h + n_layers) jobs, a row of 16 lanes each.  A query's slots in the order its records stand:
+//                            group 0's matrices at q and q + M_0/2 (depth log M_0), each lower group's matrices once at depth log M_h with idx_add = 0 (the kernel's
+//                            mask gives q mod M_h), the FRI layers
+//   mixed_value_kernel       a wave per (query, half) — group 0's rule at q / q + M_0/2 against layer 0's values (check 8) — and a wave per (query, lower group h):
+//                            F_h(q mod M_h) by group h's rule at x = 31 w_{M_h}^(q mod M_h), four Montgomery words to the F buffer, no comparison
+//   mixed_fold_kernel        a lane per (query, layer j): layer j's own values folded and compared with the next layer's v[slot] — PLUS the stored F_h when the next
+//                            layer has size M_h — or, for the last layer, with the final layer (no M_h is the final layer's size)
 // WHY THREE.  A fold lane whose next layer has size M_h needs F_h of its query, which another workgroup forms; a lane cannot wait for a workgroup of its own launch (it
 // may not be resident yet), so the folds are a launch of their own behind the values' launch and the stream's order is the only synchronisation: no flag in device memory
 // is ever waited for.  (Forming F_h inside the fold lane would keep two launches but puts a width-long column sum on one lane; 152 columns a wave is the measured case.)
-//
-// UNTRUSTED INPUT, as in pcs_verify.inl: the stage runs after checks 1 and 3, so the proof's length is EXACTLY its header's and every word is below p; every offset and
-// extent is a function of the checked header; the row a job opens is the transcript's sample, never the proof's index word (which only the host compares: check 6).
 namespace {
+
+// The hash jobs' shape, BY VALUE: query_stage.inl's slots (leaf_off from the query's first word, the Merkle index (q + idx_add) mod 2^depth) for one proof whose query
+// has up to MIXED_MAX_SLOTS of them, in this file's own order.
+struct MixedHashShape {
+  uint64_t at_queries, qsize;
+  uint32_t n_slots, n_jobs;
+  uint32_t leaf_off[zkir::MIXED_MAX_SLOTS], leaf_words[zkir::MIXED_MAX_SLOTS], depth[zkir::MIXED_MAX_SLOTS], root_at[zkir::MIXED_MAX_SLOTS], idx_add[zkir::MIXED_MAX_SLOTS];
+};
+
+// One leaf-and-path job a row of 16 lanes: flags[job] = 0 / 1, one plain store.
+__global__ __launch_bounds__(NT_MV) void mixed_hash_jobs_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ w, const uint32_t* __restrict__ qs, MixedHashShape sh, uint32_t* __restrict__ flags) {
+  const uint32_t job = (blockIdx.x * NT_MV + threadIdx.x) / 16;
+  const uint32_t l = threadIdx.x & 15;
+  if (job >= sh.n_jobs) return;                                  // (whole rows)
+  const uint32_t t = job / sh.n_slots, slot = job - t * sh.n_slots;
+  const uint32_t depth = sh.depth[slot], width = sh.leaf_words[slot];
+  const uint32_t j = (qs[t] + sh.idx_add[slot]) & ((1u << depth) - 1u);
+  const uint32_t* r = w + sh.at_queries + (uint64_t)t * sh.qsize + sh.leaf_off[slot];
+  const uint32_t eq = pcs_row16_hashes_to(cp, r, width, depth, j, w + sh.root_at[slot], l);
+  if (l == 0) flags[job] = eq ? 0u : 1u;
+}
 
 // A group's layer-0 rule (PcsQueries' rule fields) as the value kernel reads it: DEVICE MEMORY, one per group — a wave picks its group at run time.  rec_off[m]: matrix
 // m's record from the query's first word (group 0: the record at q; the one at q + M_0/2 follows it, widths[m] + 4 log_M words on).
@@ -27,43 +47,24 @@ struct MixedRule {
   uint32_t sel_point[zkir::PCS_MAX_SEL], sel_mat[zkir::PCS_MAX_SEL], sel_e0[zkir::PCS_MAX_SEL];
   uint32_t z_m[2][4], a_m[2][4];
 };
-constexpr uint32_t MIXED_L_ADD = 10;                             // layer table word (pcs_verify.inl's layout, its spare word): h >= 1 when the NEXT layer has size M_h, else 0
+constexpr uint32_t MIXED_L_ADD = 10;                             // layer table word (query_stage.inl's layout, its spare word): h >= 1 when the NEXT layer has size M_h, else 0
 struct MixedValueShape {
   uint64_t at_queries, qsize, at_fin;
   uint32_t n_layers, num_queries, n_groups, fin_mask;
   uint32_t lay0_off;                                             // layer 0's values in a query
 };
 
-// pcs_value_kernel's layer-0 wave on rule r: sum_i (a_i - A_i) / (z_i - x), x = 31 w_M^pos, A_i from the rows at qb + rec_off (+ the second record's stride when s2) —
-// lanes over the columns, exact field sums, a butterfly over the wave; every lane returns the value (Montgomery)
+// query_value_kernel's layer-0 wave on rule r: sum_i (a_i - A_i) / (z_i - x), x = 31 w_M^pos, A_i from the rows at qb + rec_off (+ the second record's stride when s2);
+// every lane returns the value (Montgomery)
 __device__ __forceinline__ E4 mixed_rule_value(const uint32_t* __restrict__ qb, const uint32_t* __restrict__ gamma_m, const MixedRule& r, uint32_t pos, uint32_t s2, uint32_t lane) {
   E4 A0 = bb::e_zero(), A1 = bb::e_zero();
   for (uint32_t si = 0; si < r.n_sel; si++) {
     const uint32_t m = r.sel_mat[si], width = r.widths[m];
-    const uint32_t* row = qb + r.rec_off[m] + s2 * (width + 4 * r.log_M);
-    const uint32_t* g = gamma_m + 4 * (uint64_t)r.sel_e0[si];
-    E4 acc = bb::e_zero();
-    for (uint32_t k = lane; k < width; k += 64) acc = bb::e_add(acc, bb::e_mul_fm(E4{{g[4 * k], g[4 * k + 1], g[4 * k + 2], g[4 * k + 3]}}, row[k]));
+    const E4 acc = pcs_row_dot(gamma_m + 4 * (uint64_t)r.sel_e0[si], qb + r.rec_off[m] + s2 * (width + 4 * r.log_M), width, lane);
     if (r.sel_point[si] == 0) A0 = bb::e_add(A0, acc); else A1 = bb::e_add(A1, acc);
   }
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      A0.c[c] = bb::add(A0.c[c], (uint32_t)__shfl_xor((int)A0.c[c], d, 64));
-      A1.c[c] = bb::add(A1.c[c], (uint32_t)__shfl_xor((int)A1.c[c], d, 64));
-    }
-  const uint32_t x_m = bb::mont_mul(bb::to_mont(bb::GEN), pcs_pow_m(r.wM_m, pos));
-  E4 want = bb::e_zero();
-#pragma unroll
-  for (uint32_t i = 0; i < 2; i++) {
-    if (i >= r.n_points) break;
-    E4 d{{r.z_m[i][0], r.z_m[i][1], r.z_m[i][2], r.z_m[i][3]}};
-    const E4 a{{r.a_m[i][0], r.a_m[i][1], r.a_m[i][2], r.a_m[i][3]}};
-    d.c[0] = bb::sub(d.c[0], x_m);
-    want = bb::e_add(want, bb::e_mul_m(bb::e_sub(a, bb::e_to_mont(i ? A1 : A0)), bb::e_inv_m(d)));
-  }
-  return want;
+  pcs_wave_sum(A0, A1);
+  return pcs_point_sum(r.n_points, r.z_m, r.a_m, A0, A1, r.wM_m, pos);
 }
 
 // Workgroups [0, 2 num_queries): (query t, half s2) — check 8: flags8[2 t + s2].  The workgroups behind them: (query t, lower group h) — F_h(q mod M_h) to
@@ -88,8 +89,8 @@ __global__ __launch_bounds__(64) void mixed_value_kernel(const uint32_t* __restr
   if (lane < 4) fbuf[4 * (size_t)id + lane] = lane == 0 ? F.c[0] : lane == 1 ? F.c[1] : lane == 2 ? F.c[2] : F.c[3];
 }
 
-// pcs_value_kernel's fold lanes with the one new rule: L[MIXED_L_ADD] = h >= 1 — the next layer has size M_h — and the lane compares that layer's v[slot] with its fold
-// plus the query's F_h.  v[8] keeps compile-time indices only; the layer table and the F buffer are device memory.
+// query_value_kernel's fold lanes with the one new rule: L[MIXED_L_ADD] = h >= 1 — the next layer has size M_h — and the lane compares that layer's v[slot] with its fold
+// plus the query's F_h.  The layer table and the F buffer are device memory.
 __global__ __launch_bounds__(64) void mixed_fold_kernel(const uint32_t* __restrict__ w, const uint32_t* __restrict__ qs, const uint32_t* __restrict__ betas_m,
                                                         const uint32_t* __restrict__ ltab, const uint32_t* __restrict__ fbuf, MixedValueShape sh, uint32_t* __restrict__ flags_fold) {
   const uint32_t id = blockIdx.x * 64 + threadIdx.x;
@@ -97,18 +98,9 @@ __global__ __launch_bounds__(64) void mixed_fold_kernel(const uint32_t* __restri
   const uint32_t t = id / sh.n_layers, j = id - t * sh.n_layers;
   const uint32_t* qb = w + sh.at_queries + (uint64_t)t * sh.qsize;
   const uint32_t* L = ltab + PCS_LAYER_WORDS * j;
-  const uint32_t k = L[PCS_L_K], depth = L[PCS_L_DEPTH], log_m = L[PCS_L_LOG_M], add = L[MIXED_L_ADD];
-  const uint32_t idx = qs[t] & ((1u << depth) - 1u);
-  const uint32_t sl = 3 - k;
-  const uint32_t* vals = qb + L[PCS_L_OFF];
-  E4 v[8];
-#pragma unroll
-  for (uint32_t p = 0; p < 8; p++) v[p] = (p & ((1u << sl) - 1u)) == 0 ? pcs_load_m(vals + 4 * (p >> sl)) : bb::e_zero();
-  E4 beta{{betas_m[4 * j], betas_m[4 * j + 1], betas_m[4 * j + 2], betas_m[4 * j + 3]}};
-  if (k > 0) pcs_fold_step<0>(v, beta, L, log_m, idx, sl, depth);
-  if (k > 1) pcs_fold_step<1>(v, beta, L, log_m, idx, sl, depth);
-  if (k > 2) pcs_fold_step<2>(v, beta, L, log_m, idx, sl, depth);
-  E4 got = v[0];
+  const uint32_t add = L[MIXED_L_ADD];
+  const uint32_t idx = qs[t] & ((1u << L[PCS_L_DEPTH]) - 1u);
+  E4 got = pcs_fold_lane(qb + L[PCS_L_OFF], L, betas_m + 4 * j, idx);
   if (add) {
     const uint32_t* f = fbuf + 4 * ((size_t)t * (sh.n_groups - 1) + add - 1);
     got = bb::e_add(got, E4{{f[0], f[1], f[2], f[3]}});
@@ -164,14 +156,22 @@ struct MixedDeviceStage {
                  o_rules = o_ltab + al256((size_t)Q.n_layers * PCS_LAYER_WORDS * 4), o_flags = o_rules + al256(Q.n_groups * sizeof(MixedRule)), o_fbuf = o_flags + al256(n_flags * 4),
                  total = o_fbuf + al256((size_t)nq * n_lower * 16);
     // ---- the shapes: every offset from the checked header ----
-    PcsHashShapeT<zkir::MIXED_MAX_SLOTS> hs{};
+    MixedHashShape hs{};
     MixedValueShape vs{};
     MixedRule rules[zkir::MIXED_MAX_GROUPS] = {};
     hs.at_queries = vs.at_queries = Q.at_queries; hs.qsize = vs.qsize = Q.qsize; vs.at_fin = Q.at_fin;
     hs.n_slots = n_slots; hs.n_jobs = (uint32_t)hash_jobs;
     vs.n_layers = Q.n_layers; vs.num_queries = nq; vs.n_groups = Q.n_groups; vs.fin_mask = (4u << Q.b) - 1u;
-    uint32_t off = 1, sl = 0;                                    // (the index word)
-    for (uint32_t h = 0; h < Q.n_groups; h++) {
+    QueryMat mats[zkir::MIXED_MAX_GROUPS * zkir::PCS_MAX_MATS];   // the records in the order they stand: group 0's twice, a lower group's once (the kernel's mask gives q mod M_h)
+    uint32_t n_mats = 0;
+    for (uint32_t h = 0; h < Q.n_groups; h++)
+      for (uint32_t m = 0; m < Q.g[h].n_mats; m++) mats[n_mats++] = QueryMat{Q.g[h].widths[m], Q.g[h].log_M, (uint32_t)Q.at_roots + 4 * (Q.first_mat[h] + m), h ? 1u : 2u, 0};
+    uint32_t ltab[zkir::MIXED_MAX_LAYERS * PCS_LAYER_WORDS];
+    if (query_layout(Q.g[0].log_M, Q.b, Q.ks, Q.n_layers, (uint32_t)Q.at_lroots, mats, n_mats, Q.qsize, QuerySlots{hs.leaf_off, hs.leaf_words, hs.depth, hs.root_at, hs.idx_add}, ltab, &vs.lay0_off) ||
+        Q.at_queries + (uint64_t)nq * Q.qsize != Q.len) { zkir::set_last_error({ZKIR_ERR_OTHER, bad_shape}); return -ZKIR_ERR_OTHER; }
+    for (uint32_t j = 0; j + 1 < Q.n_layers; j++)                // the layer whose NEXT layer has the size of a lower group adds that group's F_h
+      for (uint32_t h = 1; h < Q.n_groups; h++) if (Q.g[h].log_M == ltab[PCS_LAYER_WORDS * (j + 1) + PCS_L_LOG_M]) ltab[PCS_LAYER_WORDS * j + MIXED_L_ADD] = h;
+    for (uint32_t h = 0, at = 0; h < Q.n_groups; h++) {
       const zkir::PcsQueries& g = Q.g[h];
       MixedRule& r = rules[h];
       r.log_M = g.log_M; r.n_points = g.n_points; r.n_sel = g.n_sel; r.wM_m = bb::to_mont(bb::root_of_unity((int)g.log_M));
@@ -180,34 +180,8 @@ struct MixedDeviceStage {
         r.sel_point[i] = g.sel[i].point; r.sel_mat[i] = g.sel[i].mat; r.sel_e0[i] = g.sel[i].e0;
       }
       memcpy(r.z_m, g.z_m, sizeof r.z_m); memcpy(r.a_m, g.a_m, sizeof r.a_m);
-      for (uint32_t m = 0; m < g.n_mats; m++) {
-        r.widths[m] = g.widths[m]; r.rec_off[m] = off;
-        for (uint32_t s2 = 0; s2 < (h ? 1u : 2u); s2++, sl++) {
-          hs.leaf_off[sl] = off; hs.leaf_words[sl] = g.widths[m]; hs.depth[sl] = g.log_M; hs.root_at[sl] = (uint32_t)Q.at_roots + 4 * (Q.first_mat[h] + m);
-          hs.idx_add[sl] = s2 ? 1u << (g.log_M - 1) : 0u;        // (a lower group: 0, and the kernel's mask gives q mod M_h)
-          off += g.widths[m] + 4 * g.log_M;
-        }
-      }
+      for (uint32_t m = 0; m < g.n_mats; m++, at++) { r.widths[m] = g.widths[m]; r.rec_off[m] = mats[at].rec_off; }
     }
-    uint32_t ltab[zkir::MIXED_MAX_LAYERS * PCS_LAYER_WORDS] = {0};
-    uint32_t shift = bb::GEN, log_m = Q.g[0].log_M;
-    for (uint32_t j = 0; j < Q.n_layers; j++, sl++) {
-      const uint32_t k = Q.ks[j];
-      if (k < 1 || k > 3 || log_m < k) { zkir::set_last_error({ZKIR_ERR_OTHER, bad_shape}); return -ZKIR_ERR_OTHER; }
-      const uint32_t depth = log_m - k;
-      hs.leaf_off[sl] = off; hs.leaf_words[sl] = 4u << k; hs.depth[sl] = depth; hs.root_at[sl] = (uint32_t)Q.at_lroots + 4 * j; hs.idx_add[sl] = 0;
-      uint32_t* L = ltab + PCS_LAYER_WORDS * j;
-      L[PCS_L_OFF] = off; L[PCS_L_K] = k; L[PCS_L_DEPTH] = depth; L[PCS_L_LOG_M] = log_m;
-      if (j == 0) vs.lay0_off = off;
-      for (uint32_t f = 0; f < k; f++) {
-        L[PCS_L_INV2SHIFT + f] = bb::to_mont(bb::inv(bb::mul(2, shift))); L[PCS_L_WM + f] = bb::to_mont(bb::root_of_unity((int)log_m));
-        shift = bb::mul(shift, shift); log_m--;
-      }
-      if (j + 1 < Q.n_layers)                                    // (log_m: the next layer's size)
-        for (uint32_t h = 1; h < Q.n_groups; h++) if (Q.g[h].log_M == log_m) L[MIXED_L_ADD] = h;
-      off += (4u << k) + 4 * depth;
-    }
-    if (off != Q.qsize || Q.at_queries + (uint64_t)nq * Q.qsize != Q.len || log_m != 2 + Q.b) { zkir::set_last_error({ZKIR_ERR_OTHER, bad_shape}); return -ZKIR_ERR_OTHER; }
     // ---- one staged upload ----
     const bool timed = getenv("ZKIR_PCS_VERIFY_TIMES") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -228,7 +202,7 @@ struct MixedDeviceStage {
     const uint32_t* d_betas = (const uint32_t*)(V.d + o_betas); const uint32_t* d_ltab = (const uint32_t*)(V.d + o_ltab); const MixedRule* d_rules = (const MixedRule*)(V.d + o_rules);
     uint32_t* d_flags = (uint32_t*)(V.d + o_flags); uint32_t* d_fbuf = (uint32_t*)(V.d + o_fbuf);
     uint32_t *d_f8 = d_flags + hash_jobs, *d_ff = d_f8 + 2 * (size_t)nq;
-    hipLaunchKernelGGL(pcs_hash_jobs_kernel<zkir::MIXED_MAX_SLOTS>, dim3(grid_for(hash_jobs * 16, NT_MV)), dim3(NT_MV), 0, s, V.d_p2, d_w, d_qs, hs, d_flags);
+    hipLaunchKernelGGL(mixed_hash_jobs_kernel, dim3(grid_for(hash_jobs * 16, NT_MV)), dim3(NT_MV), 0, s, V.d_p2, d_w, d_qs, hs, d_flags);
     hipLaunchKernelGGL(mixed_value_kernel, dim3(2 * nq + nq * n_lower), dim3(64), 0, s, d_w, d_qs, d_gamma, d_rules, vs, d_f8, d_fbuf);
     hipLaunchKernelGGL(mixed_fold_kernel, dim3(grid_for((uint64_t)nq * Q.n_layers, 64)), dim3(64), 0, s, d_w, d_qs, d_betas, d_ltab, (const uint32_t*)d_fbuf, vs, d_ff);
     pcs_last_jobs[0] = hash_jobs; pcs_last_jobs[1] = value_jobs;

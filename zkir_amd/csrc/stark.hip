@@ -1123,6 +1123,7 @@ int zkir_merkle_cap_launch(const zkir_stark_ctx* c, uint32_t* tree, uint64_t n_d
 #include "lowdeg.inl"
 #include "eval_open.inl"
 #include "mixed_eval.inl"
+#include "query_stage.inl"
 #include "pcs_verify.inl"
 #include "mixed_verify.inl"
 #include "stark_verify.inl"
