@@ -742,6 +742,32 @@ int zkir_pcs_verify_many_device(const uint32_t* kinds, const uint32_t* const* pr
  * [2] the hash tape's share of the table side, [3] the wide tape's, [4] the rest; *device_stages = how many of these stages ran on the device (0 for every host entry).
  * Either pointer may be NULL.  ZKIR_ERR_ARGUMENT before the thread's first verification.  ZKIR_VERIFY_TIMES in the environment prints the clocks on stderr. */
 int zkir_verify_last_stages(double ms[5], uint32_t* device_stages);
+/* ---- (modes 3 / 4) the TOUCHED-CELL section's three stages on the current HIP device --------------------------------------------------------------------------------
+ * The section is [n] + 7 n words: per cell [address limb 0 (20 bits, a multiple of 8)] [limb 1 (20 bits)] [time of the last access] [final bytes: four 16-bit pieces].
+ * Linear in it are (a) the cell checks 54 / 55 (and 4: the proof ends inside the section), (b) its chunk digests in the transcript, (c) its share of the lookup table
+ * side: per cell + 1 / (alpha - fp(cell, 0, the program image's bytes)) - 1 / (alpha - fp(cell, t_last, final bytes)).  zkir_verify and EVERY entry above run them on the
+ * host, unchanged; the two entries below run them as kernels (csrc/mem_stage.inl), one upload of the section and the program image, three launches, a synchronisation
+ * where each result is needed — the same verdict as the host entry on every input, well-formed or not.  An empty section touches no device memory, and a section
+ * below 512 cells stays with the host stages (the measured crossover: profiles/r24_verify_memory_device.txt); ZKIR_VERIFY_DEVICE_MIN_CELLS in the environment sets
+ * another threshold (0: every non-empty section on the device), for measuring the routes against each other.
+ * zkir_verify_last_stages' device_stages counts the memory stages beside the tape stages: 3 for a non-empty section.
+ * Not covered: the memory stages inside zkir_verify_many_on_device / zkir_verify_rate_many_device (their mode-3 fronts stay on the host). */
+/* zkir_verify's verdict; the memory section's three stages and a mode-4 proof's tape stages on the device;
+   queries != 0: the query stage too (zkir_verify_on_device's). Modes 0-2: the existing entry's behaviour. */
+int zkir_verify_memory_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, int queries, void* hip_stream);
+/* zkir_verify_rate_device with the memory stages on the device */
+int zkir_verify_rate_memory_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, void* hip_stream);
+/* this thread's last verification: cells whose stages ran on the device, launches, words uploaded for them (all 0 after any other entry) */
+int zkir_verify_memory_last(uint64_t* cells, uint32_t* launches, uint64_t* uploaded_words);
+/* the stages on their own, as zkir_hash_tape_check_* and zkir_tape_table_side_* are: sec = [n] + 7 n words (host).
+ * _check_*: *verdict = 0 / 4 (n_words < 1 + 7 n) / 54 / 55 — of the LOWEST failing cell, and within it the first failing check in the host's order (limb ranges, byte
+ * pieces, strictly increasing address, overlap with the code_words code words at 0x1000; mode 4 admits the boundary cell of an odd code_words); a malformed section is a
+ * verdict and ZKIR_OK, not a refusal.  _table_side_*: n_words == 1 + 7 n and cells that pass check 54 (else ZKIR_ERR_ARGUMENT); blob: the program (its image bytes; a
+ * blob shorter than 32 bytes, or than its header claims, has an all-zero image); alpha, lambda and sum canonical.  _host: verify.cpp's code, no HIP call. */
+int zkir_mem_section_check_host  (const uint32_t* sec, uint64_t n_words, uint32_t mode, uint64_t code_words, int32_t* verdict);
+int zkir_mem_section_check_launch(const uint32_t* sec, uint64_t n_words, uint32_t mode, uint64_t code_words, int32_t* verdict, void* hip_stream);
+int zkir_mem_table_side_host  (const uint32_t* sec, uint64_t n_words, const uint8_t* blob, size_t blob_len, const uint32_t alpha[4], const uint32_t lambda[4], uint32_t sum[4]);
+int zkir_mem_table_side_launch(const uint32_t* sec, uint64_t n_words, const uint8_t* blob, size_t blob_len, const uint32_t alpha[4], const uint32_t lambda[4], uint32_t sum[4], void* hip_stream);
 /* points pub's mode-3 fields at the witness (which must outlive the proving call) and sets pub->deferred = 3 */
 void zkir_public_inputs_set_memory(zkir_public_inputs* pub, const zkir_memcheck_witness* w);
 /* Poseidon2 sponge digest of a byte string (host): [len as four 16-bit pieces] ++ [LE 16-bit halfwords] */

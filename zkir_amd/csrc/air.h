@@ -228,6 +228,17 @@ BB_HD constexpr bool fri_params_ok(uint32_t fri_params) { return num_queries_of(
 // proof format: modes 0 / 1 are v10 word for word; modes 2 / 3 are v11 (EBREAK class, the I/O section in the transcript, no access to the code segment in mode 3)
 BB_HD constexpr uint32_t proof_version(int mode) { return mode == 4 ? 12u : mode >= 2 ? 11u : 10u; }     // (v12 = mode 4: the wide-arithmetic class)
 constexpr uint64_t CODE_BASE = 0x1000;
+// (modes 3 / 4) the verifier's checks of ONE record of the touched-cell section: c = [address limb 0 (20 bits, a multiple of 8)] [limb 1 (20 bits)] [time] [final bytes: four
+// 16-bit pieces], prev = the record before it (nullptr: the first).  0, or the first check that fails in the verifier's order: limb ranges, byte pieces, strictly increasing
+// address (54), then no overlap with the n_code code words at CODE_BASE (55) — except, in mode 4, the boundary cell.  verify.cpp's loop and mem_section_check_kernel share it.
+BB_HD int mem_cell_code(const uint32_t* c, const uint32_t* prev, int mode, uint64_t n_code) {
+  if (c[0] >= (1u << 20) || (c[0] & 7) || c[1] >= (1u << 20)) return 54;
+  for (int i = 0; i < 4; i++) if (c[3 + i] > 0xFFFF) return 54;
+  const uint64_t addr = (uint64_t)c[0] | ((uint64_t)c[1] << 20);
+  if (prev && addr <= ((uint64_t)prev[0] | ((uint64_t)prev[1] << 20))) return 54;
+  if (addr + 8 > CODE_BASE && addr < CODE_BASE + 4 * n_code && !(mode == 4 && (n_code & 1) && addr == boundary_cell(4 * n_code))) return 55;
+  return 0;
+}
 BB_HD constexpr int kcol(int k) { return k < 7 ? C_K + k : k < 11 ? C_K2 + (k - 7) : k < 13 ? C_K3 + (k - 11) : C_K4 + (k - 13); }
 BB_HD constexpr bool class_absent(int k, int mode) { return is_virtual(kcol(k), mode) || (mode == 4 && k == K_OTH); }   // a class no row of the mode has: its selector reads as zero (mode 4: "other" — its column carries ot)
 static_assert(C_OT == kcol(K_OTH), "mode 4 re-uses the class column 'other' as the wide-tape selector");

@@ -126,6 +126,22 @@ int zkir_verify_rate_device(const uint32_t* proof, uint64_t proof_words, const z
   return rc;
 }
 
+// zkir_verify_rate_device with a mode-3 / mode-4 proof's memory stages (mem_stage.inl) on the device too, under the device state's mutex for the whole call
+int zkir_verify_rate_memory_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, void* stream) {
+  if (!has_memory_section(proof, proof_words)) return zkir_verify_rate_device(proof, proof_words, expect, min_queries, min_pow_bits, stream);
+  pcs_last_jobs[0] = pcs_last_jobs[1] = 0;
+  pcs_last_ms[0] = pcs_last_ms[1] = pcs_last_ms[2] = 0;
+  PcsDeviceStage st{(hipStream_t)stream};
+  st.held = true;
+  MemRunNote note;
+  const int rc = with_memory_stages(proof, proof_words, stream, "zkir_verify_rate_memory_device", [&](const zkir::TapeStages* tapes, const zkir::MemStages* mem) {
+    return zkir::rate_verify_with_stage(proof, proof_words, expect, min_queries, min_pow_bits, zkir::QueryStage{&st, pcs_device_run}, tapes, mem);
+  }, &note);
+  zkir::verify_note_device_stages(note.stages_run);
+  zkir::verify_note_memory(note.cells, note.launches, note.uploaded_words);
+  return rc;
+}
+
 int zkir_pcs_verify_last_jobs(uint64_t* hash_jobs, uint64_t* value_jobs) {
   if (hash_jobs) *hash_jobs = pcs_last_jobs[0];
   if (value_jobs) *value_jobs = pcs_last_jobs[1];

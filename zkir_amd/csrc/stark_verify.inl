@@ -106,6 +106,29 @@ int zkir_verify_on_device(const uint32_t* proof, uint64_t proof_words, const zki
   });
 }
 
+// zkir_verify's verdict with the memory section's three stages (mem_stage.inl) and a mode-4 proof's tape stages on the device; queries != 0: the query stage too.
+int zkir_verify_memory_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, int queries, void* stream) {
+  // modes 0 - 2 have no memory section (and a proof too short to name its mode has no verdict that depends on one): the existing entries
+  if (!has_memory_section(proof, proof_words)) return queries ? zkir_verify_on_device(proof, proof_words, expect, stream) : zkir_verify_device(proof, proof_words, expect, stream);
+  stark_last_ms[0] = stark_last_ms[1] = stark_last_ms[2] = 0;
+  return guarded([&]() -> int {
+    zkir::StarkQueries Q;
+    MemRunNote note;
+    const int rc = with_memory_stages(proof, proof_words, stream, "zkir_verify_memory_device", [&](const zkir::TapeStages* tapes, const zkir::MemStages* mem) {
+      return zkir::stark_verify_collect(proof, proof_words, expect, true, tapes, queries ? &Q : nullptr, mem);
+    }, &note);
+    zkir::verify_note_device_stages(note.stages_run);
+    zkir::verify_note_memory(note.cells, note.launches, note.uploaded_words);
+    if (rc || !queries) return rc;
+    StarkDeviceStage st{(hipStream_t)stream};
+    int code = 0;
+    const int src = st.run(&Q, 1, &code);
+    if (src) return src;
+    st.note();
+    return code ? code : zkir::stark_length_check(Q);
+  });
+}
+
 int zkir_verify_many_on_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, void* stream) {
   stark_last_ms[0] = stark_last_ms[1] = stark_last_ms[2] = 0;
   if (!proofs || !proof_words || !verdicts) return stark_refuse("zkir_verify_many_on_device: null proofs, proof_words or verdicts");

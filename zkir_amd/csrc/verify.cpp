@@ -196,7 +196,7 @@ void initial_state(uint64_t entry, uint32_t st[NS]) {
 constexpr uint32_t RATE_MAGIC = 0x52534B5Au, RATE_VERSION = 1, BATCH_EVAL_MAGIC = 0x45424B5Au;      // 'ZKSR'; 'ZKBE'
 struct RateCheck { uint32_t min_queries, min_pow_bits; const zkir::QueryStage* stage; };
 int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out = nullptr,
-                const zkir::TapeStages* stages = nullptr, zkir::StarkQueries* defer = nullptr, const RateCheck* rate = nullptr);
+                const zkir::TapeStages* stages = nullptr, zkir::StarkQueries* defer = nullptr, const RateCheck* rate = nullptr, const zkir::MemStages* mem = nullptr);
 int host_stark_run(void*, const zkir::StarkQueries* list, uint32_t n, int* codes);
 int host_stark_queries_of(const zkir::StarkQueries& Q, uint32_t first);
 inline int header_words_of(int mode) { return HEADER_WORDS + (mode >= 2 ? 4 : 0); }     // modes 2 / 3: + (oc, ic) of the first row, of the last row
@@ -246,6 +246,8 @@ struct LastStages { double ms[5] = {0, 0, 0, 0, 0}; uint32_t device_stages = 0; 
 thread_local LastStages last_stages;
 struct LastQueries { uint64_t hash_jobs = 0, value_jobs = 0, uploaded_words = 0; uint32_t launches = 0; };      // zkir_verify_queries_last: the device query stage of the thread's last verification
 thread_local LastQueries last_queries;
+struct LastMemory { uint64_t cells = 0, uploaded_words = 0; uint32_t launches = 0; };      // zkir_verify_memory_last: the device memory stages of the thread's last verification
+thread_local LastMemory last_memory;
 struct StageClock {
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   double ms[5] = {0, 0, 0, 0, 0};
@@ -255,6 +257,7 @@ struct StageClock {
     for (int k = 0; k < 5; k++) last_stages.ms[k] = ms[k];
     last_stages.device_stages = 0; last_stages.valid = true;
     last_queries = LastQueries{};                                            // (every host verification: the *_on_device entries note theirs once the stage has run)
+    last_memory = LastMemory{};                                              // (likewise: zkir_verify_memory_device notes its own afterwards)
     if (getenv("ZKIR_VERIFY_TIMES"))
       fprintf(stderr, "zkir_verify: parse %.3f ms | section digests %.3f | hash table side %.3f | wide table side %.3f | rest %.3f\n", ms[0], ms[1], ms[2], ms[3], ms[4]);
   }
@@ -366,6 +369,66 @@ int host_wide_side(void* self, const uint32_t* lk_m, uint32_t T[4]) {
   return 0;
 }
 
+// ---- the host forms of the memory stages (verify_stages.h): what a device stage leaves small sections to, and zkir_mem_section_check_host / zkir_mem_table_side_host ----
+int host_mem_check(void* self, const uint32_t* sec, size_t avail, int mode, uint64_t code_words, size_t* used) {
+  if (avail < 1) return 4;
+  const size_t nc = sec[0];
+  if (nc > ((size_t)1 << 28) || (avail - 1) / 7 < nc) return 4;
+  for (size_t k = 0; k < nc; k++) {
+    const uint32_t* c = sec + 1 + 7 * k;
+    const int code = air::mem_cell_code(c, k ? c - 7 : nullptr, mode, code_words);
+    if (code) return code;
+  }
+  if (self) { zkir::HostMem& h = *static_cast<zkir::HostMem*>(self); h.sec = sec; h.n = nc; }
+  *used = 1 + 7 * nc;
+  return 0;
+}
+int host_mem_digests(void*, const uint32_t* sec, size_t len, uint32_t* dg) { section_digests_host(sec, len, dg); return 0; }
+// sec: a CHECKED section of n cells.  Host threads; each part inverts its own batch of 2 (hi - lo) denominators.
+void mem_side_sum(const uint32_t* sec, size_t n, const uint8_t* blob, size_t blob_len, const uint32_t* lk_m, uint32_t T[4]) {
+  E4 T_mem = bb::e_zero();
+  if (n) {
+    const E4 alpha_l = lk_e4(lk_m, air::LK_ALPHA);
+    E4 lam[air::N_TUPLE + 1];
+    for (int j = 0; j <= air::N_TUPLE; j++) lam[j] = lk_e4(lk_m, air::LK_LAM + 4 * j);
+    auto mem_d = [&](const uint32_t* c, uint32_t t, uint64_t bytes) {
+      E4 fp = bb::e_mul_fm(lam[air::N_TUPLE], bb::to_mont((uint32_t)air::TAG_MEM));
+      fp.c[0] = bb::add(fp.c[0], bb::to_mont(c[0]));
+      fp = bb::e_add(fp, bb::e_mul_fm(lam[1], bb::to_mont(c[1])));
+      fp = bb::e_add(fp, bb::e_mul_fm(lam[2], bb::to_mont(t)));
+      for (int k = 0; k < 8; k++) fp = bb::e_add(fp, bb::e_mul_fm(lam[3 + k], bb::to_mont((uint32_t)((bytes >> (8 * k)) & 0xFF))));
+      return bb::e_sub(alpha_l, fp);
+    };
+    const unsigned parts = hashcall::parts_for(n / 4);
+    std::vector<E4> Tpart(parts, bb::e_zero());
+    hashcall::for_calls(n, parts, [&](unsigned part, size_t lo, size_t hi) {
+      std::vector<E4> d(2 * (hi - lo)), pre(2 * (hi - lo));
+      for (size_t k = lo; k < hi; k++) {
+        const uint32_t* c = sec + 1 + 7 * k;
+        const uint64_t addr = (uint64_t)c[0] | ((uint64_t)c[1] << 20), fin = (uint64_t)c[3] | ((uint64_t)c[4] << 16) | ((uint64_t)c[5] << 32) | ((uint64_t)c[6] << 48);
+        d[2 * (k - lo)] = mem_d(c, 0, image_cell(blob, blob_len, addr));
+        d[2 * (k - lo) + 1] = mem_d(c, c[2], fin);
+      }
+      E4 acc = bb::e_one_m(), Tp = bb::e_zero();
+      for (size_t i = 0; i < d.size(); i++) { pre[i] = acc; acc = bb::e_mul_m(acc, d[i]); }
+      E4 inv = bb::e_inv_m(acc);
+      for (size_t i = d.size(); i-- > 0;) {
+        const E4 di = bb::e_mul_m(inv, pre[i]);
+        inv = bb::e_mul_m(inv, d[i]);
+        Tp = (i & 1) ? bb::e_sub(Tp, di) : bb::e_add(Tp, di);               // + initial tuple, - final tuple
+      }
+      Tpart[part] = Tp;
+    });
+    for (const E4& tp : Tpart) T_mem = bb::e_add(T_mem, tp);
+  }
+  memcpy(T, T_mem.c, 16);
+}
+int host_mem_side(void* self, const uint32_t* lk_m, const uint8_t* blob, size_t blob_len, uint32_t T[4]) {
+  const zkir::HostMem& h = *static_cast<zkir::HostMem*>(self);
+  mem_side_sum(h.sec, h.n, blob, blob_len, lk_m, T);
+  return 0;
+}
+
 }  // namespace
 
 namespace zkir {
@@ -373,12 +436,45 @@ TapeStages host_tape_stages(HostTapes* h) { return TapeStages{h, host_hash_check
 int verify_with_stages(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, const TapeStages& stages) {
   return verify_impl(proof, proof_words, expect, true, nullptr, nullptr, &stages);
 }
+MemStages host_mem_stages(HostMem* h) { return MemStages{h, host_mem_check, host_mem_digests, host_mem_side}; }
+uint64_t mem_image_cell(const uint8_t* blob, size_t blob_len, uint64_t addr) { return image_cell(blob, blob_len, addr); }
+const uint8_t* mem_image_of(const uint8_t* blob, size_t blob_len, uint64_t* image_len) {      // (image_cell's rule)
+  *image_len = 0;
+  if (!blob || blob_len < 32) return nullptr;
+  uint32_t code_size, data_size; memcpy(&code_size, blob + 16, 4); memcpy(&data_size, blob + 20, 4);
+  if (32 + (uint64_t)code_size + data_size > blob_len) return nullptr;
+  *image_len = (uint64_t)code_size + data_size;
+  return blob + 32;
+}
+uint64_t stark_proof_blob_bytes(const uint32_t* proof, uint64_t proof_words) {
+  if (!proof || proof_words < 10 || proof[9] > 4) return 0;
+  const uint64_t at = (uint64_t)header_words_of((int)proof[9]);
+  if (proof_words <= at) return 0;
+  return std::min<uint64_t>(proof[at], 2 * (proof_words - at - 1));
+}
+void section_chunk_digests(const uint32_t* sw, size_t sl, uint32_t* dg) { section_digests_host(sw, sl, dg); }
+const char* mem_side_args(const uint32_t* sec, uint64_t n_words, const uint8_t* blob, size_t blob_len, const uint32_t alpha[4], const uint32_t lambda[4], const uint32_t* sum,
+                          uint32_t* lk, uint64_t* n) {
+  if (!sec || !alpha || !lambda || !sum || (!blob && blob_len)) return "null argument";
+  if (n_words < 1 || sec[0] > (1u << 28) || n_words != 1 + 7 * (uint64_t)sec[0]) return "the section must be [n] + 7 n words";
+  for (int k = 0; k < 4; k++) if (alpha[k] >= bb::P || lambda[k] >= bb::P) return "alpha and lambda must be canonical";
+  *n = sec[0];
+  for (int k = 0; k < air::N_LK; k++) lk[k] = 0;
+  E4 a, l1, lam = bb::e_one_m();
+  memcpy(a.c, alpha, 16); memcpy(l1.c, lambda, 16);
+  a = bb::e_to_mont(a); l1 = bb::e_to_mont(l1);
+  memcpy(lk + air::LK_ALPHA, a.c, 16);
+  for (int j = 0; j <= air::N_TUPLE; j++) { memcpy(lk + air::LK_LAM + 4 * j, lam.c, 16); lam = bb::e_mul_m(lam, l1); }
+  return nullptr;
+}
+void verify_note_memory(uint64_t cells, uint32_t launches, uint64_t uploaded_words) { last_memory = LastMemory{cells, uploaded_words, launches}; }
 void verify_note_device_stages(uint32_t n) { last_stages.device_stages = n; }
 void verify_note_queries(uint64_t hash_jobs, uint64_t value_jobs, uint32_t launches, uint64_t uploaded_words) { last_queries = LastQueries{hash_jobs, value_jobs, uploaded_words, launches}; }
 StarkQueryStage host_stark_query_stage() { return StarkQueryStage{nullptr, host_stark_run}; }
 int stark_host_queries_from(const StarkQueries& q, uint32_t first) { return first >= q.num_queries ? 0 : host_stark_queries_of(q, first); }
-int stark_verify_collect(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, bool whole_run, const TapeStages* stages, StarkQueries* out) {
-  return verify_impl(proof, proof_words, expect, whole_run, nullptr, nullptr, stages, out);
+int stark_verify_collect(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, bool whole_run, const TapeStages* stages, StarkQueries* out,
+                         const MemStages* mem) {
+  return verify_impl(proof, proof_words, expect, whole_run, nullptr, nullptr, stages, out, nullptr, mem);
 }
 }  // namespace zkir
 
@@ -476,6 +572,34 @@ int zkir_verify_last_stages(double ms[5], uint32_t* device_stages) {
   if (!last_stages.valid) return ZKIR_ERR_ARGUMENT;
   if (ms) for (int k = 0; k < 5; k++) ms[k] = last_stages.ms[k];
   if (device_stages) *device_stages = last_stages.device_stages;
+  return ZKIR_OK;
+}
+int zkir_verify_memory_last(uint64_t* cells, uint32_t* launches, uint64_t* uploaded_words) {
+  if (cells) *cells = last_memory.cells;
+  if (launches) *launches = last_memory.launches;
+  if (uploaded_words) *uploaded_words = last_memory.uploaded_words;
+  return ZKIR_OK;
+}
+int zkir_mem_section_check_host(const uint32_t* sec, uint64_t n_words, uint32_t mode, uint64_t code_words, int32_t* verdict) {
+  if (!verdict || (!sec && n_words)) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_mem_section_check_host: null argument"}); return ZKIR_ERR_ARGUMENT; }
+  size_t used = 0;
+  *verdict = host_mem_check(nullptr, sec, (size_t)n_words, (int)mode, code_words, &used);
+  return ZKIR_OK;
+}
+int zkir_mem_table_side_host(const uint32_t* sec, uint64_t n_words, const uint8_t* blob, size_t blob_len, const uint32_t alpha[4], const uint32_t lambda[4], uint32_t sum[4]) {
+  uint32_t lk[air::N_LK];
+  uint64_t n = 0;
+  size_t used = 0;
+  const char* why = zkir::mem_side_args(sec, n_words, blob, blob_len, alpha, lambda, sum, lk, &n);
+  if (!why && host_mem_check(nullptr, sec, (size_t)n_words, 3, 0, &used)) why = "the section's cells are not in range and strictly increasing";
+  if (why) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, std::string("zkir_mem_table_side_host: ") + why}); return ZKIR_ERR_ARGUMENT; }
+  try {
+    uint32_t T[4];
+    mem_side_sum(sec, (size_t)n, blob, blob_len, lk, T);
+    E4 t; memcpy(t.c, T, 16);
+    t = bb::e_from_mont(t);
+    memcpy(sum, t.c, 16);
+  } catch (const std::exception& e) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string("zkir_mem_table_side_host: ") + e.what()}); return ZKIR_ERR_OTHER; }
   return ZKIR_OK;
 }
 
@@ -777,8 +901,8 @@ int zkir_verify_chain_io(const uint32_t* const* proofs, const uint64_t* lens, ui
 namespace {
 
 int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out, const zkir::TapeStages* stages,
-                zkir::StarkQueries* defer, const RateCheck* rate) {
-  StageClock clk;                                                          // (diagnostics: the host wall time of the call's phases, kept for zkir_verify_last_stages)
+                zkir::StarkQueries* defer, const RateCheck* rate, const zkir::MemStages* mem) {
+  StageClock clk;                                                         // (diagnostics: the host wall time of the call's phases, kept for zkir_verify_last_stages)
   zkir::HostTapes host_tapes;
   const zkir::TapeStages host_stages = zkir::host_tape_stages(&host_tapes);
   const zkir::TapeStages& S = stages ? *stages : host_stages;
@@ -861,7 +985,13 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   struct Cell { uint64_t addr, bytes; uint32_t t; };
   std::vector<Cell> cells;
   const uint32_t* mem_words = nullptr; size_t mem_len = 0;
-  if (mode >= 3) {
+  if (mode >= 3 && mem) {                                                  // (a memory stage: its verdict on the section — 4, 54 or 55, as below)
+    size_t used = 0;
+    const int mrc = mem->check(mem->self, w + p, (size_t)(len - p), mode, n_code, &used);
+    if (mrc) return mrc;
+    mem_words = w + p; mem_len = used;
+    p += mem_len;
+  } else if (mode >= 3) {
     if (!need(1)) return 4;
     const size_t nc = w[p];
     if (nc > ((size_t)1 << 28) || !need(1 + 7 * nc)) return 4;
@@ -869,15 +999,13 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     cells.resize(nc);
     for (size_t k = 0; k < nc; k++) {
       const uint32_t* c = w + p + 1 + 7 * k;
-      if (c[0] >= (1u << 20) || (c[0] & 7) || c[1] >= (1u << 20)) return 54;
-      uint64_t bytes = 0;
-      for (int i = 0; i < 4; i++) { if (c[3 + i] > 0xFFFF) return 54; bytes |= (uint64_t)c[3 + i] << (16 * i); }
-      cells[k] = Cell{(uint64_t)c[0] | ((uint64_t)c[1] << 20), bytes, c[2]};
-      if (k && cells[k].addr <= cells[k - 1].addr) return 54;
-      // (v11, check 55) no access to the CODE: instruction fetch is tied to the program's words, so a store into [0x1000, 0x1000 + code_size) would change what the VM executes
-      // next (vm.rs:175) but not what the AIR lets through — every accessed cell is in this list (the memory check does not balance otherwise), and none may overlap the code
+      // limb ranges, byte pieces and strictly increasing addresses (54), then (v11, check 55) no access to the CODE: instruction fetch is tied to the program's words, so a
+      // store into [0x1000, 0x1000 + code_size) would change what the VM executes next (vm.rs:175) but not what the AIR lets through — every accessed cell is in this list (the
+      // memory check does not balance otherwise), and none may overlap the code
       // (mode 4) .. except the BOUNDARY cell (code_size % 8 == 4: the last code word and the first four data bytes): the AIR states there that no store writes its low half
-      if (cells[k].addr + 8 > air::CODE_BASE && cells[k].addr < air::CODE_BASE + 4 * (uint64_t)n_code && !(mode == 4 && (n_code & 1) && cells[k].addr == air::boundary_cell(4 * (uint64_t)n_code))) return 55;
+      const int ccode = air::mem_cell_code(c, k ? c - 7 : nullptr, mode, (uint64_t)n_code);
+      if (ccode) return ccode;
+      cells[k] = Cell{(uint64_t)c[0] | ((uint64_t)c[1] << 20), (uint64_t)c[3] | ((uint64_t)c[4] << 16) | ((uint64_t)c[5] << 32) | ((uint64_t)c[6] << 48), c[2]};
     }
     p += mem_len;
   }
@@ -950,7 +1078,12 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     ch.observe_n(dg.data(), dg.size());
   };
   clk.lap(4);
-  if (mode >= 3) observe_section(mem_words, mem_len);
+  if (mode >= 3 && mem) {
+    std::vector<uint32_t> dg(4 * ((mem_len + 511) / 512));
+    const int drc = mem->digests(mem->self, mem_words, mem_len, dg.data());
+    if (drc) return drc;
+    ch.observe_n(dg.data(), dg.size());
+  } else if (mode >= 3) observe_section(mem_words, mem_len);
   if (mode == 4) {
     std::vector<uint32_t> dg;
     for (int which = 0; which < 2; which++) {
@@ -1012,6 +1145,13 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
         clk.lap(3);
         if (ws) return ws;
         T_hash = bb::e_add(Th, Tw);
+      }
+      // (a memory stage) the cells' two ends are the stage's sum: `cells` is empty here, so none of them is in d
+      if (mem) {
+        E4 Tm = bb::e_zero();
+        const int ms = mem->side(mem->self, lk_m, blob.data(), blob_len, Tm.c);
+        if (ms) return ms;
+        T_hash = bb::e_add(T_hash, Tm);
       }
     }
     for (size_t u = 0; u < n_code; u++) {
@@ -1772,9 +1912,10 @@ int zkir_mixed_eval_verify(const uint32_t* w, uint64_t len, const uint32_t* expe
 
 namespace zkir {
 QueryStage host_query_stage() { return QueryStage{nullptr, host_query_run}; }
-int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage, const TapeStages* tapes) {
+int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage, const TapeStages* tapes,
+                           const MemStages* mem) {
   const RateCheck rate{min_queries, min_pow_bits, &stage};
-  return verify_impl(proof, n_words, expect, true, nullptr, nullptr, tapes, nullptr, &rate);
+  return verify_impl(proof, n_words, expect, true, nullptr, nullptr, tapes, nullptr, &rate, mem);
 }
 int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage) {
   if (kind == 0) return lowdeg_verify_impl(proof, n_words, expect_roots, stage);

@@ -16,7 +16,8 @@ struct VerifyDevice {
   unsigned char* d = nullptr; size_t cap = 0;
   p2::Consts* d_p2 = nullptr;
   zkir::HostPin pin;
-  int ensure(size_t bytes) {
+  // keep: the first `keep` bytes of the block hold data AT REST (the memory stages' region, mem_stage.inl: its last use has been synchronised) that a larger block must still hold
+  int ensure(size_t bytes, size_t keep = 0) {
     if (!d_p2) {
       p2::Consts k; p2::generate(k);
       HIP_OK(hipMalloc((void**)&d_p2, sizeof k));
@@ -24,6 +25,16 @@ struct VerifyDevice {
       if (e != hipSuccess) { (void)hipFree(d_p2); d_p2 = nullptr; HIP_OK(e); }
     }
     if (bytes <= cap) return ZKIR_OK;
+    if (d && keep) {
+      unsigned char* nd = nullptr;
+      HIP_OK(hipMalloc((void**)&nd, bytes));
+      hipError_t e = hipMemcpy(nd, d, keep, hipMemcpyDeviceToDevice);
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+      if (e != hipSuccess) { (void)hipFree(nd); HIP_OK(e); }
+      (void)hipFree(d);
+      d = nd; cap = bytes;
+      return ZKIR_OK;
+    }
     if (d) { (void)hipFree(d); d = nullptr; cap = 0; }
     HIP_OK(hipMalloc((void**)&d, bytes));
     cap = bytes;
@@ -59,6 +70,8 @@ struct DeviceTapes {
   uint64_t n_calls = 0, H = 0, hash_words = 0, n_wide = 0;
   size_t o_prefix = 0, o_side = 0, o_hlist = 0, o_wide = 0, o_wlist = 0, o_lk = 0, o_part = 0, o_check = 0, o_dg = 0, o_patch = 0, patch_cap = 0;
   DeviceTapes(VerifyDevice& v, hipStream_t st) : V(v), s(st), host_st(zkir::host_tape_stages(&host)) {}
+  size_t base = 0;                                               // bytes at the block's start that belong to the memory stages (mem_stage.inl; a multiple of 256): the layout starts behind them
+  unsigned char* D() const { return V.d + base; }
 
   int upload(size_t off, const void* src, size_t bytes) {
     if (!bytes) return ZKIR_OK;
@@ -68,7 +81,7 @@ struct DeviceTapes {
     for (size_t at = 0; at < bytes; at += PIECE) {
       const size_t n = std::min(PIECE, bytes - at);
       memcpy((unsigned char*)h + at, (const unsigned char*)src + at, n);
-      HIP_OK(hipMemcpyAsync(V.d + off + at, (unsigned char*)h + at, n, hipMemcpyHostToDevice, s));
+      HIP_OK(hipMemcpyAsync(D() + off + at, (unsigned char*)h + at, n, hipMemcpyHostToDevice, s));
     }
     return ZKIR_OK;
   }
@@ -85,12 +98,12 @@ struct DeviceTapes {
     o_check = o_part + al256(2 * (size_t)TAPE_MAX_BLOCKS * sizeof(E4)); o_dg = o_check + 256; o_patch = o_dg + al256(16 * n_chunks + 16);
     patch_cap = al256((size_t)words / 16 + 64);                 // (a call the host hashes is above 1 KiB: at least 640 words of tape for its 80 bytes of patches)
     if (n_check) {
-      int rc = V.ensure(o_patch + 2 * patch_cap + 256); if (rc) return -rc;
+      int rc = V.ensure(base + o_patch + 2 * patch_cap + 256, base); if (rc) return -rc;
       stages_run++;
       rc = upload(0, w, words * 4); if (rc) return -rc;
       rc = upload(o_prefix, prefix.data(), n_check * 8); if (rc) return -rc;
       int dcode = 0; uint64_t dcall = ~0ull;
-      rc = hash_tape_check_run((const uint32_t*)V.d, (const uint64_t*)(V.d + o_prefix), n_check, wk.n_full, n_real, code_end, (unsigned long long*)(V.d + o_check), V.pin, s, &dcode, &dcall);
+      rc = hash_tape_check_run((const uint32_t*)D(), (const uint64_t*)(D() + o_prefix), n_check, wk.n_full, n_real, code_end, (unsigned long long*)(D() + o_check), V.pin, s, &dcode, &dcall);
       if (rc) return -rc;
       if (check_launch("zkir_verify_device: record checks") != ZKIR_OK) return -ZKIR_ERR_DEVICE;
       if (dcode) best = std::min(best, ((unsigned long long)dcall << 8) | (unsigned)dcode);
@@ -99,7 +112,7 @@ struct DeviceTapes {
     // every record is what the kernels take it for: the full prefix goes up and the new bytes are formed while the host goes on parsing
     hash_dev = true; h_hash = w; n_calls = wk.n_calls; H = wk.cells; hash_words = wk.used; *used = (size_t)wk.used;
     int rc = upload(o_prefix, prefix.data(), (n_calls + 1) * 8); if (rc) return -rc;
-    hash_new_bytes_enqueue((const uint32_t*)V.d, (const uint64_t*)(V.d + o_prefix), n_calls, H, (uint64_t*)(V.d + o_side), s);
+    hash_new_bytes_enqueue((const uint32_t*)D(), (const uint64_t*)(D() + o_prefix), n_calls, H, (uint64_t*)(D() + o_side), s);
     return 0;
   }
   int wide_check(const uint32_t* sec, size_t n, uint64_t n_real) {
@@ -107,16 +120,16 @@ struct DeviceTapes {
     if (!hash_dev) {                                            // (no hash call went up: the block holds the wide tape alone)
       o_wide = 0; o_wlist = al256((1 + 8 * n) * 4 + 16); o_lk = o_wlist + al256(n * sizeof(HashAux) + 32); o_part = o_lk + al256(air::N_LK * 4);
       o_check = o_part + al256(2 * (size_t)TAPE_MAX_BLOCKS * sizeof(E4)); o_dg = o_check + 256; o_patch = o_dg + al256(16 * ((1 + 8 * n + 511) / 512) + 16);
-      const int rc = V.ensure(o_patch + 256); if (rc) return -rc;
+      const int rc = V.ensure(base + o_patch + 256, base); if (rc) return -rc;
     }
     stages_run++;
     n_wide = n; wide_dev = true;
     int rc = upload(o_wide + 12, sec, (1 + 8 * n) * 4); if (rc) return -rc;      // (the records behind the count word start on 16 bytes: wide_table_side_kernel loads uint4)
     uint32_t* hb = V.pin.take_n<uint32_t>(1);
     if (!hb) return -ZKIR_ERR_DEVICE;
-    uint32_t* d_bad = (uint32_t*)(V.d + o_check + 64);
+    uint32_t* d_bad = (uint32_t*)(D() + o_check + 64);
     if (hipMemsetAsync(d_bad, 0, 4, s) != hipSuccess) return -ZKIR_ERR_DEVICE;
-    hipLaunchKernelGGL(wide_tape_check_kernel, dim3(grid_for(n)), dim3(NT), 0, s, (const uint32_t*)(V.d + o_wide + 16), (uint64_t)n, n_real, d_bad);
+    hipLaunchKernelGGL(wide_tape_check_kernel, dim3(grid_for(n)), dim3(NT), 0, s, (const uint32_t*)(D() + o_wide + 16), (uint64_t)n, n_real, d_bad);
     if (hipMemcpyAsync(hb, d_bad, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess || check_launch("zkir_verify_device: wide record checks") != ZKIR_OK) return -ZKIR_ERR_DEVICE;
     return *hb ? 57 : 0;
   }
@@ -124,10 +137,10 @@ struct DeviceTapes {
     if (!(which ? wide_dev : hash_dev)) return host_st.digests(&host, which, sw, sl, dg);
     stages_run++;
     const size_t n_chunks = (sl + 511) / 512, at = which ? (size_t)(hash_dev ? (hash_words + 511) / 512 : 0) : 0;
-    uint32_t* d_dg = (uint32_t*)(V.d + o_dg) + 4 * at;
+    uint32_t* d_dg = (uint32_t*)(D() + o_dg) + 4 * at;
     uint32_t* h = V.pin.take_n<uint32_t>(4 * n_chunks);
     if (!h) return -ZKIR_ERR_DEVICE;
-    hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks + 63) / 64)), dim3(64), 0, s, V.d_p2, (const uint32_t*)(V.d + (which ? o_wide + 12 : 0)), (uint64_t)sl, d_dg);
+    hipLaunchKernelGGL(section_hash_kernel, dim3((unsigned)((4 * n_chunks + 63) / 64)), dim3(64), 0, s, V.d_p2, (const uint32_t*)(D() + (which ? o_wide + 12 : 0)), (uint64_t)sl, d_dg);
     if (hipMemcpyAsync(h, d_dg, 16 * n_chunks, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess || check_launch("zkir_verify_device: section digests") != ZKIR_OK) return -ZKIR_ERR_DEVICE;
     memcpy(dg, h, 16 * n_chunks);
     return 0;
@@ -143,12 +156,12 @@ struct DeviceTapes {
       if (idx.size() * 8 > patch_cap) { zkir::set_last_error({ZKIR_ERR_OTHER, "zkir_verify_device: more long calls than the tape can hold"}); return -ZKIR_ERR_OTHER; }
       rc = upload(o_patch, idx.data(), idx.size() * 8); if (rc) return -rc;
       rc = upload(o_patch + patch_cap, val.data(), val.size() * 8); if (rc) return -rc;
-      hipLaunchKernelGGL(side_patch_kernel, dim3(grid_for(idx.size())), dim3(NT), 0, s, (const uint64_t*)(V.d + o_patch), (const uint64_t*)(V.d + o_patch + patch_cap), (uint64_t)idx.size(),
-                         (uint64_t*)(V.d + o_side));
+      hipLaunchKernelGGL(side_patch_kernel, dim3(grid_for(idx.size())), dim3(NT), 0, s, (const uint64_t*)(D() + o_patch), (const uint64_t*)(D() + o_patch + patch_cap), (uint64_t)idx.size(),
+                         (uint64_t*)(D() + o_side));
     }
     TapePartials hp;
-    rc = hash_table_side_enqueue((const uint32_t*)V.d, (const uint64_t*)(V.d + o_prefix), (const uint64_t*)(V.d + o_side), n_calls, H, (const uint32_t*)(V.d + o_lk), (HashAux*)(V.d + o_hlist),
-                                 (E4*)(V.d + o_part), V.pin, s, &hp);
+    rc = hash_table_side_enqueue((const uint32_t*)D(), (const uint64_t*)(D() + o_prefix), (const uint64_t*)(D() + o_side), n_calls, H, (const uint32_t*)(D() + o_lk), (HashAux*)(D() + o_hlist),
+                                 (E4*)(D() + o_part), V.pin, s, &hp);
     if (rc) return -rc;
     if (hipStreamSynchronize(s) != hipSuccess || check_launch("zkir_verify_device: hash table side") != ZKIR_OK) return -ZKIR_ERR_DEVICE;
     E4 t = bb::e_zero(); hp.add_to(t);
@@ -160,7 +173,7 @@ struct DeviceTapes {
     stages_run++;
     int rc = upload(o_lk, lk_m, air::N_LK * 4); if (rc) return -rc;
     TapePartials wp;
-    rc = wide_table_side_enqueue((const uint32_t*)(V.d + o_wide + 16), (uint32_t)n_wide, (const uint32_t*)(V.d + o_lk), (HashAux*)(V.d + o_wlist), (E4*)(V.d + o_part) + TAPE_MAX_BLOCKS, V.pin, s, &wp);
+    rc = wide_table_side_enqueue((const uint32_t*)(D() + o_wide + 16), (uint32_t)n_wide, (const uint32_t*)(D() + o_lk), (HashAux*)(D() + o_wlist), (E4*)(D() + o_part) + TAPE_MAX_BLOCKS, V.pin, s, &wp);
     if (rc) return -rc;
     if (hipStreamSynchronize(s) != hipSuccess || check_launch("zkir_verify_device: wide table side") != ZKIR_OK) return -ZKIR_ERR_DEVICE;
     E4 t = bb::e_zero(); wp.add_to(t);

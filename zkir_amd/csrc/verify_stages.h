@@ -1,6 +1,7 @@
 // verify_stages.h — the three stages of a mode-4 verification that are linear in the size of the proof's tapes (the hash section and the wide section), behind one
 // small interface: verify.cpp fills it with its host code (zkir_verify and its siblings: host only, no HIP call), zkir_verify_device (verify_device.inl, in the prover's
-// translation unit) with the device forms.  Everything else a verifier does (header, program, touched cells, constraints at zeta, FRI, queries) is verify.cpp's alone.
+// translation unit) with the device forms.  The touched cells' three stages have an interface of their own below (MemStages); the query stages follow.  Everything else a
+// verifier does (header, program, constraints at zeta, FRI) is verify.cpp's alone.
 //
 // A stage returns a VERDICT: 0 or the failed check's number, exactly what the host code returns at that point — or a NEGATIVE value: no verdict could be formed (a device
 // failure, no memory; zkir_last_error says which), which the verifier passes through unchanged.
@@ -33,6 +34,37 @@ TapeStages host_tape_stages(HostTapes* h);
 int verify_with_stages(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, const TapeStages& stages);
 void verify_note_device_stages(uint32_t n);                      // (zkir_verify_device) how many stages of the calling thread's last verification ran on the device
 
+// ---- the three stages of a mode-3 / mode-4 verification that are linear in the TOUCHED-CELL section ([n] + 7 n words: air::mem_cell_code names a record's fields) ----
+// A verifier handed NO MemStages runs its own inline host code (zkir_verify and every entry from before this interface: literally the code they always ran); handed one, it
+// skips its cell loop, observes the stage's digests, leaves the cells' 2 n denominators out of its batch inversion and adds the stage's share of the table side.  verify.cpp
+// fills the interface with host functions (what the device form leaves small sections to, and what zkir_mem_section_check_host / zkir_mem_table_side_host run),
+// mem_stage.inl with the device forms.  Verdicts as above.
+struct MemStages {
+  void* self;
+  // the section that starts at sec (avail words to the proof's end): 4 (the proof ends inside it, or its count is above 2^28), else the code of the LOWEST failing cell
+  // (air::mem_cell_code: 54 / 55); 0: *used = 1 + 7 n.  code_words: the program's code size in words
+  int (*check)(void* self, const uint32_t* sec, size_t avail, int mode, uint64_t code_words, size_t* used);
+  // so::observe_section's chunk digests of the checked section: dg = 4 words per chunk of 512
+  int (*digests)(void* self, const uint32_t* sec, size_t len, uint32_t* dg);
+  // the checked section's share of the table side, Montgomery E4: per cell + 1 / (alpha - fp(cell, 0, the program image's bytes)) - 1 / (alpha - fp(cell, t_last, final
+  // bytes)); lk_m: air.h LK_ALPHA and LK_LAM, Montgomery; blob: the program the proof carries (the image bytes are mem_image_cell's)
+  int (*side)(void* self, const uint32_t* lk_m, const uint8_t* blob, size_t blob_len, uint32_t T[4]);
+};
+struct HostMem { const uint32_t* sec = nullptr; size_t n = 0; };      // what the host stages keep between their calls
+MemStages host_mem_stages(HostMem* h);
+// the bytes of cell `addr` in the VM's initial memory (code at 0x1000, data behind it, zero elsewhere; all zero where the blob is shorter than its header or than what the
+// header claims), and the part of the blob that holds them: *image_len = code + data bytes behind blob + 32, 0 under the same rule
+uint64_t mem_image_cell(const uint8_t* blob, size_t blob_len, uint64_t addr);
+const uint8_t* mem_image_of(const uint8_t* blob, size_t blob_len, uint64_t* image_len);
+// the byte length the proof states for the program blob it carries, cut to what the proof can hold (0: a proof too short to say): no image a memory stage is handed is longer
+uint64_t stark_proof_blob_bytes(const uint32_t* proof, uint64_t proof_words);
+void section_chunk_digests(const uint32_t* sw, size_t sl, uint32_t* dg);      // so::observe_section's chunk digests on host threads
+// zkir_mem_table_side_host / _launch's argument checks: nullptr and lk (air::N_LK Montgomery words: alpha, lambda^0 .. lambda^11 from the canonical challenges), *n = the
+// section's cells — or why the call is refused.  The cells themselves (in range, strictly increasing: check 54) are the caller's to check.
+const char* mem_side_args(const uint32_t* sec, uint64_t n_words, const uint8_t* blob, size_t blob_len, const uint32_t alpha[4], const uint32_t lambda[4], const uint32_t* sum,
+                          uint32_t* lk, uint64_t* n);
+void verify_note_memory(uint64_t cells, uint32_t launches, uint64_t uploaded_words);      // (zkir_verify_memory_device) zkir_verify_memory_last's record
+
 // ---- the QUERY STAGE of the commitment layer's verifiers (zkir_lowdeg_verify, zkir_eval_verify, zkir_batch_eval_verify and their *_device forms) ----
 // Checks 6 .. 11 of all the queries of a 'ZKLD' / 'ZKEV' / 'ZKBE' proof.  verify.cpp's fri_part_verify hands the stage what it has CHECKED (the shape: checks 1 and 3 passed,
 // so the length is exactly the header's and every word is below p) and what it has DRAWN from the transcript; verify.cpp fills the stage with its host loop (no HIP call),
@@ -57,9 +89,9 @@ QueryStage host_query_stage();                                   // the loop of 
 // the three verifiers, by the proof's kind (0 'ZKLD', 1 'ZKEV', 2 'ZKBE'; 'ZKLD' has one root and no points): everything but the query stage is verify.cpp's host code
 int pcs_verify_with_stage(int kind, const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const QueryStage& stage);
 // a 'ZKSR' proof (zkir_verify_rate): verify.cpp's STARK front and constraint check on the host, the embedded evaluation proof's query stage behind `stage`; a mode-4
-// proof's three tape stages behind `tapes` (NULL: the host forms)
+// proof's three tape stages behind `tapes` (NULL: the host forms), a mode-3 / mode-4 proof's memory stages behind `mem` (NULL: the verifier's inline host code)
 int rate_verify_with_stage(const uint32_t* proof, uint64_t n_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, const QueryStage& stage,
-                           const TapeStages* tapes = nullptr);
+                           const TapeStages* tapes = nullptr, const MemStages* mem = nullptr);
 
 // ---- the query stage over a LIST of proofs (zkir_verify_rate_chain, zkir_verify_rate_many_device, zkir_pcs_verify_many_device and their siblings) ----
 // A PcsCollected OWNS what a PcsQueries points at except the proof (samples, gamma table, betas): pcs_collect_stage is a QueryStage that copies the description it is handed
@@ -125,8 +157,10 @@ struct StarkQueries {
 struct StarkQueryStage { void* self; int (*run)(void* self, const StarkQueries* list, uint32_t n, int* codes); };
 StarkQueryStage host_stark_query_stage();                        // the loop of verify.cpp: host threads, ZKIR_VERIFY_THREADS
 // verify_impl up to check 11 (whole runs: check 7 included; a segment: whole_run = false, its boundary states and counters out): 0 = *out is filled and the queries are the
-// caller's (then check 30: stark_length_check), else the failed check.  stages: nullable (the host tape stages).
-int stark_verify_collect(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, bool whole_run, const TapeStages* stages, StarkQueries* out);
+// caller's (then check 30: stark_length_check), else the failed check.  stages: nullable (the host tape stages); mem: nullable (the inline host code).
+// out == NULL: the whole verification, queries and check 30 included (zkir_verify's verdict).
+int stark_verify_collect(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, bool whole_run, const TapeStages* stages, StarkQueries* out,
+                         const MemStages* mem = nullptr);
 int stark_host_queries_from(const StarkQueries& q, uint32_t first);      // the host loop over queries first .. num_queries - 1 (the device stage: the queries a short proof cuts)
 void verify_note_queries(uint64_t hash_jobs, uint64_t value_jobs, uint32_t launches, uint64_t uploaded_words);      // (the *_on_device entries) zkir_verify_queries_last's record
 inline int stark_length_check(const StarkQueries& q) { return q.at_queries + (uint64_t)q.num_queries * q.qsize != q.len ? 30 : 0; }

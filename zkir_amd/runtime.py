@@ -406,6 +406,14 @@ def lib() -> C.CDLL:
         L.zkir_hash_tape_new_bytes_host.restype = C.c_int; L.zkir_hash_tape_new_bytes_host.argtypes = [V, U64, V]
         L.zkir_verify_device.restype = C.c_int; L.zkir_verify_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
         L.zkir_verify_last_stages.restype = C.c_int; L.zkir_verify_last_stages.argtypes = [V, C.POINTER(C.c_uint32)]
+    if hasattr(L, "zkir_verify_memory_device"):               # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_verify_memory_device.restype = C.c_int; L.zkir_verify_memory_device.argtypes = [V, U64, C.POINTER(PublicInputsC), C.c_int, V]
+        L.zkir_verify_rate_memory_device.restype = C.c_int; L.zkir_verify_rate_memory_device.argtypes = [V, U64, C.POINTER(PublicInputsC), U32, U32, V]
+        L.zkir_verify_memory_last.restype = C.c_int; L.zkir_verify_memory_last.argtypes = [C.POINTER(U64), C.POINTER(U32), C.POINTER(U64)]
+        L.zkir_mem_section_check_host.restype = C.c_int; L.zkir_mem_section_check_host.argtypes = [V, U64, U32, U64, C.POINTER(C.c_int32)]
+        L.zkir_mem_section_check_launch.restype = C.c_int; L.zkir_mem_section_check_launch.argtypes = [V, U64, U32, U64, C.POINTER(C.c_int32), V]
+        L.zkir_mem_table_side_host.restype = C.c_int; L.zkir_mem_table_side_host.argtypes = [V, U64, C.c_char_p, C.c_size_t, V, V, V]
+        L.zkir_mem_table_side_launch.restype = C.c_int; L.zkir_mem_table_side_launch.argtypes = [V, U64, C.c_char_p, C.c_size_t, V, V, V, V]
     if hasattr(L, "zkir_verify_on_device"):                   # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
         L.zkir_verify_on_device.restype = C.c_int; L.zkir_verify_on_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
         L.zkir_verify_many_on_device.restype = C.c_int; L.zkir_verify_many_on_device.argtypes = [V, V, V, C.c_uint32, V, V]
@@ -672,6 +680,40 @@ def verify_queries_last() -> dict:
     return {"hash_jobs": int(h.value), "value_jobs": int(v.value), "launches": int(l.value), "uploaded_words": int(u.value)}
 
 
+def verify_memory_last() -> dict:
+    """zkir_verify_memory_last: the device memory stages of this thread's last verification — the cells whose stages ran on the GPU, their launches and the words uploaded
+    for them (all zero after any entry but verify(device=True, memory=True) / verify_rate(device=True, memory=True))."""
+    c, l, u = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+    lib().zkir_verify_memory_last(C.byref(c), C.byref(l), C.byref(u))
+    return {"cells": int(c.value), "launches": int(l.value), "uploaded_words": int(u.value)}
+
+
+def mem_section_check(sec, mode: int, code_words: int, device: bool = True, stream=None) -> int:
+    """zkir_mem_section_check_launch / _host: the verifier's checks of a touched-cell section ([n] + 7 n words) — 0 well-formed, 4 shorter than its count states, 54 a
+    cell out of range or not above its predecessor, 55 a cell on the code_words code words at 0x1000 (mode 4 admits the boundary cell); of the lowest failing cell."""
+    s = np.ascontiguousarray(sec, dtype=np.uint32).reshape(-1)
+    verdict = C.c_int32(-1)
+    args = [s.ctypes.data if len(s) else None, len(s), int(mode), int(code_words), C.byref(verdict)]
+    rc = lib().zkir_mem_section_check_launch(*args, stream) if device else lib().zkir_mem_section_check_host(*args)
+    if rc != ZKIR_OK:
+        _raise(rc)
+    return int(verdict.value)
+
+
+def mem_table_side(sec, blob: bytes, alpha, lam, device: bool = True, stream=None) -> np.ndarray:
+    """zkir_mem_table_side_launch / _host: the touched cells' share of the lookup table side, sum over the cells of 1 / (alpha - fp(cell, 0, image bytes)) -
+    1 / (alpha - fp(cell, t_last, final bytes)) -> canonical E4 (np.uint32[4]).  alpha, lam: canonical E4; blob: the program (its image bytes)."""
+    s = np.ascontiguousarray(sec, dtype=np.uint32).reshape(-1)
+    a, l = np.ascontiguousarray(alpha, dtype=np.uint32), np.ascontiguousarray(lam, dtype=np.uint32)
+    blob = bytes(blob)
+    out = np.zeros(4, dtype=np.uint32)
+    args = [s.ctypes.data if len(s) else None, len(s), blob, len(blob), a.ctypes.data, l.ctypes.data, out.ctypes.data]
+    rc = lib().zkir_mem_table_side_launch(*args, stream) if device else lib().zkir_mem_table_side_host(*args)
+    if rc != ZKIR_OK:
+        _raise(rc)
+    return out
+
+
 def verify_queries_last_stage_ms():
     """zkir_verify_queries_last_stage_ms: (upload, kernels, download) host clocks in ms of this thread's last device query stage, measured only with
     ZKIR_VERIFY_QUERIES_TIMES set."""
@@ -715,15 +757,24 @@ def verify_chain_io(proofs, expect: Optional[PublicInputsC], inputs, outputs, ha
     return L.zkir_verify_chain_io(ptrs, lens, len(ps), C.byref(expect) if expect is not None else None, i.ctypes.data, len(i), o.ctypes.data, len(o), int(kind), int(code or 0))
 
 
-def verify(proof: np.ndarray, expect: Optional[PublicInputsC] = None, device: bool = False, stream=None, queries: bool = False) -> int:
+def verify(proof: np.ndarray, expect: Optional[PublicInputsC] = None, device: bool = False, stream=None, queries: bool = False, memory: bool = False) -> int:
     """zkir_verify (host only): 0 = accepted, otherwise the number of the failed check.  device=True: zkir_verify_device — the same verdict, a mode-4 proof's tape stages
     (record checks, chunk digests, the table side with every hash call's digest) on the GPU; device=True, queries=True: zkir_verify_on_device — the same verdict, any mode,
-    the query stage (Merkle paths, layer-0 values, folds) on the GPU as well; a negative result is a device failure, not a verdict (raised)."""
+    the query stage (Merkle paths, layer-0 values, folds) on the GPU as well; device=True, memory=True: zkir_verify_memory_device — the same verdict, a mode-3 / mode-4
+    proof's touched-cell stages (cell checks, chunk digests, the cells' share of the table side) on the GPU too, with or without queries=True; a negative result is a
+    device failure, not a verdict (raised)."""
     proof = np.ascontiguousarray(proof, dtype=np.uint32)
     if not device:
         if queries:
             raise ValueError("queries=True needs device=True")
+        if memory:
+            raise ValueError("memory=True needs device=True")
         return lib().zkir_verify(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None)
+    if memory:
+        rc = lib().zkir_verify_memory_device(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None, 1 if queries else 0, stream)
+        if rc < 0:
+            _raise(-rc)
+        return rc
     entry = lib().zkir_verify_on_device if queries else lib().zkir_verify_device
     rc = entry(proof.ctypes.data, len(proof), C.byref(expect) if expect is not None else None, stream)
     if rc < 0:
@@ -836,16 +887,20 @@ def batch_eval_proof_words(log_n: int, log_blowup: int, widths, masks, n_points:
 RATE_DEFAULT_QUERIES = {1: 50, 2: 25, 3: 17}                  # by log_blowup: about 100 bits from the queries at rate 2^-b, plus the grinding bits
 
 
-def verify_rate(proof, expect: Optional[PublicInputsC] = None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None) -> int:
+def verify_rate(proof, expect: Optional[PublicInputsC] = None, min_queries: int = 1, min_pow_bits: int = 0, device: bool = False, stream=None, memory: bool = False) -> int:
     """zkir_verify_rate, on the host — no GPU: 0 = the 'ZKSR' proof (stark.prove_rate: a ZKIR-STARK run at the rate its header states) is accepted and states at least
     `min_queries` queries and `min_pow_bits` grinding bits; otherwise the number of the failed check (include/zkir_amd.h: zkir_verify's codes for the front — 54 - 57 in modes 3 / 4 —, 2 also for too
     few queries or bits, 5 an embedded proof of another shape, 10 the constraints at zeta, 100 + c for the embedded evaluation proof's code c).  `expect.fri_params` is not
-    consulted.  device=True: zkir_verify_rate_device — the same verdict, the embedded proof's query stage on the GPU; a negative result is a device failure (raised)."""
+    consulted.  device=True: zkir_verify_rate_device — the same verdict, the embedded proof's query stage on the GPU; device=True, memory=True:
+    zkir_verify_rate_memory_device — a mode-3 / mode-4 proof's touched-cell stages on the GPU too; a negative result is a device failure (raised)."""
     w = np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1)
     e = C.byref(expect) if expect is not None else None
     if not device:
+        if memory:
+            raise ValueError("memory=True needs device=True")
         return lib().zkir_verify_rate(w.ctypes.data, len(w), e, int(min_queries), int(min_pow_bits))
-    rc = lib().zkir_verify_rate_device(w.ctypes.data, len(w), e, int(min_queries), int(min_pow_bits), stream)
+    entry = lib().zkir_verify_rate_memory_device if memory else lib().zkir_verify_rate_device
+    rc = entry(w.ctypes.data, len(w), e, int(min_queries), int(min_pow_bits), stream)
     if rc < 0:
         _raise(-rc)
     return rc
