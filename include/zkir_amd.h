@@ -751,12 +751,25 @@ int zkir_verify_last_stages(double ms[5], uint32_t* device_stages);
  * below 512 cells stays with the host stages (the measured crossover: profiles/r24_verify_memory_device.txt); ZKIR_VERIFY_DEVICE_MIN_CELLS in the environment sets
  * another threshold (0: every non-empty section on the device), for measuring the routes against each other.
  * zkir_verify_last_stages' device_stages counts the memory stages beside the tape stages: 3 for a non-empty section.
- * Not covered: the memory stages inside zkir_verify_many_on_device / zkir_verify_rate_many_device (their mode-3 fronts stay on the host). */
+ * zkir_verify_many_on_device / zkir_verify_rate_many_device keep their mode-3 / mode-4 fronts' memory sections on the host; the *_many_memory_device entries below are
+ * their forms with the sections of ALL proofs as one device batch. */
 /* zkir_verify's verdict; the memory section's three stages and a mode-4 proof's tape stages on the device;
    queries != 0: the query stage too (zkir_verify_on_device's). Modes 0-2: the existing entry's behaviour. */
 int zkir_verify_memory_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, int queries, void* hip_stream);
 /* zkir_verify_rate_device with the memory stages on the device */
 int zkir_verify_rate_memory_device(const uint32_t* proof, uint64_t proof_words, const zkir_public_inputs* expect, uint32_t min_queries, uint32_t min_pow_bits, void* hip_stream);
+/* MANY PROOFS, ONE BATCH (csrc/mem_stage_many.inl).  zkir_verify_many_on_device / zkir_verify_rate_many_device with the memory sections of all their mode-3 / mode-4
+ * proofs verified together: every section is uploaded once and checked and hashed by ONE launch each before any front runs; the fronts then run on the host, proof
+ * after proof, and DEFER check 10 (the only reader of the cells' share of the table side, on which no challenge, grinding or sample depends); behind the last front ONE
+ * launch forms every deferred proof's share, the host completes the kept checks, and a proof whose deferred check fails has verdict 10 whatever its front answered
+ * afterwards.  Three launches and two synchronisations for the memory stages of the whole call; a mode-4 proof's tape stages run per proof behind the batch region; the
+ * queries are the existing batched stage.  n = 1 .. 1024, modes 0 - 4 mixed; verdicts[i] is zkir_verify's / zkir_verify_rate's on every input.  The batch goes to the
+ * device when the TOTAL cells of its sections reach the threshold above (ZKIR_VERIFY_DEVICE_MIN_CELLS overrides it); below it every front runs the inline host code.
+ * zkir_verify_memory_last then reports the batch: the cells of all sections that went up, launches = 3 (2 when no front deferred, 0 when the batch stayed on the
+ * host) and the uploaded words.  Returns ZKIR_OK, ZKIR_ERR_ARGUMENT, or a negative value: no verdict for any proof. */
+int zkir_verify_many_memory_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, void* hip_stream);
+int zkir_verify_rate_many_memory_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                        const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts, void* hip_stream);
 /* this thread's last verification: cells whose stages ran on the device, launches, words uploaded for them (all 0 after any other entry) */
 int zkir_verify_memory_last(uint64_t* cells, uint32_t* launches, uint64_t* uploaded_words);
 /* the stages on their own, as zkir_hash_tape_check_* and zkir_tape_table_side_* are: sec = [n] + 7 n words (host).

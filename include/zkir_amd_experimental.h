@@ -90,6 +90,25 @@ int zkir_verify_queries_last_stage_ms(double ms[3]);
  * failing one is returned as it is), perturbs, then runs the host form of the stage (device = 0: no HIP call) or the device form, then check 30.  what: 0 nothing, 1 a0 + 1,
  * 2 b0 + 1, 3 zeta + 1, 4 betas[index] + 1, 5 qs[index] ^= 1.  Returns the verdict; negative: -ZKIR_ERR_ARGUMENT (no such what / layer / query) or a device failure. */
 int zkir_stark_query_stage_probe(const uint32_t* proof, uint64_t proof_words, uint32_t what, uint32_t index, int device, void* hip_stream);
+/* THE MEMORY STAGES OVER A LIST OF PROOFS (zkir_verify_many_memory_device, zkir_verify_rate_many_memory_device; csrc/verify_stages.h: MemManyStage).
+ * _host: the same orchestration (section locator, phase A, deferring fronts, phase B, resolution, one query stage) over the HOST list stage and the host query stage, no HIP
+ * call; EVERY located section goes through the list stage (no threshold).  zkir_verify_memory_last reports the cells that did, no launches, no upload. */
+int zkir_verify_many_memory_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts);
+int zkir_verify_rate_many_memory_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                      const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts);
+/* The list stage on its own: n = 1 .. 1024 whole sections (secs[i]: [n_i] + 7 n_i = n_words[i] words, n_i = 0 included), modes[i] 3 / 4, code_words[i], the program blobs
+ * and per section four canonical words of alpha and lambda (alphas, lambdas: 4 n words).  verdicts[i] = 0 / 54 / 55 as zkir_mem_section_check_*; digests: 4 words per
+ * chunk of 512, section after section (ceil(n_words[i] / 512) chunks each; zero where the verdict is not 0); sums: 4 canonical words per section as
+ * zkir_mem_table_side_* (zero where the verdict is not 0).  _launch: three launches for all sections (mem_stage_many.inl); _host: verify.cpp's code. */
+int zkir_mem_sections_stage_host(const uint32_t* const* secs, const uint64_t* n_words, const uint32_t* modes, const uint64_t* code_words, const uint8_t* const* blobs, const size_t* blob_lens,
+                                 const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* verdicts, uint32_t* digests, uint32_t* sums);
+int zkir_mem_sections_stage_launch(const uint32_t* const* secs, const uint64_t* n_words, const uint32_t* modes, const uint64_t* code_words, const uint8_t* const* blobs, const size_t* blob_lens,
+                                   const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* verdicts, uint32_t* digests, uint32_t* sums, void* hip_stream);
+/* TEST HOOK: zkir_verify_many_memory_host (device = 0) / _device (device != 0, with every section on the device whatever the threshold) with a PERTURBED share.  An honest
+ * proof's cells cannot make check 10 fail alone where grinding precedes it; what = 1 adds one to proof `index`'s T_mem before its deferred check, so that proof answers 10
+ * if (and only if) its front deferred — whatever it answered afterwards.  what = 0: nothing. */
+int zkir_verify_many_memory_probe(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, uint32_t what,
+                                  uint32_t index, int device, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,9 @@ __global__ __launch_bounds__(NT) void mem_section_side_kernel(const uint32_t* __
 // up to 0.3 ms, far outside the host form's spread of 0.05 ms (profiles/r24_verify_memory_device.txt, "small sections").  ZKIR_VERIFY_DEVICE_MIN_CELLS (read once per
 // call) sets another threshold, 0 included, for measuring the routes against each other.  The count word that routes is the proof's own and unchecked: both routes give
 // the same verdict, so it can choose the slower one and nothing else.
+// The list entries (mem_stage_many.inl) apply the same threshold to the SUM of a batch's cells: their flat cost is of the same kind with one synchronisation fewer, and
+// batches of 64-cell sections cross between 256 cells in all (4 proofs: host 4.159 ms, device 4.290 ms) and 512 (8 proofs: 8.101 / 8.027); from there on the device route
+// wins by ~0.7 us a cell (64 proofs, 4096 cells: 64.03 / 61.22 ms) — profiles/r25_verify_many_memory.txt, "the routing crossing".
 constexpr uint64_t MEM_DEVICE_MIN_CELLS = 512;
 uint64_t verify_device_min_cells() { if (const char* e = getenv("ZKIR_VERIFY_DEVICE_MIN_CELLS")) { const long long v = atoll(e); if (v >= 0) return (uint64_t)v; } return MEM_DEVICE_MIN_CELLS; }
 

@@ -900,6 +900,31 @@ int zkir_verify_chain_io(const uint32_t* const* proofs, const uint64_t* lens, ui
 
 namespace {
 
+// sum_c alpha^c C_c(zeta) == Q(zeta) Z_H(zeta) on openings or evaluations (main | aux at zeta: tz, the same at zeta w: tzw, the quotient's four: qzs; Montgomery E4) — check 10
+// of verify_impl, and of a list entry that deferred it (zkir::mem_deferred_check).  lk_m: air.h LK_*, complete; first / last / cnt: canonical words.
+bool constraints_at_zeta(const E4* tz, const E4* tzw, const E4* qzs, const uint32_t* lk_m, const E4& alpha, const E4& zeta, int log_n, uint64_t n_real, int mode, int WM,
+                         const uint32_t* first, const uint32_t* last, const uint32_t* cnt) {
+  const size_t N = (size_t)1 << log_n;
+  const uint32_t wn = bb::root_of_unity(log_n);
+  std::vector<E4> ap(air::N_CONSTRAINTS);                                  // (modes 0 / 1 use the first N_CONSTRAINTS_BASE)
+  ap[0] = bb::e_one_m();
+  for (int c = 1; c < air::N_CONSTRAINTS; c++) ap[c] = bb::e_mul_m(ap[c - 1], alpha);
+  E4 zh = m_pow(zeta, N); zh.c[0] = bb::sub(zh.c[0], bb::R1);
+  E4 d1 = zeta; d1.c[0] = bb::sub(d1.c[0], bb::R1);
+  E4 dl = zeta; dl.c[0] = bb::sub(dl.c[0], bb::to_mont(bb::pow(wn, n_real - 1)));
+  const E4 is_first = bb::e_mul_m(zh, bb::e_inv_m(d1)), is_last = bb::e_mul_m(zh, bb::e_inv_m(dl));
+  E4 is_trans = zeta; is_trans.c[0] = bb::sub(is_trans.c[0], bb::to_mont(bb::inv(wn)));
+  uint32_t first_m[NS], last_m[NS];
+  for (int i = 0; i < NS; i++) { first_m[i] = bb::to_mont(first[i]); last_m[i] = bb::to_mont(last[i]); }
+  uint32_t cnt_m[4];
+  for (int k = 0; k < 4; k++) cnt_m[k] = bb::to_mont(cnt[k]);
+  VerifierOps o{tz, tzw, tz + WM, tzw + WM, lk_m, ap.data(), bb::e_zero(), mode, is_first, is_last, is_trans};
+  air::eval(o, first_m, last_m, mode, cnt_m);
+  E4 qz = bb::e_zero();                                                    // Q(zeta) = sum_i X^i q_i(zeta): basis element X^i times the E4 opening
+  for (int i = 0; i < 4; i++) { E4 basis = bb::e_zero(); basis.c[i] = bb::R1; qz = bb::e_add(qz, bb::e_mul_m(basis, qzs[i])); }
+  return e_eq(o.acc, bb::e_mul_m(qz, zh));
+}
+
 int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expect, bool whole_run, uint32_t* states_out, uint32_t* counters_out, const zkir::TapeStages* stages,
                 zkir::StarkQueries* defer, const RateCheck* rate, const zkir::MemStages* mem) {
   StageClock clk;                                                         // (diagnostics: the host wall time of the call's phases, kept for zkir_verify_last_stages)
@@ -1102,6 +1127,7 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   // lookup parameters (air.h LK_*), Montgomery: alpha, lambda^0..10, T / N — T is the table side of the lookup identity, computed HERE
   // from the program in the proof and the multiplicities: sum_t m_t / (alpha - t) + sum_u r_u / (alpha - fingerprint(ROM row u))
   uint32_t lk_m[air::N_LK];
+  zkir::MemDeferred* deferred = nullptr;                                   // (a list entry's memory stage) check 10 waits for the cells' share of the table side
   {
     E4 lam[air::N_TUPLE + 1];
     lam[0] = bb::e_one_m();
@@ -1147,7 +1173,8 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
         T_hash = bb::e_add(Th, Tw);
       }
       // (a memory stage) the cells' two ends are the stage's sum: `cells` is empty here, so none of them is in d
-      if (mem) {
+      if (mem && mem->defer && mem->defer->armed) deferred = mem->defer;
+      else if (mem) {
         E4 Tm = bb::e_zero();
         const int ms = mem->side(mem->self, lk_m, blob.data(), blob_len, Tm.c);
         if (ms) return ms;
@@ -1192,6 +1219,7 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
       for (uint64_t k = cnt[0]; k < cnt[2]; k++) term(k, io.out[k], 2);
       for (uint64_t k = cnt[1]; k < cnt[3]; k++) term(k, io.in[k], 3);
     }
+    if (deferred) memcpy(deferred->T_m, T.c, 16);                            // (without the cells' share: LK_TN below is not final, and nothing reads it before check 10)
     const E4 tn = bb::e_mul_fm(T, bb::to_mont(bb::inv((uint32_t)(N % bb::P))));
     for (int k = 0; k < 4; k++) lk_m[air::LK_TN + k] = tn.c[k];
   }
@@ -1202,23 +1230,19 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   // ---- 1. constraints at zeta: sum_c alpha^c C_c(zeta) == Q(zeta) Z_H(zeta), on the openings the proof states (main | aux at zeta, the same at zeta w, the quotient's four) ----
   const uint32_t wn = bb::root_of_unity(log_n), wn_m = bb::to_mont(wn);
   auto constraints_hold = [&](const E4* tz, const E4* tzw, const E4* qzs) {
-    std::vector<E4> ap(air::N_CONSTRAINTS);                                // (modes 0 / 1 use the first N_CONSTRAINTS_BASE)
-    ap[0] = bb::e_one_m();
-    for (int c = 1; c < air::N_CONSTRAINTS; c++) ap[c] = bb::e_mul_m(ap[c - 1], alpha);
-    E4 zh = m_pow(zeta, N); zh.c[0] = bb::sub(zh.c[0], bb::R1);
-    E4 d1 = zeta; d1.c[0] = bb::sub(d1.c[0], bb::R1);
-    E4 dl = zeta; dl.c[0] = bb::sub(dl.c[0], bb::to_mont(bb::pow(wn, pub.n_real - 1)));
-    const E4 is_first = bb::e_mul_m(zh, bb::e_inv_m(d1)), is_last = bb::e_mul_m(zh, bb::e_inv_m(dl));
-    E4 is_trans = zeta; is_trans.c[0] = bb::sub(is_trans.c[0], bb::to_mont(bb::inv(wn)));
-    uint32_t first_m[NS], last_m[NS];
-    for (int i = 0; i < NS; i++) { first_m[i] = bb::to_mont(first[i]); last_m[i] = bb::to_mont(last[i]); }
-    uint32_t cnt_m[4];
-    for (int k = 0; k < 4; k++) cnt_m[k] = bb::to_mont(cnt[k]);
-    VerifierOps o{tz, tzw, tz + WM, tzw + WM, lk_m, ap.data(), bb::e_zero(), mode, is_first, is_last, is_trans};
-    air::eval(o, first_m, last_m, mode, cnt_m);
-    E4 qz = bb::e_zero();                                                  // Q(zeta) = sum_i X^i q_i(zeta): basis element X^i times the E4 opening
-    for (int i = 0; i < 4; i++) { E4 basis = bb::e_zero(); basis.c[i] = bb::R1; qz = bb::e_add(qz, bb::e_mul_m(basis, qzs[i])); }
-    return e_eq(o.acc, bb::e_mul_m(qz, zh));
+    return constraints_at_zeta(tz, tzw, qzs, lk_m, alpha, zeta, log_n, pub.n_real, mode, WM, first, last, cnt);
+  };
+  // (deferred) check 10 BY VALUE: what constraints_hold reads, kept for zkir::mem_deferred_check; the front goes on as if the check held
+  auto keep_check10 = [&](const E4* tz, const E4* tzw, const E4* qzs) {
+    zkir::MemDeferred& D = *deferred;
+    D.mode = mode; D.log_n = log_n; D.WM = WM; D.n_real = pub.n_real;
+    D.ev.resize(4 * (size_t)(2 * WT + 4));
+    memcpy(D.ev.data(), tz[0].c, 16 * (size_t)WT); memcpy(D.ev.data() + 4 * (size_t)WT, tzw[0].c, 16 * (size_t)WT); memcpy(D.ev.data() + 8 * (size_t)WT, qzs[0].c, 64);
+    D.lk_m.assign(lk_m, lk_m + air::N_LK);
+    D.states.assign(first, first + 2 * NS);
+    memcpy(D.cnt, cnt, 16); memcpy(D.alpha_m, alpha.c, 16); memcpy(D.zeta_m, zeta.c, 16);
+    D.blob = std::move(blob);                                              // (nothing behind check 10 reads the program)
+    D.filled = true;
   };
   if (rate) {
     // ---- the 'ZKSR' tail: the embedded 'ZKBE' proof opens main (WM) | aux (WA) | quotient (4) with masks {3, 3, 1} at [zeta, zeta w], under the header's rate and parameters
@@ -1232,7 +1256,8 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
     if (memcmp(e, shape, sizeof shape)) return 5;
     std::vector<E4> ev(n_ev);                                               // exponent order: main | aux | quotient at zeta, main | aux at zeta w
     for (size_t k = 0; k < n_ev; k++) { E4 x; memcpy(x.c, e + at_ev + 4 * k, 16); ev[k] = bb::e_to_mont(x); }
-    if (!constraints_hold(ev.data(), ev.data() + WT + 4, ev.data() + WT)) return 10;
+    if (deferred) keep_check10(ev.data(), ev.data() + WT + 4, ev.data() + WT);
+    else if (!constraints_hold(ev.data(), ev.data() + WT + 4, ev.data() + WT)) return 10;
     uint32_t pts[8];
     const E4 z = bb::e_from_mont(zeta), zw = bb::e_from_mont(bb::e_mul_fm(zeta, wn_m));
     memcpy(pts, z.c, 16); memcpy(pts + 4, zw.c, 16);
@@ -1243,7 +1268,8 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
   const E4 gamma = bb::e_to_mont(ch.sample_ext());
   std::vector<E4> betas;
   if (!fri_transcript(ch, lroots, n_layers, w + at_fin, n_fin, pow_nonce, POW_BITS, betas)) return 12;
-  if (!constraints_hold(t_z.data(), t_zw.data(), q_z.data())) return 10;
+  if (deferred) keep_check10(t_z.data(), t_zw.data(), q_z.data());
+  else if (!constraints_hold(t_z.data(), t_zw.data(), q_z.data())) return 10;
   // ---- 2. final codeword has degree < 4: the four upper coefficients of its interpolant over an order-8 coset vanish ----
   if (!fri_final_degree_ok(fin, 1)) return 11;
   // ---- 3. queries: the stage behind zkir::StarkQueryStage (verify_stages.h) gets what has been CHECKED and what has been DRAWN ----
@@ -1949,4 +1975,266 @@ MixedQueryStage host_mixed_query_stage() { return MixedQueryStage{nullptr, host_
 int mixed_eval_verify_with_stage(const uint32_t* proof, uint64_t n_words, const uint32_t* expect_roots, const uint32_t* expect_points, const uint32_t* expect_evals, const MixedQueryStage& stage) {
   return mixed_eval_verify_impl(proof, n_words, expect_roots, expect_points, expect_evals, stage);
 }
+
+// ---- the memory stages over a list of proofs (verify_stages.h) ----
+MemLocated mem_section_locate(const uint32_t* w, uint64_t len, bool rate) {
+  MemLocated L;
+  if (!w || len < (uint64_t)HEADER_WORDS || w[0] != (rate ? RATE_MAGIC : PROOF_MAGIC) || (w[9] != 3 && w[9] != 4)) return L;
+  const int mode = (int)w[9];
+  size_t p = (size_t)header_words_of(mode);
+  if (p >= len) return L;
+  const size_t blob_len = w[p++];
+  if (blob_len > ((size_t)1 << 30) || blob_len < 32 || p + (blob_len + 1) / 2 > len) return L;
+  const uint64_t code_size = (uint64_t)(w[p + 8] & 0xFFFF) | ((uint64_t)(w[p + 9] & 0xFFFF) << 16);      // blob bytes 16 .. 19 (the front has checked the halfwords by then)
+  p += (blob_len + 1) / 2;
+  IoSection io;
+  if (!parse_io_section(w + p, (size_t)len - p, io)) return L;
+  p += io.words;
+  L.ok = true; L.at = p; L.avail = len - p; L.mode = mode; L.code_words = code_size / 4;
+  return L;
+}
+bool mem_deferred_check(const MemDeferred& d, const uint32_t T_mem[4]) {
+  const size_t WT = (d.ev.size() / 4 - 4) / 2;
+  std::vector<E4> ev(d.ev.size() / 4);
+  memcpy(ev[0].c, d.ev.data(), d.ev.size() * 4);
+  std::vector<uint32_t> lk(d.lk_m);
+  E4 T, Tm, alpha, zeta;
+  memcpy(T.c, d.T_m, 16); memcpy(Tm.c, T_mem, 16); memcpy(alpha.c, d.alpha_m, 16); memcpy(zeta.c, d.zeta_m, 16);
+  const uint64_t N = (uint64_t)1 << d.log_n;
+  const E4 tn = bb::e_mul_fm(bb::e_add(T, Tm), bb::to_mont(bb::inv((uint32_t)(N % bb::P))));
+  for (int k = 0; k < 4; k++) lk[air::LK_TN + k] = tn.c[k];
+  return constraints_at_zeta(ev.data(), ev.data() + WT, ev.data() + 2 * WT, lk.data(), alpha, zeta, d.log_n, d.n_real, d.mode, d.WM, d.states.data(), d.states.data() + NS, d.cnt);
+}
+namespace {
+int host_mem_many_prepare(void*, const MemSection* list, uint32_t n, int* verdicts, uint32_t* digests) {
+  uint64_t chunk0 = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    size_t used = 0;
+    verdicts[i] = host_mem_check(nullptr, list[i].sec, 1 + 7 * (size_t)list[i].n, list[i].mode, list[i].code_words, &used);
+    if (!verdicts[i]) section_digests_host(list[i].sec, used, digests + 4 * chunk0);
+    chunk0 += mem_section_chunks(list[i].n);
+  }
+  return 0;
+}
+int host_mem_many_side(void*, const MemSection* list, const MemSideJob* jobs, uint32_t n_jobs, uint32_t* sums) {
+  for (uint32_t j = 0; j < n_jobs; j++) { const MemSection& S = list[jobs[j].section]; mem_side_sum(S.sec, (size_t)S.n, jobs[j].blob, jobs[j].blob_len, jobs[j].lk_m, sums + 4 * j); }
+  return 0;
+}
+
+// One proof of a list entry: its MemStages answer from what prepare returned where the front hands over the located section, else from the host stage functions.
+struct ManyMemProof {
+  const uint32_t* w = nullptr;
+  MemLocated loc;
+  int slot = -1;                                                 // the proof's section in the list (-1: none went to the list stage)
+  uint64_t n = 0;
+  int verdict = 0; const uint32_t* dg = nullptr;                 // prepare's answers
+  HostMem host;
+  MemDeferred def;
+};
+int mm_check(void* p, const uint32_t* sec, size_t avail, int mode, uint64_t code_words, size_t* used) {
+  ManyMemProof& P = *static_cast<ManyMemProof*>(p);
+  if (P.slot < 0 || sec != P.w + P.loc.at || avail != P.loc.avail || mode != P.loc.mode || code_words != P.loc.code_words) return host_mem_check(&P.host, sec, avail, mode, code_words, used);
+  if (P.verdict) return P.verdict;
+  P.def.armed = true;
+  *used = 1 + 7 * (size_t)P.n;
+  return 0;
+}
+int mm_digests(void* p, const uint32_t* sec, size_t len, uint32_t* dg) {
+  ManyMemProof& P = *static_cast<ManyMemProof*>(p);
+  if (!P.def.armed) return host_mem_digests(nullptr, sec, len, dg);
+  if (len != 1 + 7 * (size_t)P.n) { set_last_error({ZKIR_ERR_OTHER, "zkir_verify_many_memory: a front asked for the digests of another section than the one it checked"}); return -ZKIR_ERR_OTHER; }
+  memcpy(dg, P.dg, 16 * (size_t)mem_section_chunks(P.n));
+  return 0;
+}
+int mm_side(void* p, const uint32_t* lk_m, const uint8_t* blob, size_t blob_len, uint32_t T[4]) {
+  ManyMemProof& P = *static_cast<ManyMemProof*>(p);
+  if (!P.def.armed) return host_mem_side(&P.host, lk_m, blob, blob_len, T);
+  set_last_error({ZKIR_ERR_OTHER, "zkir_verify_many_memory: a deferring front asked for its table side"});
+  return -ZKIR_ERR_OTHER;
+}
+struct MemManyDone {                                             // the stage's done on every way out
+  const MemManyStage& st; bool called = false;
+  void call() { if (!called && st.done) st.done(st.self); called = true; }
+  ~MemManyDone() { call(); }
+};
+
+// Phase A, the fronts and phase B of a list entry; front(i, mem) is proof i's front (mem: NULL where the batch stays with the inline host code) and answers its verdict so
+// far (negative: no verdict for the call).  out[i]: 10 where a deferred check failed, else the front's answer.
+template <typename Front>
+int mem_many_fronts(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n, bool rate, const MemManyStage& st, uint64_t min_cells, const MemManyProbe& probe,
+                    Front front, std::vector<int32_t>& out, MemManyNote* note) {
+  *note = MemManyNote{};
+  MemManyDone done{st};
+  std::vector<ManyMemProof> P(n);
+  std::vector<MemSection> list;
+  uint64_t cells = 0, chunks = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t* w = proofs[i];
+    P[i].w = w;
+    P[i].loc = mem_section_locate(w, proof_words[i], rate);
+    if (!P[i].loc.ok || P[i].loc.avail < 1) continue;
+    const uint64_t nc = w[P[i].loc.at];
+    if (nc == 0 || nc > ((uint64_t)1 << 28) || (P[i].loc.avail - 1) / 7 < nc) continue;      // (empty, or the host stage's check 4)
+    P[i].slot = (int)list.size(); P[i].n = nc;
+    list.push_back(MemSection{w + P[i].loc.at, nc, P[i].loc.mode, P[i].loc.code_words});
+    cells += nc; chunks += mem_section_chunks(nc);
+  }
+  const bool batch = !list.empty() && cells >= min_cells;
+  std::vector<int> sv(list.size(), 0);
+  std::vector<uint32_t> dg(batch ? 4 * (size_t)chunks : 0);
+  if (batch) {
+    const int rc = st.prepare(st.self, list.data(), (uint32_t)list.size(), sv.data(), dg.data());
+    if (rc) return rc < 0 ? rc : -rc;
+    uint64_t chunk0 = 0;
+    for (uint32_t i = 0; i < n; i++) if (P[i].slot >= 0) { P[i].verdict = sv[P[i].slot]; P[i].dg = dg.data() + 4 * chunk0; chunk0 += mem_section_chunks(P[i].n); }
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const MemStages ms{&P[i], mm_check, mm_digests, mm_side, &P[i].def};
+    const int rc = front(i, batch ? &ms : nullptr);
+    if (rc < 0) return rc;
+    out[i] = rc;
+  }
+  std::vector<MemSideJob> jobs;
+  std::vector<uint32_t> who;
+  for (uint32_t i = 0; i < n; i++) if (P[i].def.filled) { jobs.push_back(MemSideJob{(uint32_t)P[i].slot, P[i].def.lk_m.data(), P[i].def.blob.data(), P[i].def.blob.size()}); who.push_back(i); }
+  if (!jobs.empty()) {
+    std::vector<uint32_t> sums(4 * jobs.size(), 0);
+    const int rc = st.side(st.self, list.data(), jobs.data(), (uint32_t)jobs.size(), sums.data());
+    if (rc) return rc < 0 ? rc : -rc;
+    for (size_t j = 0; j < jobs.size(); j++) {
+      uint32_t* Tm = sums.data() + 4 * j;
+      if (probe.what == 1 && probe.index == who[j]) Tm[0] = bb::add(Tm[0], bb::R1);
+      if (!mem_deferred_check(P[who[j]].def, Tm)) out[who[j]] = 10;
+    }
+  }
+  done.call();
+  if (batch) { note->cells = cells; note->sections = (uint32_t)list.size(); note->deferred = (uint32_t)jobs.size(); }
+  return 0;
+}
+}  // namespace
+MemManyStage host_mem_many_stage() { return MemManyStage{nullptr, host_mem_many_prepare, host_mem_many_side, nullptr}; }
+
+int verify_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, const MemManyStage& mem,
+                               uint64_t min_cells, const TapeStagesFor* tapes, const StarkQueryStage& queries, const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note) {
+  std::vector<int32_t> out(n, 0);
+  std::vector<StarkQueries> Q(n);
+  const int frc = mem_many_fronts(proofs, proof_words, n, false, mem, min_cells, probe, [&](uint32_t i, const MemStages* ms) -> int {
+    const uint32_t* w = proofs[i];
+    const bool with_tapes = tapes && w && proof_words[i] >= 10 && w[9] == 4;
+    const TapeStages* ts = with_tapes ? tapes->begin(tapes->self, i) : nullptr;
+    if (with_tapes && !ts) return -ZKIR_ERR_DEVICE;
+    const int rc = stark_verify_collect(w, proof_words[i], expects ? expects[i] : nullptr, true, ts, &Q[i], ms);
+    return with_tapes ? tapes->end(tapes->self, rc) : rc;
+  }, out, note);
+  if (frc) return frc;
+  std::vector<StarkQueries> list;
+  std::vector<uint32_t> who;
+  for (uint32_t i = 0; i < n; i++) if (!out[i]) { list.push_back(std::move(Q[i])); who.push_back(i); }
+  std::vector<int> codes(list.size() + 1, 0);
+  if (!list.empty()) {                                             // (no proof reached its queries: nothing is run)
+    const int src = queries.run(queries.self, list.data(), (uint32_t)list.size(), codes.data());
+    if (src) return src < 0 ? src : -src;
+  }
+  for (size_t k = 0; k < list.size(); k++) out[who[k]] = codes[k] ? codes[k] : stark_length_check(list[k]);
+  memcpy(verdicts, out.data(), (size_t)n * sizeof(int32_t));
+  return 0;
+}
+
+int rate_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                             const uint32_t* min_pow_bits, uint32_t n, const MemManyStage& mem, uint64_t min_cells, const TapeStagesFor* tapes, const PcsManyStage& queries,
+                             const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note) {
+  std::vector<int32_t> out(n, 0);
+  std::vector<PcsCollected> C(n);
+  const int frc = mem_many_fronts(proofs, proof_words, n, true, mem, min_cells, probe, [&](uint32_t i, const MemStages* ms) -> int {
+    const uint32_t* w = proofs[i];
+    const bool with_tapes = tapes && w && proof_words[i] >= 10 && w[9] == 4;
+    const TapeStages* ts = with_tapes ? tapes->begin(tapes->self, i) : nullptr;
+    if (with_tapes && !ts) return -ZKIR_ERR_DEVICE;
+    int rc = rate_verify_with_stage(w, proof_words[i], expects ? expects[i] : nullptr, min_queries ? min_queries[i] : 1u, min_pow_bits ? min_pow_bits[i] : 0u, pcs_collect_stage(&C[i]), ts, ms);
+    if (with_tapes) rc = tapes->end(tapes->self, rc);
+    if (!rc && !C[i].filled) { set_last_error({ZKIR_ERR_OTHER, "zkir_verify_rate_many_memory: a front accepted a proof without reaching its queries"}); return -(int)ZKIR_ERR_OTHER; }
+    return rc;
+  }, out, note);
+  if (frc) return frc;
+  std::vector<PcsCollected> list;
+  std::vector<uint32_t> who;
+  for (uint32_t i = 0; i < n; i++) if (!out[i]) { list.push_back(std::move(C[i])); who.push_back(i); }
+  for (PcsCollected& c : list) { c.q.qs = c.qs.data(); c.q.betas_m = c.betas_m.data(); c.q.gamma_m = c.gamma_m.data(); }      // (a moved description points at its own tables)
+  std::vector<int> codes(list.size() + 1, 0);
+  if (!list.empty()) {
+    const int src = queries.run(queries.self, list.data(), (uint32_t)list.size(), codes.data());
+    if (src) return src < 0 ? src : -src;
+  }
+  for (size_t k = 0; k < list.size(); k++) out[who[k]] = codes[k] ? 100 + codes[k] : 0;
+  memcpy(verdicts, out.data(), (size_t)n * sizeof(int32_t));
+  return 0;
+}
+
+int mem_sections_stage(const char* who, const MemManyStage& st, const uint32_t* const* secs, const uint64_t* n_words, const uint32_t* modes, const uint64_t* code_words, const uint8_t* const* blobs,
+                       const size_t* blob_lens, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* verdicts, uint32_t* digests, uint32_t* sums) {
+  auto refuse = [&](const std::string& why) { set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": " + why}); return (int)ZKIR_ERR_ARGUMENT; };
+  if (!secs || !n_words || !modes || !code_words || !blobs || !blob_lens || !alphas || !lambdas || !verdicts || !digests || !sums) return refuse("null argument");
+  if (n < 1 || n > 1024) return refuse("n must be 1 .. 1024");
+  try {
+    MemManyDone done{st};
+    std::vector<MemSection> list(n);
+    std::vector<uint32_t> lk((size_t)n * air::N_LK);
+    for (uint32_t i = 0; i < n; i++) {
+      uint64_t nc = 0;
+      if (const char* why = mem_side_args(secs[i], n_words[i], blobs[i], blob_lens[i], alphas + 4 * i, lambdas + 4 * i, sums, lk.data() + (size_t)i * air::N_LK, &nc)) return refuse(why);
+      if (modes[i] != 3 && modes[i] != 4) return refuse("a mode must be 3 or 4");
+      list[i] = MemSection{secs[i], nc, (int)modes[i], code_words[i]};
+    }
+    std::vector<int> sv(n, 0);
+    int rc = st.prepare(st.self, list.data(), n, sv.data(), digests);
+    if (rc) return rc < 0 ? -rc : rc;
+    std::vector<MemSideJob> jobs;
+    uint64_t chunk0 = 0;
+    for (uint32_t i = 0; i < n; i++) {                               // (a failing section has no digests: zero)
+      const uint64_t nch = mem_section_chunks(list[i].n);
+      verdicts[i] = sv[i];
+      if (sv[i]) memset(digests + 4 * chunk0, 0, 16 * (size_t)nch); else jobs.push_back(MemSideJob{i, lk.data() + (size_t)i * air::N_LK, blobs[i], blob_lens[i]});
+      chunk0 += nch;
+    }
+    std::vector<uint32_t> T(4 * jobs.size() + 4, 0);
+    if (!jobs.empty()) { rc = st.side(st.self, list.data(), jobs.data(), (uint32_t)jobs.size(), T.data()); if (rc) return rc < 0 ? -rc : rc; }
+    memset(sums, 0, 16 * (size_t)n);
+    for (size_t j = 0; j < jobs.size(); j++) { E4 t; memcpy(t.c, T.data() + 4 * j, 16); t = bb::e_from_mont(t); memcpy(sums + 4 * (size_t)jobs[j].section, t.c, 16); }
+  } catch (const std::exception& e) { set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": " + e.what()}); return ZKIR_ERR_OTHER; }
+  return ZKIR_OK;
+}
 }  // namespace zkir
+
+extern "C" {
+
+int zkir_mem_sections_stage_host(const uint32_t* const* secs, const uint64_t* n_words, const uint32_t* modes, const uint64_t* code_words, const uint8_t* const* blobs, const size_t* blob_lens,
+                                 const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* verdicts, uint32_t* digests, uint32_t* sums) {
+  return zkir::mem_sections_stage("zkir_mem_sections_stage_host", zkir::host_mem_many_stage(), secs, n_words, modes, code_words, blobs, blob_lens, alphas, lambdas, n, verdicts, digests, sums);
+}
+static int mem_many_host_refuse(const char* m) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, m}); return ZKIR_ERR_ARGUMENT; }
+// The list entries over host_mem_many_stage: EVERY located section goes through the list stage (no threshold), so the deferral runs on a machine without a device.
+// zkir_verify_memory_last: the cells that went through it, no launches, no upload (noted behind the last front: every front's clock resets the record).
+int zkir_verify_many_memory_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts) {
+  if (!proofs || !proof_words || !verdicts) return mem_many_host_refuse("zkir_verify_many_memory_host: null proofs, proof_words or verdicts");
+  if (n < 1 || n > 1024) return mem_many_host_refuse("zkir_verify_many_memory_host: n must be 1 .. 1024");
+  try {
+    zkir::MemManyNote note;
+    const int rc = zkir::verify_many_with_mem_stage(proofs, proof_words, expects, n, zkir::host_mem_many_stage(), 0, nullptr, zkir::host_stark_query_stage(), zkir::MemManyProbe{}, verdicts, &note);
+    zkir::verify_note_memory(note.cells, 0, 0);
+    return rc;
+  } catch (const std::exception& e) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string("zkir_verify_many_memory_host: ") + e.what()}); return -ZKIR_ERR_OTHER; }
+}
+int zkir_verify_rate_many_memory_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                      const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts) {
+  if (!proofs || !proof_words || !verdicts) return mem_many_host_refuse("zkir_verify_rate_many_memory_host: null proofs, proof_words or verdicts");
+  if (n < 1 || n > 1024) return mem_many_host_refuse("zkir_verify_rate_many_memory_host: n must be 1 .. 1024");
+  try {
+    zkir::MemManyNote note;
+    const int rc = zkir::rate_many_with_mem_stage(proofs, proof_words, expects, min_queries, min_pow_bits, n, zkir::host_mem_many_stage(), 0, nullptr, zkir::host_pcs_many_stage(), zkir::MemManyProbe{},
+                                                  verdicts, &note);
+    zkir::verify_note_memory(note.cells, 0, 0);
+    return rc;
+  } catch (const std::exception& e) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string("zkir_verify_rate_many_memory_host: ") + e.what()}); return -ZKIR_ERR_OTHER; }
+}
+
+}  // extern "C"

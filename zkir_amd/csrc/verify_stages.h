@@ -39,6 +39,7 @@ void verify_note_device_stages(uint32_t n);                      // (zkir_verify
 // skips its cell loop, observes the stage's digests, leaves the cells' 2 n denominators out of its batch inversion and adds the stage's share of the table side.  verify.cpp
 // fills the interface with host functions (what the device form leaves small sections to, and what zkir_mem_section_check_host / zkir_mem_table_side_host run),
 // mem_stage.inl with the device forms.  Verdicts as above.
+struct MemDeferred;
 struct MemStages {
   void* self;
   // the section that starts at sec (avail words to the proof's end): 4 (the proof ends inside it, or its count is above 2^28), else the code of the LOWEST failing cell
@@ -49,6 +50,9 @@ struct MemStages {
   // the checked section's share of the table side, Montgomery E4: per cell + 1 / (alpha - fp(cell, 0, the program image's bytes)) - 1 / (alpha - fp(cell, t_last, final
   // bytes)); lk_m: air.h LK_ALPHA and LK_LAM, Montgomery; blob: the program the proof carries (the image bytes are mem_image_cell's)
   int (*side)(void* self, const uint32_t* lk_m, const uint8_t* blob, size_t blob_len, uint32_t T[4]);
+  // (the list form below) NULL for every stage from before it: side runs where it always ran.  Else, where defer->armed is set when the front reaches the table side, the
+  // front does NOT call side: it forms T without the cells' share, keeps check 10 in *defer and goes on as if that check held
+  MemDeferred* defer = nullptr;
 };
 struct HostMem { const uint32_t* sec = nullptr; size_t n = 0; };      // what the host stages keep between their calls
 MemStages host_mem_stages(HostMem* h);
@@ -64,6 +68,61 @@ void section_chunk_digests(const uint32_t* sw, size_t sl, uint32_t* dg);      //
 const char* mem_side_args(const uint32_t* sec, uint64_t n_words, const uint8_t* blob, size_t blob_len, const uint32_t alpha[4], const uint32_t lambda[4], const uint32_t* sum,
                           uint32_t* lk, uint64_t* n);
 void verify_note_memory(uint64_t cells, uint32_t launches, uint64_t uploaded_words);      // (zkir_verify_memory_device) zkir_verify_memory_last's record
+
+// ---- the memory stages over a LIST of proofs (zkir_verify_many_memory_device, zkir_verify_rate_many_memory_device and their *_host forms) ----
+// check and digests depend on the proof's words alone, so a list stage answers them for every proof BEFORE any front runs (prepare).  side needs the lookup challenges,
+// which the transcript yields only behind the digests — but its result enters LK_TN alone, which nothing but check 10 reads and no challenge, grinding or sample depends
+// on.  So a front whose check was answered by the list DEFERS check 10: it keeps in a MemDeferred, BY VALUE, what the check reads, and goes on as if it held (check 11,
+// the sampling, the collecting query stage).  After the last front ONE side call serves every proof that deferred; the caller completes LK_TN = (T + T_mem) / N and
+// evaluates the kept check (mem_deferred_check).  A proof whose deferred check fails has verdict 10 whatever its front answered afterwards (every check before 10 had
+// passed, 10 precedes all later ones); every other proof keeps its front's verdict.
+struct MemDeferred {
+  bool armed = false;                                            // (the check callback) this proof's table side is deferred
+  bool filled = false;                                           // (the front) check 10 was reached: everything below is set
+  int mode = 0, log_n = 0, WM = 0; uint64_t n_real = 0;
+  std::vector<uint32_t> ev;                                      // Montgomery E4 words: main | aux at zeta, the same at zeta w, the quotient's four
+  std::vector<uint32_t> lk_m;                                    // air.h LK_*; LK_TN is not final
+  std::vector<uint32_t> states;                                  // the boundary states, first | last, canonical
+  uint32_t cnt[4] = {0, 0, 0, 0}, alpha_m[4] = {0, 0, 0, 0}, zeta_m[4] = {0, 0, 0, 0};
+  uint32_t T_m[4] = {0, 0, 0, 0};                                // the table side WITHOUT the cells' share, Montgomery E4
+  std::vector<uint8_t> blob;                                     // the program the proof carries (the side's image bytes)
+};
+bool mem_deferred_check(const MemDeferred& d, const uint32_t T_mem[4]);      // check 10 with LK_TN = (T + T_mem) / N
+// A LOCATED section: sec[0] = n <= 2^28 and 1 + 7 n words lie at sec inside the proof (the list entries send no empty one).  Its chunk digests are 4 mem_section_chunks(n) words.
+struct MemSection { const uint32_t* sec; uint64_t n; int mode; uint64_t code_words; };
+inline uint64_t mem_section_chunks(uint64_t n) { return (1 + 7 * n + 511) / 512; }
+struct MemSideJob { uint32_t section; const uint32_t* lk_m; const uint8_t* blob; size_t blob_len; };      // section: an index into the list prepare was handed
+struct MemManyStage {
+  void* self;
+  // per section MemStages::check's verdict (0 / 54 / 55) and, where it is 0, MemStages::digests' words at digests + 4 (the chunks of the sections before it)
+  int (*prepare)(void* self, const MemSection* list, uint32_t n, int* verdicts, uint32_t* digests);
+  // per job MemStages::side's sum (sums + 4 job); list: what prepare was handed, every job's section had verdict 0 and its words are below p
+  int (*side)(void* self, const MemSection* list, const MemSideJob* jobs, uint32_t n_jobs, uint32_t* sums);
+  void (*done)(void* self);                                      // nullable: the stage keeps nothing of the list from here on (called once, before the query stage)
+};
+MemManyStage host_mem_many_stage();                              // loops over the host stage functions
+// Where a proof's touched-cell section starts, by the front's own rules (magic, mode, header, the blob's length word, the code size in blob bytes 16 .. 19, the I/O
+// section): at = its word offset, avail = the words behind it.  A ROUTING AID ONLY: the list entries compare what the front hands their check callback with this and
+// fall back to the host stage on any difference, so a wrong answer can choose the slower route and nothing else.
+struct MemLocated { bool ok = false; uint64_t at = 0, avail = 0; int mode = 0; uint64_t code_words = 0; };
+MemLocated mem_section_locate(const uint32_t* proof, uint64_t proof_words, bool rate);
+// a mode-4 proof's tape stages for front i (NULL: the host forms): begin before the front, end(rc) behind it (what it answers is the front's result)
+struct TapeStagesFor { void* self; const TapeStages* (*begin)(void* self, uint32_t i); int (*end)(void* self, int rc); };
+struct MemManyProbe { uint32_t what = 0, index = 0; };           // (zkir_verify_many_memory_probe) what = 1: + 1 on proof index's T_mem before its deferred check
+struct MemManyNote { uint64_t cells = 0; uint32_t sections = 0, deferred = 0; };      // what went through the list stage (all zero: the batch stayed with the inline host code)
+// zkir_mem_sections_stage_host / _launch: the list stage on its own over n whole sections ([n_i] + 7 n_i words each, n_i = 0 included) with their modes, code sizes, blobs and
+// canonical challenges: per section the verdict, the chunk digests (zero where the verdict is not 0) and the canonical sum (likewise)
+int mem_sections_stage(const char* who, const MemManyStage& st, const uint32_t* const* secs, const uint64_t* n_words, const uint32_t* modes, const uint64_t* code_words, const uint8_t* const* blobs,
+                       const size_t* blob_lens, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* verdicts, uint32_t* digests, uint32_t* sums);
+struct PcsManyStage;
+struct StarkQueryStage;
+// zkir_verify / zkir_verify_rate of n proofs (modes mixed), the memory stages through `mem` where the located sections' total cells reach min_cells, the queries through ONE
+// run of `queries`.  Host only: whatever touches a device is behind the three interfaces.  0, or a negative value (no verdict for any of them).
+int verify_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, const MemManyStage& mem,
+                               uint64_t min_cells, const TapeStagesFor* tapes, const StarkQueryStage& queries, const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note);
+int rate_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                             const uint32_t* min_pow_bits, uint32_t n, const MemManyStage& mem, uint64_t min_cells, const TapeStagesFor* tapes, const PcsManyStage& queries,
+                             const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note);
 
 // ---- the QUERY STAGE of the commitment layer's verifiers (zkir_lowdeg_verify, zkir_eval_verify, zkir_batch_eval_verify and their *_device forms) ----
 // Checks 6 .. 11 of all the queries of a 'ZKLD' / 'ZKEV' / 'ZKBE' proof.  verify.cpp's fri_part_verify hands the stage what it has CHECKED (the shape: checks 1 and 3 passed,

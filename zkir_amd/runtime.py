@@ -414,6 +414,14 @@ def lib() -> C.CDLL:
         L.zkir_mem_section_check_launch.restype = C.c_int; L.zkir_mem_section_check_launch.argtypes = [V, U64, U32, U64, C.POINTER(C.c_int32), V]
         L.zkir_mem_table_side_host.restype = C.c_int; L.zkir_mem_table_side_host.argtypes = [V, U64, C.c_char_p, C.c_size_t, V, V, V]
         L.zkir_mem_table_side_launch.restype = C.c_int; L.zkir_mem_table_side_launch.argtypes = [V, U64, C.c_char_p, C.c_size_t, V, V, V, V]
+    if hasattr(L, "zkir_verify_many_memory_device"):          # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
+        L.zkir_verify_many_memory_device.restype = C.c_int; L.zkir_verify_many_memory_device.argtypes = [V, V, V, C.c_uint32, V, V]
+        L.zkir_verify_many_memory_host.restype = C.c_int; L.zkir_verify_many_memory_host.argtypes = [V, V, V, C.c_uint32, V]
+        L.zkir_verify_many_memory_probe.restype = C.c_int; L.zkir_verify_many_memory_probe.argtypes = [V, V, V, C.c_uint32, V, C.c_uint32, C.c_uint32, C.c_int, V]
+        L.zkir_verify_rate_many_memory_device.restype = C.c_int; L.zkir_verify_rate_many_memory_device.argtypes = [V, V, V, V, V, U32, V, V]
+        L.zkir_verify_rate_many_memory_host.restype = C.c_int; L.zkir_verify_rate_many_memory_host.argtypes = [V, V, V, V, V, U32, V]
+        L.zkir_mem_sections_stage_host.restype = C.c_int; L.zkir_mem_sections_stage_host.argtypes = [V, V, V, V, V, V, V, V, U32, V, V, V]
+        L.zkir_mem_sections_stage_launch.restype = C.c_int; L.zkir_mem_sections_stage_launch.argtypes = [V, V, V, V, V, V, V, V, U32, V, V, V, V]
     if hasattr(L, "zkir_verify_on_device"):                   # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
         L.zkir_verify_on_device.restype = C.c_int; L.zkir_verify_on_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
         L.zkir_verify_many_on_device.restype = C.c_int; L.zkir_verify_many_on_device.argtypes = [V, V, V, C.c_uint32, V, V]
@@ -656,9 +664,12 @@ def verify_chain(proofs, expect: Optional[PublicInputsC] = None, device: bool = 
     return lib().zkir_verify_chain(ptrs, lens, len(ps), C.byref(expect) if expect is not None else None)
 
 
-def verify_many(proofs, expects=None, stream=None):
+def verify_many(proofs, expects=None, stream=None, memory: bool = False, device: bool = True, probe=None):
     """zkir_verify_many_on_device: n independent proofs (1 .. 1024) -> [zkir_verify(proofs[i], expects[i]) for i] with every proof's queries in ONE batch on the GPU.
-    `expects`: None, or one entry (a PublicInputsC or None) per proof.  An empty list, more than 1024 proofs or a device failure raise."""
+    `expects`: None, or one entry (a PublicInputsC or None) per proof.  An empty list, more than 1024 proofs or a device failure raise.
+    memory=True: zkir_verify_many_memory_device — the same verdicts with the memory sections of all mode-3 / mode-4 proofs as ONE device batch (three launches for the
+    whole call; verify_memory_last() reports it).  memory=True, device=False: zkir_verify_many_memory_host, the same orchestration over the host stages (no HIP call).
+    probe=(what, index): zkir_verify_many_memory_probe (test hook; what = 1 adds one to proof index's cell share before its deferred check 10), host or device."""
     ps = [np.ascontiguousarray(p, dtype=np.uint32) for p in proofs]
     n = len(ps)
     if expects is not None and len(expects) != n:
@@ -667,7 +678,12 @@ def verify_many(proofs, expects=None, stream=None):
     lens = (C.c_uint64 * max(n, 1))(*[len(p) for p in ps])
     exps = (C.c_void_p * max(n, 1))(*[C.addressof(e) if e is not None else None for e in expects]) if expects is not None else None
     verdicts = (C.c_int32 * max(n, 1))()
-    rc = lib().zkir_verify_many_on_device(ptrs, lens, exps, n, verdicts, stream)
+    if probe is not None:
+        rc = lib().zkir_verify_many_memory_probe(ptrs, lens, exps, n, verdicts, int(probe[0]), int(probe[1]), 1 if device else 0, stream)
+    elif memory:
+        rc = lib().zkir_verify_many_memory_device(ptrs, lens, exps, n, verdicts, stream) if device else lib().zkir_verify_many_memory_host(ptrs, lens, exps, n, verdicts)
+    else:
+        rc = lib().zkir_verify_many_on_device(ptrs, lens, exps, n, verdicts, stream)
     if rc != 0:
         _raise(abs(rc))
     return [int(verdicts[i]) for i in range(n)]
@@ -712,6 +728,38 @@ def mem_table_side(sec, blob: bytes, alpha, lam, device: bool = True, stream=Non
     if rc != ZKIR_OK:
         _raise(rc)
     return out
+
+
+def mem_sections_stage(secs, modes, code_words, blobs, alphas, lams, device: bool = True, stream=None):
+    """zkir_mem_sections_stage_launch / _host: the memory stages of n whole sections ([n_i] + 7 n_i words each) as ONE list — three launches on the GPU, or the host stage
+    functions.  modes[i] 3 / 4, code_words[i], blobs[i] the program, alphas[i] / lams[i] canonical E4 -> (verdicts [int], digests [np.uint32[chunks_i, 4]; zero where
+    the verdict is not 0], sums np.uint32[n, 4] canonical; zero likewise)."""
+    ss = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in secs]
+    n = len(ss)
+    bs = [bytes(b) for b in blobs]
+    if not (len(modes) == len(code_words) == len(bs) == len(alphas) == len(lams) == n):
+        raise ValueError("one mode, code size, blob, alpha and lambda per section")
+    ptrs = (C.c_void_p * max(n, 1))(*[x.ctypes.data if len(x) else None for x in ss])
+    lens = (C.c_uint64 * max(n, 1))(*[len(x) for x in ss])
+    md = (C.c_uint32 * max(n, 1))(*[int(m) for m in modes])
+    cw = (C.c_uint64 * max(n, 1))(*[int(c) for c in code_words])
+    bp = (C.c_char_p * max(n, 1))(*bs)
+    bl = (C.c_size_t * max(n, 1))(*[len(b) for b in bs])
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.uint32).reshape(-1)) if n else np.zeros(4, np.uint32)
+    l = np.ascontiguousarray(np.asarray(lams, dtype=np.uint32).reshape(-1)) if n else np.zeros(4, np.uint32)
+    chunks = [(len(x) + 511) // 512 for x in ss]
+    verdicts = (C.c_int32 * max(n, 1))()
+    dg = np.zeros(4 * max(sum(chunks), 1), dtype=np.uint32)
+    sums = np.zeros((max(n, 1), 4), dtype=np.uint32)
+    args = [ptrs, lens, md, cw, bp, bl, a.ctypes.data, l.ctypes.data, n, verdicts, dg.ctypes.data, sums.ctypes.data]
+    rc = lib().zkir_mem_sections_stage_launch(*args, stream) if device else lib().zkir_mem_sections_stage_host(*args)
+    if rc != ZKIR_OK:
+        _raise(abs(rc))
+    out, at = [], 0
+    for c in chunks:
+        out.append(dg[4 * at:4 * (at + c)].reshape(c, 4).copy())
+        at += c
+    return [int(verdicts[i]) for i in range(n)], out, sums[:n]
 
 
 def verify_queries_last_stage_ms():
@@ -944,10 +992,12 @@ def _many_args(proofs):
     return ps, n, ptrs, lens
 
 
-def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, stream=None):
+def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, stream=None, memory: bool = False, device: bool = True):
     """zkir_verify_rate_many_device: n independent whole-run 'ZKSR' proofs (1 .. 1024) of any mode and rate -> [verify_rate(proofs[i], expects[i], min_queries[i],
     min_pow_bits[i]) for i] with every proof's queries in ONE batch on the GPU.  `expects`: None, or one entry (a PublicInputsC or None) per proof; `min_queries` /
-    `min_pow_bits`: None (1 / 0) or one value per proof.  An empty list, more than 1024 proofs or a device failure raise, and no verdict is formed."""
+    `min_pow_bits`: None (1 / 0) or one value per proof.  An empty list, more than 1024 proofs or a device failure raise, and no verdict is formed.
+    memory=True: zkir_verify_rate_many_memory_device — the memory sections of all mode-3 / mode-4 proofs as ONE device batch, as verify_many(memory=True); with
+    device=False zkir_verify_rate_many_memory_host (no HIP call)."""
     ps, n, ptrs, lens = _many_args(proofs)
     for name, a in (("expectations", expects), ("min_queries", min_queries), ("min_pow_bits", min_pow_bits)):
         if a is not None and len(a) != n:
@@ -956,7 +1006,12 @@ def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, 
     mq = (C.c_uint32 * max(n, 1))(*[int(x) for x in min_queries]) if min_queries is not None else None
     mb = (C.c_uint32 * max(n, 1))(*[int(x) for x in min_pow_bits]) if min_pow_bits is not None else None
     verdicts = (C.c_int32 * max(n, 1))()
-    rc = lib().zkir_verify_rate_many_device(ptrs, lens, exps, mq, mb, n, verdicts, stream)
+    if memory and not device:
+        rc = lib().zkir_verify_rate_many_memory_host(ptrs, lens, exps, mq, mb, n, verdicts)
+    elif memory:
+        rc = lib().zkir_verify_rate_many_memory_device(ptrs, lens, exps, mq, mb, n, verdicts, stream)
+    else:
+        rc = lib().zkir_verify_rate_many_device(ptrs, lens, exps, mq, mb, n, verdicts, stream)
     if rc != 0:
         _raise(abs(rc))
     return [int(verdicts[i]) for i in range(n)]
