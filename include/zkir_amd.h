@@ -772,6 +772,20 @@ int zkir_verify_rate_many_memory_device(const uint32_t* const* proofs, const uin
                                         const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts, void* hip_stream);
 /* this thread's last verification: cells whose stages ran on the device, launches, words uploaded for them (all 0 after any other entry) */
 int zkir_verify_memory_last(uint64_t* cells, uint32_t* launches, uint64_t* uploaded_words);
+/* MANY MODE-4 PROOFS' TAPES, ONE BATCH (csrc/tape_stage_many.inl).  The *_many_memory_device entries PLUS the hash and wide tapes of all their mode-4 proofs verified
+ * together, around the same pass of fronts and the same query stage.  Before any front: one upload of every located tape, ONE launch each for the hash record checks, the
+ * wide record checks and both sections' chunk digests, one synchronisation; the bytes every hash call wrote are then formed by two launches that overlap the host fronts.
+ * A front whose tape checks were answered by the batch DEFERS check 10 exactly as it does for its cells (the tapes' shares of the table side enter nothing else); behind
+ * the last front two side launches (and one patch launch where a call is longer than 1024 bytes) serve every deferred proof, and the kept check is evaluated with the sum
+ * of all deferred shares: cells, hash calls, wide records.  At most 8 launches and 2 synchronisations for the tapes of the whole call, however many proofs.  n = 1 .. 1024,
+ * modes 0 - 4 mixed; verdicts[i] is zkir_verify's / zkir_verify_rate's on every input.  The tape batch goes to the device when the located tapes' records (hash calls plus
+ * wide records) in all reach ZKIR_VERIFY_DEVICE_MIN_RECORDS (default 0: every batch that holds a record); below it every mode-4 front keeps its own tape stages, as in the
+ * *_many_memory_device entries.  zkir_verify_tapes_last then reports the batch: its records, launches (0 when the batch stayed with the fronts) and uploaded words; it is
+ * all 0 after every other entry.  Returns ZKIR_OK, ZKIR_ERR_ARGUMENT, or a negative value: no verdict for any proof. */
+int zkir_verify_many_tapes_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, void* hip_stream);
+int zkir_verify_rate_many_tapes_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                       const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts, void* hip_stream);
+int zkir_verify_tapes_last(uint64_t* records, uint32_t* launches, uint64_t* uploaded_words);
 /* the stages on their own, as zkir_hash_tape_check_* and zkir_tape_table_side_* are: sec = [n] + 7 n words (host).
  * _check_*: *verdict = 0 / 4 (n_words < 1 + 7 n) / 54 / 55 — of the LOWEST failing cell, and within it the first failing check in the host's order (limb ranges, byte
  * pieces, strictly increasing address, overlap with the code_words code words at 0x1000; mode 4 admits the boundary cell of an odd code_words); a malformed section is a

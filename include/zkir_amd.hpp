@@ -519,6 +519,15 @@ inline int verify_many_memory_device(const std::vector<std::vector<uint32_t>>& p
   if (!expects.empty() && expects.size() != proofs.size()) return ZKIR_ERR_ARGUMENT;
   return zkir_verify_many_memory_device(ptrs.data(), lens.data(), expects.empty() ? nullptr : expects.data(), (uint32_t)proofs.size(), verdicts.data(), hip_stream);
 }
+// verify_many_memory_device with the hash and wide tapes of all mode-4 proofs as ONE device batch too (zkir_verify_many_tapes_device)
+inline int verify_many_tapes_device(const std::vector<std::vector<uint32_t>>& proofs, std::vector<int32_t>& verdicts, const std::vector<const zkir_public_inputs*>& expects = {},
+                                    void* hip_stream = nullptr) {
+  std::vector<const uint32_t*> ptrs; std::vector<uint64_t> lens;
+  for (const auto& p : proofs) { ptrs.push_back(p.data()); lens.push_back(p.size()); }
+  verdicts.assign(proofs.size(), 0);
+  if (!expects.empty() && expects.size() != proofs.size()) return ZKIR_ERR_ARGUMENT;
+  return zkir_verify_many_tapes_device(ptrs.data(), lens.data(), expects.empty() ? nullptr : expects.data(), (uint32_t)proofs.size(), verdicts.data(), hip_stream);
+}
 inline int verify_chain_on_device(const std::vector<std::vector<uint32_t>>& proofs, const zkir_public_inputs* expect = nullptr, void* hip_stream = nullptr) {
   std::vector<const uint32_t*> ptrs; std::vector<uint64_t> lens;
   for (const auto& p : proofs) { ptrs.push_back(p.data()); lens.push_back(p.size()); }

@@ -109,6 +109,29 @@ int zkir_mem_sections_stage_launch(const uint32_t* const* secs, const uint64_t* 
  * if (and only if) its front deferred — whatever it answered afterwards.  what = 0: nothing. */
 int zkir_verify_many_memory_probe(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, uint32_t what,
                                   uint32_t index, int device, void* hip_stream);
+/* THE TAPE STAGES OVER A LIST OF PROOFS (zkir_verify_many_tapes_device, zkir_verify_rate_many_tapes_device; csrc/verify_stages.h: TapeManyStage).
+ * _host: the whole deferral (both locators, phase A, deferring fronts, phase B, resolution, one query stage) over the HOST list stages, no HIP call; every located section and
+ * every located pair of tapes that holds a record goes through them.  zkir_verify_tapes_last reports the records that did, no launches, no upload. */
+int zkir_verify_many_tapes_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts);
+int zkir_verify_rate_many_tapes_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                     const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts);
+/* The list stage on its own: n = 1 .. 1024 pairs of whole sections.  hash_secs[i]: a hash section of hash_words[i] words ([0] included; words behind its last record are
+ * refused, a section that ENDS inside a record is a verdict: 4); wide_secs[i]: [n_i] + 8 n_i = wide_words[i] words; n_real[i], code_end[i] (below 2^32) and per pair four
+ * canonical words of alpha and lambda.  hash_verdicts[i] = 0 / 4 / 55 / 56 as zkir_hash_tape_check_*, wide_verdicts[i] = 0 / 57; digests: 4 words per chunk of 512, per
+ * pair ceil(hash_words[i] / 512) chunks then ceil(wide_words[i] / 512) (zero where that section's verdict is not 0); sums: per pair 4 canonical words of the hash calls'
+ * share as zkir_tape_table_side_*, then 4 of the wide records' (zero unless BOTH verdicts are 0).  _launch: at most 8 launches for all pairs (tape_stage_many.inl;
+ * zkir_verify_tapes_last reports them); _host: verify.cpp's code. */
+int zkir_tape_sections_stage_host(const uint32_t* const* hash_secs, const uint64_t* hash_words, const uint32_t* const* wide_secs, const uint64_t* wide_words, const uint64_t* n_real,
+                                  const uint64_t* code_end, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* hash_verdicts, int32_t* wide_verdicts, uint32_t* digests,
+                                  uint32_t* sums);
+int zkir_tape_sections_stage_launch(const uint32_t* const* hash_secs, const uint64_t* hash_words, const uint32_t* const* wide_secs, const uint64_t* wide_words, const uint64_t* n_real,
+                                    const uint64_t* code_end, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* hash_verdicts, int32_t* wide_verdicts, uint32_t* digests,
+                                    uint32_t* sums, void* hip_stream);
+/* TEST HOOK: zkir_verify_many_tapes_host (device = 0) / _device (device != 0, every batch on the device whatever the thresholds) with a PERTURBED share: what = 1 adds one to
+ * proof `index`'s hash share, what = 2 to its wide share, before its deferred check — so that proof answers 10 if (and only if) the batch answered that tape's check for its
+ * front.  what = 0: nothing. */
+int zkir_verify_many_tapes_probe(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, uint32_t what,
+                                 uint32_t index, int device, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ OBJ = os.path.join(HERE, "build")
 
 HOST_SOURCES = ["interp.cpp", "hashes.cpp", "verify.cpp"]
 HIP_SOURCES = ["trace_fill.hip", "witness.hip", "ntt.hip", "stark.hip", "memcheck.hip", "abi.hip"]
-HEADERS = ["host.h", "hashcall.h", "babybear.h", "poseidon2.h", "air.h", "fri_shape.h", "fri.inl", "stark_prove.inl", "tape_table.inl", "tape_digest.inl", "verify_device.inl", "mem_stage.inl", "mem_stage_many.inl", "merkle_open.inl", "lowdeg.inl", "eval_open.inl", "mixed_eval.inl", "query_stage.inl", "pcs_verify.inl", "mixed_verify.inl", "stark_verify.inl", "pcs_verify_many.inl", "verify_stages.h", os.path.join("..", "..", "include", "zkir_amd.h"), os.path.join("..", "..", "include", "zkir_amd_experimental.h")]
+HEADERS = ["host.h", "hashcall.h", "babybear.h", "poseidon2.h", "air.h", "fri_shape.h", "fri.inl", "stark_prove.inl", "tape_table.inl", "tape_digest.inl", "verify_device.inl", "mem_stage.inl", "mem_stage_many.inl", "tape_stage_many.inl", "merkle_open.inl", "lowdeg.inl", "eval_open.inl", "mixed_eval.inl", "query_stage.inl", "pcs_verify.inl", "mixed_verify.inl", "stark_verify.inl", "pcs_verify_many.inl", "verify_stages.h", os.path.join("..", "..", "include", "zkir_amd.h"), os.path.join("..", "..", "include", "zkir_amd_experimental.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -100,6 +100,7 @@ struct MemManyDevice {
   size_t region = 0;
   std::vector<uint32_t> sec_off;                                 // where section i lies (words of the block)
   uint32_t launches = 0, tape_stages = 0;
+  bool tape_inflight = false;                                    // (tape_stage_many.inl) the tape list stage's byte kernels may still be writing the block
   uint64_t uploaded_words = 0;
   std::optional<DeviceTapes> dt;
   zkir::TapeStages tapes{};
@@ -178,6 +179,7 @@ struct MemManyDevice {
     }
     const size_t o_part = at, total = o_part + al256((size_t)wg * sizeof(E4));
     if (total >> 33) return refuse("the batch's program images are too large for one block");
+    if (total > V->cap && tape_inflight) { if (hipStreamSynchronize(s) != hipSuccess) return -ZKIR_ERR_DEVICE; tape_inflight = false; }      // (a larger block is a copy of this one)
     int rc = V->ensure(total, region); if (rc) return -rc;
     unsigned char* h = (unsigned char*)V->pin.take(o_part - region);
     E4* hp = wg ? V->pin.take_n<E4>((size_t)wg) : nullptr;

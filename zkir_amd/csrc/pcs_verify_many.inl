@@ -140,6 +140,30 @@ int zkir_verify_rate_many_memory_device(const uint32_t* const* proofs, const uin
   });
 }
 
+// zkir_verify_rate_many_memory_device PLUS the tape list stage (tape_stage_many.inl), as zkir_verify_many_tapes_device
+int zkir_verify_rate_many_tapes_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                       const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts, void* stream) {
+  if (!proofs || !proof_words || !verdicts) return pcs_many_refuse("zkir_verify_rate_many_tapes_device: null proofs, proof_words or verdicts");
+  if (n < 1 || n > 1024) return pcs_many_refuse("zkir_verify_rate_many_tapes_device: n must be 1 .. 1024");
+  return guarded([&]() -> int {
+    zkir::MemManyNote note; zkir::TapeManyNote tnote;
+    MemManyDevice md{(hipStream_t)stream, "zkir_verify_rate_many_tapes_device"};
+    TapeManyDevice td{md};
+    PcsManyDeviceStage st{(hipStream_t)stream};
+    const zkir::TapeStagesFor tapes = md.tapes_for();
+    const zkir::TapeManyStage ts = td.stage();
+    const zkir::TapeManyRun run{&ts, verify_device_min_records(), zkir::TapeManyProbe{}, &tnote};
+    const int rc = zkir::rate_many_with_mem_stage(proofs, proof_words, expects, min_queries, min_pow_bits, n, md.stage(), verify_device_min_cells(), &tapes,
+                                                  zkir::PcsManyStage{&st, pcs_many_device_run}, zkir::MemManyProbe{}, verdicts, &note, &run);
+    zkir::verify_note_device_stages(md.tape_stages + md.launches + td.launches);
+    if (rc) return rc;
+    st.note();
+    zkir::verify_note_memory(note.cells, md.launches, md.uploaded_words);
+    zkir::verify_note_tapes(tnote.records, td.launches, td.uploaded_words);
+    return 0;
+  });
+}
+
 int zkir_pcs_verify_many_device(const uint32_t* kinds, const uint32_t* const* proofs, const uint64_t* proof_words, const uint32_t* const* expect_roots, const uint32_t* const* expect_points,
                                 const uint32_t* const* expect_evals, uint32_t n, int32_t* verdicts, void* stream) {
   if (!kinds || !proofs || !proof_words || !verdicts) return pcs_many_refuse("zkir_pcs_verify_many_device: null kinds, proofs, proof_words or verdicts");

@@ -1095,6 +1095,7 @@ int zkir_hash_tape_check_launch(const uint32_t* hash_words, uint64_t n_hash_word
 #include "verify_device.inl"
 #include "mem_stage.inl"
 #include "mem_stage_many.inl"
+#include "tape_stage_many.inl"
 extern "C" {
 
 // Full proof of the run whose K1 output is `trace` (pub->n_real executed rows, padded to 2^ctx.log_n).  Phases are timed with HIP events

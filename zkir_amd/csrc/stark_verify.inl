@@ -195,6 +195,47 @@ int zkir_verify_many_memory_probe(const uint32_t* const* proofs, const uint64_t*
   return verify_many_memory_run("zkir_verify_many_memory_probe", proofs, proof_words, expects, n, verdicts, zkir::MemManyProbe{what, index}, device, 0, stream);
 }
 
+// zkir_verify_many_memory_device PLUS the tape list stage (tape_stage_many.inl): the hash and wide tapes of all mode-4 proofs as ONE device batch beside the memory batch,
+// around one pass of fronts and one query stage.  device = 0: the host list stages and the host query stage (the probe's host form).
+static int verify_many_tapes_run(const char* who, const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts,
+                                 const zkir::TapeManyProbe& probe, int device, uint64_t min_cells, uint64_t min_records, void* stream) {
+  stark_last_ms[0] = stark_last_ms[1] = stark_last_ms[2] = 0;
+  if (!proofs || !proof_words || !verdicts) return stark_refuse((std::string(who) + ": null proofs, proof_words or verdicts").c_str());
+  if (n < 1 || n > 1024) return stark_refuse((std::string(who) + ": n must be 1 .. 1024").c_str());
+  return guarded([&]() -> int {
+    zkir::MemManyNote note; zkir::TapeManyNote tnote;
+    if (!device) {
+      const zkir::TapeManyStage hs = zkir::host_tape_many_stage();
+      const zkir::TapeManyRun run{&hs, 0, probe, &tnote};
+      const int rc = zkir::verify_many_with_mem_stage(proofs, proof_words, expects, n, zkir::host_mem_many_stage(), 0, nullptr, zkir::host_stark_query_stage(), zkir::MemManyProbe{}, verdicts, &note, &run);
+      zkir::verify_note_memory(note.cells, 0, 0);
+      zkir::verify_note_tapes(tnote.records, 0, 0);
+      return rc;
+    }
+    MemManyDevice md{(hipStream_t)stream, who};
+    TapeManyDevice td{md};
+    StarkDeviceStage st{(hipStream_t)stream};
+    const zkir::TapeStagesFor tapes = md.tapes_for();
+    const zkir::TapeManyStage ts = td.stage();
+    const zkir::TapeManyRun run{&ts, min_records, probe, &tnote};
+    const int rc = zkir::verify_many_with_mem_stage(proofs, proof_words, expects, n, md.stage(), min_cells, &tapes, zkir::StarkQueryStage{&st, stark_device_run}, zkir::MemManyProbe{}, verdicts, &note, &run);
+    zkir::verify_note_device_stages(md.tape_stages + md.launches + td.launches);
+    if (rc) return rc;
+    st.note();
+    zkir::verify_note_memory(note.cells, md.launches, md.uploaded_words);
+    zkir::verify_note_tapes(tnote.records, td.launches, td.uploaded_words);
+    return 0;
+  });
+}
+int zkir_verify_many_tapes_device(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, void* stream) {
+  return verify_many_tapes_run("zkir_verify_many_tapes_device", proofs, proof_words, expects, n, verdicts, zkir::TapeManyProbe{}, 1, verify_device_min_cells(), verify_device_min_records(), stream);
+}
+int zkir_verify_many_tapes_probe(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, uint32_t what,
+                                 uint32_t index, int device, void* stream) {
+  if (what > 2 || index >= n) return stark_refuse("zkir_verify_many_tapes_probe: what must be 0 .. 2 and index below n");
+  return verify_many_tapes_run("zkir_verify_many_tapes_probe", proofs, proof_words, expects, n, verdicts, zkir::TapeManyProbe{what, index}, device, 0, 0, stream);
+}
+
 int zkir_verify_chain_on_device(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n_segments, const zkir_public_inputs* expect, void* stream) {
   if (proofs && proof_words && n_segments == 1 && proofs[0] && proof_words[0] > 9 && proofs[0][9] >= 3) return zkir_verify_on_device(proofs[0], proof_words[0], expect, stream);      // a whole run by itself
   stark_last_ms[0] = stark_last_ms[1] = stark_last_ms[2] = 0;

@@ -248,6 +248,8 @@ struct LastQueries { uint64_t hash_jobs = 0, value_jobs = 0, uploaded_words = 0;
 thread_local LastQueries last_queries;
 struct LastMemory { uint64_t cells = 0, uploaded_words = 0; uint32_t launches = 0; };      // zkir_verify_memory_last: the device memory stages of the thread's last verification
 thread_local LastMemory last_memory;
+struct LastTapes { uint64_t records = 0, uploaded_words = 0; uint32_t launches = 0; };      // zkir_verify_tapes_last: the tape list stage of the thread's last many-proof verification
+thread_local LastTapes last_tapes;
 struct StageClock {
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   double ms[5] = {0, 0, 0, 0, 0};
@@ -258,6 +260,7 @@ struct StageClock {
     last_stages.device_stages = 0; last_stages.valid = true;
     last_queries = LastQueries{};                                            // (every host verification: the *_on_device entries note theirs once the stage has run)
     last_memory = LastMemory{};                                              // (likewise: zkir_verify_memory_device notes its own afterwards)
+    last_tapes = LastTapes{};                                                // (likewise: the *_many_tapes_* entries)
     if (getenv("ZKIR_VERIFY_TIMES"))
       fprintf(stderr, "zkir_verify: parse %.3f ms | section digests %.3f | hash table side %.3f | wide table side %.3f | rest %.3f\n", ms[0], ms[1], ms[2], ms[3], ms[4]);
   }
@@ -468,6 +471,7 @@ const char* mem_side_args(const uint32_t* sec, uint64_t n_words, const uint8_t* 
   return nullptr;
 }
 void verify_note_memory(uint64_t cells, uint32_t launches, uint64_t uploaded_words) { last_memory = LastMemory{cells, uploaded_words, launches}; }
+void verify_note_tapes(uint64_t records, uint32_t launches, uint64_t uploaded_words) { last_tapes = LastTapes{records, uploaded_words, launches}; }
 void verify_note_device_stages(uint32_t n) { last_stages.device_stages = n; }
 void verify_note_queries(uint64_t hash_jobs, uint64_t value_jobs, uint32_t launches, uint64_t uploaded_words) { last_queries = LastQueries{hash_jobs, value_jobs, uploaded_words, launches}; }
 StarkQueryStage host_stark_query_stage() { return StarkQueryStage{nullptr, host_stark_run}; }
@@ -578,6 +582,12 @@ int zkir_verify_memory_last(uint64_t* cells, uint32_t* launches, uint64_t* uploa
   if (cells) *cells = last_memory.cells;
   if (launches) *launches = last_memory.launches;
   if (uploaded_words) *uploaded_words = last_memory.uploaded_words;
+  return ZKIR_OK;
+}
+int zkir_verify_tapes_last(uint64_t* records, uint32_t* launches, uint64_t* uploaded_words) {
+  if (records) *records = last_tapes.records;
+  if (launches) *launches = last_tapes.launches;
+  if (uploaded_words) *uploaded_words = last_tapes.uploaded_words;
   return ZKIR_OK;
 }
 int zkir_mem_section_check_host(const uint32_t* sec, uint64_t n_words, uint32_t mode, uint64_t code_words, int32_t* verdict) {
@@ -1164,13 +1174,17 @@ int verify_impl(const uint32_t* w, uint64_t len, const zkir_public_inputs* expec
       if (mode == 4) {
         E4 Th = bb::e_zero(), Tw = bb::e_zero();
         clk.lap(4);
-        const int hs = S.hash_side(S.self, lk_m, Th.c);
-        clk.lap(2);
-        if (hs) return hs;
-        const int ws = S.wide_side(S.self, lk_m, Tw.c);
-        clk.lap(3);
-        if (ws) return ws;
-        T_hash = bb::e_add(Th, Tw);
+        // (a list entry's tape stage) both shares wait with check 10; a memory stage that defers too must defer into the same record
+        if (S.defer && S.defer->tapes_armed && !(mem && mem->defer && mem->defer->armed && mem->defer != S.defer)) deferred = S.defer;
+        else {
+          const int hs = S.hash_side(S.self, lk_m, Th.c);
+          clk.lap(2);
+          if (hs) return hs;
+          const int ws = S.wide_side(S.self, lk_m, Tw.c);
+          clk.lap(3);
+          if (ws) return ws;
+          T_hash = bb::e_add(Th, Tw);
+        }
       }
       // (a memory stage) the cells' two ends are the stage's sum: `cells` is empty here, so none of them is in d
       if (mem && mem->defer && mem->defer->armed) deferred = mem->defer;
@@ -2052,18 +2066,94 @@ int mm_side(void* p, const uint32_t* lk_m, const uint8_t* blob, size_t blob_len,
   set_last_error({ZKIR_ERR_OTHER, "zkir_verify_many_memory: a deferring front asked for its table side"});
   return -ZKIR_ERR_OTHER;
 }
+// ---- the tape stages over a list of proofs (verify_stages.h) ----
+int host_tape_many_prepare(void*, const TapeSection* list, uint32_t n, int* hv, uint64_t* used, int* wv, uint32_t* digests) {
+  uint64_t chunk0 = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const TapeSection& S = list[i];
+    HostTapes h; size_t u = 0;
+    hv[i] = host_hash_check(&h, S.hash, (size_t)S.avail, S.n_real, S.code_end, &u);
+    used[i] = hv[i] ? 0 : u;
+    wv[i] = S.wide ? host_wide_check(&h, S.wide, (size_t)S.n_wide, S.n_real) : 0;
+    const uint64_t c0 = tape_section_chunks(S, 0), c1 = tape_section_chunks(S, 1);
+    if (!hv[i] && c0) section_digests_host(S.hash, u, digests + 4 * chunk0);      // (a passing section is whole: u = hash_words)
+    if (c1) section_digests_host(S.wide, 1 + 8 * (size_t)S.n_wide, digests + 4 * (chunk0 + c0));
+    chunk0 += c0 + c1;
+  }
+  return 0;
+}
+int host_tape_many_sides(void*, const TapeSection* list, const TapeSideJob* jobs, uint32_t n_jobs, uint32_t* sums) {
+  for (uint32_t j = 0; j < n_jobs; j++) {
+    const TapeSection& S = list[jobs[j].section];
+    HostTapes h; size_t u = 0;
+    memset(sums + 8 * (size_t)j, 0, 32);
+    if (jobs[j].hash) {
+      if (host_hash_check(&h, S.hash, (size_t)S.avail, S.n_real, S.code_end, &u)) { set_last_error({ZKIR_ERR_OTHER, "the tape list stage: a side was asked for of a hash section that fails its check"}); return -ZKIR_ERR_OTHER; }
+      host_hash_side(&h, jobs[j].lk_m, sums + 8 * (size_t)j);
+    }
+    if (jobs[j].wide && S.wide) { h.wide = S.wide; h.n_wide = (size_t)S.n_wide; host_wide_side(&h, jobs[j].lk_m, sums + 8 * (size_t)j + 4); }
+  }
+  return 0;
+}
+// One mode-4 proof of a list entry: its TapeStages answer from what prepare returned where the front hands over what was located, else from the host stage functions.
+struct ManyTapeProof {
+  TapeSection sec{};
+  int slot = -1;                                                 // the proof's tapes in the list (-1: none went to the list stage)
+  int hv = 0, wv = 0; uint64_t used = 0; const uint32_t* dg = nullptr;      // prepare's answers
+  bool hash_batch = false, wide_batch = false;                   // the front's check was answered by the list: that share waits for the sides call
+  HostTapes host;                                                // what the host stage functions keep where they ran instead
+  MemDeferred* def = nullptr;
+};
+int tm_hash_check(void* p, const uint32_t* w, size_t avail, uint64_t n_real, uint64_t code_end, size_t* used) {
+  ManyTapeProof& P = *static_cast<ManyTapeProof*>(p);
+  // (an EMPTY hash tape beside a wide tape that went to the list has nothing to defer: the host stage, one word)
+  if (P.slot < 0 || w != P.sec.hash || avail != P.sec.avail || n_real != P.sec.n_real || code_end != P.sec.code_end || P.sec.hash[0] == 0) return host_hash_check(&P.host, w, avail, n_real, code_end, used);
+  if (P.hv) return P.hv;
+  P.hash_batch = true; P.def->tapes_armed = true;
+  *used = (size_t)P.used;
+  return 0;
+}
+int tm_wide_check(void* p, const uint32_t* sec, size_t n_wide, uint64_t n_real) {
+  ManyTapeProof& P = *static_cast<ManyTapeProof*>(p);
+  if (P.slot < 0 || !P.sec.wide || sec != P.sec.wide || n_wide != P.sec.n_wide || n_real != P.sec.n_real) return host_wide_check(&P.host, sec, n_wide, n_real);
+  if (P.wv) return P.wv;
+  P.wide_batch = true; P.def->tapes_armed = true;
+  return 0;
+}
+int tm_digests(void* p, int which, const uint32_t* sw, size_t sl, uint32_t* dg) {
+  ManyTapeProof& P = *static_cast<ManyTapeProof*>(p);
+  if (!(which ? P.wide_batch : P.hash_batch)) return host_digests(nullptr, which, sw, sl, dg);
+  if (sl != (which ? 1 + 8 * (size_t)P.sec.n_wide : (size_t)P.used)) { set_last_error({ZKIR_ERR_OTHER, "zkir_verify_many_tapes: a front asked for the digests of another section than the one it checked"}); return -ZKIR_ERR_OTHER; }
+  memcpy(dg, P.dg + (which ? 4 * (size_t)tape_section_chunks(P.sec, 0) : 0), 16 * (size_t)tape_section_chunks(P.sec, which));
+  return 0;
+}
+int tm_side(ManyTapeProof& P, bool wide, const uint32_t* lk_m, uint32_t T[4]) {
+  if (!P.def->tapes_armed) return wide ? host_wide_side(&P.host, lk_m, T) : host_hash_side(&P.host, lk_m, T);
+  set_last_error({ZKIR_ERR_OTHER, "zkir_verify_many_tapes: a deferring front asked for a table side"});
+  return -ZKIR_ERR_OTHER;
+}
+int tm_hash_side(void* p, const uint32_t* lk_m, uint32_t T[4]) { return tm_side(*static_cast<ManyTapeProof*>(p), false, lk_m, T); }
+int tm_wide_side(void* p, const uint32_t* lk_m, uint32_t T[4]) { return tm_side(*static_cast<ManyTapeProof*>(p), true, lk_m, T); }
+struct TapeManyDone {
+  const TapeManyStage* st; bool called = false;
+  void call() { if (!called && st && st->done) st->done(st->self); called = true; }
+  ~TapeManyDone() { call(); }
+};
 struct MemManyDone {                                             // the stage's done on every way out
   const MemManyStage& st; bool called = false;
   void call() { if (!called && st.done) st.done(st.self); called = true; }
   ~MemManyDone() { call(); }
 };
 
-// Phase A, the fronts and phase B of a list entry; front(i, mem) is proof i's front (mem: NULL where the batch stays with the inline host code) and answers its verdict so
-// far (negative: no verdict for the call).  out[i]: 10 where a deferred check failed, else the front's answer.
+// Phase A, the fronts and phase B of a list entry; front(i, mem, tapes) is proof i's front (mem: NULL where the memory batch stays with the inline host code; tapes: NULL
+// where no tape batch went through the list stage, and the front keeps the tape stages it always had) and answers its verdict so far (negative: no verdict for the call).
+// out[i]: 10 where a deferred check failed, else the front's answer.  tr: NULL, or the tape list stage around the same fronts.
 template <typename Front>
 int mem_many_fronts(const uint32_t* const* proofs, const uint64_t* proof_words, uint32_t n, bool rate, const MemManyStage& st, uint64_t min_cells, const MemManyProbe& probe,
-                    Front front, std::vector<int32_t>& out, MemManyNote* note) {
+                    const TapeManyRun* tr, Front front, std::vector<int32_t>& out, MemManyNote* note) {
   *note = MemManyNote{};
+  if (tr && tr->note) *tr->note = TapeManyNote{};
+  TapeManyDone tdone{tr ? tr->stage : nullptr};
   MemManyDone done{st};
   std::vector<ManyMemProof> P(n);
   std::vector<MemSection> list;
@@ -2080,6 +2170,22 @@ int mem_many_fronts(const uint32_t* const* proofs, const uint64_t* proof_words, 
     cells += nc; chunks += mem_section_chunks(nc);
   }
   const bool batch = !list.empty() && cells >= min_cells;
+  // the tapes: every located pair that holds a record at all (a proof with two empty tapes has nothing to defer)
+  std::vector<ManyTapeProof> TP(tr ? n : 0);
+  std::vector<TapeSection> tlist;
+  uint64_t records = 0, tchunks = 0;
+  if (tr) for (uint32_t i = 0; i < n; i++) {
+    TP[i].def = &P[i].def;
+    const TapeLocated L = tape_sections_locate(proofs[i], proof_words[i], P[i].loc);
+    if (!L.ok) continue;
+    TapeSection S = L.sec;
+    if (!S.n_wide) S.wide = nullptr;
+    if (S.hash[0] == 0 && !S.wide) continue;
+    TP[i].sec = S; TP[i].slot = (int)tlist.size();
+    tlist.push_back(S);
+    records += S.n_full + S.n_wide; tchunks += tape_section_chunks(S, 0) + tape_section_chunks(S, 1);
+  }
+  const bool tbatch = tr && !tlist.empty() && records >= tr->min_records;
   std::vector<int> sv(list.size(), 0);
   std::vector<uint32_t> dg(batch ? 4 * (size_t)chunks : 0);
   if (batch) {
@@ -2088,15 +2194,37 @@ int mem_many_fronts(const uint32_t* const* proofs, const uint64_t* proof_words, 
     uint64_t chunk0 = 0;
     for (uint32_t i = 0; i < n; i++) if (P[i].slot >= 0) { P[i].verdict = sv[P[i].slot]; P[i].dg = dg.data() + 4 * chunk0; chunk0 += mem_section_chunks(P[i].n); }
   }
+  std::vector<int> thv(tlist.size(), 0), twv(tlist.size(), 0);
+  std::vector<uint64_t> tused(tlist.size(), 0);
+  std::vector<uint32_t> tdg(tbatch ? 4 * (size_t)tchunks : 0);
+  if (tbatch) {
+    const int rc = tr->stage->prepare(tr->stage->self, tlist.data(), (uint32_t)tlist.size(), thv.data(), tused.data(), twv.data(), tdg.data());
+    if (rc) return rc < 0 ? rc : -rc;
+    uint64_t chunk0 = 0;
+    for (uint32_t i = 0; i < n; i++) if (TP[i].slot >= 0) {
+      ManyTapeProof& T = TP[i];
+      T.hv = thv[T.slot]; T.wv = twv[T.slot]; T.used = tused[T.slot]; T.dg = tdg.data() + 4 * chunk0;
+      chunk0 += tape_section_chunks(T.sec, 0) + tape_section_chunks(T.sec, 1);
+    }
+  } else for (ManyTapeProof& T : TP) T.slot = -1;
   for (uint32_t i = 0; i < n; i++) {
     const MemStages ms{&P[i], mm_check, mm_digests, mm_side, &P[i].def};
-    const int rc = front(i, batch ? &ms : nullptr);
+    TapeStages ts{nullptr, tm_hash_check, tm_wide_check, tm_digests, tm_hash_side, tm_wide_side, &P[i].def};
+    if (tbatch) ts.self = &TP[i];
+    const int rc = front(i, batch ? &ms : nullptr, tbatch ? &ts : nullptr);
     if (rc < 0) return rc;
     out[i] = rc;
   }
+  // phase B: every proof whose front kept check 10, with the shares it left out
   std::vector<MemSideJob> jobs;
-  std::vector<uint32_t> who;
-  for (uint32_t i = 0; i < n; i++) if (P[i].def.filled) { jobs.push_back(MemSideJob{(uint32_t)P[i].slot, P[i].def.lk_m.data(), P[i].def.blob.data(), P[i].def.blob.size()}); who.push_back(i); }
+  std::vector<TapeSideJob> tjobs;
+  std::vector<uint32_t> who, twho;
+  for (uint32_t i = 0; i < n; i++) if (P[i].def.filled) {
+    if (P[i].def.armed) { jobs.push_back(MemSideJob{(uint32_t)P[i].slot, P[i].def.lk_m.data(), P[i].def.blob.data(), P[i].def.blob.size()}); who.push_back(i); }
+    if (P[i].def.tapes_armed && (TP[i].hash_batch || TP[i].wide_batch)) { tjobs.push_back(TapeSideJob{(uint32_t)TP[i].slot, P[i].def.lk_m.data(), TP[i].hash_batch, TP[i].wide_batch}); twho.push_back(i); }
+  }
+  std::vector<E4> share(n, bb::e_zero());
+  auto add_to = [&](uint32_t i, const uint32_t* t) { E4 x; memcpy(x.c, t, 16); share[i] = bb::e_add(share[i], x); };
   if (!jobs.empty()) {
     std::vector<uint32_t> sums(4 * jobs.size(), 0);
     const int rc = st.side(st.self, list.data(), jobs.data(), (uint32_t)jobs.size(), sums.data());
@@ -2104,22 +2232,63 @@ int mem_many_fronts(const uint32_t* const* proofs, const uint64_t* proof_words, 
     for (size_t j = 0; j < jobs.size(); j++) {
       uint32_t* Tm = sums.data() + 4 * j;
       if (probe.what == 1 && probe.index == who[j]) Tm[0] = bb::add(Tm[0], bb::R1);
-      if (!mem_deferred_check(P[who[j]].def, Tm)) out[who[j]] = 10;
+      add_to(who[j], Tm);
     }
   }
+  if (!tjobs.empty()) {
+    std::vector<uint32_t> sums(8 * tjobs.size(), 0);
+    const int rc = tr->stage->sides(tr->stage->self, tlist.data(), tjobs.data(), (uint32_t)tjobs.size(), sums.data());
+    if (rc) return rc < 0 ? rc : -rc;
+    for (size_t j = 0; j < tjobs.size(); j++) { add_to(twho[j], sums.data() + 8 * j); add_to(twho[j], sums.data() + 8 * j + 4); }
+  }
+  for (uint32_t i = 0; i < n; i++) if (P[i].def.filled) {
+    if (P[i].def.tapes_armed) {                                    // (a check the list did not answer for this front: the host stage kept what its side needs)
+      uint32_t t[4];
+      if (!TP[i].hash_batch) { host_hash_side(&TP[i].host, P[i].def.lk_m.data(), t); add_to(i, t); }
+      if (!TP[i].wide_batch) { host_wide_side(&TP[i].host, P[i].def.lk_m.data(), t); add_to(i, t); }
+      if (tr->probe.index == i && ((tr->probe.what == 1 && TP[i].hash_batch) || (tr->probe.what == 2 && TP[i].wide_batch))) share[i].c[0] = bb::add(share[i].c[0], bb::R1);      // (the probed share, where the list answered that check)
+    }
+    if (!mem_deferred_check(P[i].def, share[i].c)) out[i] = 10;
+  }
+  tdone.call();
   done.call();
   if (batch) { note->cells = cells; note->sections = (uint32_t)list.size(); note->deferred = (uint32_t)jobs.size(); }
+  if (tbatch && tr->note) { tr->note->records = records; tr->note->sections = (uint32_t)tlist.size(); tr->note->deferred = (uint32_t)tjobs.size(); }
   return 0;
 }
 }  // namespace
 MemManyStage host_mem_many_stage() { return MemManyStage{nullptr, host_mem_many_prepare, host_mem_many_side, nullptr}; }
+TapeManyStage host_tape_many_stage() { return TapeManyStage{nullptr, host_tape_many_prepare, host_tape_many_sides, nullptr}; }
+TapeLocated tape_sections_locate(const uint32_t* w, uint64_t len, const MemLocated& loc) {
+  TapeLocated L;
+  if (!w || !loc.ok || loc.mode != 4 || loc.avail < 1) return L;
+  const uint64_t nc = w[loc.at];
+  if (nc > ((uint64_t)1 << 28) || (loc.avail - 1) / 7 < nc) return L;      // (the memory stage's check 4)
+  const uint64_t at = loc.at + 1 + 7 * nc;
+  if (at >= len) return L;
+  TapeSection& S = L.sec;
+  S.hash = w + at; S.avail = len - at;
+  const TapeExtent x = tape_section_walk(S.hash, S.avail, nullptr);
+  S.n_full = x.n_full; S.hash_words = x.used; S.whole = x.whole;
+  S.n_real = (uint64_t)w[7] | ((uint64_t)w[8] << 30); S.code_end = air::CODE_BASE + 4 * loc.code_words;
+  if (S.code_end >> 32) return L;                                   // (a code size no program has: the device record holds 32 bits, the host stage takes it)
+  S.wide = nullptr; S.n_wide = 0;
+  if (x.whole && x.used < S.avail) {
+    const uint64_t nw = S.hash[x.used];
+    if (nw <= S.n_real && nw <= ((uint64_t)1 << 28) && (S.avail - x.used - 1) / 8 >= nw) { S.wide = S.hash + x.used; S.n_wide = nw; }
+  }
+  L.ok = true;
+  return L;
+}
 
 int verify_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, const MemManyStage& mem,
-                               uint64_t min_cells, const TapeStagesFor* tapes, const StarkQueryStage& queries, const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note) {
+                               uint64_t min_cells, const TapeStagesFor* tapes, const StarkQueryStage& queries, const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note,
+                               const TapeManyRun* tape_run) {
   std::vector<int32_t> out(n, 0);
   std::vector<StarkQueries> Q(n);
-  const int frc = mem_many_fronts(proofs, proof_words, n, false, mem, min_cells, probe, [&](uint32_t i, const MemStages* ms) -> int {
+  const int frc = mem_many_fronts(proofs, proof_words, n, false, mem, min_cells, probe, tape_run, [&](uint32_t i, const MemStages* ms, const TapeStages* listed) -> int {
     const uint32_t* w = proofs[i];
+    if (listed) return stark_verify_collect(w, proof_words[i], expects ? expects[i] : nullptr, true, listed, &Q[i], ms);
     const bool with_tapes = tapes && w && proof_words[i] >= 10 && w[9] == 4;
     const TapeStages* ts = with_tapes ? tapes->begin(tapes->self, i) : nullptr;
     if (with_tapes && !ts) return -ZKIR_ERR_DEVICE;
@@ -2142,13 +2311,13 @@ int verify_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* pr
 
 int rate_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
                              const uint32_t* min_pow_bits, uint32_t n, const MemManyStage& mem, uint64_t min_cells, const TapeStagesFor* tapes, const PcsManyStage& queries,
-                             const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note) {
+                             const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note, const TapeManyRun* tape_run) {
   std::vector<int32_t> out(n, 0);
   std::vector<PcsCollected> C(n);
-  const int frc = mem_many_fronts(proofs, proof_words, n, true, mem, min_cells, probe, [&](uint32_t i, const MemStages* ms) -> int {
+  const int frc = mem_many_fronts(proofs, proof_words, n, true, mem, min_cells, probe, tape_run, [&](uint32_t i, const MemStages* ms, const TapeStages* listed) -> int {
     const uint32_t* w = proofs[i];
-    const bool with_tapes = tapes && w && proof_words[i] >= 10 && w[9] == 4;
-    const TapeStages* ts = with_tapes ? tapes->begin(tapes->self, i) : nullptr;
+    const bool with_tapes = !listed && tapes && w && proof_words[i] >= 10 && w[9] == 4;
+    const TapeStages* ts = listed ? listed : with_tapes ? tapes->begin(tapes->self, i) : nullptr;
     if (with_tapes && !ts) return -ZKIR_ERR_DEVICE;
     int rc = rate_verify_with_stage(w, proof_words[i], expects ? expects[i] : nullptr, min_queries ? min_queries[i] : 1u, min_pow_bits ? min_pow_bits[i] : 0u, pcs_collect_stage(&C[i]), ts, ms);
     if (with_tapes) rc = tapes->end(tapes->self, rc);
@@ -2203,10 +2372,80 @@ int mem_sections_stage(const char* who, const MemManyStage& st, const uint32_t* 
   } catch (const std::exception& e) { set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": " + e.what()}); return ZKIR_ERR_OTHER; }
   return ZKIR_OK;
 }
+
+int tape_sections_stage(const char* who, const TapeManyStage& st, const uint32_t* const* hash_secs, const uint64_t* hash_words, const uint32_t* const* wide_secs, const uint64_t* wide_words,
+                        const uint64_t* n_real, const uint64_t* code_end, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* hash_verdicts, int32_t* wide_verdicts,
+                        uint32_t* digests, uint32_t* sums) {
+  auto refuse = [&](const std::string& why) { set_last_error({ZKIR_ERR_ARGUMENT, std::string(who) + ": " + why}); return (int)ZKIR_ERR_ARGUMENT; };
+  if (!hash_secs || !hash_words || !wide_secs || !wide_words || !n_real || !code_end || !alphas || !lambdas || !hash_verdicts || !wide_verdicts || !digests || !sums) return refuse("null argument");
+  if (n < 1 || n > 1024) return refuse("n must be 1 .. 1024");
+  try {
+    std::vector<TapeSection> list(n);
+    std::vector<uint32_t> lk((size_t)n * air::N_LK, 0);
+    TapeManyDone done{&st};
+    std::vector<uint8_t> wide_over(n, 0);                          // a count above n_real is the front's own 57: such a list does not reach the stage
+    uint64_t out_chunks = 0, in_chunks = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      if (!hash_secs[i] || !wide_secs[i] || hash_words[i] < 1 || wide_words[i] < 1) return refuse("a section must hold its count word");
+      if (hash_words[i] >> 31 || wide_words[i] >> 31) return refuse("a section is too long");
+      for (int k = 0; k < 4; k++) if (alphas[4 * i + k] >= bb::P || lambdas[4 * i + k] >= bb::P) return refuse("alpha and lambda must be canonical");
+      if (wide_words[i] != 1 + 8 * (uint64_t)wide_secs[i][0]) return refuse("a wide section must be [n] + 8 n words");
+      TapeSection& S = list[i];
+      S.hash = hash_secs[i]; S.avail = hash_words[i];
+      const TapeExtent x = tape_section_walk(S.hash, S.avail, nullptr);
+      if (x.whole && x.used != S.avail) return refuse("words behind a hash section's last record");
+      S.n_full = x.n_full; S.hash_words = x.used; S.whole = x.whole;
+      S.n_real = n_real[i]; S.code_end = code_end[i];
+      S.n_wide = wide_secs[i][0]; S.wide = S.n_wide ? wide_secs[i] : nullptr;
+      if (S.n_wide > S.n_real) { wide_over[i] = 1; S.wide = nullptr; S.n_wide = 0; }
+      uint32_t* l = lk.data() + (size_t)i * air::N_LK;
+      E4 a, l1, lam = bb::e_one_m();
+      memcpy(a.c, alphas + 4 * i, 16); memcpy(l1.c, lambdas + 4 * i, 16);
+      a = bb::e_to_mont(a); l1 = bb::e_to_mont(l1);
+      memcpy(l + air::LK_ALPHA, a.c, 16);
+      for (int j = 0; j <= air::N_TUPLE; j++) { memcpy(l + air::LK_LAM + 4 * j, lam.c, 16); lam = bb::e_mul_m(lam, l1); }
+      out_chunks += (hash_words[i] + 511) / 512 + (wide_words[i] + 511) / 512;
+      in_chunks += tape_section_chunks(S, 0) + tape_section_chunks(S, 1);
+    }
+    std::vector<int> hv(n, 0), wv(n, 0);
+    std::vector<uint64_t> used(n, 0);
+    std::vector<uint32_t> dg(4 * (size_t)in_chunks + 4, 0);
+    int rc = st.prepare(st.self, list.data(), n, hv.data(), used.data(), wv.data(), dg.data());
+    if (rc) return rc < 0 ? -rc : rc;
+    memset(digests, 0, 16 * (size_t)out_chunks);
+    memset(sums, 0, 32 * (size_t)n);
+    std::vector<TapeSideJob> jobs;
+    uint64_t oc = 0, ic = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const TapeSection& S = list[i];
+      const uint64_t c0 = tape_section_chunks(S, 0), c1 = tape_section_chunks(S, 1), o0 = (hash_words[i] + 511) / 512;
+      hash_verdicts[i] = hv[i]; wide_verdicts[i] = wide_over[i] ? 57 : wv[i];
+      if (!hv[i]) memcpy(digests + 4 * oc, dg.data() + 4 * ic, 16 * (size_t)c0);      // (a passing section is whole: c0 = o0)
+      if (!wide_verdicts[i]) {
+        if (S.wide) memcpy(digests + 4 * (oc + o0), dg.data() + 4 * (ic + c0), 16 * (size_t)c1);
+        else section_digests_host(wide_secs[i], 1, digests + 4 * (oc + o0));      // (the empty wide section: its count word alone)
+      }
+      if (!hv[i] && !wide_verdicts[i]) jobs.push_back(TapeSideJob{i, lk.data() + (size_t)i * air::N_LK, true, S.wide != nullptr});
+      oc += o0 + (wide_words[i] + 511) / 512; ic += c0 + c1;
+    }
+    std::vector<uint32_t> T(8 * jobs.size() + 8, 0);
+    if (!jobs.empty()) { rc = st.sides(st.self, list.data(), jobs.data(), (uint32_t)jobs.size(), T.data()); if (rc) return rc < 0 ? -rc : rc; }
+    for (size_t j = 0; j < jobs.size(); j++) for (int h = 0; h < 2; h++) {
+      E4 t; memcpy(t.c, T.data() + 8 * j + 4 * h, 16); t = bb::e_from_mont(t); memcpy(sums + 8 * (size_t)jobs[j].section + 4 * h, t.c, 16);
+    }
+  } catch (const std::exception& e) { set_last_error({ZKIR_ERR_OTHER, std::string(who) + ": " + e.what()}); return ZKIR_ERR_OTHER; }
+  return ZKIR_OK;
+}
 }  // namespace zkir
 
 extern "C" {
 
+int zkir_tape_sections_stage_host(const uint32_t* const* hash_secs, const uint64_t* hash_words, const uint32_t* const* wide_secs, const uint64_t* wide_words, const uint64_t* n_real,
+                                  const uint64_t* code_end, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* hash_verdicts, int32_t* wide_verdicts, uint32_t* digests,
+                                  uint32_t* sums) {
+  return zkir::tape_sections_stage("zkir_tape_sections_stage_host", zkir::host_tape_many_stage(), hash_secs, hash_words, wide_secs, wide_words, n_real, code_end, alphas, lambdas, n, hash_verdicts,
+                                   wide_verdicts, digests, sums);
+}
 int zkir_mem_sections_stage_host(const uint32_t* const* secs, const uint64_t* n_words, const uint32_t* modes, const uint64_t* code_words, const uint8_t* const* blobs, const size_t* blob_lens,
                                  const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* verdicts, uint32_t* digests, uint32_t* sums) {
   return zkir::mem_sections_stage("zkir_mem_sections_stage_host", zkir::host_mem_many_stage(), secs, n_words, modes, code_words, blobs, blob_lens, alphas, lambdas, n, verdicts, digests, sums);
@@ -2235,6 +2474,36 @@ int zkir_verify_rate_many_memory_host(const uint32_t* const* proofs, const uint6
     zkir::verify_note_memory(note.cells, 0, 0);
     return rc;
   } catch (const std::exception& e) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string("zkir_verify_rate_many_memory_host: ") + e.what()}); return -ZKIR_ERR_OTHER; }
+}
+// The *_many_memory_host entries PLUS the tape list stage over host_tape_many_stage: every located pair of tapes goes through it (no threshold).  zkir_verify_tapes_last:
+// the records that went through it, no launches, no upload.
+int zkir_verify_many_tapes_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts) {
+  if (!proofs || !proof_words || !verdicts) return mem_many_host_refuse("zkir_verify_many_tapes_host: null proofs, proof_words or verdicts");
+  if (n < 1 || n > 1024) return mem_many_host_refuse("zkir_verify_many_tapes_host: n must be 1 .. 1024");
+  try {
+    zkir::MemManyNote note; zkir::TapeManyNote tnote;
+    const zkir::TapeManyStage ts = zkir::host_tape_many_stage();
+    const zkir::TapeManyRun run{&ts, 0, zkir::TapeManyProbe{}, &tnote};
+    const int rc = zkir::verify_many_with_mem_stage(proofs, proof_words, expects, n, zkir::host_mem_many_stage(), 0, nullptr, zkir::host_stark_query_stage(), zkir::MemManyProbe{}, verdicts, &note, &run);
+    zkir::verify_note_memory(note.cells, 0, 0);
+    zkir::verify_note_tapes(tnote.records, 0, 0);
+    return rc;
+  } catch (const std::exception& e) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string("zkir_verify_many_tapes_host: ") + e.what()}); return -ZKIR_ERR_OTHER; }
+}
+int zkir_verify_rate_many_tapes_host(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
+                                     const uint32_t* min_pow_bits, uint32_t n, int32_t* verdicts) {
+  if (!proofs || !proof_words || !verdicts) return mem_many_host_refuse("zkir_verify_rate_many_tapes_host: null proofs, proof_words or verdicts");
+  if (n < 1 || n > 1024) return mem_many_host_refuse("zkir_verify_rate_many_tapes_host: n must be 1 .. 1024");
+  try {
+    zkir::MemManyNote note; zkir::TapeManyNote tnote;
+    const zkir::TapeManyStage ts = zkir::host_tape_many_stage();
+    const zkir::TapeManyRun run{&ts, 0, zkir::TapeManyProbe{}, &tnote};
+    const int rc = zkir::rate_many_with_mem_stage(proofs, proof_words, expects, min_queries, min_pow_bits, n, zkir::host_mem_many_stage(), 0, nullptr, zkir::host_pcs_many_stage(), zkir::MemManyProbe{},
+                                                  verdicts, &note, &run);
+    zkir::verify_note_memory(note.cells, 0, 0);
+    zkir::verify_note_tapes(tnote.records, 0, 0);
+    return rc;
+  } catch (const std::exception& e) { zkir::set_last_error({ZKIR_ERR_OTHER, std::string("zkir_verify_rate_many_tapes_host: ") + e.what()}); return -ZKIR_ERR_OTHER; }
 }
 
 }  // extern "C"

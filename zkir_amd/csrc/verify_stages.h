@@ -14,6 +14,7 @@
 
 namespace zkir {
 
+struct MemDeferred;
 struct TapeStages {
   void* self;
   // hashcall::parse_section's verdict on the hash section that starts at w (avail words to the proof's end); 0: *used = the section's length
@@ -25,6 +26,10 @@ struct TapeStages {
   // the sections' shares of the lookup table side (Montgomery E4 words); lk_m: air.h LK_ALPHA and LK_LAM, Montgomery
   int (*hash_side)(void* self, const uint32_t* lk_m, uint32_t T[4]);
   int (*wide_side)(void* self, const uint32_t* lk_m, uint32_t T[4]);
+  // (the list form below: TapeManyStage) NULL for every stage from before it: the sides run where they always ran.  Else, where defer->tapes_armed is set when the front
+  // reaches the table side, the front calls NEITHER side: it forms T without the tapes' shares, keeps check 10 in *defer and goes on as if that check held.  May be the
+  // record MemStages::defer points at (a proof defers its cells, its tapes or both; two DIFFERENT armed records: the tapes' one is ignored)
+  MemDeferred* defer = nullptr;
 };
 
 // what the host stages keep between their calls
@@ -67,6 +72,7 @@ void section_chunk_digests(const uint32_t* sw, size_t sl, uint32_t* dg);      //
 // section's cells — or why the call is refused.  The cells themselves (in range, strictly increasing: check 54) are the caller's to check.
 const char* mem_side_args(const uint32_t* sec, uint64_t n_words, const uint8_t* blob, size_t blob_len, const uint32_t alpha[4], const uint32_t lambda[4], const uint32_t* sum,
                           uint32_t* lk, uint64_t* n);
+void verify_note_tapes(uint64_t records, uint32_t launches, uint64_t uploaded_words);      // (the *_many_tapes_* entries) zkir_verify_tapes_last's record
 void verify_note_memory(uint64_t cells, uint32_t launches, uint64_t uploaded_words);      // (zkir_verify_memory_device) zkir_verify_memory_last's record
 
 // ---- the memory stages over a LIST of proofs (zkir_verify_many_memory_device, zkir_verify_rate_many_memory_device and their *_host forms) ----
@@ -78,6 +84,7 @@ void verify_note_memory(uint64_t cells, uint32_t launches, uint64_t uploaded_wor
 // passed, 10 precedes all later ones); every other proof keeps its front's verdict.
 struct MemDeferred {
   bool armed = false;                                            // (the check callback) this proof's table side is deferred
+  bool tapes_armed = false;                                      // (a list entry's tape callbacks) the hash and wide tapes' shares are deferred
   bool filled = false;                                           // (the front) check 10 was reached: everything below is set
   int mode = 0, log_n = 0, WM = 0; uint64_t n_real = 0;
   std::vector<uint32_t> ev;                                      // Montgomery E4 words: main | aux at zeta, the same at zeta w, the quotient's four
@@ -114,15 +121,83 @@ struct MemManyNote { uint64_t cells = 0; uint32_t sections = 0, deferred = 0; };
 // canonical challenges: per section the verdict, the chunk digests (zero where the verdict is not 0) and the canonical sum (likewise)
 int mem_sections_stage(const char* who, const MemManyStage& st, const uint32_t* const* secs, const uint64_t* n_words, const uint32_t* modes, const uint64_t* code_words, const uint8_t* const* blobs,
                        const size_t* blob_lens, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* verdicts, uint32_t* digests, uint32_t* sums);
+
+// ---- a mode-4 proof's TAPE stages over a LIST of proofs (zkir_verify_many_tapes_device, zkir_verify_rate_many_tapes_device and their *_host forms) ----
+// The same key as above.  hash_check, wide_check and both sections' digests depend on the proof's words alone (plus n_real and the code's end from the header and the blob),
+// and so do the bytes every hash call wrote: a list stage answers them for every proof BEFORE any front runs (prepare).  hash_side and wide_side need the lookup challenges,
+// but their sums enter T, then LK_TN, which check 10 alone reads: a front whose tape checks were answered by the list DEFERS check 10 (TapeStages::defer, tapes_armed) and
+// goes on; after the last front ONE sides call serves every proof that deferred, and mem_deferred_check is handed the sum of ALL the deferred shares (cells + hash + wide).
+//
+// A LOCATED pair of tapes.  hash: the hash section's start, avail: the words from there to the proof's end (>= 1).  The records are placed by hashcall::n_cells_of of their
+// own fields, never by a count word: n_full records of hash[0] lie in the proof whole and take hash_words words with the count word; whole: the walk placed all hash[0] of
+// them.  wide: NULL, or the wide section ([n_wide] + 8 n_wide words) at hash + hash_words, where the hash section is whole, n_wide <= n_real and those words lie in the proof.
+struct TapeSection {
+  const uint32_t* hash; uint64_t avail;
+  uint64_t n_full, hash_words; bool whole;
+  const uint32_t* wide; uint64_t n_wide;
+  uint64_t n_real, code_end;
+};
+// hash_tape_walk's rule (tape_table.inl) without the device's needs.  prefix: NULL, or min(w[0], avail / 8) + 1 entries: how many cells the records before record k hold.
+// header_only: record n_full's eight header words lie in the buffer, its cells do not.
+struct TapeExtent { uint64_t n_full = 0, cells = 0, used = 1; bool whole = false, header_only = false; };
+inline TapeExtent tape_section_walk(const uint32_t* w, uint64_t avail, uint64_t* prefix) {
+  TapeExtent t;
+  const uint64_t nh = w[0];
+  uint64_t q = 1;
+  t.whole = true;
+  for (uint64_t k = 0; k < nh; k++) {
+    if (q + 8 > avail) { t.whole = false; break; }
+    const uint32_t* c = w + q;
+    if (prefix) prefix[k] = t.cells;
+    const uint64_t n = hashcall::n_cells_of((uint64_t)c[1] | ((uint64_t)c[2] << 20), c[3], (uint64_t)c[4] | ((uint64_t)c[5] << 20));
+    if (q + 8 + 5 * n > avail) { t.whole = false; t.header_only = true; break; }
+    q += 8 + 5 * n; t.cells += n; t.n_full++;
+  }
+  if (prefix && t.whole) prefix[nh] = t.cells;
+  t.used = q;
+  return t;
+}
+// a section's chunk digests in prepare's answer: the hash section's (only where it is whole: hash_words is its length if its check passes), then the wide section's
+inline uint64_t tape_section_chunks(const TapeSection& S, int which) { return which ? (S.wide ? (1 + 8 * S.n_wide + 511) / 512 : 0) : (S.whole ? (S.hash_words + 511) / 512 : 0); }
+// Where a mode-4 proof's tapes lie: mem_section_locate's result (loc), then 1 + 7 n words of touched cells.  ok = false: not mode 4, or the proof ends before the hash
+// section's count word.  A ROUTING AID ONLY, as mem_section_locate is: the list entries compare what the front hands their callbacks with this (pointer, available words,
+// n_real, code_end, n_wide) and fall back to the host stage on any difference.
+struct TapeLocated { bool ok = false; TapeSection sec{}; };
+TapeLocated tape_sections_locate(const uint32_t* proof, uint64_t proof_words, const MemLocated& loc);
+struct TapeSideJob { uint32_t section; const uint32_t* lk_m; bool hash, wide; };      // section: an index into the list prepare was handed; which of the two sums are wanted
+struct TapeManyStage {
+  void* self;
+  // per section TapeStages::hash_check's verdict and *used (used[i], where the verdict is 0), TapeStages::wide_check's verdict (wide_verdicts[i]; 0 where wide is NULL) and
+  // TapeStages::digests' words of both sections at digests + 4 (the chunks of the sections before it: tape_section_chunks(S, 0) + tape_section_chunks(S, 1) each)
+  int (*prepare)(void* self, const TapeSection* list, uint32_t n, int* hash_verdicts, uint64_t* used, int* wide_verdicts, uint32_t* digests);
+  // per job TapeStages::hash_side's sum at sums + 8 job and wide_side's at sums + 8 job + 4 (zero where not wanted); list: what prepare was handed, a wanted side's check
+  // had verdict 0 and the proof's words are below p
+  int (*sides)(void* self, const TapeSection* list, const TapeSideJob* jobs, uint32_t n_jobs, uint32_t* sums);
+  void (*done)(void* self);                                      // nullable, as MemManyStage::done
+};
+TapeManyStage host_tape_many_stage();                            // loops over the host stage functions
+struct TapeManyProbe { uint32_t what = 0, index = 0; };          // (zkir_verify_many_tapes_probe) what = 1: + 1 on proof index's hash share, 2: on its wide share, before its deferred check
+struct TapeManyNote { uint64_t records = 0; uint32_t sections = 0, deferred = 0; };      // what went through the tape list stage (all zero: every proof kept its own tape stages)
+// the tape list stage of a many-proof call: the located tapes go through `stage` where their calls plus wide records reach min_records (and there is one at all)
+struct TapeManyRun { const TapeManyStage* stage; uint64_t min_records; TapeManyProbe probe; TapeManyNote* note; };
+// zkir_tape_sections_stage_host / _launch: the list stage on its own over n whole hash sections (hash_words[i] words each: [0] included) and wide sections ([n] + 8 n
+// words) with their n_real, code_end and canonical challenges: per section both verdicts, the chunk digests (hash: ceil(hash_words / 512), then wide: ceil(wide_words / 512);
+// zero where the verdict is not 0) and the two canonical sums (sums + 8 i, + 4; zero unless BOTH verdicts are 0)
+int tape_sections_stage(const char* who, const TapeManyStage& st, const uint32_t* const* hash_secs, const uint64_t* hash_words, const uint32_t* const* wide_secs, const uint64_t* wide_words,
+                        const uint64_t* n_real, const uint64_t* code_end, const uint32_t* alphas, const uint32_t* lambdas, uint32_t n, int32_t* hash_verdicts, int32_t* wide_verdicts,
+                        uint32_t* digests, uint32_t* sums);
 struct PcsManyStage;
 struct StarkQueryStage;
 // zkir_verify / zkir_verify_rate of n proofs (modes mixed), the memory stages through `mem` where the located sections' total cells reach min_cells, the queries through ONE
 // run of `queries`.  Host only: whatever touches a device is behind the three interfaces.  0, or a negative value (no verdict for any of them).
+// tape_run: NULL (every mode-4 front has its own tape stages: `tapes`), or the tape list stage around the same pass of fronts.  Where the tape batch goes through it, a
+// mode-4 proof it does not serve (not located, no record) runs the host tape stages; where it does not (below min_records), every front keeps `tapes`.
 int verify_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, const MemManyStage& mem,
-                               uint64_t min_cells, const TapeStagesFor* tapes, const StarkQueryStage& queries, const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note);
+                               uint64_t min_cells, const TapeStagesFor* tapes, const StarkQueryStage& queries, const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note,
+                               const TapeManyRun* tape_run = nullptr);
 int rate_many_with_mem_stage(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, const uint32_t* min_queries,
                              const uint32_t* min_pow_bits, uint32_t n, const MemManyStage& mem, uint64_t min_cells, const TapeStagesFor* tapes, const PcsManyStage& queries,
-                             const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note);
+                             const MemManyProbe& probe, int32_t* verdicts, MemManyNote* note, const TapeManyRun* tape_run = nullptr);
 
 // ---- the QUERY STAGE of the commitment layer's verifiers (zkir_lowdeg_verify, zkir_eval_verify, zkir_batch_eval_verify and their *_device forms) ----
 // Checks 6 .. 11 of all the queries of a 'ZKLD' / 'ZKEV' / 'ZKBE' proof.  verify.cpp's fri_part_verify hands the stage what it has CHECKED (the shape: checks 1 and 3 passed,

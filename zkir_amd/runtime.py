@@ -422,6 +422,15 @@ def lib() -> C.CDLL:
         L.zkir_verify_rate_many_memory_host.restype = C.c_int; L.zkir_verify_rate_many_memory_host.argtypes = [V, V, V, V, V, U32, V]
         L.zkir_mem_sections_stage_host.restype = C.c_int; L.zkir_mem_sections_stage_host.argtypes = [V, V, V, V, V, V, V, V, U32, V, V, V]
         L.zkir_mem_sections_stage_launch.restype = C.c_int; L.zkir_mem_sections_stage_launch.argtypes = [V, V, V, V, V, V, V, V, U32, V, V, V, V]
+    if hasattr(L, "zkir_verify_many_tapes_device"):           # likewise
+        L.zkir_verify_many_tapes_device.restype = C.c_int; L.zkir_verify_many_tapes_device.argtypes = [V, V, V, C.c_uint32, V, V]
+        L.zkir_verify_many_tapes_host.restype = C.c_int; L.zkir_verify_many_tapes_host.argtypes = [V, V, V, C.c_uint32, V]
+        L.zkir_verify_many_tapes_probe.restype = C.c_int; L.zkir_verify_many_tapes_probe.argtypes = [V, V, V, C.c_uint32, V, C.c_uint32, C.c_uint32, C.c_int, V]
+        L.zkir_verify_rate_many_tapes_device.restype = C.c_int; L.zkir_verify_rate_many_tapes_device.argtypes = [V, V, V, V, V, U32, V, V]
+        L.zkir_verify_rate_many_tapes_host.restype = C.c_int; L.zkir_verify_rate_many_tapes_host.argtypes = [V, V, V, V, V, U32, V]
+        L.zkir_tape_sections_stage_host.restype = C.c_int; L.zkir_tape_sections_stage_host.argtypes = [V, V, V, V, V, V, V, V, U32, V, V, V, V]
+        L.zkir_tape_sections_stage_launch.restype = C.c_int; L.zkir_tape_sections_stage_launch.argtypes = [V, V, V, V, V, V, V, V, U32, V, V, V, V, V]
+        L.zkir_verify_tapes_last.restype = C.c_int; L.zkir_verify_tapes_last.argtypes = [V, V, V]
     if hasattr(L, "zkir_verify_on_device"):                   # absent from older builds loaded through ZKIR_AMD_LIB (kernel experiments)
         L.zkir_verify_on_device.restype = C.c_int; L.zkir_verify_on_device.argtypes = [V, U64, C.POINTER(PublicInputsC), V]
         L.zkir_verify_many_on_device.restype = C.c_int; L.zkir_verify_many_on_device.argtypes = [V, V, V, C.c_uint32, V, V]
@@ -664,12 +673,15 @@ def verify_chain(proofs, expect: Optional[PublicInputsC] = None, device: bool = 
     return lib().zkir_verify_chain(ptrs, lens, len(ps), C.byref(expect) if expect is not None else None)
 
 
-def verify_many(proofs, expects=None, stream=None, memory: bool = False, device: bool = True, probe=None):
+def verify_many(proofs, expects=None, stream=None, memory: bool = False, device: bool = True, probe=None, tapes: bool = False):
     """zkir_verify_many_on_device: n independent proofs (1 .. 1024) -> [zkir_verify(proofs[i], expects[i]) for i] with every proof's queries in ONE batch on the GPU.
     `expects`: None, or one entry (a PublicInputsC or None) per proof.  An empty list, more than 1024 proofs or a device failure raise.
     memory=True: zkir_verify_many_memory_device — the same verdicts with the memory sections of all mode-3 / mode-4 proofs as ONE device batch (three launches for the
     whole call; verify_memory_last() reports it).  memory=True, device=False: zkir_verify_many_memory_host, the same orchestration over the host stages (no HIP call).
-    probe=(what, index): zkir_verify_many_memory_probe (test hook; what = 1 adds one to proof index's cell share before its deferred check 10), host or device."""
+    probe=(what, index): zkir_verify_many_memory_probe (test hook; what = 1 adds one to proof index's cell share before its deferred check 10), host or device.
+    tapes=True (implies memory=True): zkir_verify_many_tapes_device — the hash and wide tapes of all mode-4 proofs as ONE device batch too (at most 8 launches for the
+    whole call; verify_tapes_last() reports it); device=False: zkir_verify_many_tapes_host.  With probe=(what, index): zkir_verify_many_tapes_probe (what = 1 adds one to
+    proof index's hash share, 2 to its wide share)."""
     ps = [np.ascontiguousarray(p, dtype=np.uint32) for p in proofs]
     n = len(ps)
     if expects is not None and len(expects) != n:
@@ -678,7 +690,11 @@ def verify_many(proofs, expects=None, stream=None, memory: bool = False, device:
     lens = (C.c_uint64 * max(n, 1))(*[len(p) for p in ps])
     exps = (C.c_void_p * max(n, 1))(*[C.addressof(e) if e is not None else None for e in expects]) if expects is not None else None
     verdicts = (C.c_int32 * max(n, 1))()
-    if probe is not None:
+    if tapes and probe is not None:
+        rc = lib().zkir_verify_many_tapes_probe(ptrs, lens, exps, n, verdicts, int(probe[0]), int(probe[1]), 1 if device else 0, stream)
+    elif tapes:
+        rc = lib().zkir_verify_many_tapes_device(ptrs, lens, exps, n, verdicts, stream) if device else lib().zkir_verify_many_tapes_host(ptrs, lens, exps, n, verdicts)
+    elif probe is not None:
         rc = lib().zkir_verify_many_memory_probe(ptrs, lens, exps, n, verdicts, int(probe[0]), int(probe[1]), 1 if device else 0, stream)
     elif memory:
         rc = lib().zkir_verify_many_memory_device(ptrs, lens, exps, n, verdicts, stream) if device else lib().zkir_verify_many_memory_host(ptrs, lens, exps, n, verdicts)
@@ -702,6 +718,47 @@ def verify_memory_last() -> dict:
     c, l, u = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
     lib().zkir_verify_memory_last(C.byref(c), C.byref(l), C.byref(u))
     return {"cells": int(c.value), "launches": int(l.value), "uploaded_words": int(u.value)}
+
+
+def verify_tapes_last() -> dict:
+    """zkir_verify_tapes_last: the tape list stage of this thread's last many-proof verification — the records (hash calls plus wide records) that went through it, its
+    launches and the words uploaded for it (all zero after any entry but verify_many(tapes=True) / verify_rate_many(tapes=True) / tape_sections_stage)."""
+    c, l, u = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+    lib().zkir_verify_tapes_last(C.byref(c), C.byref(l), C.byref(u))
+    return {"records": int(c.value), "launches": int(l.value), "uploaded_words": int(u.value)}
+
+
+def tape_sections_stage(hash_secs, wide_secs, n_real, code_end, alphas, lams, device: bool = True, stream=None):
+    """zkir_tape_sections_stage_launch / _host: a mode-4 proof's tape stages over n pairs of whole sections (hash_secs[i]: a hash section, [0] included; wide_secs[i]:
+    [n_i] + 8 n_i words) as ONE list — at most 8 launches on the GPU, or the host stage functions.  n_real[i], code_end[i], alphas[i] / lams[i] canonical E4 ->
+    (hash_verdicts [int], wide_verdicts [int], digests [(np.uint32[hash chunks_i, 4], np.uint32[wide chunks_i, 4]); zero where that verdict is not 0],
+    sums np.uint32[n, 2, 4] canonical: hash share, wide share; zero unless both verdicts are 0)."""
+    hs = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in hash_secs]
+    ws = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in wide_secs]
+    n = len(hs)
+    if not (len(ws) == len(n_real) == len(code_end) == len(alphas) == len(lams) == n):
+        raise ValueError("one wide section, n_real, code_end, alpha and lambda per hash section")
+    hp = (C.c_void_p * max(n, 1))(*[x.ctypes.data if len(x) else None for x in hs])
+    hl = (C.c_uint64 * max(n, 1))(*[len(x) for x in hs])
+    wp = (C.c_void_p * max(n, 1))(*[x.ctypes.data if len(x) else None for x in ws])
+    wl = (C.c_uint64 * max(n, 1))(*[len(x) for x in ws])
+    nr = (C.c_uint64 * max(n, 1))(*[int(x) for x in n_real])
+    ce = (C.c_uint64 * max(n, 1))(*[int(x) for x in code_end])
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.uint32).reshape(-1)) if n else np.zeros(4, np.uint32)
+    l = np.ascontiguousarray(np.asarray(lams, dtype=np.uint32).reshape(-1)) if n else np.zeros(4, np.uint32)
+    chunks = [((len(x) + 511) // 512, (len(y) + 511) // 512) for x, y in zip(hs, ws)]
+    hv, wv = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    dg = np.zeros(4 * max(sum(c0 + c1 for c0, c1 in chunks), 1), dtype=np.uint32)
+    sums = np.zeros((max(n, 1), 2, 4), dtype=np.uint32)
+    args = [hp, hl, wp, wl, nr, ce, a.ctypes.data, l.ctypes.data, n, hv, wv, dg.ctypes.data, sums.ctypes.data]
+    rc = lib().zkir_tape_sections_stage_launch(*args, stream) if device else lib().zkir_tape_sections_stage_host(*args)
+    if rc != ZKIR_OK:
+        _raise(abs(rc))
+    out, at = [], 0
+    for c0, c1 in chunks:
+        out.append((dg[4 * at:4 * (at + c0)].reshape(c0, 4).copy(), dg[4 * (at + c0):4 * (at + c0 + c1)].reshape(c1, 4).copy()))
+        at += c0 + c1
+    return [int(hv[i]) for i in range(n)], [int(wv[i]) for i in range(n)], out, sums[:n]
 
 
 def mem_section_check(sec, mode: int, code_words: int, device: bool = True, stream=None) -> int:
@@ -992,12 +1049,13 @@ def _many_args(proofs):
     return ps, n, ptrs, lens
 
 
-def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, stream=None, memory: bool = False, device: bool = True):
+def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, stream=None, memory: bool = False, device: bool = True, tapes: bool = False):
     """zkir_verify_rate_many_device: n independent whole-run 'ZKSR' proofs (1 .. 1024) of any mode and rate -> [verify_rate(proofs[i], expects[i], min_queries[i],
     min_pow_bits[i]) for i] with every proof's queries in ONE batch on the GPU.  `expects`: None, or one entry (a PublicInputsC or None) per proof; `min_queries` /
     `min_pow_bits`: None (1 / 0) or one value per proof.  An empty list, more than 1024 proofs or a device failure raise, and no verdict is formed.
     memory=True: zkir_verify_rate_many_memory_device — the memory sections of all mode-3 / mode-4 proofs as ONE device batch, as verify_many(memory=True); with
-    device=False zkir_verify_rate_many_memory_host (no HIP call)."""
+    device=False zkir_verify_rate_many_memory_host (no HIP call).  tapes=True (implies memory=True): zkir_verify_rate_many_tapes_device / _host — the mode-4 proofs'
+    hash and wide tapes as ONE batch too, as verify_many(tapes=True)."""
     ps, n, ptrs, lens = _many_args(proofs)
     for name, a in (("expectations", expects), ("min_queries", min_queries), ("min_pow_bits", min_pow_bits)):
         if a is not None and len(a) != n:
@@ -1006,7 +1064,9 @@ def verify_rate_many(proofs, expects=None, min_queries=None, min_pow_bits=None, 
     mq = (C.c_uint32 * max(n, 1))(*[int(x) for x in min_queries]) if min_queries is not None else None
     mb = (C.c_uint32 * max(n, 1))(*[int(x) for x in min_pow_bits]) if min_pow_bits is not None else None
     verdicts = (C.c_int32 * max(n, 1))()
-    if memory and not device:
+    if tapes:
+        rc = lib().zkir_verify_rate_many_tapes_device(ptrs, lens, exps, mq, mb, n, verdicts, stream) if device else lib().zkir_verify_rate_many_tapes_host(ptrs, lens, exps, mq, mb, n, verdicts)
+    elif memory and not device:
         rc = lib().zkir_verify_rate_many_memory_host(ptrs, lens, exps, mq, mb, n, verdicts)
     elif memory:
         rc = lib().zkir_verify_rate_many_memory_device(ptrs, lens, exps, mq, mb, n, verdicts, stream)
