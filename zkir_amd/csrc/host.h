@@ -205,7 +205,14 @@ struct LdeTables {
   const uint32_t* small_inv;  // w_{2^Bm}^-k, k < 2^(Bm-1)      (Bm = min(log_n, 10))
   const uint32_t* small_fwd;  // w_{2^(Bm+b)}^k, k < 2^(Bm+b-1), b = log_blowup   (blow-up 2: w_{2^(Bm+1)}^k, k < 2^Bm)
   int log_blowup = 1;         // 1, 2, 3: rows of `out` = N << log_blowup
+  // All-zero column blocks (blow-up 2, chains whose first inverse kernel is an LDS pass): ZERO_FLAG_BLOCKS device words that belong to THIS call alone until its kernels
+  // have run, and a non-zero stamp no other call on the slot uses.  The first inverse pass writes the stamp into the word of every block it sees a non-zero tile of; the
+  // kernels after it skip the blocks whose word is not the stamp (zeros in, zeros out).  A word left by an earlier call differs from the stamp, or — a replayed graph —
+  // equals it and merely costs the shortcut: the slot never needs clearing.  nullptr / 0: every kernel runs as if the feature did not exist.
+  uint32_t* zero_slot = nullptr;
+  uint32_t zero_epoch = 0;
 };
+constexpr uint32_t ZERO_FLAG_BLOCKS = 64;                     // the kernels hold the flags as one 64-bit mask; wider matrices run without them
 void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out, void* hip_stream);   // matrices in the B8 layout: n_blocks x [rows][8]
 bool strided_variant_run(const LdeTables& t, uint32_t* data, uint32_t n_blocks, int variant, bool dit, void* hip_stream);   // experiment: one strided pass, chosen tile geometry (timing only)
 // experiment (profiles/HISTORY.md, round 4): blocks 0 and 1 of `in` generated from the trace inside the first inverse pass; false = not applicable at this size (nothing launched)

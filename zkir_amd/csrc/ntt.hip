@@ -145,7 +145,8 @@ __device__ __forceinline__ u32x4 trace_quad01(const TraceSrc01& q, uint32_t blk,
 // LDS holds the two halves as separate planes so that consecutive lanes touch consecutive 16-byte words.
 template <bool DIT, int R, int C, int NTH, bool FUSED = false>
 __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__ data, uint64_t blk_u4, uint32_t tiles_per_block, uint32_t total, int L, int s0,
-                                                              const uint32_t* __restrict__ tw, const uint32_t* __restrict__ small, int log_small, uint32_t j4_m, int canon, TraceSrc01 fsrc = TraceSrc01{}) {
+                                                              const uint32_t* __restrict__ tw, const uint32_t* __restrict__ small, int log_small, uint32_t j4_m, int canon, TraceSrc01 fsrc = TraceSrc01{},
+                                                              uint32_t* zflags = nullptr, uint32_t epoch = 0, int produce = 0) {
   constexpr int B = 2 * R;
   constexpr uint32_t POS = 1u << (B + C), QUADS = POS / 4, CMASK = (1u << C) - 1, PLANE = POS + 4;       // +4: the two planes start in different banks
   constexpr uint32_t MOVES = 2 * POS / NTH;
@@ -167,7 +168,15 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
   static_assert(QUADS == NTH, "one quad per lane and round");
   u32x4 pre[MOVES];
   uint4* x; uint32_t base, lo0, hi;
-  uint32_t w = blockIdx.x;
+  // All-zero column blocks (zflags != nullptr; the word of block b holds `epoch` once some tile of it was seen non-zero by THIS lde_run): every pass is linear, tile
+  // by tile, so a zero tile stays a zero tile.  The chain's first inverse pass (`produce`) is the one that reads `in`: it finds out, tile by tile, skips the rounds and the
+  // copy-out of a zero tile (in place: the tile already holds zeros) and stamps the block of every other tile.  The kernels launched after it read the stamps ONCE, before
+  // their first prefetch, into a wave-uniform bit mask (at most 64 blocks: host.h) and step past the tiles of unstamped blocks in their walk over the work list: the
+  // middle kernel has written zeros there, and zero is canonical.
+  uint64_t live = ~0ull;
+  if (zflags && !produce) { const uint32_t l = threadIdx.x & 63; live = __ballot(l < total / tiles_per_block && zflags[l] == epoch); }
+  auto next_live = [&](uint32_t ww) { while (ww < total && !((live >> (ww / tiles_per_block)) & 1)) ww += gridDim.x; return ww; };
+  uint32_t w = next_live(blockIdx.x);
   if (w >= total) return;
   // vmcnt retires IN ORDER: a table read issued after the next tile's prefetch would make its s_waitcnt drain the whole prefetch
   // before the first round starts (rocm 7.2 emitted s_waitcnt vmcnt(0) in round 0 for exactly that) — so nothing is read from global
@@ -201,10 +210,12 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
   if (DIT) tw_cur = tw[(lo0 + (threadIdx.x & CMASK)) << (L - s0 - B)];
   tile_factors(hi);
   for (;;) {
+    uint32_t nz = 0;                                           // produce: the OR of the lane's words of this tile
     static_for<0, (int)MOVES>([&](auto kc) {
       constexpr uint32_t k = decltype(kc)::value;
       const uint32_t e = threadIdx.x + k * NTH, row = e >> (C + 1), wv = e & ((2u << C) - 1);
       st4(&lds4[(wv & 1) * PLANE + ((row << C) | (wv >> 1))], pre[k]);
+      if (produce) nz |= (pre[k].x | pre[k].y) | (pre[k].z | pre[k].w);
     });
     uint32_t tp[R];                                            // forward: per-lane power used by round r; inverse: this tile's uniform factor of round r
     if (DIT) {                                                 // round r needs w^(lo << (L-1-s0-(2r+1))): finest at r = R-1, each earlier round is its 4th power
@@ -215,8 +226,14 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
 #pragma unroll
       for (int r = 0; r < R; r++) tp[r] = tf_next[r];
     }
-    __syncthreads();
-    const uint32_t wn = w + gridDim.x;
+    bool dense = true;
+    if (produce) {
+      dense = __syncthreads_or(nz != 0) != 0;                  // the barrier in front of round 0, with the tile test riding on it
+      if (dense && threadIdx.x == 0) zflags[w / tiles_per_block] = epoch;          // (every non-zero tile of the block stores the same word)
+    } else {
+      __syncthreads();
+    }
+    const uint32_t wn = next_live(w + gridDim.x);
     uint4* xn = x; uint32_t base_n = base, lo0_n = lo0, hi_n = hi;
     if (wn < total) {                                          // next tile: loads issued now, consumed after this tile's rounds
       geometry(wn, xn, base_n, lo0_n, hi_n);
@@ -229,6 +246,7 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
       if (DIT) tw_cur = tw[(lo0_n + (threadIdx.x & CMASK)) << (L - s0 - B)];
       tile_factors(hi_n);
     }
+    if (dense) {
 #pragma unroll
     for (int r = 0; r < R; r++) {
       const int b = 2 * r;
@@ -284,10 +302,11 @@ __global__ __launch_bounds__(NTH) void ntt_strided_r4_kernel(uint4* __restrict__
       if (DIT && canon) v = canon4(v);                       // the chain's last forward pass: (-p, p) -> [0, p)
       x[((uint64_t)base + (uint64_t)row * stride_mid) * 2 + wv] = v;
     }
+    }                                                          // (a zero tile of the producing pass: no rounds, nothing to store)
     if (wn >= total) break;
     w = wn; x = xn; base = base_n; lo0 = lo0_n; hi = hi_n;
     // (no barrier here: a lane refills exactly the LDS words it has just copied out — the copy-in and copy-out loops share one slot map —
-    //  and the barrier after the refill orders everything before the first round)
+    //  and the barrier after the refill orders everything before the first round; after a skipped zero tile nothing has read LDS at all)
   }
 }
 
@@ -364,7 +383,7 @@ inline int persist() { static const int v = getenv("ZKIR_NTT_PERSIST") ? atoi(ge
 
 template <bool DIT, int R, int C, int NTH, bool FUSED = false>
 void launch_strided_r4(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, int s0, const uint32_t* tw, const uint32_t* small, int log_small, uint32_t j4_m, hipStream_t s,
-                       const TraceSrc01* fsrc = nullptr, int canon = 0) {
+                       const TraceSrc01* fsrc = nullptr, int canon = 0, uint32_t* zflags = nullptr, uint32_t epoch = 0, int produce = 0) {
   constexpr size_t lds = 16u * 2 * ((1u << (2 * R + C)) + 4);
   auto k = ntt_strided_r4_kernel<DIT, R, C, NTH, FUSED>;
   static std::atomic<uint64_t> attr_done{0};                                   // one bit per device id: the attribute is per (function, device)
@@ -375,16 +394,20 @@ void launch_strided_r4(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, int
   const unsigned per_cu = (unsigned)((160u << 10) / lds) > 0 ? (unsigned)((160u << 10) / lds) : 1u;       // workgroups resident per CU (LDS-limited)
   unsigned grid = persist() ? cu_count() * (per_cu > 8 ? 8 : per_cu) : total;
   if (grid > total) grid = total;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NTH), lds, s, (uint4*)data, 2 * n, tiles, total, L, s0, tw, small, log_small, j4_m, canon, fsrc ? *fsrc : TraceSrc01{});
+  hipLaunchKernelGGL(k, dim3(grid), dim3(NTH), lds, s, (uint4*)data, 2 * n, tiles, total, L, s0, tw, small, log_small, j4_m, canon, fsrc ? *fsrc : TraceSrc01{}, zflags, epoch, produce);
 }
 
 inline int strided_c() { static const int c = getenv("ZKIR_NTT_C") ? atoi(getenv("ZKIR_NTT_C")) : 2; return c; }
 
 // `stages` radix-2 stages starting at s0 in as few passes over the data as possible: LDS radix-4 passes of 10 / 8 / 6 / 4 stages and
 // register passes of 3 / 2 stages (13 = 10 + 3, 12 = 10 + 2, 11 = 8 + 3, 9 = 6 + 3, 7 = 4 + 3, 5 = 3 + 2); a lone stage only for 1
+// Zero-block flags (see ntt_strided_r4_kernel): with `produce` the chain's FIRST kernel is asked to find out which blocks are non-zero — only an LDS pass can; where a
+// register pass comes first nobody finds out and the flags are dropped for the whole chain.  Returns the flag slot the kernels after this chain may read (or nullptr).
+// The register and single-stage passes ignore the flags: they turn zeros into zeros.
 template <bool DIT>
-void run_strided_stages(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, int s0, int stages, const uint32_t* tw, const uint32_t* small, int log_small, uint32_t j4_m,
-                        uint32_t r8_m, uint32_t r8_3_m, hipStream_t s) {
+uint32_t* run_strided_stages(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, int s0, int stages, const uint32_t* tw, const uint32_t* small, int log_small, uint32_t j4_m,
+                             uint32_t r8_m, uint32_t r8_3_m, hipStream_t s, uint32_t* zflags = nullptr, uint32_t epoch = 0, bool produce = false) {
+  bool first = true;
   while (stages > 0) {
     int take;
     if (stages >= 10 && stages != 11) take = 10;
@@ -394,16 +417,19 @@ void run_strided_stages(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, in
     else if (stages == 5) take = 3;
     else take = stages;                                          // 8, 6, 4, 3, 2, 1
     const int canon = DIT && take == stages;                     // the chain's last forward kernel hands out canonical words
+    int pr = 0;
+    if (produce && first) { if (take >= 4) pr = 1; else zflags = nullptr; }
+    first = false;
     switch (take) {
       case 10:
         // tile rows of 4 positions = 128 contiguous bytes (a full cache line; 128 KiB of LDS, one workgroup of 16 waves per CU) or of
         // 2 positions = 64 bytes (64 KiB, two workgroups of 8 waves): ZKIR_NTT_C picks (benchmarking), default from the measurements
-        if (strided_c() == 2) launch_strided_r4<DIT, 5, 2, 1024>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon);
-        else launch_strided_r4<DIT, 5, 1, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon);
+        if (strided_c() == 2) launch_strided_r4<DIT, 5, 2, 1024>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon, zflags, epoch, pr);
+        else launch_strided_r4<DIT, 5, 1, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon, zflags, epoch, pr);
         break;
-      case 8: launch_strided_r4<DIT, 4, 3, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon); break;
-      case 6: launch_strided_r4<DIT, 3, 4, 256>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon); break;
-      case 4: launch_strided_r4<DIT, 2, 5, 128>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon); break;
+      case 8: launch_strided_r4<DIT, 4, 3, 512>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon, zflags, epoch, pr); break;
+      case 6: launch_strided_r4<DIT, 3, 4, 256>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon, zflags, epoch, pr); break;
+      case 4: launch_strided_r4<DIT, 2, 5, 128>(data, n, n_blocks, L, s0, tw, small, log_small, j4_m, s, nullptr, canon, zflags, epoch, pr); break;
       case 3:
         hipLaunchKernelGGL((ntt_reg_kernel<DIT, 3>), dim3((unsigned)(((n >> 3) * 2 + NT - 1) / NT), n_blocks), dim3(NT), 0, s, (uint4*)data, 2 * n, L, s0, tw, j4_m, r8_m, r8_3_m, canon);
         break;
@@ -416,6 +442,7 @@ void run_strided_stages(uint32_t* data, uint64_t n, uint32_t n_blocks, int L, in
     }
     s0 += take; stages -= take;
   }
+  return zflags;
 }
 
 // ---- fused middle for N < 1024 (tests, tiny traces): the whole transform of one column block in LDS, column by column, radix 2 ----
@@ -472,14 +499,28 @@ __global__ __launch_bounds__(NT) void lde_small_kernel(const uint32_t* __restric
 constexpr int MID_NT = 512;
 __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void lde_middle_r4_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, uint32_t chunks_per_block, uint32_t total, int L,
                                                                 const uint32_t* __restrict__ tw_inv, const uint32_t* __restrict__ small_inv, const uint32_t* __restrict__ small_fwd,
-                                                                const uint32_t* __restrict__ g_lo, const uint32_t* __restrict__ g_hi, uint32_t j4_inv_m, uint32_t j4_fwd_m, int canon) {
+                                                                const uint32_t* __restrict__ g_lo, const uint32_t* __restrict__ g_hi, uint32_t j4_inv_m, uint32_t j4_fwd_m, int canon,
+                                                                const uint32_t* __restrict__ zflags, uint32_t epoch) {
   constexpr int Bm = 10;
   constexpr uint32_t APL = 1024;
   __shared__ uint4 A[2 * APL];
   __shared__ uint4 Bf[2048];
   const uint32_t n = 1u << L, t = threadIdx.x;
+  // All-zero column blocks (zflags != nullptr: the stamps of the chain's first inverse pass, see ntt_strided_r4_kernel; read once, before the first prefetch): the chunk
+  // of an unstamped block is not fetched — its 2048 positions of `out` (which holds whatever the last call left there) are written as zeros, both planes of a position
+  // from one lane, the store shape of a computed chunk.  The walk zero-fills such chunks on its way to the next chunk that has to be computed.
+  uint64_t live = ~0ull;
+  if (zflags) { const uint32_t l = t & 63; live = __ballot(l < total / chunks_per_block && zflags[l] == epoch); }
+  auto next_live = [&](uint32_t ww) {
+    for (; ww < total && !((live >> (ww / chunks_per_block)) & 1); ww += gridDim.x) {
+      uint4* yz = out + (uint64_t)(ww / chunks_per_block) * n * 4 + ((uint64_t)(ww % chunks_per_block) << (Bm + 2));
+#pragma unroll
+      for (int k = 0; k < 4; k++) { const uint32_t e = t + k * MID_NT; yz[2 * e] = make_uint4(0, 0, 0, 0); yz[2 * e + 1] = make_uint4(0, 0, 0, 0); }
+    }
+    return ww;
+  };
   // persistent workgroups with the next chunk's loads in flight during the 15 rounds of the current one (see the strided kernel)
-  uint32_t w = blockIdx.x;
+  uint32_t w = next_live(blockIdx.x);
   if (w >= total) return;
   // vmcnt retires in order (see the strided kernel): no global read between the issue of the next chunk's prefetch and its use.
   // The compact-table twiddles of the ten rounds depend on (lane, round) only: read once per workgroup.  The coset scale of the lane's four
@@ -520,7 +561,7 @@ __global__ __launch_bounds__(MID_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 #pragma unroll
     for (int r = 0; r < 5; r++) cf[r] = cf_next[r];
     __syncthreads();
-    const uint32_t wn = w + gridDim.x;
+    const uint32_t wn = next_live(w + gridDim.x);               // (the zero-fill stores of skipped chunks go out BEFORE the prefetch is issued)
     if (wn < total) fetch(wn);
     // ---- inverse, rounds r = 0..4: stages (2r, 2r+1) of the chunk, spans h1 = 2^(9-2r), h2 = h1/2; lane = (quad q, half h); block = hi ----
     {
@@ -782,17 +823,19 @@ void lde_run(const LdeTables& t, uint32_t* in, uint32_t n_blocks, uint32_t* out,
     hipLaunchKernelGGL(lde_small_kernel, dim3(n_blocks), dim3(NT), (8u << L), s, in, out, L, t.small_inv, t.small_fwd, t.g_lo, t.g_hi);
     return;
   }
-  // inverse strided stages 0 .. L-11 (multiply-first; the compact table then has order 1024)
-  run_strided_stages<false>(in, N, n_blocks, L, 0, L - 10, t.tw_inv, t.small_inv, 10, j4_inv_m, r8_inv_m, r8_inv3_m, s);
+  // inverse strided stages 0 .. L-11 (multiply-first; the compact table then has order 1024).  The caller's flag slot (host.h) is used where the chain's first kernel is an
+  // LDS pass (log_n >= 14, != 15) and the blocks fit the kernels' 64-bit mask; otherwise every kernel gets a null pointer and runs exactly as without the slot.
+  uint32_t* zf = t.zero_slot && t.zero_epoch && n_blocks <= ZERO_FLAG_BLOCKS ? t.zero_slot : nullptr;
+  zf = run_strided_stages<false>(in, N, n_blocks, L, 0, L - 10, t.tw_inv, t.small_inv, 10, j4_inv_m, r8_inv_m, r8_inv3_m, s, zf, t.zero_epoch, zf != nullptr);
   {
     const uint32_t chunks = N >> 10, total = chunks * n_blocks;
     unsigned grid = persist() ? cu_count() * 2 : total;                     // 64 KiB of LDS: two workgroups per CU
     if (grid > total) grid = total;
     hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.tw_inv, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
-                       j4_inv_m, j4_fwd_m, L == 10);
+                       j4_inv_m, j4_fwd_m, L == 10, (const uint32_t*)zf, t.zero_epoch);
   }
   // forward DIT strided stages 11 .. L of the size-2N transform
-  run_strided_stages<true>(out, (uint64_t)2 * N, n_blocks, L + 1, 11, L - 10, t.tw_fwd, t.small_fwd, 11, j4_fwd_m, r8_fwd_m, r8_fwd3_m, s);
+  run_strided_stages<true>(out, (uint64_t)2 * N, n_blocks, L + 1, 11, L - 10, t.tw_fwd, t.small_fwd, 11, j4_fwd_m, r8_fwd_m, r8_fwd3_m, s, zf, t.zero_epoch);
 }
 
 
@@ -845,7 +888,7 @@ bool lde_run_fused01(const LdeTables& t, const zkir_trace_columns* trace, uint64
     unsigned grid = persist() ? cu_count() * 2 : total;
     if (grid > total) grid = total;
     hipLaunchKernelGGL(lde_middle_r4_kernel, dim3(grid), dim3(MID_NT), 0, s, (const uint4*)in, (uint4*)out, chunks, total, L, t.tw_inv, t.small_inv, t.small_fwd, t.g_lo, t.g_hi,
-                       j4_inv_m, j4_fwd_m, L == 10);
+                       j4_inv_m, j4_fwd_m, L == 10, nullptr, 0u);
   }
   run_strided_stages<true>(out, (uint64_t)2 * N, n_blocks, L + 1, 11, L - 10, t.tw_fwd, t.small_fwd, 11, j4_fwd_m, r8_fwd_m, r8_fwd3_m, s);
   return true;

@@ -715,6 +715,20 @@ struct SyncRing {
   uint32_t* take() { return d_slots + (next.fetch_add(1, std::memory_order_relaxed) % SYNC_SLOTS); }
 };
 
+// The zero-block flags of lde_run (host.h: LdeTables::zero_slot), kept the same way: a ring of slots of ZERO_FLAG_BLOCKS words, one slot and one stamp PER LDE LAUNCH, so that
+// launches of one context that overlap on two streams, or sit in captured graphs, never share the words they write.  Nothing is ever cleared: a launch only asks whether a word
+// equals its own stamp, and the stamps of the ZERO_SLOTS launches that share a slot over time all differ (a 32-bit counter, zero left out).
+constexpr uint32_t ZERO_SLOTS = 1024;
+struct ZeroFlagRing {
+  uint32_t* d_words = nullptr;
+  std::atomic<uint32_t> next{0};
+  void take(uint32_t*& slot, uint32_t& epoch) {
+    uint32_t e = next.fetch_add(1, std::memory_order_relaxed) + 1;
+    if (e == 0) e = next.fetch_add(1, std::memory_order_relaxed) + 1;
+    slot = d_words + (size_t)(e % ZERO_SLOTS) * zkir::ZERO_FLAG_BLOCKS; epoch = e;
+  }
+};
+
 // all levels above the leaf digests: wide levels (throughput-bound) one launch each, then subtree launches
 void launch_tree_levels(const p2::Consts* cp, uint32_t* leaf_digests, uint64_t n_leaves, SyncRing& ring, hipStream_t s) {
   uint32_t* cur = leaf_digests;
@@ -750,6 +764,7 @@ struct zkir_stark_ctx {
   // zkir_commit_overlapped_launch (experiment): a second stream, two events and the per-leaf sponge states, made on first use
   mutable hipStream_t ov_stream = nullptr; mutable hipEvent_t ov_ev[2] = {nullptr, nullptr}; mutable std::vector<hipEvent_t> ov_group_ev; mutable uint4* d_ov_state = nullptr; mutable size_t ov_state_bytes = 0;
   mutable SyncRing sync;          // subtree_kernel's "who finishes last" counters, one slot per launch (launches of one context may overlap on the caller's streams)
+  mutable ZeroFlagRing zero;      // lde_run's zero-block flags, one slot and stamp per launch
   mutable std::mutex mu;          // a context serves one proof at a time (its workspace arena); different contexts are independent
   // prover workspace: one device allocation made on the first zkir_prove and reused (hipMalloc of GBs costs more than the kernels)
   mutable unsigned char* arena = nullptr;
@@ -771,7 +786,8 @@ bool blowup2_only(const zkir_stark_ctx* c, const char* who) {
 // The LDE with the scale table chosen by the form its output is to rest in: mont_out = the words of `out` carry the Montgomery factor R (the
 // prover's matrices; the scale g^k / N of the fused middle pass comes from the table that has R folded in — same kernels, same instruction count).
 int lde_launch(const zkir_stark_ctx* c, uint32_t* in, uint32_t width, uint32_t* out, bool mont_out, hipStream_t s) {
-  const zkir::LdeTables t{(int)c->log_n, c->d_tw_inv, c->d_tw_fwd, mont_out ? c->d_g_lo_m : c->d_g_lo, c->d_g_hi, c->d_small_inv, c->d_small_fwd, (int)c->log_blowup};
+  zkir::LdeTables t{(int)c->log_n, c->d_tw_inv, c->d_tw_fwd, mont_out ? c->d_g_lo_m : c->d_g_lo, c->d_g_hi, c->d_small_inv, c->d_small_fwd, (int)c->log_blowup};
+  if (c->log_blowup == 1 && c->log_n >= 14) c->zero.take(t.zero_slot, t.zero_epoch);          // (smaller chains have no kernel that could fill the slot)
   zkir::lde_run(t, in, (width + 7) / 8, out, s);               // ntt.hip
   return check_launch("lde");
 }
@@ -896,6 +912,8 @@ int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** 
   if (e == hipSuccess) e = hipMemcpy(c->d_p2, &c->consts, sizeof(p2::Consts), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&c->sync.d_slots, SYNC_SLOTS * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(c->sync.d_slots, 0, SYNC_SLOTS * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&c->zero.d_words, (size_t)ZERO_SLOTS * zkir::ZERO_FLAG_BLOCKS * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(c->zero.d_words, 0, (size_t)ZERO_SLOTS * zkir::ZERO_FLAG_BLOCKS * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&c->d_tw_inv, (size_t)n_inv * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_tw_fwd, (size_t)n_fwd * 4);
   if (e == hipSuccess) e = hipMalloc(&c->d_g_lo, 1024 * 4);
@@ -924,7 +942,7 @@ int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** 
 void zkir_stark_ctx_free(zkir_stark_ctx* c) {
   if (!c) return;
   (void)hipFree(c->d_tw_inv); (void)hipFree(c->d_tw_fwd); (void)hipFree(c->d_g_lo); (void)hipFree(c->d_g_hi); (void)hipFree(c->d_g_lo_m); (void)hipFree(c->d_inv_xm1);
-  (void)hipFree(c->d_small_inv); (void)hipFree(c->d_small_fwd); (void)hipFree(c->d_p2); (void)hipFree(c->sync.d_slots);
+  (void)hipFree(c->d_small_inv); (void)hipFree(c->d_small_fwd); (void)hipFree(c->d_p2); (void)hipFree(c->sync.d_slots); (void)hipFree(c->zero.d_words);
   if (c->ov_stream) (void)hipStreamDestroy(c->ov_stream);
   for (hipEvent_t e : c->ov_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ov_group_ev) (void)hipEventDestroy(e);
