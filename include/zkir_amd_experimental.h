@@ -132,6 +132,12 @@ int zkir_tape_sections_stage_launch(const uint32_t* const* hash_secs, const uint
  * front.  what = 0: nothing. */
 int zkir_verify_many_tapes_probe(const uint32_t* const* proofs, const uint64_t* proof_words, const zkir_public_inputs* const* expects, uint32_t n, int32_t* verdicts, uint32_t what,
                                  uint32_t index, int device, void* hip_stream);
+/* TEST HOOKS, host builds of the leaf sponge's pieces (poseidon2.h, round 28).  _scaled_quads: n states of twelve RAW input words of permute_scaled (anything inside its
+ * documented input range, below 1.96 p); full[12 i ..] = its raw output words, quads[12 i + 4 Q + j] = word j of the quad permute_scaled_quad<Q> defines.
+ * _sponge_full_blocks: the rate-8 sponge over n_words = 8, 16, .. words as leaf_hash_kernel runs it; form 0: the constants every kernel uses (canonical words), 1: the
+ * constants derived from the input factor 1 (canonical words), 2: from the input factor R (words in Montgomery form); digest: four canonical words. */
+void zkir_poseidon2_scaled_quads(const uint32_t* in, uint64_t n, uint32_t* full, uint32_t* quads);
+int zkir_poseidon2_sponge_full_blocks(const uint32_t* words, uint32_t n_words, uint32_t form, uint32_t digest[4]);
 
 #ifdef __cplusplus
 }

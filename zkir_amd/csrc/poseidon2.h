@@ -48,6 +48,10 @@ struct Consts {              // Montgomery form unless noted
   int32_t pr_c[RP];          // h_(r+1) R^2 / f_r: what the reduced  sum - 2 s0  of round r is multiplied by on its way to the next S-box (r = RP - 1: towards G = f_(RP-1) / R)
   uint64_t pr_a[RP];         // h_(r+1) in[r + 1] R: the next round's constant, the addend of that product (r = RP - 1: G ext[RF/2][0] R)
   uint64_t pr_k[T];          // f_(RP-1) ext[RF/2][i]: the constants of the full round that follows, added to the passive words before their last reduction
+  // int_rounds_scaled<true>(): word 0 ENTERS the partial rounds through one product that takes it from the factor F the full rounds left to h_0 and adds in[0]
+  // (generate() with f0: F follows from the input factor and is not R; with the default derivation F = h_0 = R and the product is the identity + in[0])
+  int32_t pr_c0;             // h_0 R / F
+  uint64_t pr_a0;            // h_0 in[0] R
 };
 
 inline uint64_t splitmix64(uint64_t& s) {
@@ -81,7 +85,11 @@ inline void ext_matrix_inverse(uint32_t inv[T][T]) {
   for (int i = 0; i < T; i++) for (int j = 0; j < T; j++) inv[i][j] = a[i][T + j];
 }
 
-inline void generate(Consts& c) {
+// f0 = 0: the constants every kernel uses (the input factor F_IN derived BACKWARDS from "the partial rounds see the factor R", below).  f0 != 0 (canonical): the
+// input factor is GIVEN — F_IN = f0, the factor the caller's words already carry: 1 for canonical words, R for words resting in Montgomery form — and every later factor
+// is derived FORWARDS from it, so a sponge absorbs its words as they lie (no product per absorbed word) and pays one product on word 0 at the partial rounds' entry
+// (pr_c0 / pr_a0, int_rounds_scaled<true>).  Same permutation on the canonical values either way.
+inline void generate(Consts& c, uint32_t f0 = 0) {
   uint64_t s = 0x5A4B49522D50322Dull;
   auto next = [&]() -> uint32_t { for (;;) { const uint32_t v = (uint32_t)(splitmix64(s) >> 33); if (v < bb::P) return bb::to_mont(v); } };
   for (int r = 0; r < RF; r++) for (int i = 0; i < T; i++) c.ext[r][i] = next();
@@ -108,12 +116,20 @@ inline void generate(Consts& c) {
     const uint32_t R = bb::R1, Rinv = bb::inv(R);
     const uint32_t R6 = bb::pow(R, 6);
     uint32_t g[RF + 1], h[RF];                                 // g[r]: factor entering the S-boxes of full round r; h[r]: after them
-    g[RF / 2] = R;
-    for (int r = RF / 2 - 1; r >= 0; r--) { h[r] = bb::mul(g[r + 1], R); g[r] = bb::pow(bb::mul(h[r], R6), INV7); }
+    if (f0 == 0) {
+      g[RF / 2] = R;
+      for (int r = RF / 2 - 1; r >= 0; r--) { h[r] = bb::mul(g[r + 1], R); g[r] = bb::pow(bb::mul(h[r], R6), INV7); }
+    } else {
+      g[0] = bb::mul(f0 % bb::P, Rinv);                        // the initial layer's reduction
+      for (int r = 0; r < RF / 2; r++) { h[r] = bb::mul(bb::pow(g[r], 7), bb::inv(R6)); g[r + 1] = bb::mul(h[r], Rinv); }
+    }
     {
       // the partial rounds (int_rounds_scaled): f[r] the passive words' factor during round r, hx[r] word 0's at its S-box, G the common factor they leave with
+      const uint32_t F = g[RF / 2];                            // the factor they are entered with: R, or what f0 leads to
       uint32_t f[RP], hx[RP];
-      for (int r = 0; r < RP; r++) { f[r] = r < 3 ? R : bb::mul(f[r - 3], Rinv); hx[r] = bb::pow(bb::mul(f[r], R6), INV7); }
+      for (int r = 0; r < RP; r++) { f[r] = r < 3 ? F : bb::mul(f[r - 3], Rinv); hx[r] = bb::pow(bb::mul(f[r], R6), INV7); }
+      c.pr_c0 = (int32_t)bb::mul(bb::mul(hx[0], R), bb::inv(F));
+      c.pr_a0 = bb::mul(bb::mul(hx[0], bb::from_mont(c.in[0])), R);
       const uint32_t G = bb::mul(f[RP - 1], Rinv), R2c = bb::mul(R, R);
       for (int r = 0; r < RP; r++) {
         const uint32_t hn = r + 1 < RP ? hx[r + 1] : G, rcn = bb::from_mont(r + 1 < RP ? c.in[r + 1] : c.ext[RF / 2][0]);
@@ -314,8 +330,11 @@ constexpr uint64_t lazy_reduced_bound(uint64_t acc) { return (acc >> 32) + bb::P
 static_assert(lazy_rounds_bound(1ull << 31, 3) < (1ull << 62), "three partial rounds on words below 2^31 stay inside what a Montgomery reduction takes");
 static_assert(lazy_reduced_bound(lazy_rounds_bound(1ull << 31, 3)) <= (1ull << 31), ".. and their reduction is a word below 2^31 again");
 static_assert(lazy_reduced_bound(lazy_rounds_bound(1ull << 31, 1) + bb::P) < bb::P, "the words leave the last round (one round + the next full round's constant) inside (-p, p)");
-BB_HD void int_rounds_scaled(uint32_t* s, const Consts& c) {   // in: unsigned words below p + 128, factor R; out: signed words in (-p, p), factor G, next round's constants added
-  int32_t x = (int32_t)s[0] + c.in0_neg;
+// ENTRY: word 0 arrives with the passive words' factor F, not with h_0, and goes through one product first: |s[0] pr_c0 + pr_a0| / 2^32 + p / 2 < (p + 128) p / 2^32 + 1 + p / 2 < 0.97 p
+static_assert((((uint64_t)bb::P + 128) * bb::P >> 32) + 2 + bb::P / 2 < bb::P, "word 0 enters its first S-box inside (-p, p)");
+template <bool ENTRY = false>
+BB_HD void int_rounds_scaled(uint32_t* s, const Consts& c) {   // in: unsigned words below p + 128, factor R (ENTRY: F); out: signed words in (-p, p), factor G, next round's constants added
+  int32_t x = ENTRY ? bb::smont_mul_add((int32_t)s[0], c.pr_c0, c.pr_a0) : (int32_t)s[0] + c.in0_neg;
   int32_t t[T];
   int64_t w[T];
 #pragma unroll
@@ -348,6 +367,93 @@ BB_HD void permute_scaled(uint32_t* s, const Consts& c) {
     for (int i = 0; i < T; i++) s[i] = sbox_biased(s[i], c.pre_b[r][i]);
     ext_linear_scaled<false>(s, nullptr);
   }
+}
+
+// ---- the same permutation when the caller reads ONE QUAD of its output (round 28) --------------------------------------------------------------------
+// A rate-8 sponge over full blocks overwrites s[0..7] with every absorption: between two permutations only the capacity s[8..11] lives, after the last only the
+// digest s[0..3]; a 2-to-1 compression reads s[0..3] alone.  The external matrix is circ(2 M4, M4, M4) and M4 is linear over the integers, so quad Q of the layer's
+// output is  M4(q0 + q1 + q2 + qQ)  for the input quads q0, q1, q2: four sums u_j = s[j] + s[4 + j] + s[8 + j] + s[4Q + j] (two multiply-adds each: the quad counted
+// twice enters with the inline multiplier 2), ONE M4 on 64-bit words (8) and four reductions (8) — 24 instructions against ext_linear_scaled's 68.  The integers
+// reduced are the ones ext_linear_scaled reduces for these four words (y[4Q + j] + sum[j], by linearity), so the words are the same bit for bit and so are the bounds:
+constexpr uint64_t EXT_IN_MAX = (uint64_t)bb::P * 196 / 100 + 1;      // 1.96 p: what a layer takes (a biased S-box output, an absorbed or carried word)
+static_assert(4 * EXT_IN_MAX < (1ull << 34), "u_j, the sum of a column's three words with one counted twice, is below 2^34");
+static_assert(16 * 4 * EXT_IN_MAX < (1ull << 38), "M4's rows sum to at most 16: every output is below 2^38 before its reduction, as in ext_linear_scaled");
+static_assert(((16 * 4 * EXT_IN_MAX) >> 32) + bb::P < bb::P + 64, ".. and leaves it below p + 64");
+BB_HD void m4_wide64(uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t* y) {      // m4_wide on 64-bit words (inputs below 2^58)
+  const uint64_t t0 = a + b, t1 = c + d;
+  const uint64_t t2 = (b << 1) + t1, t3 = (d << 1) + t0;
+  const uint64_t t4 = (t1 << 2) + t3, t5 = (t0 << 2) + t2;
+  y[0] = t3 + t5; y[1] = t5; y[2] = t2 + t4; y[3] = t4;
+}
+template <int Q>
+BB_HD void ext_linear_scaled_quad(const uint32_t* s, uint32_t* out4) {      // out4[j] = word 4Q + j of ext_linear_scaled<false>(s); out4 may be any quad of s
+  static_assert(Q >= 0 && Q < 3, "a state has three quads");
+  constexpr int A = Q == 0 ? 1 : 0, B = Q == 2 ? 1 : 2;        // the two quads that enter once
+  uint64_t u[4], y[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) u[j] = bb::acc_add(bb::mad_wide<2>((uint64_t)s[4 * A + j], s[4 * Q + j]), s[4 * B + j]);
+  m4_wide64(u[0], u[1], u[2], u[3], y);
+#pragma unroll
+  for (int j = 0; j < 4; j++) out4[j] = bb::mont_reduce_wide(y[j]);
+}
+// permute_scaled up to, and without, its last linear layer: the twelve S-box outputs of full round 7.  ENTRY: for constants derived from a given input factor (generate(c, f0))
+template <bool ENTRY = false>
+BB_HD void permute_scaled_head(uint32_t* s, const Consts& c) {
+  ext_linear_scaled<true>(s, c.ext0_s);
+#pragma unroll P2_RF_UNROLL
+  for (int r = 0; r < RF / 2; r++) {
+#pragma unroll
+    for (int i = 0; i < T; i++) s[i] = sbox_biased(s[i], c.pre_b[r][i]);
+    ext_linear_scaled<false>(s, nullptr);
+  }
+  int_rounds_scaled<ENTRY>(s, c);
+#pragma unroll P2_RF_UNROLL
+  for (int r = RF / 2; r < RF - 1; r++) {
+#pragma unroll
+    for (int i = 0; i < T; i++) s[i] = sbox_biased(s[i], c.pre_b[r][i]);
+    ext_linear_scaled<false>(s, nullptr);
+  }
+  // (the round index opaque: with a visible one the 24 scalar registers of pre_b[7] are loaded once before the caller's block loop and held across it — leaf_hash_kernel then
+  // spilled 18 scalar registers and took 70 vector ones; a loop left from its middle instead, `if (r == RF - 1) break`, took 74)
+  int r_last = RF - 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(r_last));
+#endif
+#pragma unroll
+  for (int i = 0; i < T; i++) s[i] = sbox_biased(s[i], c.pre_b[r_last][i]);
+}
+// permute_scaled for a caller that reads quad Q only: afterwards s[4Q .. 4Q + 3] are permute_scaled's words, the other eight are NOT defined
+template <int Q, bool ENTRY = false>
+BB_HD void permute_scaled_quad(uint32_t* s, const Consts& c) {
+  permute_scaled_head<ENTRY>(s, c);
+  ext_linear_scaled_quad<Q>(s, s + 4 * Q);
+}
+// The rate-8 sponge over n_blocks >= 1 FULL blocks (so::hash_elems on 8 n_blocks words), digest4 = its four canonical digest words.  load(b, v): the eight words of block b.
+// Every absorption overwrites s[0..7], so a permutation that is not the last owes the next one its capacity s[8..11] alone (Q = 2) and the last owes the digest (Q = 0);
+// no word asks whether its column exists, and the first block meets a capacity of literal zeros, not carried words.
+//   FORWARD = false: c = generate(c), the words are multiplied by `in_scale` on their way in (c.in_scale for canonical words, from_mont(c.in_scale) for Montgomery ones)
+//   FORWARD = true:  c = generate(c, f0) with f0 the factor the words carry (1 / R): they are absorbed as they lie — the first layer takes ANY 32-bit words: its sums stay far inside what
+//                    the reduction takes and its outputs below p + 128, what an S-box takes (static_assert) — and in_scale is not read
+static_assert(16 * (4 * 0xFFFFFFFFull) < (1ull << 38) && ((16 * (4 * 0xFFFFFFFFull) + bb::P) >> 32) + bb::P < bb::P + 128, "the initial layer takes absorbed words of any value");
+template <bool FORWARD, class Load>
+BB_HD void sponge_full_blocks(Load&& load, uint32_t n_blocks, uint32_t in_scale, const Consts& c, uint32_t* digest4) {
+  uint32_t s[T];
+#pragma unroll
+  for (int i = RATE; i < T; i++) s[i] = 0;
+  for (uint32_t b = 0;;) {
+    uint32_t v[RATE];
+    load(b, v);
+#pragma unroll
+    for (int i = 0; i < RATE; i++) s[i] = FORWARD ? v[i] : bb::mont_mul_lazy(v[i], in_scale);
+    permute_scaled_head<FORWARD>(s, c);
+    if (++b == n_blocks) break;
+    ext_linear_scaled_quad<2>(s, s + 8);
+#pragma unroll
+    for (int i = RATE; i < T; i++) s[i] = bb::mont_mul_lazy(s[i], c.carry);
+  }
+  ext_linear_scaled_quad<0>(s, s);
+#pragma unroll
+  for (int i = 0; i < DIGEST; i++) digest4[i] = bb::mont_mul(s[i], c.out_scale);
 }
 
 #if defined(__HIPCC__)

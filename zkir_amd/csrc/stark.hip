@@ -525,10 +525,31 @@ __global__ __launch_bounds__(NT) void selector_inverse_kernel(uint32_t log_m, co
 // one lane per leaf (= row position); a B8 block is exactly one absorption of the rate-8 sponge: two 16-byte loads per permutation
 // in_scale: cp->in_scale for canonical matrix words; from_mont(cp->in_scale) when the matrix rests in Montgomery form (the prover's LDE matrices): the
 // factor R the words carry is divided out by the multiplication that brings them to the sponge's input scale — same instructions, same digests.
-__global__ __launch_bounds__(NT) void leaf_hash_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ mat, uint32_t width, uint64_t n, uint32_t in_scale, uint32_t* __restrict__ digests) {
+//
+// Two instances of one body (round 28).  FULL_BLOCKS: the width is a non-zero multiple of 8 (every committed trace: 152 / 160 / 168 columns) — every absorption overwrites
+// s[0..7], so a permutation that is not the last owes the next one its capacity s[8..11] alone and the last owes the digest s[0..3]: p2::permute_scaled_head and ONE quad of
+// the last linear layer (p2::ext_linear_scaled_quad: 24 instructions against 68); no word of the loop asks whether its column exists, and the first block meets a capacity of
+// literal zeros, not carried words.  Otherwise: the general sponge, whose ragged last block keeps the rate words the previous permutation left.  Same digests (the words a
+// quad layer returns are the full layer's, bit for bit).  The launchers choose on the host (leaf_hash_launch); the kernel NAMES are what the profiles and bench.py key on, so
+// the instance the commit step runs keeps the name leaf_hash_kernel.  That instance also takes its constants derived FORWARDS from the factor the matrix words carry
+// (p2::generate(c, f0): the context keeps one set for canonical matrices, f0 = 1, and one for matrices resting in Montgomery form, f0 = R), so the eight products of an
+// absorption are gone and in_scale is not read; every other kernel keeps the one set it had.
+constexpr bool LEAF_FORWARD = true;
+template <bool FULL_BLOCKS>
+__device__ __forceinline__ void leaf_hash_body(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ mat, uint32_t width, uint64_t n, uint32_t in_scale, uint32_t* __restrict__ digests) {
   const uint64_t j = (uint64_t)blockIdx.x * NT + threadIdx.x;
   if (j >= n) return;
   uint32_t s[p2::T];
+  if constexpr (FULL_BLOCKS) {
+    const uint4* m4 = reinterpret_cast<const uint4*>(mat) + 2 * j;
+    uint32_t d[p2::DIGEST];
+    p2::sponge_full_blocks<LEAF_FORWARD>([&](uint32_t blk, uint32_t* v) {
+      const uint4 lo = m4[(uint64_t)blk * n * 2], hi = m4[(uint64_t)blk * n * 2 + 1];
+      v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+    }, width >> 3, in_scale, *cp, d);
+    reinterpret_cast<uint4*>(digests)[j] = make_uint4(d[0], d[1], d[2], d[3]);
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < p2::T; i++) s[i] = 0;
   const uint4* m4 = reinterpret_cast<const uint4*>(mat);
@@ -547,6 +568,17 @@ __global__ __launch_bounds__(NT) void leaf_hash_kernel(const p2::Consts* __restr
   if (width == 0) p2::permute_scaled(s, *cp);
   uint4 d = make_uint4(bb::mont_mul(s[0], out_scale), bb::mont_mul(s[1], out_scale), bb::mont_mul(s[2], out_scale), bb::mont_mul(s[3], out_scale));
   reinterpret_cast<uint4*>(digests)[j] = d;
+}
+__global__ __launch_bounds__(NT) void leaf_hash_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ mat, uint32_t width, uint64_t n, uint32_t in_scale, uint32_t* __restrict__ digests) {
+  leaf_hash_body<true>(cp, mat, width, n, in_scale, digests);
+}
+__global__ __launch_bounds__(NT) void leaf_hash_ragged_kernel(const p2::Consts* __restrict__ cp, const uint32_t* __restrict__ mat, uint32_t width, uint64_t n, uint32_t in_scale, uint32_t* __restrict__ digests) {
+  leaf_hash_body<false>(cp, mat, width, n, in_scale, digests);
+}
+// cp, in_scale: the constants every kernel uses and the scale of this matrix's words under them; cp_fwd: the set derived from the factor those words carry
+void leaf_hash_launch(const p2::Consts* cp, const p2::Consts* cp_fwd, const uint32_t* mat, uint32_t width, uint64_t n, uint32_t in_scale, uint32_t* digests, hipStream_t s) {
+  if (width != 0 && width % p2::RATE == 0) hipLaunchKernelGGL(leaf_hash_kernel, dim3(grid_for(n)), dim3(NT), 0, s, LEAF_FORWARD ? cp_fwd : cp, mat, width, n, in_scale, digests);
+  else hipLaunchKernelGGL(leaf_hash_ragged_kernel, dim3(grid_for(n)), dim3(NT), 0, s, cp, mat, width, n, in_scale, digests);
 }
 
 // EXPERIMENT (round 6): the leaf sponge BLOCK-WISE — blocks [b0, b1) of the matrix are absorbed into a 12-word sponge state kept per leaf in global memory
@@ -591,7 +623,7 @@ __global__ __launch_bounds__(NT) void compress_kernel(const p2::Consts* __restri
   const uint32_t k = cp->in_scale, ko = cp->out_scale;
   uint32_t s[p2::T] = {bb::mont_mul_lazy(l.x, k), bb::mont_mul_lazy(l.y, k), bb::mont_mul_lazy(l.z, k), bb::mont_mul_lazy(l.w, k), bb::mont_mul_lazy(r.x, k), bb::mont_mul_lazy(r.y, k),
                        bb::mont_mul_lazy(r.z, k), bb::mont_mul_lazy(r.w, k), 0, 0, 0, 0};
-  p2::permute_scaled(s, *cp);
+  p2::permute_scaled_quad<0>(s, *cp);                          // the digest is all a compression reads
   reinterpret_cast<uint4*>(out)[i] = make_uint4(bb::mont_mul(s[0], ko), bb::mont_mul(s[1], ko), bb::mont_mul(s[2], ko), bb::mont_mul(s[3], ko));
 }
 
@@ -761,6 +793,7 @@ struct zkir_stark_ctx {
   uint32_t* d_small_fwd = nullptr;  // w_{2^(Bm+b)}^k, k < 2^(Bm+b-1), b = log_blowup   (blow-up 2: w_{2^(Bm+1)}^k, k < 2^Bm)
   p2::Consts consts;              // host copy (transcript, verifier side)
   p2::Consts* d_p2 = nullptr;     // device copy: every hash kernel takes the pointer (no process-wide __constant__ state)
+  p2::Consts* d_p2_fwd[2] = {nullptr, nullptr};   // the full-block leaf sponge's sets (p2::generate(c, f0)): [0] f0 = 1, canonical matrices; [1] f0 = R, matrices resting in Montgomery form
   // zkir_commit_overlapped_launch (experiment): a second stream, two events and the per-leaf sponge states, made on first use
   mutable hipStream_t ov_stream = nullptr; mutable hipEvent_t ov_ev[2] = {nullptr, nullptr}; mutable std::vector<hipEvent_t> ov_group_ev; mutable uint4* d_ov_state = nullptr; mutable size_t ov_state_bytes = 0;
   mutable SyncRing sync;          // subtree_kernel's "who finishes last" counters, one slot per launch (launches of one context may overlap on the caller's streams)
@@ -793,7 +826,7 @@ int lde_launch(const zkir_stark_ctx* c, uint32_t* in, uint32_t width, uint32_t* 
 }
 // leaf layer + the levels above it; mont_in = the matrix words carry the Montgomery factor (the digests are those of the canonical words either way)
 int merkle_commit(const zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, uint64_t n_leaves, uint32_t* tree, bool mont_in, hipStream_t s) {
-  hipLaunchKernelGGL(leaf_hash_kernel, dim3(grid_for(n_leaves)), dim3(NT), 0, s, c->d_p2, mat, width, n_leaves, mont_in ? bb::from_mont(c->consts.in_scale) : c->consts.in_scale, tree);
+  leaf_hash_launch(c->d_p2, c->d_p2_fwd[mont_in ? 1 : 0], mat, width, n_leaves, mont_in ? bb::from_mont(c->consts.in_scale) : c->consts.in_scale, tree, s);
   launch_tree_levels(c->d_p2, tree, n_leaves, c->sync, s);
   return check_launch("merkle_commit");
 }
@@ -834,6 +867,37 @@ void zkir_poseidon2_permute_scaled(uint32_t state[12], uint32_t rounds) {
     p2::permute_scaled(s, consts);
   }
   for (int i = 0; i < p2::T; i++) state[i] = rounds ? bb::mont_mul(s[i], consts.out_scale) : state[i] % bb::P;
+}
+
+// TEST HOOKS, host builds of what leaf_hash_kernel and compress_kernel run (zkir_amd_experimental.h).  n states of twelve RAW input words of permute_scaled (whatever
+// lies in its documented range: below 1.96 p): full = its twelve raw output words, quads[12 i + 4 Q + j] = word j of what permute_scaled_quad<Q> leaves in s[4 Q ..].
+void zkir_poseidon2_scaled_quads(const uint32_t* in, uint64_t n, uint32_t* full, uint32_t* quads) {
+  static const p2::Consts consts = [] { p2::Consts c; p2::generate(c); return c; }();
+  for (uint64_t k = 0; k < n; k++) {
+    uint32_t s[p2::T], q[p2::T];
+    for (int i = 0; i < p2::T; i++) s[i] = in[12 * k + i];
+    p2::permute_scaled(s, consts);
+    for (int i = 0; i < p2::T; i++) full[12 * k + i] = s[i];
+    for (int i = 0; i < p2::T; i++) q[i] = in[12 * k + i];
+    p2::permute_scaled_quad<0>(q, consts);
+    for (int j = 0; j < 4; j++) quads[12 * k + j] = q[j];
+    for (int i = 0; i < p2::T; i++) q[i] = in[12 * k + i];
+    p2::permute_scaled_quad<1>(q, consts);
+    for (int j = 0; j < 4; j++) quads[12 * k + 4 + j] = q[4 + j];
+    for (int i = 0; i < p2::T; i++) q[i] = in[12 * k + i];
+    p2::permute_scaled_quad<2>(q, consts);
+    for (int j = 0; j < 4; j++) quads[12 * k + 8 + j] = q[8 + j];
+  }
+}
+// The full-block sponge over n_words = 8, 16, .. words.  form 0: the constants every kernel uses, canonical words scaled on their way in; 1: the constants derived
+// forwards from f0 = 1, canonical words absorbed as they lie; 2: from f0 = R, the words in Montgomery form.  digest: four canonical words (so::hash_elems).
+int zkir_poseidon2_sponge_full_blocks(const uint32_t* words, uint32_t n_words, uint32_t form, uint32_t digest[4]) {
+  if (!words || !digest || n_words == 0 || n_words % p2::RATE != 0 || form > 2) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "zkir_poseidon2_sponge_full_blocks: need a non-zero multiple of 8 words and form 0 / 1 / 2"}); return ZKIR_ERR_ARGUMENT; }
+  static const p2::Consts consts[3] = {[] { p2::Consts c; p2::generate(c); return c; }(), [] { p2::Consts c; p2::generate(c, 1u); return c; }(), [] { p2::Consts c; p2::generate(c, bb::R1); return c; }()};
+  const auto load = [&](uint32_t b, uint32_t* v) { for (int i = 0; i < p2::RATE; i++) v[i] = words[8 * b + i]; };
+  if (form == 0) p2::sponge_full_blocks<false>(load, n_words / p2::RATE, consts[0].in_scale, consts[0], digest);
+  else p2::sponge_full_blocks<true>(load, n_words / p2::RATE, 0, consts[form], digest);
+  return ZKIR_OK;
 }
 
 // Diagnostic: measured peak Montgomery-multiplication rate (modmul/s) of the device, used as the ALU roofline of the Poseidon2 kernels.
@@ -910,6 +974,12 @@ int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** 
   p2::generate(c->consts);
   hipError_t e = hipMalloc((void**)&c->d_p2, sizeof(p2::Consts));
   if (e == hipSuccess) e = hipMemcpy(c->d_p2, &c->consts, sizeof(p2::Consts), hipMemcpyHostToDevice);
+  for (int m = 0; m < 2 && e == hipSuccess; m++) {
+    p2::Consts fwd;
+    p2::generate(fwd, m ? bb::R1 : 1u);
+    e = hipMalloc((void**)&c->d_p2_fwd[m], sizeof(p2::Consts));
+    if (e == hipSuccess) e = hipMemcpy(c->d_p2_fwd[m], &fwd, sizeof(p2::Consts), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess) e = hipMalloc(&c->sync.d_slots, SYNC_SLOTS * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(c->sync.d_slots, 0, SYNC_SLOTS * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&c->zero.d_words, (size_t)ZERO_SLOTS * zkir::ZERO_FLAG_BLOCKS * sizeof(uint32_t));
@@ -942,7 +1012,7 @@ int zkir_stark_ctx_create(uint32_t log_n, uint32_t log_blowup, zkir_stark_ctx** 
 void zkir_stark_ctx_free(zkir_stark_ctx* c) {
   if (!c) return;
   (void)hipFree(c->d_tw_inv); (void)hipFree(c->d_tw_fwd); (void)hipFree(c->d_g_lo); (void)hipFree(c->d_g_hi); (void)hipFree(c->d_g_lo_m); (void)hipFree(c->d_inv_xm1);
-  (void)hipFree(c->d_small_inv); (void)hipFree(c->d_small_fwd); (void)hipFree(c->d_p2); (void)hipFree(c->sync.d_slots); (void)hipFree(c->zero.d_words);
+  (void)hipFree(c->d_small_inv); (void)hipFree(c->d_small_fwd); (void)hipFree(c->d_p2); (void)hipFree(c->d_p2_fwd[0]); (void)hipFree(c->d_p2_fwd[1]); (void)hipFree(c->sync.d_slots); (void)hipFree(c->zero.d_words);
   if (c->ov_stream) (void)hipStreamDestroy(c->ov_stream);
   for (hipEvent_t e : c->ov_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ov_group_ev) (void)hipEventDestroy(e);
@@ -1121,7 +1191,7 @@ int zkir_merkle_commit_launch(const zkir_stark_ctx* c, const uint32_t* mat, uint
 // can bracket the dominant kernel of the commit step with its own events.
 int zkir_merkle_leaves_launch(const zkir_stark_ctx* c, const uint32_t* mat, uint32_t width, uint64_t n_leaves, uint32_t* digests, void* stream) {
   if (!c || !mat || !digests || n_leaves == 0) { zkir::set_last_error({ZKIR_ERR_ARGUMENT, "merkle leaves: null argument or no leaves"}); return ZKIR_ERR_ARGUMENT; }
-  hipLaunchKernelGGL(leaf_hash_kernel, dim3(grid_for(n_leaves)), dim3(NT), 0, (hipStream_t)stream, c->d_p2, mat, width, n_leaves, c->consts.in_scale, digests);
+  leaf_hash_launch(c->d_p2, c->d_p2_fwd[0], mat, width, n_leaves, c->consts.in_scale, digests, (hipStream_t)stream);
   return check_launch("merkle_leaves");
 }
 
